@@ -14,11 +14,20 @@ world size and --gpus disagree or when fewer than N devices are visible.
 
 Prints ONE JSON line on rank 0 (contract in the task statement), including
   roofline      live HIP-event timing of the dominant kernel (conv-layer edge kernel) over the timed
-                region, plus a `kernels` list (edge encoder, node kernel, neighbour stage) from
-                event-timed replays after it
+                region
+A plain run does nothing else: set-up, warm-up, the timed steps, --dump-outputs, the line.  With
+--full it also measures, after the timed region (N=1 only unless noted):
+  roofline      a `kernels` list (edge encoder, node kernel, neighbour stage) from event-timed
+                replays, and the cost of a candidate-list rebuild (any N)
+  force_eval_only  synchronous force evaluations without the integrator
   cpu_baseline  the CPU oracle (port of the reference's PyTorch path) timed on this host on the
-                SAME 10 000-atom inputs and weights (N=1 only)
-  secondary     short runs of the other single-GPU BASELINE configs (C1, C3, C5) (N=1 only)
+                SAME 10 000-atom inputs and weights
+  secondary     short runs of the other single-GPU BASELINE configs (C1, C3, C5)
+and writes the full record to --detail (default bench_detail.json).
+
+--dump-outputs DIR writes what the timed path hands its caller after the last timed step (rank 0's
+positions, velocities and forces) as DIR/<name>.npy, float32; the inputs are seeded, so two builds
+run with the same arguments can be compared array for array.
 """
 import argparse
 import hashlib
@@ -108,10 +117,17 @@ def parse_args():
     ap.add_argument("--line", default="compact", choices=["compact", "full"],
                     help="compact (default; the driver's contract): the ONE stdout line is the compact record.  full: print the "
                          "full record instead (tools/ only: the per-kernel list and per-step distributions on stdout)")
-    ap.add_argument("--detail", default=os.path.join(ROOT, "bench_detail.json"),
+    ap.add_argument("--detail", default=None,
                     help="where the full record goes (per-step distributions, per-kernel list, per-rank summaries, prose notes, "
                          "secondary workloads): the ONE line on stdout is the compact contract record, <= 6 000 characters; "
-                         "'-' = do not write a detail file")
+                         "'-' = do not write a detail file.  Default: bench_detail.json with --full, none without")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need, after the timed region: per-kernel replays, the "
+                         "rebuild cost, force-eval-only, the CPU baseline and the secondary workloads (--no-cpu-baseline / "
+                         "--secondary still select among them), and write the detail file")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write rank 0's positions, velocities and forces (the arrays the timed MD run "
+                         "returns) as DIR/<name>.npy in float32")
     ap.add_argument("--workload", default="c2", choices=["c1", "c1_batch", "c2", "c2_batch8", "c3", "c5", "c5b", "dft"],
                     help="c2 (default, the headline metric): 10k-atom LJ fp32; c1: the reference's own 258-atom LJ snapshot "
                          "(code/LJ/init_pos.npy); c1_batch: 38 such boxes in one set of launches (gamd_config.n_boxes); c2_batch8: the eight 10k-atom boxes the ranks of "
@@ -127,7 +143,12 @@ def parse_args():
                     help="c2 / c3. f32 (default, the headline): fp32 MFMA, bit-exact fp32 FMAs.  f16x3: the same GEMMs on the "
                          "fp16 matrix pipe with every operand split into hi + lo fp16 (3 MFMAs per product term, fp32 "
                          "accumulate): fp32-grade results (same 1e-5 parity bar), 3/16 of the fp32 matrix time")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.detail is None:
+        args.detail = os.path.join(ROOT, "bench_detail.json") if args.full else "-"
+    return args
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -332,11 +353,20 @@ def timed_run(w, steps, warmup, ctx, dev, ddev):
     return dt, ens.max_over_ranks(dt, ctx, device=ddev), conv_ms, conv_n
 
 
-def step_report(w, steps):
+def dump_outputs(w, out_dir):
+    """What the timed MD run hands back to its caller after its last step: positions, velocities and forces (kJ/mol/nm) of
+    every atom of this rank's boxes, float32 as the device holds them (10 000 atoms: 360 KB in all)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in (("positions", w.x), ("velocities", w.v), ("forces", w.f)):
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().cpu().numpy().astype(np.float32))
+
+
+def step_report(w, steps, replays=True):
     """What the timed region was made of, so that the record can explain its own number: the per-step distribution (device
     time between the HIP events in front of consecutive MD steps), how many candidate-list rebuilds and buffer regrows fell
-    inside it, and what one candidate rebuild costs (event-timed replays of the neighbour stage after the timed region,
-    with and without a forced rebuild)."""
+    inside it, and (replays: --full) what one candidate rebuild costs (event-timed replays of the neighbour stage after the
+    timed region, with and without a forced rebuild)."""
     import numpy as np
     s = np.sort(np.asarray(w.step_ms, dtype=np.float64))
     rep = {"step_ms": ({"min": float(s[0]), "p50": float(np.percentile(s, 50)), "p99": float(np.percentile(s, 99)),
@@ -349,7 +379,7 @@ def step_report(w, steps):
     if s.size and s.size != steps:
         rep["step_ms"]["note"] = (f"{s.size} intervals for {steps} steps: a run that froze on a buffer overflow contributes its "
                                   "frozen steps and the resumed ones separately")
-    if w.uses_skin:
+    if w.uses_skin and replays:
         def nbr_ms(force):
             acc = []
             for _ in range(3):
@@ -572,6 +602,8 @@ def main():
     skin = args.skin
     w = build_workload(args.workload, ctx, dev, skin, args.edge_dtype)
     dt, dt_max, conv_ms, conv_n = timed_run(w, args.steps, args.warmup, ctx, dev, ddev)
+    if args.dump_outputs and ctx.rank == 0:
+        dump_outputs(w, args.dump_outputs)
     n_edges = w.eng.counts()[0]
     summary = ens.gather_summary({"seconds": dt, "edges": float(n_edges), "fsum": float(w.f.abs().sum().item()),
                                   "box_seed": float(ens.box_seed(1234, ctx)), "host_threads": float(host_threads),
@@ -597,7 +629,7 @@ def main():
                                       if w.uses_skin else "exact cell-list rebuild every step"),
                    "step": "BAOAB half + neighbour build + GNN forces + BAOAB half, on device",
                    "buffers_regrown_in_timed_run": bool(getattr(w, "timed_status", 0) == 1),
-                   "timed_region": step_report(w, args.steps),
+                   "timed_region": step_report(w, args.steps, replays=args.full),
                    "launch": "torch.distributed.run" if os.environ.get("TORCHELASTIC_RUN_ID") else
                              ("self-spawned ranks" if ctx.world > 1 else "single process")},
         "ensemble": {"boxes": ctx.world, "collective_on_step_path": False,
@@ -654,7 +686,8 @@ def main():
                                            "gather is reachable only by the bf16 kernel (see secondary c5)"}
         rl["neighbour_gather_hbm"] = gather_hbm_block()
     single = ctx.world == 1
-    if single and args.secondary != "none":
+    # everything below takes runs of its own after the timed region: --full only
+    if single and args.full and args.secondary != "none":
         # the other MFMA kernels, from the same live HIP events of the timed region as the conv kernel: the edge encoder has
         # its own event pair; the node kernel between two conv layers is the interval between their event pairs (both
         # kernel boundaries included).  The neighbour stage comes from event-timed replays afterwards.
@@ -682,7 +715,7 @@ def main():
                          "bytes_algorithmic": 12.0 * w.n_atoms + 8.0 * n_edges})
         rl["kernels"] = kern
         rl["kernels_note"] = "k_edge_encode / k_node: live HIP events over the timed region; neighbour stage: 4 event-timed replays"
-    if single:
+    if single and args.full:
         # "report also force-eval-only atom-evals/s" — the call the rollout drivers make once per step
         # (predict_forces: neighbour stage + GNN, no integrator), synchronous like theirs, on the state the timed run left
         # behind; device-resident positions (the PCIe-inclusive form of the call is in DESIGN.md section 5)
@@ -698,9 +731,9 @@ def main():
                                    "what": "gamd_forces: neighbour stage (" + ("Verlet-skin reuse" if w.uses_skin else "exact rebuild")
                                            + ") + edge encoder + conv layers + decoder, one synchronous call per evaluation, "
                                            "positions resident on the device, no integrator"}
-    if single and not args.no_cpu_baseline and args.workload == "c2":
+    if single and args.full and not args.no_cpu_baseline and args.workload == "c2":
         line["cpu_baseline"] = cpu_baseline(w, dev)
-    if single and args.secondary != "none" and args.workload == "c2":
+    if single and args.full and args.secondary != "none" and args.workload == "c2":
         sec = {}
         w.eng.close()
         # (entry, workload, edge dtype): the other single-GPU BASELINE configs, the batched C1, the opt-in split-fp16 and bf16

@@ -23,7 +23,8 @@ Usage:  python oracle/make_golden.py                     writes tests/golden/*.n
                                                          the same, but floating-point arrays may differ by that much relative to
                                                          their largest element (torch's CPU GEMM blocking depends on the thread
                                                          count of the host); keys, dtypes, shapes, integer arrays stay exact.
-                                                         tests/test_oracle_golden.py runs this wherever /root/reference exists.
+                                                         A maintainer's check, run by hand where the reference project is at hand
+                                                         (the test suite does not depend on it).
 """
 import os
 import sys

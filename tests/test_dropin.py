@@ -3,8 +3,8 @@ sys.path, carrying the reference's module constants and constructor signature (C
 predict_forces)."""
 import importlib
 import inspect
+import json
 import os
-import re
 import sys
 from types import SimpleNamespace
 
@@ -16,7 +16,7 @@ from gamd_amd.weights import ModelConfig, make_state_dict
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DROPIN = os.path.join(ROOT, "gamd_amd", "dropin")
-REF = "/root/reference/code"
+GOLDEN = os.path.join(ROOT, "tests", "golden")
 MODULES = {"train_network_lj": "LJ", "train_network_tip3p": "water", "train_network_tip4p": "water",
            "train_network_real_large": "water"}
 # the drivers' args, verbatim: LJ/test_script/test_langevin.py:63-73, water/test_script/test_nosehoover.py:69-76,
@@ -50,28 +50,23 @@ def test_module_constants_are_the_references(dropin):
         assert callable(m.build_model) and inspect.isclass(m.ParticleNetLightning)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="the reference is not present on this machine")
 def test_constants_and_signatures_against_the_reference_sources(dropin):
-    """Read (never import: jax / dgl / lightning are absent) the reference modules' top-level assignments and the
-    ParticleNetLightning / predict_forces signatures and compare."""
-    for name, sub in MODULES.items():
-        src = open(os.path.join(REF, sub, name + ".py")).read()
+    """The reference modules' top-level assignments and the ParticleNetLightning / predict_forces signatures, as read from
+    their sources (never imported: jax / dgl / lightning are absent) into tests/golden/reference_dropin_interface.json:
+    every constant the reference assigns has the same value here, every one it does not assign is absent here too."""
+    with open(os.path.join(GOLDEN, "reference_dropin_interface.json")) as f:
+        ref = json.load(f)
+    assert set(ref["modules"]) == set(MODULES)
+    for name, want in ref["modules"].items():
         mod = dropin[name]
-        env = {}
-        for const in ("CUTOFF_RADIUS", "left_bound", "right_bound", "BOX_SIZE", "NUM_OF_ATOMS", "LAMBDA1", "LAMBDA2"):
-            m = re.search(rf"^{const}\s*=\s*(.+?)\s*(#.*)?$", src, flags=re.M)
-            if m:
-                env[const] = eval(m.group(1), {}, dict(env))
-                assert getattr(mod, const) == env[const], (name, const)
+        for const in ref["checked_constants"]:
+            if const in want["constants"]:
+                assert getattr(mod, const) == want["constants"][const], (name, const)
             else:
                 assert not hasattr(mod, const), (name, const)
-        init = re.search(r"class ParticleNetLightning\(pl\.LightningModule\):\s*def __init__\(self, (.*?)\):", src, flags=re.S).group(1)
-        want = [p.split("=")[0].strip() for p in init.replace("\n", " ").split(",")]
         got = [p for p in inspect.signature(mod.ParticleNetLightning.__init__).parameters if p not in ("self", "engine_kw")]
-        assert got == want, (name, got, want)
-        pf = re.search(r"def predict_forces\(self, (.*?)\):", src).group(1)
-        want_pf = [p.split(":")[0].split("=")[0].strip() for p in pf.split(",")]
-        assert list(inspect.signature(mod.ParticleNetLightning.predict_forces).parameters)[1:] == want_pf, name
+        assert got == want["init_params"], (name, got)
+        assert list(inspect.signature(mod.ParticleNetLightning.predict_forces).parameters)[1:] == want["predict_forces_params"], name
 
 
 def _ckpt(tmp_path, sd, lightning=True):

@@ -56,10 +56,10 @@ def test_default_line_has_the_contract_keys():
         tr, fe = d["config"]["timed_region"], d["force_eval_only"]
         return (abs(tr["mean"] - d["ms_per_step"]) / d["ms_per_step"] < 0.05
                 and 0.8 * d["ms_per_step"] < fe["ms_per_eval"] < 1.3 * d["ms_per_step"])
-    d, full = _run("--no-cpu-baseline", "--no-secondary", with_detail=True)
+    d, full = _run("--full", "--no-cpu-baseline", "--no-secondary", with_detail=True)
     if not timing_consistent(d):
         print("first attempt:", d["ms_per_step"], d["config"]["timed_region"], d["force_eval_only"]["ms_per_eval"])
-        d, full = _run("--no-cpu-baseline", "--no-secondary", with_detail=True)
+        d, full = _run("--full", "--no-cpu-baseline", "--no-secondary", with_detail=True)
     assert list(d)[:len(CONTRACT_ORDER)] == CONTRACT_ORDER, list(d)
     assert d["n_gpus"] == 1 and d["steps"] == 6 and d["warmup"] == 2 and d["higher_is_better"] is True
     assert d["scaling"] == "weak" and d["vs_baseline"] is None and d["dtype"] == "f32" and d["data"] == "synthetic"
@@ -130,6 +130,28 @@ def test_split_fp16_line_is_labelled_as_such():
     d = _run("--no-cpu-baseline", "--no-secondary", "--edge-dtype", "f16x3")
     assert d["dtype"].startswith("f16x3") and d["roofline"]["kernel"] == "k_conv_edge_f16x3"
     assert d["roofline"]["peak"] == 2500.0 and d["roofline"]["frac"] < 1.0
+
+
+def test_plain_run_measures_only_the_headline_and_dumps_the_timed_paths_outputs(tmp_path):
+    """Without --full: the timed steps and the line, nothing measured after them.  --dump-outputs writes the positions,
+    velocities and forces the timed MD run left behind; the inputs are seeded, so a second run reproduces them."""
+    import numpy as np
+    runs = []
+    for i in range(2):
+        out = tmp_path / f"out{i}"
+        d = _run("--dump-outputs", str(out), steps=3, warmup=1)
+        assert list(d)[:len(CONTRACT_ORDER)] == CONTRACT_ORDER, list(d)
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["roofline"]["launches"] == 4 * 3
+        assert d["config"]["timed_region"]["intervals"] == 3 and d["config"]["timed_region"]["rebuild_ms"] is None
+        assert not {"cpu_baseline", "force_eval_only", "secondary"} & set(d) and "other_kernels" not in d["roofline"]
+        arrs = {n: np.load(out / f"{n}.npy") for n in ("positions", "velocities", "forces")}
+        for a in arrs.values():
+            assert a.shape == (10000, 3) and a.dtype == np.float32 and np.isfinite(a).all()
+        assert np.abs(arrs["forces"]).max() > 0.0
+        runs.append(arrs)
+    for n in runs[0]:
+        a, b = runs[0][n], runs[1][n]
+        assert np.abs(a - b).max() <= 1e-4 * np.abs(a).max(), n
 
 
 def test_gpus_2_spawns_two_ranks_by_itself():
@@ -261,10 +283,11 @@ def test_gpus_2_without_a_second_device_fails_loudly():
 
 
 def test_the_drivers_default_command_prints_one_short_line_with_roofline_and_cpu_baseline():
-    """`python3 bench.py --gpus 1 --steps 20 --warmup 5` — the driver's command: ONE line of < 6 000 characters (round 5's line
-    was 21 KB and the driver, which keeps an 8 081-character tail, parsed nothing), strict JSON, the contract keys in the
+    """`python3 bench.py --gpus 1 --steps 20 --warmup 5 --full` — the driver's command with everything measured: ONE line
+    of < 6 000 characters (round 5's line was 21 KB and the driver, which keeps an 8 081-character tail, parsed nothing),
+    strict JSON, the contract keys in the
     contract's order, `roofline` and `cpu_baseline` present, compact secondary triples; everything else in the detail file."""
-    d, full = _run("--gpus", "1", steps=20, warmup=5, with_detail=True)
+    d, full = _run("--gpus", "1", "--full", steps=20, warmup=5, with_detail=True)
     assert list(d)[:len(CONTRACT_ORDER)] == CONTRACT_ORDER, list(d)
     assert list(d)[len(CONTRACT_ORDER):len(CONTRACT_ORDER) + 2] == ["cpu_baseline", "force_eval_only"]
     assert list(d["config"])[:5] == ["workload", "n_atoms", "edges_per_step", "boxes", "neighbour_list"]
@@ -299,7 +322,7 @@ def test_the_drivers_default_command_prints_one_short_line_with_roofline_and_cpu
 def test_secondary_full_goes_to_the_detail_file_only():
     """--secondary full: all twelve secondary workloads with their per-step distributions — in the detail record; the line
     still carries only the compact triples and stays under the limit."""
-    d, full = _run("--no-cpu-baseline", "--secondary", "full", steps=10, warmup=3, with_detail=True)
+    d, full = _run("--full", "--no-cpu-baseline", "--secondary", "full", steps=10, warmup=3, with_detail=True)
     assert set(d["secondary"]) == {"c1", "c3", "c5", "c5b", "dft"}
     s = full["secondary"]
     assert set(s) == {"c1", "c1_batch", "c1_batch_f16x3", "c2_batch8", "c3", "c5", "c5b", "c2_f16x3", "c2_bf16", "dft", "dft_f16x3",

@@ -227,6 +227,27 @@ def test_bench_refuses_a_world_size_that_disagrees_with_gpus():
     assert p.returncode != 0 and "WORLD_SIZE=2" in p.stderr
 
 
+def test_bench_extra_measurements_and_the_detail_file_are_opt_in(monkeypatch):
+    """A plain `bench.py --gpus 1 --steps N --warmup W` measures the headline only and writes no detail file; --full turns
+    the extras and the default detail file on; --dump-outputs takes a directory; --steps must be positive."""
+    import importlib.util, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse_args()
+    assert a.full is False and a.detail == "-" and a.dump_outputs is None and (a.steps, a.warmup) == (7, 2)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    a = bench.parse_args()
+    assert a.full is True and a.detail == os.path.join(root, "bench_detail.json") and a.dump_outputs == "out"
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--detail", "d.json"])
+    assert bench.parse_args().detail == "d.json"
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse_args()
+
+
 def test_pmc_record_is_tied_to_kernel_sources():
     """profiles/pmc_conv_edge.json carries the hash of the kernel sources it was measured on; bench.py prints
     traffic = null (plus a note) when they no longer match."""

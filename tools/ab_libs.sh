@@ -11,7 +11,7 @@ for lib in ${LIBS:-old} new; do
   for w in $ws; do
     extra=""; wl=$w
     if [ $w = c2x ]; then wl=c2; extra="--skin 0"; fi
-    python3 bench.py --workload $wl $extra --steps 300 --warmup 30 --no-secondary --no-cpu-baseline --line full 2>/dev/null | python3 -c "
+    python3 bench.py --workload $wl $extra --steps 300 --warmup 30 --full --no-secondary --no-cpu-baseline --line full 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read()); t=d['config']['timed_region']; n=t.get('neighbour_stage_ms') or {}
 st=d.get('stages_ms') or {}

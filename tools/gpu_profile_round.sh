@@ -49,8 +49,8 @@ python3 tools/conv_variants.py 3593 --cycles > $out/conv_variants_cycles.log 2>&
 cp $out/pmc_conv_edge.json profiles/pmc_conv_edge.json; cp $out/gather_hbm.json profiles/gather_hbm.json
 # (the ONE stdout line is the compact contract record; the full record — per-step distributions, per-kernel list, all twelve
 #  secondary workloads — goes to --detail)
-python3 bench.py --secondary full --detail $out/bench_default_detail.json > $out/bench_default.json 2> $out/bench_default.err
-python3 bench.py --gpus 1 --steps 20 --warmup 5 --detail $out/bench_driver_cmd_detail.json > $out/bench_driver_cmd.json 2>> $out/bench_default.err   # the driver's command
+python3 bench.py --full --secondary full --detail $out/bench_default_detail.json > $out/bench_default.json 2> $out/bench_default.err
+python3 bench.py --gpus 1 --steps 20 --warmup 5 --full --detail $out/bench_driver_cmd_detail.json > $out/bench_driver_cmd.json 2>> $out/bench_default.err   # the driver's command, --full
 python3 bench.py --no-cpu-baseline --no-secondary --edge-dtype f16x3 --detail - > $out/bench_f16x3.json 2>> $out/bench_default.err
 # keep the merge-back small: only the summaries and the per-kernel stats csv
 find $out -name "*_kernel_trace.csv" -delete; find $out -name "*counter_collection.csv" -delete; find $out -name "*agent_info.csv" -delete
