@@ -10,7 +10,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # GAMD_LIB: load another build of the SAME C ABI instead (tools/ point it at libgamd_hip_prof.so, the -DGAMD_PROFILING
-# build with instrumented kernel variants).  It must exist: there is no fallback either way.
+# build with s_memtime segment marks).  It must exist: there is no fallback either way.
 LIB_PATH = os.environ.get("GAMD_LIB") or os.path.join(_HERE, "libgamd_hip.so")
 
 

@@ -11,7 +11,6 @@
 // layout the conv-layer kernel loads with perfectly coalesced 16-byte reads.
 #include "gamd_common.h"
 #include "gamd_internal.h"
-#include <cstdlib>
 
 namespace {
 
@@ -21,7 +20,7 @@ constexpr int ENC_LDS_FLOATS = ENC_W1_FLOATS + 2 * GAMD_WFRAG_FLOATS + 5 * 128 +
 // Edge features of nn_module.py:603-634 (+ the bond flag of :510-511) for this lane's edge, already in the operand order of
 // the first GEMM: MFMA K step s covers features (2 s, 2 s + 1), lanes 0-31 supply the even one, lanes 32-63 the odd one.
 //   features: 0-2 unit vector, 3 standardised length d, 4-43 RBFs of d, 44 bond flag (NFEAT == 45)
-template <int NFEAT, int ABL, typename CPtr>
+template <int NFEAT, typename CPtr>
 __device__ __forceinline__ void edge_features(const EncArgs& a, CPtr cen, int src, int dst, const float4& ps, const float4& pd,
                                               int half, float (&F)[24]) {
     // No floating-point contraction in here: which multiply-add pairs hipcc fuses depends on the kernel the function is inlined
@@ -38,13 +37,13 @@ __device__ __forceinline__ void edge_features(const EncArgs& a, CPtr cen, int sr
     const float d = (nrm - a.length_mean) / a.length_std;          // :630
     F[0] = half ? ry / den : rx / den;
     F[1] = half ? d : rz / den;
-    if (!(ABL & 8) && a.rbf.uniform) {
+    if (a.rbf.uniform) {
         gamd_rbf_chains(d, half, a.gamma * -1.4426950408889634f, a.rbf, F);
     } else {
 #pragma unroll
         for (int s = 2; s < 22; ++s) {
             const float radial = d - cen[2 * (s - 2) + half];           // :261-263
-            F[s] = (ABL & 8) ? radial : __builtin_amdgcn_exp2f((a.gamma * -1.4426950408889634f) * (radial * radial));
+            F[s] = __builtin_amdgcn_exp2f((a.gamma * -1.4426950408889634f) * (radial * radial));
         }
     }
     F[22] = 0.f; F[23] = 0.f;
@@ -60,26 +59,26 @@ __device__ __forceinline__ void edge_features(const EncArgs& a, CPtr cen, int sr
     }
 }
 
-// X = GELU(acc) on a 32 x 128 block.  ABL bit 1 (profiling build): x/2 instead (timing ablation, wrong results); bit 16:
-// the scalar form
-template <int ABL>
+// The GELU blocks and the feature construction (the dense vector stretches of a tile) run at s_setprio 1.  The two waves
+// of a SIMD share its vector issue; a wave inside such a stretch that keeps losing issue slots to its partner's scattered
+// vector instructions finishes later and delays the partner's next stretch as well (found on k_conv_edge_bf16's SiLU blocks,
+// round 6).  Same-box at C2: 418 -> 396 us, 0.74 -> 0.78 of the fp32 matrix peak, bit-identical e; LayerNorm at priority as
+// well: 408 (not kept).
+
+// X = GELU(acc) on a 32 x 128 block
 __device__ __forceinline__ void gelu_block(const f32x16 (&acc)[4], f32x16 (&X)[4], const GeluCoef& k) {
-    if (ABL & 32) __builtin_amdgcn_s_setprio(1);           // ABL 32: the block at priority 1 (conv_edge_bf16.hip's finding, tried here)
+    __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int t = 0; t < 4; ++t)
 #pragma unroll
         for (int r = 0; r < 16; r += 2) {
-            if (ABL & 1) { X[t][r] = acc[t][r] * 0.5f; X[t][r + 1] = acc[t][r + 1] * 0.5f; }
-            else if (ABL & 16) { X[t][r] = gamd_gelu_hw(acc[t][r]); X[t][r + 1] = gamd_gelu_hw(acc[t][r + 1]); }
-            else {
-                const gelu_f2 y = gelu_pair(gelu_f2{acc[t][r], acc[t][r + 1]}, k);
-                X[t][r] = y[0]; X[t][r + 1] = y[1];
-            }
+            const gelu_f2 y = gelu_pair(gelu_f2{acc[t][r], acc[t][r + 1]}, k);
+            X[t][r] = y[0]; X[t][r + 1] = y[1];
         }
-    if (ABL & 32) __builtin_amdgcn_s_setprio(0);
+    __builtin_amdgcn_s_setprio(0);
 }
 
-template <int NFEAT, int ABL>
+template <int NFEAT>
 __global__ void __launch_bounds__(512, 2) k_edge_encode(EncArgs a) {
     if (a.devflags[DEVFLAG_FROZEN]) return;          // frozen run: nothing to compute until the host has regrown and resumed
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -153,9 +152,10 @@ __global__ void __launch_bounds__(512, 2) k_edge_encode(EncArgs a) {
         const bool valid = x < E;
         const int src = src_c, dst = dst_c;
         float F[24];
-        if (ABL & 128) __builtin_amdgcn_s_setprio(1);
-        edge_features<NFEAT, ABL>(a, cen, src, dst, ps, pd, half, F);
-        if (ABL & 128) { asm volatile("" : "+v"(F[0]), "+v"(F[23])); __builtin_amdgcn_s_setprio(0); }
+        __builtin_amdgcn_s_setprio(1);
+        edge_features<NFEAT>(a, cen, src, dst, ps, pd, half, F);
+        asm volatile("" : "+v"(F[0]), "+v"(F[23]));      // the features are complete before the priority drops
+        __builtin_amdgcn_s_setprio(0);
         if (a.feat_dbg && valid) {
 #pragma unroll
             for (int s = 0; s < 24; ++s) a.feat_dbg[x * 48 + 2 * s + half] = F[s];
@@ -175,11 +175,11 @@ __global__ void __launch_bounds__(512, 2) k_edge_encode(EncArgs a) {
                     if (4 * g + j < KSTEPS) acc[tp] = mfma32(w[j], F[4 * g + j], acc[tp]);
             }
         }
-        gelu_block<ABL>(acc, X, gk);
+        gelu_block(acc, X, gk);
         // ---- GEMM 2 ----
         load_bias_chain(vb2, half, acc);
         gemm128<false>((const f32x4*)w2, lane, X, acc);
-        gelu_block<ABL>(acc, X, gk);
+        gelu_block(acc, X, gk);
         // next tile's positions (its indices were fetched at the top of this iteration); consumed at the top of the next
         // iteration.  Issued HERE and waited for just before the stores of e below: with loads and stores both in flight hipcc
         // can only wait with vmcnt(0), i.e. a wait for these two loads placed behind the stores would sit out the write
@@ -189,9 +189,7 @@ __global__ void __launch_bounds__(512, 2) k_edge_encode(EncArgs a) {
         // ---- GEMM 3 + LayerNorm ----
         load_bias_chain(vb3, half, acc);
         gemm128<false>((const f32x4*)w3, lane, X, acc);
-        if (ABL & 64) __builtin_amdgcn_s_setprio(1);
-        if (!(ABL & 2)) layernorm_chain_centered(acc, vg, vbeta, half, 1e-5f, a.ln_inv_width);     // W3, b3 arrive centred
-        if (ABL & 64) { asm volatile("" : "+v"(acc[0]), "+v"(acc[3])); __builtin_amdgcn_s_setprio(0); }
+        layernorm_chain_centered(acc, vg, vbeta, half, 1e-5f, a.ln_inv_width);     // W3, b3 arrive centred
         if (a.self_loop) {
             // self_loop_mode 1: the last edge of every row is the loop an in-place add_self_loop would have appended AFTER
             // edata['e'] was set (nn_module.py:649-652): its embedding is DGL's zero fill, not an encoded feature row
@@ -212,7 +210,7 @@ __global__ void __launch_bounds__(512, 2) k_edge_encode(EncArgs a) {
                 f32x4 v;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) v[j] = acc[t][q * 4 + j];
-                if (!(ABL & 4) || v[0] == 123.456f) out[(t * 4 + q) * 64 + lane] = v;
+                out[(t * 4 + q) * 64 + lane] = v;
             }
     }
 }
@@ -247,7 +245,7 @@ __global__ void __launch_bounds__(256) k_edge_encode_small(EncArgs a) {
         WQuarter wa, wb;
         load_wquarter(a.w2p, quarter, lane, wa);
         float F[24];
-        edge_features<NFEAT, 0>(a, a.centers, src, dst, ps, pd, half, F);
+        edge_features<NFEAT>(a, a.centers, src, dst, ps, pd, half, F);
         if (a.feat_dbg && valid && quarter == 0) {
 #pragma unroll
             for (int s = 0; s < 24; ++s) a.feat_dbg[x * 48 + 2 * s + half] = F[s];
@@ -305,43 +303,13 @@ int launch_edge_encode_small(const EncArgs& a, int n_blocks, hipStream_t st) {
     return 0;
 }
 
-template <int ABL>
-static int launch_abl(const EncArgs& a, int n_blocks, hipStream_t st) {
+int launch_edge_encode(const EncArgs& a, int n_blocks, hipStream_t st) {
     const size_t lds = sizeof(float) * ENC_LDS_FLOATS;
     static PerDeviceOnce once;
-    if (int e = gamd_allow_dynamic_lds(once, (int)lds, k_edge_encode<44, ABL>, k_edge_encode<45, ABL>)) return e;
-    if (a.n_feat == 44) hipLaunchKernelGGL((k_edge_encode<44, ABL>), dim3(n_blocks), dim3(512), lds, st, a);
-    else if (a.n_feat == 45) hipLaunchKernelGGL((k_edge_encode<45, ABL>), dim3(n_blocks), dim3(512), lds, st, a);
+    if (int e = gamd_allow_dynamic_lds(once, (int)lds, k_edge_encode<44>, k_edge_encode<45>)) return e;
+    if (a.n_feat == 44) hipLaunchKernelGGL((k_edge_encode<44>), dim3(n_blocks), dim3(512), lds, st, a);
+    else if (a.n_feat == 45) hipLaunchKernelGGL((k_edge_encode<45>), dim3(n_blocks), dim3(512), lds, st, a);
     else return -22;
     GAMD_CHECK_LAUNCH();
     return 0;
-}
-
-// Production: the GELU blocks and the feature construction (the dense vector stretches of a tile) at s_setprio 1.  The two waves
-// of a SIMD share its vector issue; a wave inside such a stretch that keeps losing issue slots to its partner's scattered
-// vector instructions finishes later and delays the partner's next stretch as well (found on k_conv_edge_bf16's SiLU blocks,
-// round 6).  Same-box at C2: 418 -> 396 us, 0.74 -> 0.78 of the fp32 matrix peak, bit-identical e; LayerNorm at priority as
-// well: 408 (not kept).  GAMD_ENC_VARIANT=0 (profiling build) is the round-5 kernel for the A/B.
-constexpr int ENC_PRODUCTION = 32 | 128;
-int launch_edge_encode(const EncArgs& a, int n_blocks, hipStream_t st) {
-#ifdef GAMD_PROFILING
-    // timing ablations (wrong results by construction): compiled into libgamd_hip_prof.so only
-    static int v = -1;
-    if (v < 0) { const char* s = getenv("GAMD_ENC_VARIANT"); v = s ? atoi(s) : ENC_PRODUCTION; }
-    switch (v) {
-        case 0: return launch_abl<0>(a, n_blocks, st);
-        case 1: return launch_abl<1>(a, n_blocks, st);
-        case 2: return launch_abl<2>(a, n_blocks, st);
-        case 4: return launch_abl<4>(a, n_blocks, st);
-        case 8: return launch_abl<8>(a, n_blocks, st);
-        case 15: return launch_abl<15>(a, n_blocks, st);
-        case 16: return launch_abl<16>(a, n_blocks, st);      // scalar GELU (round-2 form; same bits)
-        case 32: return launch_abl<32>(a, n_blocks, st);      // GELU blocks at s_setprio 1 (same bits)
-        case 96: return launch_abl<96>(a, n_blocks, st);      // + LayerNorm
-        case 160: return launch_abl<160>(a, n_blocks, st);    // GELU + feature construction
-        case 224: return launch_abl<224>(a, n_blocks, st);    // all three
-        default: break;
-    }
-#endif
-    return launch_abl<ENC_PRODUCTION>(a, n_blocks, st);
 }

@@ -1141,8 +1141,8 @@ int32_t gamd_finalize_weights(gamd_handle* h) {
     // node-side matrices: the 128-wide node kernel (node.hip) runs on 16x16x4 MFMAs with its own operand order; the
     // generic-width node kernel of wide.hip keeps the 32x32x2 fragment blocks
     // Reduced-precision edge modes (bf16, split-fp16) on the 128-wide kernels: the node kernel's five GEMMs run in split-fp16 too
-    // (fp32-grade results at 3/16 of the fp32 matrix time, node.hip and wide.hip's k_node_wide); GAMD_NODE_F32=1 keeps them on the fp32 pipe (A/B timing)
-    h->node_f16 = h->cfg.edge_dtype != GAMD_EDGE_F32 && !getenv("GAMD_NODE_F32");
+    // (fp32-grade results at 3/16 of the fp32 matrix time, node.hip and wide.hip's k_node_wide)
+    h->node_f16 = h->cfg.edge_dtype != GAMD_EDGE_F32;
     auto put_node = [&](const HostTensor* t, int OB, int KB) {
         if (h->wide_conv) return h->node_f16 ? put_blocks_f16x3_fn(t, OB, KB) : put_blocks(t, OB, KB);
         size_t o = bb.add(GAMD_WFRAG_FLOATS);

@@ -58,10 +58,10 @@ __device__ __forceinline__ void gemm128_bf16(WPtr W, int lane, const bf16x8 (&P)
 
 // The same GEMM with the weight fragments read D MFMAs ahead through an explicit ring of D x 4 registers.  hipcc's own schedule
 // of gemm128_bf16 is read -> s_waitcnt -> MFMA with one or two fragments in flight, so every 32-cycle MFMA sits out most of an
-// LDS round trip: 97 cycles per MFMA measured in k_conv_edge_bf16 (tools/bf16_variants.py: the kernel without its MFMAs took
-// 17 us, with them 49 us, for 10 us of matrix time).  Scheduling barriers in front of and behind the GEMM keep other memory
-// instructions out of it, sched_group_barrier pins the pattern (one LDS read, one MFMA) inside; the waits are hipcc's own
-// counted lgkmcnt (LDS reads return in order), so they stay correct whatever else is in flight.
+// LDS round trip: 97 cycles per MFMA measured in k_conv_edge_bf16 (timing ablations, profiles/r04_bf16_experiments.md: the
+// kernel without its MFMAs took 17 us, with them 49 us, for 10 us of matrix time).  Scheduling barriers in front of and behind
+// the GEMM keep other memory instructions out of it, sched_group_barrier pins the pattern (one LDS read, one MFMA) inside; the
+// waits are hipcc's own counted lgkmcnt (LDS reads return in order), so they stay correct whatever else is in flight.
 template <bool F2, int D>
 __device__ __forceinline__ void gemm128_bf16_pf(const bf16x8* W, int lane, const bf16x8 (&P)[4][2], f32x16 (&acc)[4]) {
     // MFMA i = (t, u, tp) with tp fastest: four independent accumulators rotate; its fragment sits at ((tp*4 + t)*2 + u) * 64

@@ -83,8 +83,8 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 // error is multiplied by in the result).  |fit error| <= 1.1e-7 in |x| Phi(-|x|); evaluated in fp32 the result is within
 // 0.95 (half-ulp + 1.2e-7) of the exact erf-GELU (nn.GELU(), nn_module.py:41-42) on [-8, 8] — closer than the Abramowitz &
 // Stegun 7.1.26 erfc form used in round 1 (1.8) — with 11 VALU instructions (one v_exp_f32) instead of 17 (v_exp_f32 +
-// v_rcp_f32): measured 465 -> 432 us on k_edge_encode at C2 (tools/enc_variants.py; a packed v_pk_fma_f32 Horner chain
-// was slower than the scalar one).  Beyond |x| = 6 the tail is below 1e-9: the argument is
+// v_rcp_f32): measured 465 -> 432 us on k_edge_encode at C2 (profiles/r02_raw/enc_variants_gelu2.log; a packed
+// v_pk_fma_f32 Horner chain was slower than the scalar one).  Beyond |x| = 6 the tail is below 1e-9: the argument is
 // clamped there (one v_min with the |.| source modifier), which also keeps the fit's positive leading coefficient harmless.
 #define GAMD_GELU_Q0 -9.999880791e-01f
 #define GAMD_GELU_Q1 -1.151242852e+00f
@@ -192,14 +192,8 @@ __device__ __forceinline__ float gamd_min_image_wrapped(float d, float L, float 
 // atom) next to gathers of node-table rows (hn, S: 1 KB per atom) that are re-used by the ~60 edges of each neighbour.  Loaded
 // with the non-temporal hint (global_load ... nt) the stream does not push the rows out of the XCD's 4 MiB L2: measured where
 // the tables no longer fit (10^5 - 10^6 atoms, profiles/r05_gather_hbm.md); at the BASELINE sizes everything is L2-resident
-// either way.  -DGAMD_E_TEMPORAL builds the plain loads for the A/B.
-__device__ __forceinline__ f32x4 gamd_load_stream(const f32x4* p) {
-#ifdef GAMD_E_TEMPORAL
-    return *p;
-#else
-    return __builtin_nontemporal_load(p);
-#endif
-}
+// either way.
+__device__ __forceinline__ f32x4 gamd_load_stream(const f32x4* p) { return __builtin_nontemporal_load(p); }
 
 // Message of one edge folded into the running sum of its partial-sum piece (nn_module.py:142, u_mul_e -> sum): a single fused
 // multiply-add, i.e. hn[src] * e_emb is not rounded before it is added (the reference multiplies and adds separately; the

@@ -28,7 +28,6 @@
 // (pack16 in gamd_api.hip):  Wp[((ob * 8 + blk) * 64 + lane)][r] = W[16 ob + (lane & 15)][16 blk + 4 (lane >> 4) + r].
 #include "gamd_common.h"
 #include "gamd_internal.h"
-#include <cstdlib>
 
 namespace {
 
@@ -64,8 +63,7 @@ __device__ __forceinline__ void load_whalf(const float* __restrict__ Wp, int w, 
 
 // acc[o] (features 16 (2 w + o) + 4 g + r of atom a) += W[quarter w][:, K half] * X^T; the two row blocks alternate so that
 // the two dependent accumulator chains (40-cycle latency, 32-cycle issue) keep the pipe full
-__device__ __forceinline__ void gemm16_half(const WHalf& h, int half, const f32x4 (&XB)[8], f32x4 (&acc)[2], bool skip = false) {
-    if (skip) { asm volatile("" ::"v"(h.w[0]), "v"(h.w[7]), "v"(XB[0])); return; }
+__device__ __forceinline__ void gemm16_half(const WHalf& h, int half, const f32x4 (&XB)[8], f32x4 (&acc)[2]) {
 #pragma unroll
     for (int b = 0; b < 4; ++b)
 #pragma unroll
@@ -96,8 +94,7 @@ __device__ __forceinline__ void split16(const f32x4 (&XB)[8], XSplit& s) {
             s.l[m][j] = lo[0]; s.l[m][j + 1] = lo[1];
         }
 }
-__device__ __forceinline__ void gemm16_half_f16(const WHalf& h, int half, const XSplit& X, f32x4 (&acc)[2], bool skip = false) {
-    if (skip) { asm volatile("" ::"v"(h.w[0]), "v"(h.w[7]), "v"(X.h[0])); return; }
+__device__ __forceinline__ void gemm16_half_f16(const WHalf& h, int half, const XSplit& X, f32x4 (&acc)[2]) {
 #pragma unroll
     for (int mm = 0; mm < 2; ++mm) {
         const int m = 2 * half + mm;
@@ -115,13 +112,13 @@ __device__ __forceinline__ void gemm16_half_f16(const WHalf& h, int half, const 
 // first half of `next` (the matrix of the GEMM that follows; NEXT = false: none).  The compiler barriers pin the fetches
 // where they are written: hipcc otherwise hoists every load to the top of the kernel and pays with 50 more registers.
 // (The (hi | lo) fp16 image of a matrix has the size and the quarter / half structure of the fp32 one: same fetches.)
-template <bool NEXT, bool SKIP, bool F16, typename XT>
+template <bool NEXT, bool F16, typename XT>
 __device__ __forceinline__ void gemm16(const float* W, const float* next, WHalf& wn, const XT& XB, f32x4 (&acc)[2], int w, int lane) {
     WHalf cur = wn;
     asm volatile("" ::: "memory");
     load_whalf(W, w, lane, 1, wn);                          // second half: lands during the first half's 32 MFMAs
     asm volatile("" ::: "memory");
-    if constexpr (F16) gemm16_half_f16(cur, 0, XB, acc, SKIP); else gemm16_half(cur, 0, XB, acc, SKIP);
+    if constexpr (F16) gemm16_half_f16(cur, 0, XB, acc); else gemm16_half(cur, 0, XB, acc);
     __builtin_amdgcn_sched_barrier(0);
     cur = wn;
     if (NEXT) {
@@ -129,7 +126,7 @@ __device__ __forceinline__ void gemm16(const float* W, const float* next, WHalf&
         load_whalf(next, w, lane, 0, wn);                   // next GEMM's first half: lands during the second half + exchange
         asm volatile("" ::: "memory");
     }
-    if constexpr (F16) gemm16_half_f16(cur, 1, XB, acc, SKIP); else gemm16_half(cur, 1, XB, acc, SKIP);
+    if constexpr (F16) gemm16_half_f16(cur, 1, XB, acc); else gemm16_half(cur, 1, XB, acc);
     __builtin_amdgcn_sched_barrier(0);
 }
 
@@ -174,10 +171,8 @@ __device__ __forceinline__ float group_sum(float v) {
     return v + __shfl_xor(v, 32, 64);
 }
 
-// NABL (profiling build only, GAMD_NODE_VARIANT; wrong results): 1 = no piece loads (agg = 0: the bound of letting the conv kernels
-// write agg), 2 = every weight fragment from one cache-hot kilobyte (the bound of any better weight prefetch), 4 = no GEMMs
 // F16: the five GEMMs in split-fp16 (the reduced-precision edge modes; weights packed by pack16_f16x3)
-template <int NABL, bool F16 = false>
+template <bool F16>
 __global__ void __launch_bounds__(256, 3) k_node(NodeArgs a) {
     __shared__ __attribute__((aligned(16))) float xbuf[NT * XLD];
     __shared__ float obuf[4][NT][3];
@@ -201,14 +196,10 @@ __global__ void __launch_bounds__(256, 3) k_node(NodeArgs a) {
 #define NMARK(I) do { } while (0)
 #endif
     NMARK(0);                                                      // 0: start
-    if (NABL & 2) {       // one hot kilobyte for every weight fragment
-        const float* hot = a.pre.wsp;
-        a.post.wpep = a.post.wphip = a.pre.wsp = a.pre.wdp = a.pre.wpdp = a.dec_w1p = hot;
-    }
     f32x4 XB[8];          // full activation rows (chain16 layout)
     XSplit XS;            // F16: their (hi, lo) fp16 operand images
-#define GEMM16(NEXT, W, NXT) do { if constexpr (F16) gemm16<NEXT, (NABL & 4) != 0, true>(W, NXT, wn, XS, mine, w, lane); \
-                                  else gemm16<NEXT, (NABL & 4) != 0, false>(W, NXT, wn, XB, mine, w, lane); } while (0)
+#define GEMM16(NEXT, W, NXT) do { if constexpr (F16) gemm16<NEXT, true>(W, NXT, wn, XS, mine, w, lane); \
+                                  else gemm16<NEXT, false>(W, NXT, wn, XB, mine, w, lane); } while (0)
 #define SPLIT16() do { if constexpr (F16) split16(XB, XS); } while (0)
     f32x4 mine[2];        // this wave's 32 output features
     WHalf wn;             // the weight half that the next 32 MFMAs need (fetched one half ahead)
@@ -240,7 +231,7 @@ __global__ void __launch_bounds__(256, 3) k_node(NodeArgs a) {
         f32x4 p_in[2], h_res[2];
         load16(a.P_in + row, w, g, p_in);                          // in flight during the aggregation
         // pieces are fetched in batches of 8 (one memory round trip for the usual 4-6 pieces per atom), summed in piece order
-        for (int k0 = 0; !(NABL & 1) && __any(k0 < np); k0 += 8) {
+        for (int k0 = 0; __any(k0 < np); k0 += 8) {
             f32x4 pc[8][2];
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
@@ -397,19 +388,8 @@ __global__ void __launch_bounds__(256, 3) k_node(NodeArgs a) {
 
 int launch_node(const NodeArgs& a, hipStream_t st) {
     const int nb = (a.n + NT - 1) / NT;
-#ifdef GAMD_PROFILING
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("GAMD_NODE_VARIANT"); v = e ? atoi(e) : 0; }
-#define NODE_CASE(V) case V: if (a.f16x3) hipLaunchKernelGGL((k_node<V, true>), dim3(nb), dim3(256), 0, st, a); \
-                                 else hipLaunchKernelGGL((k_node<V, false>), dim3(nb), dim3(256), 0, st, a); GAMD_CHECK_LAUNCH(); return 0
-    switch (v) {
-        NODE_CASE(1); NODE_CASE(2); NODE_CASE(3); NODE_CASE(4); NODE_CASE(7);
-        default: break;
-    }
-#undef NODE_CASE
-#endif
-    if (a.f16x3) hipLaunchKernelGGL((k_node<0, true>), dim3(nb), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((k_node<0, false>), dim3(nb), dim3(256), 0, st, a);
+    if (a.f16x3) hipLaunchKernelGGL((k_node<true>), dim3(nb), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((k_node<false>), dim3(nb), dim3(256), 0, st, a);
     GAMD_CHECK_LAUNCH();
     return 0;
 }

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""s_memtime breakdown of k_conv_edge_bf16 at C5 (profiling build, ABL bit 64): where a wave's time goes inside a tile.
+"""s_memtime breakdown of k_conv_edge_bf16 at C5 (profiling build, GAMD_BF16_TIME=1): where a wave's time goes inside a tile.
 s_memtime ticks are not core cycles on this part: read the columns as proportions.
-    GAMD_LIB=gamd_amd/libgamd_hip_prof.so GAMD_BF16_VARIANT=64 python tools/bf16_marks.py"""
+    GAMD_LIB=gamd_amd/libgamd_hip_prof.so GAMD_BF16_TIME=1 python tools/bf16_marks.py"""
 import os
 import sys
 

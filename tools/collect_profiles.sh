@@ -17,8 +17,7 @@ cp $src/pmc_conv_edge.json $dst/pmc_conv_edge.json
 if [ -f $src/gather_hbm.json ]; then cp $src/gather_hbm.json $dst/gather_hbm.json; cp $src/gather_summary.md $dst/${name}_gather_summary.md; fi
 raw=$dst/${name%%_*}_raw
 mkdir -p $raw
-cp $src/conv_variants_sched.log $raw/${name}_conv_variants_sched.log
-cp $src/conv_variants_cycles.log $raw/${name}_conv_variants_cycles.log
+cp $src/conv_marks.log $raw/${name}_conv_marks.log
 cp $src/f16x3_marks.log $raw/${name}_f16x3_marks.log
-for f in node_variants.log node_marks_c5.log node_marks_c1.log node_marks_10000.log bf16_variants_c5.log bf16_marks.log enc_variants.log bf16_overlap_probe.log mfma_korder_probe.log c5_error.log; do [ -f $src/$f ] && cp $src/$f $raw/${name}_$f; done
+for f in node_marks_c5.log node_marks_c1.log node_marks_10000.log bf16_marks.log bf16_overlap_probe.log mfma_korder_probe.log c5_error.log; do [ -f $src/$f ] && cp $src/$f $raw/${name}_$f; done
 true
