@@ -35,6 +35,14 @@
 // order, by the node kernel -> no atomics, bit-reproducible.
 //
 // Roofline: MFMA-bound.  8*128*128 = 131072 FLOP per edge per launch against ~1.6 KB of traffic.
+//
+// Layer-0 form (L0, LJ models only: every atom enters layer 0 with the same row hn0, so S[src] = S0, D[dst] = D0 and
+// hn[src] = hn0 for every edge): the message is hn0 * (W4 T3 + b4), and phi_edge of its per-atom sum is
+// M0 sum_j T3_j + d_i c0 with M0 = W_pe diag(hn0) W4, c0 = W_pe (hn0 * b4) (gamd_finalize_weights).  The kernel runs
+// three GEMMs per tile instead of four (6*128*128 = 98304 FLOP per edge), the third in the F2 orientation with the segment
+// sum of SiLU(W3 T2 + b3) over the REAL edges as its post-op, and the node kernel applies M0 and d_i c0 (node.hip).  S0 /
+// D0 are row 0 of the layer's S / D tables; their sum is phase 2's accumulator start (wide.hip's order: (S + D), then the
+// GEMM), kept in LDS.  Nothing is gathered per edge.
 #include "gamd_common.h"
 #include "gamd_internal.h"
 
@@ -42,7 +50,8 @@
 
 namespace {
 
-constexpr int CONV_LDS_FLOATS = 2 * GAMD_WFRAG_FLOATS + 3 * 128;
+// two 64 KiB weight slots and b1, b3, b4 (L0: b1, b3, S0 + D0)
+constexpr int conv_lds_floats(bool l0) { return 2 * GAMD_WFRAG_FLOATS + 3 * 128; }
 
 // 128x128 GEMM of the chain with a software-pipelined element-wise post-op: while output tile tp is being accumulated (64
 // MFMAs in 16 groups of 4), post(tp-1, g) finishes element g of the previous, already complete, output tile.  Only tile 3's
@@ -107,15 +116,19 @@ __device__ __forceinline__ void load_e_tile(const float* __restrict__ e_frag, in
 //   * the weight copy of the phase after next is issued by every wave 64 MFMAs into its GEMM, behind the gathers.
 // (Other schedules that were measured and dropped are recorded in profiles/r02_ / r03_conv_edge_experiments.md.)
 // TIME (profiling build only, GAMD_CONV_TIME): per-segment s_memtime counters -> a.tdbg.
-template <bool TIME>
+// L0: the layer-0 form of LJ models (see the top of the file; a.b3 and a.w3p are then packed in the F2 output order).
+template <bool TIME, bool L0>
 __global__ void __launch_bounds__(512, 2) k_conv_edge(ConvEdgeArgs a) {
     if (a.devflags[DEVFLAG_FROZEN]) return;          // frozen run: nothing to compute until the host has regrown and resumed
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    float* buf0 = lds;
-    float* buf1 = lds + GAMD_WFRAG_FLOATS;
-    float* vb1 = buf1 + GAMD_WFRAG_FLOATS;
+    // L0: the three vectors (b1, b3, S0 + D0) in front of the weight slots, where every lane's address of them is one register
+    // + an immediate offset (behind 128 KiB each needs registers of its own)
+    float* buf0 = lds + (L0 ? 3 * 128 : 0);
+    float* buf1 = buf0 + GAMD_WFRAG_FLOATS;
+    float* vb1 = L0 ? lds : buf1 + GAMD_WFRAG_FLOATS;
     float* vb3 = vb1 + 128;
     float* vb4 = vb3 + 128;
+    float* vSD0 = vb4;                // L0: no W4, its slot holds S0 + D0
 
     const int tid = threadIdx.x, lane = tid & 63, slot = lane & 31, half = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -146,7 +159,11 @@ __global__ void __launch_bounds__(512, 2) k_conv_edge(ConvEdgeArgs a) {
     long long tprev = 0;
 #define TMARK(i) do { if (TIME) { const long long tn__ = (long long)__builtin_readcyclecounter(); tacc[i] += tn__ - tprev; tprev = tn__; } } while (0)
 
-    if (tid < 128) { vb1[tid] = a.b1[tid]; vb3[tid] = a.b3[tid]; vb4[tid] = a.b4[tid]; }
+    if (tid < 128) {
+        vb1[tid] = a.b1[tid]; vb3[tid] = a.b3[tid];
+        if (L0) vSD0[tid] = a.S[tid] + a.D[tid];
+        else vb4[tid] = a.b4[tid];
+    }
     stage(a.w1p, buf0);
 
     // three 64-register sets rotate through the roles {GEMM input, GEMM output, prefetched gather}
@@ -167,8 +184,10 @@ __global__ void __launch_bounds__(512, 2) k_conv_edge(ConvEdgeArgs a) {
     int src = 0, dst = 0;
     {
         const int x = tile * GAMD_TILE + gamd_pi(slot);
-        if (active && x < E) { src = GAMD_CHK_RANGE(a.sticky, a.col[x], 0, a.zero_row, GAMD_CHK_CONV_SRC); dst = GAMD_CHK_RANGE(a.sticky, a.erow[x], 0, a.zero_row, GAMD_CHK_CONV_DST); }
-        else { src = a.zero_row; dst = a.zero_row; }
+        if (active && x < E) {
+            src = GAMD_CHK_RANGE(a.sticky, a.col[x], 0, a.zero_row, GAMD_CHK_CONV_SRC);
+            if (!L0) dst = GAMD_CHK_RANGE(a.sticky, a.erow[x], 0, a.zero_row, GAMD_CHK_CONV_DST);
+        } else { src = a.zero_row; dst = a.zero_row; }
         if (active) load_e_tile(a.e_frag, tile, lane, RA);
     }
     asm volatile("" ::"v"(src), "v"(dst));      // compiler-visible wait for the index loads (see phase 4)
@@ -236,6 +255,98 @@ __global__ void __launch_bounds__(512, 2) k_conv_edge(ConvEdgeArgs a) {
     // owe their share of the weight copy (the `else` branches below)
 #define FENCE() __builtin_amdgcn_sched_barrier(0)
 
+    if constexpr (L0) {
+    // Layer-0 form: three phases per tile, three matrices through the two LDS slots, so the slot parity flips every tile
+    // (W1 -> x, W2 -> y, W3 -> x, next tile's W1 -> y).  Registers: RA = e, then T2; RB = T1; RC = the pieces of the previous
+    // tile until phase 1's mid(), then this tile's pieces.  The only per-edge loads are e and the 4-byte indices.
+    for (int it = 0; it < n_iter; ++it) {
+        const int x0 = tile * GAMD_TILE + 16 * half;
+        int nvalid = E - x0;
+        nvalid = !active ? 0 : (nvalid >= 16 ? 16 : (nvalid <= 0 ? 0 : nvalid));
+        const int tile_n = tile_of(it + 1);
+        const bool active_n = tile_n < n_tiles;
+        int src_n = a.zero_row;
+        float* const bx = (it & 1) ? buf1 : buf0;              // W1, then W3
+        float* const by = (it & 1) ? buf0 : buf1;              // W2, then the next tile's W1
+
+        // ===== phase 1: RB = SiLU(W1 e + b1)        in RA = e, RC = pieces of the previous tile =====
+        if (active) {
+            load_bias_chain(vb1, half, RB);
+            TMARK(0);
+            gemm128_post<false>((const f32x4*)bx, lane, RA, RB,
+                                [&](int tp, int g) { RB[tp][g] = gamd_silu_hw(RB[tp][g]); },
+                                [&]() { FENCE(); piece_stores(); stage(a.w2p, by); FENCE(); });
+            TMARK(1);
+        } else {
+            piece_stores();
+            stage(a.w2p, by);
+        }
+        // boundary 1: piece stores and the copy of W2 have landed (nothing younger is issued)
+        phase_barrier<0>();
+        TMARK(2);
+        // ===== phase 2: RA = SiLU(W2 T1 + (S0 + D0))        in RB =====
+        unsigned mask = 0;
+        int p0 = 0;
+        // accumulator start first (fenced: LDS reads behind the index loads would make hipcc wait for them), then the index
+        // loads for phase 3 / the next tile: done long before boundary 2 needs vmcnt(0)
+        if (active) { load_bias_chain(vSD0, half, RA); FENCE(); }
+        if (active) {
+            mask = a.chunk_mask[tile * 2 + half];
+            p0 = GAMD_CHK_RANGE(a.sticky, a.chunk_piece[tile * 2 + half], 0, a.piece_cap - 17, GAMD_CHK_PIECE);
+        }
+        if (active_n) {
+            const int xn = tile_n * GAMD_TILE + gamd_pi(slot);
+            if (xn < E) src_n = GAMD_CHK_RANGE(a.sticky, a.col[xn], 0, a.zero_row, GAMD_CHK_CONV_SRC);
+        }
+        if (active) {
+            gemm128_post<false>((const f32x4*)by, lane, RB, RA,
+                                [&](int tp, int g) { RA[tp][g] = gamd_silu_hw(RA[tp][g]); },
+                                [&]() { FENCE(); stage(a.w3p, bx); FENCE(); });
+            TMARK(4);
+        } else {
+            stage(a.w3p, bx);
+        }
+        // boundary 2: the index loads and the copy of W3 have landed
+        phase_barrier<0>();
+        // (the compiler cannot see the wait written in assembly: naming the registers makes it emit its own here, where it
+        // costs nothing, instead of in front of the piece-store loop or the next tile's ballot)
+        asm volatile("" ::"v"(mask), "v"(p0), "v"(src_n));
+        TMARK(5);
+        // ===== phase 3: RC = T2 W3^T + b3 (F2: 16 edges x 4 features per lane), SiLU, segment sum over the real edges =====
+        if (active) {
+            // Padding slots -- the tail of the last tile, a box's padding in a batch -- have src == zero_row.  Nothing
+            // multiplies them by hn[zero_row] = 0 any more: they start from GAMD_L0_PAD instead of b3 (F2 row r = CSR edge
+            // x0 + r, whose index sits in chain lane rho(r, half) = (r & 3) + 8 (r >> 2) + 4 half) and add exactly -0.
+            const unsigned bl = (unsigned)__ballot(src != a.zero_row) >> (4 * half);
+            const unsigned real = (bl & 0xFu) | ((bl >> 4) & 0xF0u) | ((bl >> 8) & 0xF00u) | ((bl >> 12) & 0xF000u);
+#pragma unroll
+            for (int tp = 0; tp < 4; ++tp) {
+                const float b = vb3[32 * tp + slot];
+#pragma unroll
+                for (int r = 0; r < 16; ++r) RC[tp][r] = ((real >> r) & 1u) ? b : GAMD_L0_PAD;
+            }
+            TMARK(7);
+            const unsigned keep_bits = ~(mask << 1);          // bit r set: edge r continues edge r-1's piece
+            gemm128_post<true>((const f32x4*)bx, lane, RA, RC, [&](int tp, int r) {
+                RC[tp][r] = gamd_l0_acc(RC[tp][r], (r > 0 && ((keep_bits >> r) & 1u)) ? RC[tp][r - 1] : 0.f);
+            }, [&]() { FENCE(); if (it + 1 < n_iter) stage(a.w1p, by); FENCE(); });
+            pend_ends = mask;
+            if (nvalid > 0 && !((mask >> (nvalid - 1)) & 1u)) pend_ends |= 1u << (nvalid - 1);
+            pend_p = p0;
+            TMARK(10);
+        } else {
+            if (it + 1 < n_iter) stage(a.w1p, by);
+        }
+        // boundary 3: the next tile's e -> RA.  Younger than the copy of W1: e (early waves)
+        if (!early) phase_barrier<0>();
+        TMARK(11);
+        if (active_n) load_e_tile(a.e_frag, tile_n, lane, RA);
+        TMARK(12);
+        if (early) early_barrier(active_n);
+        TMARK(13);
+        tile = tile_n; active = active_n; src = src_n;
+    }
+    } else {
     for (int it = 0; it < n_iter; ++it) {
         const int x0 = tile * GAMD_TILE + 16 * half;            // this half's 16 CSR edges: x0 + r
         int nvalid = E - x0;
@@ -342,6 +453,7 @@ __global__ void __launch_bounds__(512, 2) k_conv_edge(ConvEdgeArgs a) {
         TMARK(13);
         tile = tile_n; active = active_n; src = src_n; dst = dst_n;
     }
+    }
 #undef FENCE
     piece_stores();            // the last tile's pieces
     if (TIME && a.tdbg && lane == 0) {
@@ -351,12 +463,12 @@ __global__ void __launch_bounds__(512, 2) k_conv_edge(ConvEdgeArgs a) {
 #undef TMARK
 }
 
-template <bool TIME>
+template <bool TIME, bool L0>
 int launch(const ConvEdgeArgs& a, int n_blocks, hipStream_t st) {
-    const size_t lds = sizeof(float) * CONV_LDS_FLOATS;
+    const size_t lds = sizeof(float) * conv_lds_floats(L0);
     static PerDeviceOnce once;
-    if (int e = gamd_allow_dynamic_lds(once, (int)lds, k_conv_edge<TIME>)) return e;
-    hipLaunchKernelGGL(k_conv_edge<TIME>, dim3(n_blocks), dim3(512), lds, st, a);
+    if (int e = gamd_allow_dynamic_lds(once, (int)lds, k_conv_edge<TIME, L0>)) return e;
+    hipLaunchKernelGGL((k_conv_edge<TIME, L0>), dim3(n_blocks), dim3(512), lds, st, a);
     GAMD_CHECK_LAUNCH();
     return 0;
 }
@@ -366,7 +478,15 @@ int launch(const ConvEdgeArgs& a, int n_blocks, hipStream_t st) {
 int launch_conv_edge(const ConvEdgeArgs& a, int n_blocks, hipStream_t st) {
 #ifdef GAMD_PROFILING
     static const bool timed = getenv("GAMD_CONV_TIME") != nullptr;
-    if (timed) return launch<true>(a, n_blocks, st);
+    if (timed) return launch<true, false>(a, n_blocks, st);
 #endif
-    return launch<false>(a, n_blocks, st);
+    return launch<false, false>(a, n_blocks, st);
+}
+
+int launch_conv_edge_l0(const ConvEdgeArgs& a, int n_blocks, hipStream_t st) {
+#ifdef GAMD_PROFILING
+    static const bool timed = getenv("GAMD_CONV_TIME") != nullptr;
+    if (timed) return launch<true, true>(a, n_blocks, st);
+#endif
+    return launch<false, true>(a, n_blocks, st);
 }

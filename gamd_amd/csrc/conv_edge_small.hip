@@ -19,7 +19,9 @@ constexpr int XLD = GAMD_XLD;
 // EHT, HT: edge-embedding / node width in 128-blocks (wide.hip); the weight blocks W1[:, kb] | W2 | W3 | W4[ob, :] are
 // contiguous from a.w1p (gamd_finalize_weights lays them out that way for every width).  WIDE selects the operation
 // order of wide.hip's phase 2 ((S + D) first, then the GEMM) instead of conv_edge.hip's (D, GEMM, + S).
-template <int EHT, int HT, bool WIDE>
+// L0: conv_edge.hip's layer-0 form (LJ models): S0 / D0 = row 0 of a.S / a.D (phase 2 in the WIDE order), phase 3 in the F2
+// orientation on a.w3p (packed in that order) with the segment sum of SiLU over the real edges, no phase 4.
+template <int EHT, int HT, bool WIDE, bool L0>
 __global__ void __launch_bounds__(256) k_conv_edge_small(ConvEdgeArgs a) {
     if (a.devflags[DEVFLAG_FROZEN]) return;          // frozen run: nothing to compute until the host has regrown and resumed
     constexpr int H = 128 * HT;
@@ -37,7 +39,7 @@ __global__ void __launch_bounds__(256) k_conv_edge_small(ConvEdgeArgs a) {
         const int x = tile * GAMD_TILE + gamd_pi(slot);
         const bool valid = x < E;
         const int src = valid ? GAMD_CHK_RANGE(a.sticky, a.col[x], 0, a.zero_row, GAMD_CHK_CONV_SRC) : 0;
-        const int dst = valid ? GAMD_CHK_RANGE(a.sticky, a.erow[x], 0, a.zero_row, GAMD_CHK_CONV_DST) : 0;
+        const int dst = (valid && !L0) ? GAMD_CHK_RANGE(a.sticky, a.erow[x], 0, a.zero_row, GAMD_CHK_CONV_DST) : 0;
         f32x16 X[4], XE[EHT][4], acc;
         WQuarter wa, wb;
         const float* wblk = a.w1p;                       // block k at wblk + k * GAMD_WFRAG_FLOATS
@@ -55,15 +57,17 @@ __global__ void __launch_bounds__(256) k_conv_edge_small(ConvEdgeArgs a) {
                 }
         }
         // rows this wave needs later: its quarter of S[src], D[dst]; hn[src] of its 16 edges x its 32 features
-        const f32x16 s_q = load_slice(a.S + (size_t)src * 128, quarter, half);
-        const f32x16 d_q = load_slice(a.D + (size_t)dst * 128, quarter, half);
+        const f32x16 s_q = load_slice(a.S + (L0 ? 0 : (size_t)src * 128), quarter, half);
+        const f32x16 d_q = load_slice(a.D + (L0 ? 0 : (size_t)dst * 128), quarter, half);
         f32x16 hn_q[HT];
+        if (!L0) {
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int rho = (r & 3) + 8 * (r >> 2) + 4 * half;
-            const int s = __shfl(src, rho, 64);
+            for (int r = 0; r < 16; ++r) {
+                const int rho = (r & 3) + 8 * (r >> 2) + 4 * half;
+                const int s = __shfl(src, rho, 64);
 #pragma unroll
-            for (int ob = 0; ob < HT; ++ob) hn_q[ob][r] = a.hn[(size_t)s * H + feat4(ob)];
+                for (int ob = 0; ob < HT; ++ob) hn_q[ob][r] = a.hn[(size_t)s * H + feat4(ob)];
+            }
         }
         const unsigned mask = a.chunk_mask[tile * 2 + half];
         const int p0 = GAMD_CHK_RANGE(a.sticky, a.chunk_piece[tile * 2 + half], 0, a.piece_cap - 17, GAMD_CHK_PIECE);
@@ -88,12 +92,39 @@ __global__ void __launch_bounds__(256) k_conv_edge_small(ConvEdgeArgs a) {
         WQuarter& w2 = (B2 & 1) ? wb : wa;
         WQuarter& w3 = (B2 & 1) ? wa : wb;
         // phase 2: conv_edge.hip: T3 = SiLU((D[dst] + W2 T1) + S[src]);  wide.hip: T3 = SiLU((S + D) + W2 T1)
-        if (WIDE) acc = s_q + d_q; else acc = d_q;
-        load_wquarter(wblk + (size_t)(B2 + 1) * GAMD_WFRAG_FLOATS, quarter, lane, w3);
+        if (WIDE || L0) acc = s_q + d_q; else acc = d_q;                 // (L0: conv_edge.hip's layer-0 form, (S0 + D0) first)
+        load_wquarter(L0 ? a.w3p : wblk + (size_t)(B2 + 1) * GAMD_WFRAG_FLOATS, quarter, lane, w3);
         gemm_quarter<false>(w2, X, acc);
 #pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = gamd_silu_hw(WIDE ? acc[r] : acc[r] + s_q[r]);
+        for (int r = 0; r < 16; ++r) acc[r] = gamd_silu_hw((WIDE || L0) ? acc[r] : acc[r] + s_q[r]);
         exchange(xbuf, quarter, slot, half, acc, X);
+        if constexpr (L0) {
+            // phase 3 (F2, as conv_edge.hip's layer-0 form): running sums of SiLU(W3 T2 + b3) over the real edges of each piece
+            const unsigned bl = (unsigned)__ballot(valid && src != a.zero_row) >> (4 * half);
+            const unsigned real = (bl & 0xFu) | ((bl >> 4) & 0xF0u) | ((bl >> 8) & 0xF00u) | ((bl >> 12) & 0xF000u);
+            const float b = a.b3[32 * quarter + slot];
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[r] = ((real >> r) & 1u) ? b : GAMD_L0_PAD;     // padding slots: see conv_edge.hip
+            gemm_quarter<true>(w3, X, acc);
+            const unsigned keep_bits = ~(mask << 1);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[r] = gamd_l0_acc(acc[r], (r > 0 && ((keep_bits >> r) & 1u)) ? acc[r - 1] : 0.f);
+            unsigned ends = mask;
+            if (nvalid > 0 && !((mask >> (nvalid - 1)) & 1u)) ends |= 1u << (nvalid - 1);
+            int p = p0;
+            while (__any(ends != 0)) {
+                if (ends != 0) {
+                    const int r = __builtin_ctz(ends);
+                    ends &= ends - 1;
+                    float v = acc[0];
+#pragma unroll
+                    for (int k = 1; k < 16; ++k) v = (r == k) ? acc[k] : v;
+                    a.partial[(size_t)p * H + feat4(0)] = v;
+                    ++p;
+                }
+            }
+            continue;
+        }
         // phase 3: T4 = SiLU(W3 T3 + b3)
         acc = load_slice(a.b3, quarter, half);
         load_wquarter(wblk + (size_t)(B2 + 2) * GAMD_WFRAG_FLOATS, quarter, lane, w2);
@@ -142,16 +173,22 @@ __global__ void __launch_bounds__(256) k_conv_edge_small(ConvEdgeArgs a) {
 }  // namespace
 
 int launch_conv_edge_small(const ConvEdgeArgs& a, int n_blocks, hipStream_t st) {
-    hipLaunchKernelGGL((k_conv_edge_small<1, 1, false>), dim3(n_blocks), dim3(256), 0, st, a);
+    hipLaunchKernelGGL((k_conv_edge_small<1, 1, false, false>), dim3(n_blocks), dim3(256), 0, st, a);
+    GAMD_CHECK_LAUNCH();
+    return 0;
+}
+
+int launch_conv_edge_small_l0(const ConvEdgeArgs& a, int n_blocks, hipStream_t st) {
+    hipLaunchKernelGGL((k_conv_edge_small<1, 1, false, true>), dim3(n_blocks), dim3(256), 0, st, a);
     GAMD_CHECK_LAUNCH();
     return 0;
 }
 
 int launch_conv_edge_small_wide(const ConvEdgeArgs& a, int eht, int ht, int n_blocks, hipStream_t st) {
-    if (eht == 1 && ht == 1) hipLaunchKernelGGL((k_conv_edge_small<1, 1, true>), dim3(n_blocks), dim3(256), 0, st, a);
-    else if (eht == 1 && ht == 2) hipLaunchKernelGGL((k_conv_edge_small<1, 2, true>), dim3(n_blocks), dim3(256), 0, st, a);
-    else if (eht == 2 && ht == 1) hipLaunchKernelGGL((k_conv_edge_small<2, 1, true>), dim3(n_blocks), dim3(256), 0, st, a);
-    else if (eht == 2 && ht == 2) hipLaunchKernelGGL((k_conv_edge_small<2, 2, true>), dim3(n_blocks), dim3(256), 0, st, a);
+    if (eht == 1 && ht == 1) hipLaunchKernelGGL((k_conv_edge_small<1, 1, true, false>), dim3(n_blocks), dim3(256), 0, st, a);
+    else if (eht == 1 && ht == 2) hipLaunchKernelGGL((k_conv_edge_small<1, 2, true, false>), dim3(n_blocks), dim3(256), 0, st, a);
+    else if (eht == 2 && ht == 1) hipLaunchKernelGGL((k_conv_edge_small<2, 1, true, false>), dim3(n_blocks), dim3(256), 0, st, a);
+    else if (eht == 2 && ht == 2) hipLaunchKernelGGL((k_conv_edge_small<2, 2, true, false>), dim3(n_blocks), dim3(256), 0, st, a);
     else return -22;
     GAMD_CHECK_LAUNCH();
     return 0;

@@ -87,6 +87,7 @@ struct LayerDev {
     const float *w1p, *w2p, *w3p, *w4p, *b1, *b3, *b4;
     const float *w16p = nullptr;                        // generic-width fp32: the blocks again, packed for wide16.hip
     const float *e_ln_g = nullptr, *e_ln_b = nullptr;   // update_edge_emb: this layer's edge_layer_norm
+    const float *w3p_l0 = nullptr, *b3_l0 = nullptr;    // layer-0 form (gamd_handle::l0_hoist): W3, b3 in the F2 output order
     NodeLayerW node;
 };
 
@@ -137,6 +138,7 @@ struct gamd_handle {
     bool update_edge = false;                    // update_edge_emb=True: conv.<l>.edge_layer_norm keys in the state_dict
     bool node_f16 = false;                       // node.hip's GEMMs in split-fp16 (reduced-precision edge modes, 128-wide kernels)
     bool wide_enc = false, wide_conv = false;    // generic-width kernels of wide.hip
+    bool l0_hoist = false;                       // LJ, fp32, 128-wide: layer 0 in its three-GEMM form (conv_edge.hip, node.hip post(0))
     long long small_tile_limit = 512;            // fp32 path: at most this many 32-edge tiles -> conv_edge_small.hip
     std::map<std::string, HostTensor> host_w;
     bool finalized = false;
@@ -664,6 +666,7 @@ int enqueue_forward(gamd_handle* h, const float* pos_dev, const uint8_t* species
     no.pos_s = h->pos_s.as<float4>();
     no.node_emb = h->node_emb; no.enc_w = h->nenc_w; no.enc_b = h->nenc_b;
     no.row_ptr = h->row_ptr.as<int>(); no.na_excl = h->na_excl.as<int>(); no.deg = h->deg.as<int>();
+    no.col = (h->l0_hoist && h->n_boxes > 1) ? h->col.as<int>() : nullptr;     // post(0) of the layer-0 form: box padding
     no.partial = h->partial.as<float>();
     no.piece_cap = h->piece_cap;
     no.P_in = h->P.as<float>();
@@ -710,6 +713,9 @@ int enqueue_forward(gamd_handle* h, const float* pos_dev, const uint8_t* species
         const LayerDev& ld = h->layers[l];
         ca.w1p = ld.w1p; ca.w2p = ld.w2p; ca.w3p = ld.w3p; ca.w4p = ld.w4p; ca.w16p = ld.w16p;
         ca.b1 = ld.b1; ca.b3 = ld.b3; ca.b4 = ld.b4;
+        // layer-0 form: three GEMMs per edge, phi_edge's part applied per atom by post(0) (timed as conv layer 0 all the same)
+        const bool hoist = l == 0 && h->l0_hoist;
+        if (hoist) { ca.w3p = ld.w3p_l0; ca.b3 = ld.b3_l0; }
         ca.partial = h->partial.as<float>();
         ca.piece_cap = h->piece_cap;
         ca.sticky = h->sticky_dev;
@@ -730,6 +736,7 @@ int enqueue_forward(gamd_handle* h, const float* pos_dev, const uint8_t* species
                                               : launch_conv_edge_wide(ca, h->EHT, h->HT, h->n_cu, st))
             : h->cfg.edge_dtype == GAMD_EDGE_BF16 ? launch_conv_edge_bf16(ca, h->n_cu, st)
             : h->cfg.edge_dtype == GAMD_EDGE_F16X3 ? launch_conv_edge_f16x3(ca, h->n_cu, st)
+            : hoist ? (small_tiles > 0 ? launch_conv_edge_small_l0(ca, small_tiles, st) : launch_conv_edge_l0(ca, h->n_cu, st))
             : small_tiles > 0 ? launch_conv_edge_small(ca, small_tiles, st) : launch_conv_edge(ca, h->n_cu, st);
         if (r) return fail(-1, "conv edge launch failed (%d)", r);
         if ((r = tev_end())) return r;
@@ -911,7 +918,7 @@ int32_t gamd_create(const gamd_config* cfg, gamd_handle** out) {
         return fail(-22, "unknown self_loop_mode %d", cfg->self_loop_mode);
     if (cfg->self_loop_mode != GAMD_SELF_LOOP_DGL07_NOOP && cfg->edge_dtype != GAMD_EDGE_F32)
         return fail(-22, "self_loop_mode 1 is built for the fp32 edge dtype only");
-    if (cfg->kernel_select & ~(GAMD_KSEL_FORCE_GENERIC_WIDTH | GAMD_KSEL_FORCE_HALF_QUANTUM))
+    if (cfg->kernel_select & ~(GAMD_KSEL_FORCE_GENERIC_WIDTH | GAMD_KSEL_FORCE_HALF_QUANTUM | GAMD_KSEL_NO_LAYER0_HOIST))
         return fail(-22, "unknown kernel_select bits 0x%x", cfg->kernel_select);
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
@@ -1100,7 +1107,8 @@ int32_t gamd_finalize_weights(gamd_handle* h) {
     const int64_t Dp = h->Dp, DT = h->DT;                                 // hidden_dim padded to 128-blocks (DT = 2: wide_d.hip)
     const bool expand = !h->cfg.no_expand_edge;
     BlobBuilder bb;
-    struct Off { size_t w1p, w2p, w3p, w4p, w16p = 0, b1, b3, b4, elng = 0, elnb = 0, lng, lnb, wsp, wdp, wpdp, bS, bP, wpep, wphip, bphi; };
+    struct Off { size_t w1p, w2p, w3p, w4p, w16p = 0, b1, b3, b4, elng = 0, elnb = 0, lng, lnb, wsp, wdp, wpdp, bS, bP, wpep, wphip, bphi;
+                 size_t w3p_l0 = 0, b3_l0 = 0, m0 = 0, c0 = 0; };
     std::vector<Off> lo(L);
     // get(name, true shape, padded shape): the tensor as the reference stores it, zero-padded to the kernels' block widths.
     // Padded output rows / input columns are zeros, so padded features are exact zeros through every layer.
@@ -1184,6 +1192,25 @@ int32_t gamd_finalize_weights(gamd_handle* h) {
     // BatchNorm checkpoints carry running statistics next to norm_layers' weight and bias
     const bool norm_bn = h->host_w.count("graph_conv.norm_layers.0.running_mean") != 0;
     h->norm_bn = norm_bn ? 1 : 0;
+    // Layer-0 form (conv_edge.hip): every atom of an LJ model enters layer 0 with the same row node_emb (nn_module.py:681), so
+    // hn0 = norm_layers[0](node_emb) is one row and phi_edge of the aggregated messages is M0 sum_j T3_j + d_i c0.  The fp32
+    // 128-wide kernels only; not for update_edge_emb models (their layers read e_emb) nor under GAMD_KSEL_NO_LAYER0_HOIST.
+    h->l0_hoist = h->cfg.kind == GAMD_KIND_LJ && h->cfg.edge_dtype == GAMD_EDGE_F32 && !h->wide_conv && DT == 1 && !update_edge &&
+                  !(h->cfg.kernel_select & GAMD_KSEL_NO_LAYER0_HOIST);
+    const HostTensor* emb0 = h->l0_hoist ? get("node_emb", {1, Ht}, {1, H}) : nullptr;
+    if (h->l0_hoist && !emb0) return -2;
+    // rows 32 q + s <- rows 4 s + q of a [128][128] matrix and its bias: the F2 output order of the last GEMM of the 128-wide
+    // fp32 / bf16 conv kernels (a lane holds four consecutive features of each edge)
+    auto permute_f2 = [](const HostTensor& w, const HostTensor& b, HostTensor& wo, HostTensor& bo) {
+        wo = w;
+        bo = b;
+        for (int q = 0; q < 4; ++q)
+            for (int s = 0; s < 32; ++s) {
+                std::copy(w.data.begin() + (size_t)(4 * s + q) * 128, w.data.begin() + (size_t)(4 * s + q + 1) * 128,
+                          wo.data.begin() + (size_t)(32 * q + s) * 128);
+                bo.data[32 * q + s] = b.data[4 * s + q];
+            }
+    };
     for (int l = 0; l < L; ++l) {
         const std::string p = "graph_conv.conv." + std::to_string(l);
         // edge_affine = MLP(Eh, hidden_dim, hidden_layer=2): its inner width is MLP's default 128 (nn_module.py:25,95)
@@ -1237,20 +1264,53 @@ int32_t gamd_finalize_weights(gamd_handle* h) {
             sb = scaled(sb, LOG2E); db = scaled(db, LOG2E); ea2b = scaled(ea2b, LOG2E);      // bS = (b_src + b_dst) + b_edge_affine.2
         }
         Off& o = lo[l];
+        if (l == 0 && h->l0_hoist) {
+            // hn0 as k_node mode 0 forms it (LayerNorm over the true width, or the folded eval BatchNorm), then
+            // M0 = W_pe diag(hn0) W4 and c0 = W_pe (hn0 * b4), in double and rounded once; M0 takes phi_edge's place in post(0)
+            std::vector<double> hn0((size_t)H, 0.0);
+            if (norm_bn) {
+                for (int64_t i = 0; i < H; ++i) hn0[i] = (double)emb0->data[i] * ng->data[i] + nb->data[i];
+            } else {
+                double mean = 0.0, var = 0.0;
+                for (int64_t i = 0; i < Ht; ++i) mean += emb0->data[i];
+                mean /= (double)Ht;
+                for (int64_t i = 0; i < Ht; ++i) var += ((double)emb0->data[i] - mean) * ((double)emb0->data[i] - mean);
+                var /= (double)Ht;
+                const double rstd = 1.0 / std::sqrt(var + 1e-5);
+                for (int64_t i = 0; i < Ht; ++i) hn0[i] = ((double)emb0->data[i] - mean) * rstd * ng->data[i] + nb->data[i];
+            }
+            HostTensor m0, c0;
+            m0.shape = {Dp, Dp};
+            m0.data.assign((size_t)(Dp * Dp), 0.f);
+            c0.shape = {Dp};
+            c0.data.assign((size_t)Dp, 0.f);
+            std::vector<double> row((size_t)Dp);
+            for (int64_t r = 0; r < Dp; ++r) {
+                std::fill(row.begin(), row.end(), 0.0);
+                double cr = 0.0;
+                for (int64_t i = 0; i < H; ++i) {
+                    const double a = (double)pew->data[(size_t)(r * H + i)] * hn0[i];
+                    if (a == 0.0) continue;
+                    for (int64_t k = 0; k < Dp; ++k) row[k] += a * t3w->data[(size_t)(i * Dp + k)];
+                    cr += a * t3b->data[i];
+                }
+                for (int64_t k = 0; k < Dp; ++k) m0.data[(size_t)(r * Dp + k)] = (float)row[k];
+                c0.data[r] = (float)cr;
+            }
+            HostTensor w3f, b3f;
+            permute_f2(*t1w, *t1b, w3f, b3f);
+            o.w3p_l0 = put_blocks(&w3f, 1, 1);
+            o.b3_l0 = put_vec(&b3f);
+            o.m0 = put_node(&m0, 1, 1);
+            o.c0 = put_vec(&c0);
+        }
         HostTensor b4_perm;
         // 128-wide fp32 and bf16 kernels (conv_edge.hip, conv_edge_small.hip, conv_edge_bf16.hip): output row 32 q + s of the
         // packed W4 is feature 4 s + q, so a lane of the last GEMM's F2 output holds four CONSECUTIVE features of each edge —
         // hn[src] is gathered and the pieces are stored 16 bytes at a time.  b4 is stored in the same order.
         HostTensor w4_perm;
         auto permute_w4 = [&]() {
-            w4_perm = *t3w;
-            b4_perm = *t3b;
-            for (int q = 0; q < 4; ++q)
-                for (int s = 0; s < 32; ++s) {
-                    std::copy(t3w->data.begin() + (size_t)(4 * s + q) * 128, t3w->data.begin() + (size_t)(4 * s + q + 1) * 128,
-                              w4_perm.data.begin() + (size_t)(32 * q + s) * 128);
-                    b4_perm.data[32 * q + s] = t3b->data[4 * s + q];
-                }
+            permute_f2(*t3w, *t3b, w4_perm, b4_perm);
             t3b = &b4_perm;
         };
         if (bf16_edges) {
@@ -1401,6 +1461,11 @@ int32_t gamd_finalize_weights(gamd_handle* h) {
         d.node.wsp = B + o.wsp; d.node.wdp = B + o.wdp; d.node.wpdp = B + o.wpdp;
         d.node.bS = B + o.bS; d.node.bP = B + o.bP;
         d.node.wpep = B + o.wpep; d.node.wphip = B + o.wphip; d.node.bphi = B + o.bphi;
+        d.node.c0 = nullptr;
+        if (l == 0 && h->l0_hoist) {
+            d.w3p_l0 = B + o.w3p_l0; d.b3_l0 = B + o.b3_l0;
+            d.node.wpep = B + o.m0; d.node.c0 = B + o.c0;
+        }
     }
     h->enc_w1p = B + o_e1; h->enc_w2p = B + o_e2; h->enc_w3p = B + o_e3;
     h->enc_b1 = B + o_eb1; h->enc_b2 = B + o_eb2; h->enc_b3 = B + o_eb3;

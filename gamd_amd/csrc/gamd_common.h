@@ -201,6 +201,16 @@ __device__ __forceinline__ f32x4 gamd_load_stream(const f32x4* p) { return __bui
 // bit-identical to one another.
 __device__ __forceinline__ float gamd_msg_acc(float hn, float e_emb, float prev) { return __builtin_fmaf(hn, e_emb, prev); }
 
+// Layer-0 form of the fp32 conv kernels (LJ models, conv_edge.hip): SiLU(pre) folded into the running sum of its piece, the
+// final multiply of the SiLU fused with the add (written out so that every kernel rounds the same way).  A padding slot starts
+// its accumulator at GAMD_L0_PAD instead of the bias: whatever finite sum the GEMM adds is absorbed (ulp 2^77), 2^(2^100 log2 e)
+// overflows to +inf, rcp(inf) = 0, and the slot adds exactly -0 to its piece.
+#define GAMD_L0_PAD (-0x1p100f)
+__device__ __forceinline__ float gamd_l0_acc(float pre, float prev) {
+    const float e = __builtin_amdgcn_exp2f(pre * -1.4426950408889634f);
+    return __builtin_fmaf(pre, __builtin_amdgcn_rcpf(1.0f + e), prev);
+}
+
 // fp16 node tables of the bf16 edge MLP (NodeArgs::tab16): position, in fp16 elements, of feature f inside an S / D row.  A
 // lane (slot, half) of the chain layout owns the 64 features with bit 2 == half; they are stored as eight 16-byte groups
 // c = 2 t + k (t = f >> 5, k = bit 4 of f) holding X[t][8 k .. 8 k + 7], the two halves of a group side by side: one

@@ -255,9 +255,13 @@ struct ConvEdgeArgs {
                                // in CSR order, for launch_edge_update; null otherwise
 };
 int launch_conv_edge(const ConvEdgeArgs& a, int n_blocks, hipStream_t st);
+// layer-0 form (LJ models, conv_edge.hip): three GEMMs per edge, pieces hold sums of SiLU(W3 T2 + b3) over the real edges;
+// S0 / D0 = row 0 of a.S / a.D, a.w3p / a.b3 packed in the F2 output order; hn, erow, w4p, b4 unused
+int launch_conv_edge_l0(const ConvEdgeArgs& a, int n_blocks, hipStream_t st);
 int launch_conv_edge_bf16(const ConvEdgeArgs& a, int n_blocks, hipStream_t st);   // w*p = bf16 packed fragments, e_frag bf16
 // small edge counts (conv_edge_small.hip): one tile per 4-wave workgroup, bit-identical to launch_conv_edge
 int launch_conv_edge_small(const ConvEdgeArgs& a, int n_blocks, hipStream_t st);
+int launch_conv_edge_small_l0(const ConvEdgeArgs& a, int n_blocks, hipStream_t st);    // bit-identical to launch_conv_edge_l0
 int launch_conv_edge_small_wide(const ConvEdgeArgs& a, int eht, int ht, int n_blocks, hipStream_t st);   // = launch_conv_edge_wide
 int launch_conv_edge_f16x3(const ConvEdgeArgs& a, int n_blocks, hipStream_t st);  // w*p = [hi | lo] fp16 fragments (64 KiB)
 // generic widths (wide.hip): Eh = 128 eht, H = 128 ht.  w1p points at eht + 2 + ht contiguous packed blocks
@@ -295,7 +299,8 @@ struct NodeLayerW {            // one conv layer's node-side parameters (device 
     const float* wsp; const float* wdp; const float* wpdp;   // packed src_affine, dst_affine, phi_dst
     const float* bS;           // b_src + b_dst + b_edge_affine.2
     const float* bP;           // b_phi_dst + b_phi_edge
-    const float* wpep;         // packed phi_edge
+    const float* wpep;         // packed phi_edge (layer-0 form, post(0) only: M0 = W_pe diag(hn0) W4, see conv_edge.hip)
+    const float* c0;           // layer-0 form, post(0) only: W_pe (hn0 * b4), added d_i times (d_i = real incoming edges); else null
     const float* wphip;        // packed phi.mlp_layer.1
     const float* bphi;
 };
@@ -313,6 +318,7 @@ struct NodeArgs {
     const float* node_emb;     // [128] (lj) or null
     const float* enc_w; const float* enc_b;   // node_encoder Linear(1->128): weight[:,0], bias (water)
     const int* row_ptr; const int* na_excl; const int* deg;
+    const int* col;            // post.c0 set and several boxes: the CSR sources, to count each row's box padding (source n)
     const float* partial;
     long long piece_cap;       // rows of `partial` (checked build)
     const float* h_in;         // [n][128] residual stream before this layer's conv (mode 1,2)

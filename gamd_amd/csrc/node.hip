@@ -11,6 +11,8 @@
 //            P  = phi_dst(hn) + b_phi_dst + b_phi_edge          (:147)
 //   post(l): agg = sum of this atom's partial-sum pieces, in order   (:142)
 //            h' = phi(P + phi_edge(agg)) + h                    (:147, :202 residual)
+//   post(0) of the layer-0 form (LJ, conv_edge.hip): the pieces hold sums of T3 rows, phi_edge(agg) = M0 agg + d_i c0
+//            (post.wpep = M0, post.c0; d_i = the atom's real incoming edges)
 //
 // N is small (258 ... 10^4 rows): the kernel is bound by the latency of five chained 128x128 GEMMs, not by throughput.
 // Work unit: a tile of 16 atoms per 256-thread workgroup, on v_mfma_f32_16x16x4_f32.  Wave w computes output features
@@ -226,6 +228,21 @@ __global__ void __launch_bounds__(256, 3) k_node(NodeArgs a) {
         const int p0 = rp0 / GAMD_CHUNK + na_incl;
         const int np = dg > 0 ? ((rp0 + dg - 1) / GAMD_CHUNK - rp0 / GAMD_CHUNK + 1) : 0;
         (void)GAMD_CHK_RANGE(a.sticky, (long long)p0 + np, 0, a.piece_cap, GAMD_CHK_NODE_PIECES);
+        // layer-0 form: d_i = deg minus the box padding of a batch (at most 15 slots with source n, at the end of the row of a
+        // box's last atom); lane group g looks at the row's last slots g, g + 4, g + 8, g + 12
+        float n_real = 0.f;
+        if (a.post.c0) {
+            float n_pad = 0.f;
+            if (a.col) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const int j = g + 4 * k;
+                    if (j < dg && a.col[rp0 + dg - 1 - j] == a.n) n_pad += 1.f;
+                }
+                n_pad = group_sum(n_pad);
+            }
+            n_real = (float)dg - n_pad;
+        }
         mine[0] = f32x4{0.f, 0.f, 0.f, 0.f};
         mine[1] = mine[0];
         f32x4 p_in[2], h_res[2];
@@ -250,6 +267,14 @@ __global__ void __launch_bounds__(256, 3) k_node(NodeArgs a) {
         NMARK(2);                                                  // 2: exchange 1
         mine[0] = p_in[0]; mine[1] = p_in[1];
         GEMM16(true, a.post.wpep, a.post.wphip);
+        if (a.post.c0) {                                           // layer-0 form: + d_i c0 (an atom without edges: + 0)
+            f32x4 c[2];
+            load16(a.post.c0, w, g, c);
+#pragma unroll
+            for (int o = 0; o < 2; ++o)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) mine[o][r] = fmaf(n_real, c[o][r], mine[o][r]);
+        }
         NMARK(3);                                                  // 3: GEMM phi_edge
 #pragma unroll
         for (int o = 0; o < 2; ++o)

@@ -25,6 +25,7 @@ FLAVOUR = {"jaxmd": 0, "torch": 1}
 # what `fluid_graph.add_self_loop()` with its result discarded does (nn_module.py:650-652)
 SELF_LOOP = {"dgl07_noop": 0, "append_zero_feature_loops": 1}
 KSEL_FORCE_GENERIC_WIDTH = 1
+KSEL_NO_LAYER0_HOIST = 4        # LJ, fp32: layer 0 in its general four-GEMM form (include/gamd_hip.h)
 
 
 def _box3(box) -> np.ndarray:

@@ -93,7 +93,9 @@ typedef struct gamd_config {
                                 GAMD_KSEL_FORCE_GENERIC_WIDTH (1): run a 128/128 configuration on the generic-width kernels
                                 of wide.hip; GAMD_KSEL_FORCE_HALF_QUANTUM (2): run the generic-width fp32 conv layer on 16-edge
                                 work units (wide16.hip, v_mfma_f32_16x16x4_f32; bit-identical results, measured slower at every
-                                size tried: never chosen automatically) */
+                                size tried: never chosen automatically); GAMD_KSEL_NO_LAYER0_HOIST (4): LJ models in fp32 on the
+                                128-wide kernels run layer 0 in its general form (four GEMMs per edge) instead of the layer-0
+                                form (three GEMMs per edge, the last Linear applied per atom; equal up to fp32 rounding) */
     int32_t small_tile_limit;/* fp32 path: edge counts of at most this many 32-edge tiles run the latency-oriented conv kernel
                                 (one tile per 4-wave workgroup, bit-identical results).  0 = default (512), -1 = never */
     int32_t n_boxes;         /* 0 or 1: one box (default).  B > 1: B INDEPENDENT boxes of n_atoms atoms each, evaluated and
@@ -110,7 +112,7 @@ typedef struct gamd_config {
                                 index B*n).  A neighbour-buffer overflow in any box regrows the shared buffers. */
 } gamd_config;
 enum { GAMD_SELF_LOOP_DGL07_NOOP = 0, GAMD_SELF_LOOP_APPEND_ZERO_FEATURE = 1 };
-enum { GAMD_KSEL_FORCE_GENERIC_WIDTH = 1, GAMD_KSEL_FORCE_HALF_QUANTUM = 2 };
+enum { GAMD_KSEL_FORCE_GENERIC_WIDTH = 1, GAMD_KSEL_FORCE_HALF_QUANTUM = 2, GAMD_KSEL_NO_LAYER0_HOIST = 4 };
 
 const char* gamd_version(void);
 const char* gamd_last_error(void);
