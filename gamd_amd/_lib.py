@@ -40,6 +40,11 @@ class GamdMdParams(C.Structure):
                 ("gamma_per_ps", C.c_float), ("seed", C.c_uint64), ("first_step", C.c_uint64)] + _MD_EXT
 
 
+class GamdReportParams(C.Structure):
+    _fields_ = [("interval", C.c_int64), ("max_samples", C.c_int64), ("ndf", C.c_double), ("rdf_bins", C.c_int32),
+                ("rdf_rmax", C.c_float), ("exclude_same_molecule", C.c_int32), ("reserved", C.c_int32)]
+
+
 # every symbol include/gamd_hip.h declares: name -> (restype, argtypes)
 _vp, _i32, _i64 = C.c_void_p, C.c_int32, C.c_int64
 SYMBOLS = {
@@ -64,6 +69,10 @@ SYMBOLS = {
     "gamd_debug_get": (_i32, [_vp, _i32, _vp, C.c_size_t]),
     "gamd_md_run": (_i32, [_vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_float), C.POINTER(GamdMdParams), _i64, _vp]),
     "gamd_md_run_nhc": (_i32, [_vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_float), C.POINTER(GamdNhcParams), _vp, _i64, _vp]),
+    "gamd_report_configure": (_i32, [_vp, C.POINTER(GamdReportParams)]),
+    "gamd_report_reset": (_i32, [_vp]),
+    "gamd_report_read": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, C.POINTER(_i64), _vp, _i64, C.POINTER(_i64), C.POINTER(_i64),
+                                C.POINTER(_i32)]),
     "gamd_profile": (_i32, [_vp, _vp, _vp, C.POINTER(C.c_float), _vp, _vp, C.c_char_p, C.c_size_t,
                             C.POINTER(C.c_float), _i32, C.POINTER(_i32)]),
     "gamd_timing_enable": (_i32, [_vp, _i32]),

@@ -111,11 +111,25 @@ struct MdPending {
     MdArgs m{};
     NhcArgs a{};
     unsigned long long first_step = 0;
+    float mass = 0.f, mass_h = 0.f;    // BAOAB: mass_amu / mass_h_amu as given (MdArgs keeps their reciprocals)
     long long n_steps = 0;
     float* x = nullptr;
     float* f = nullptr;
     const uint8_t* species = nullptr;
     hipStream_t st = nullptr;
+    long long report_g0 = 0;           // run reporter: completed MD steps in front of this run's first step
+};
+
+// run reporter (gamd_report_*, report.hip): configuration, step count and the device-resident log / histogram
+struct Reporter {
+    long long interval = 0;            // 0: off — nothing is enqueued, nothing is allocated
+    long long sample_interval = 0;     // the interval g was counted with (stays when the reporter is switched off: the log stays readable)
+    long long max_samples = 0;
+    double ndf = 0.0;
+    int bins = 0, pairs = 1, exclude = 0;
+    float rmax = 0.f;
+    long long g = 0;                   // completed MD steps since configure / reset, runs still in the stream included
+    DevBuf steps, ke, counts, partial;
 };
 
 }  // namespace
@@ -186,6 +200,7 @@ struct gamd_handle {
     const float* feat_dev = nullptr;   // gamd_set_node_features
     const uint8_t* rigid_checked = nullptr;   // species pointer whose O,H,H layout has been validated
     MdPending pending;
+    Reporter rep;
     bool has_bonds = false;
 
     // Verlet-skin reuse (cfg.neighbor_skin > 0)
@@ -825,6 +840,57 @@ int step_event(gamd_handle* h, hipStream_t st, bool closes = false) {
     return 0;
 }
 
+// run reporter: blocks per box of k_report_ke (fixed per handle: the summation tree never changes)
+int report_ke_blocks(const gamd_handle* h) { return std::max(1, std::min(64, (h->n_per_box + 1023) / 1024)); }
+
+// run reporter: does step s of the pending run carry a sample?  (g counts completed steps: step s completes as g0 + s + 1)
+bool report_sampled(const gamd_handle* h, long long s) {
+    return h->rep.interval > 0 && (h->pending.report_g0 + s + 1) % h->rep.interval == 0;
+}
+
+// the sample of step s of the pending run, behind its second half: the kinetic-energy row and the frame's pair histogram
+int enqueue_report_sample(gamd_handle* h, long long s) {
+    const MdPending& p = h->pending;
+    const Reporter& rp = h->rep;
+    ReportArgs a{};
+    a.n = h->n;
+    a.bx = box_ref(h);
+    a.devflags = h->devflags.as<int>();
+    a.sticky = h->sticky_dev;
+    if (p.kind == 0) {
+        a.v = p.m.v; a.species = p.m.species; a.len = (double)p.m.len;
+        a.mass = (double)p.mass; a.mass_h = (double)p.mass_h;
+    } else {
+        a.v = p.a.v; a.species = p.a.species; a.len = (double)p.a.len;
+        a.mass = (double)p.a.mass; a.mass_h = (double)p.a.mass_h;
+    }
+    a.partial = rp.partial.as<double>();
+    a.blocks = report_ke_blocks(h);
+    a.steps = rp.steps.as<long long>();
+    a.ke = rp.ke.as<double>();
+    a.g = p.report_g0 + s + 1;
+    a.slot = a.g / rp.interval - 1;
+    int r;
+    // the row is the sample's ordinal, chosen here: a sample enqueued again after a freeze writes the same row
+    if (a.slot < rp.max_samples && (r = launch_report_ke(a, p.st))) return fail(-1, "reporter launch failed (%d)", r);
+    if (rp.bins > 0) {
+        a.counters = h->cur_counters;
+        a.pos_s = h->pos_s.as<float4>();
+        a.col = h->col.as<int>(); a.erow = h->erow.as<int>(); a.row_ptr = h->row_ptr.as<int>(); a.perm = h->perm.as<int>();
+        a.e_cap = h->e_cap;
+        for (int d = 0; d < 3; ++d) { a.box[d] = h->box[d]; a.half[d] = 0.5f * h->box[d]; }
+        a.n_bins = rp.bins; a.n_pairs = rp.pairs;
+        a.r_max = rp.rmax; a.bin_scale = (float)rp.bins;
+        a.all_edges = rp.rmax >= h->cfg.cutoff ? 1 : 0;
+        a.exclude_same_molecule = rp.exclude;
+        a.counts = rp.counts.as<unsigned long long>();
+        // ~16 edge slots per thread; every workgroup flushes its non-zero bins with one atomic each
+        a.rdf_blocks = (int)std::max<long long>(1, std::min<long long>(h->n_cu, h->e_cap / h->n_boxes / 4096));
+        if ((r = launch_report_rdf(a, p.st))) return fail(-1, "reporter launch failed (%d)", r);
+    }
+    return 0;
+}
+
 // steps [s_begin, n_steps) of the pending MD run; skip_first: the first half of step s_begin has already been done
 int enqueue_md_steps(gamd_handle* h, long long s_begin, bool skip_first) {
     MdPending& p = h->pending;
@@ -836,7 +902,8 @@ int enqueue_md_steps(gamd_handle* h, long long s_begin, bool skip_first) {
             if ((r = step_event(h, p.st))) return r;
             p.m.step = p.first_step + (unsigned long long)s;
             p.m.step_index = (int)s;
-            int do_second = s > s_begin ? 1 : 0;
+            // (the B of a step that carries a reporter sample has been launched on its own, in front of the sample)
+            int do_second = (s > s_begin && !report_sampled(h, s - 1)) ? 1 : 0;
             const int do_first = (skip_first && s == s_begin) ? 0 : 1;
             if (p.m.com.enabled) {
                 // COM motion removal sits between the B of step s-1 and the first half of step s and needs a sum over all
@@ -862,10 +929,15 @@ int enqueue_md_steps(gamd_handle* h, long long s_begin, bool skip_first) {
             if ((r = enqueue_forward(h, p.x, p.species, nullptr, p.f, p.st, nullptr, nullptr, nullptr, nullptr, &fuse,
                                      s + 1 == p.n_steps, s > s_begin)))
                 return r;
+            if (s + 1 < p.n_steps && report_sampled(h, s)) {      // a sampled step completes its B before the sample
+                if ((r = launch_baoab_second(p.m, p.st))) return fail(-1, "integrator launch failed (%d)", r);
+                if ((r = enqueue_report_sample(h, s))) return r;
+            }
         }
         if (p.n_steps > s_begin) {
             p.m.step_index = (int)(p.n_steps - 1);
             if ((r = launch_baoab_second(p.m, p.st))) return fail(-1, "integrator launch failed (%d)", r);
+            if (report_sampled(h, p.n_steps - 1) && (r = enqueue_report_sample(h, p.n_steps - 1))) return r;
         }
         return step_event(h, p.st, true);
     }
@@ -885,6 +957,7 @@ int enqueue_md_steps(gamd_handle* h, long long s_begin, bool skip_first) {
             if ((r = enqueue_forward(h, p.x, p.species, nullptr, p.f, p.st, nullptr, nullptr, nullptr, nullptr, nullptr, last, s > s_begin))) return r;
             if ((r = launch_nhc_second(p.a, p.st))) return fail(-1, "integrator launch failed (%d)", r);
         }
+        if (report_sampled(h, s) && (r = enqueue_report_sample(h, s))) return r;
     }
     return step_event(h, p.st, true);
 }
@@ -1072,6 +1145,7 @@ int32_t gamd_destroy(gamd_handle* h) {
                       &h->na_excl, &h->bond_nbr, &h->hbuf, &h->hn, &h->S, &h->D, &h->P, &h->l0_h, &h->l0_hn, &h->l0_S, &h->l0_D, &h->l0_P, &h->f_norm, &h->f_den,
                       &h->cell_cnt, &h->cell_fill, &h->cell_start, &h->col, &h->erow, &h->chunk_piece,
                       &h->chunk_mask, &h->e_frag, &h->e_emb, &h->e_frag2, &h->partial, &h->feat_dbg, &h->counters, &h->tdbg, &h->tmp_eid, &h->ke_partial, &h->com_partial,
+                      &h->rep.steps, &h->rep.ke, &h->rep.counts, &h->rep.partial,
                       &h->ref_pos, &h->cand_deg, &h->cand_ptr, &h->cand_col};
     for (DevBuf* b : bufs) b->release();
     h->pos_in.release();
@@ -1779,7 +1853,10 @@ int32_t gamd_md_run(gamd_handle* h, float* x_dev, float* v_dev, float* f_dev, co
     m.devflags = h->devflags.as<int>();
     MdPending& pd = h->pending;
     pd.active = true; pd.kind = 0; pd.m = m; pd.first_step = p->first_step; pd.n_steps = n_steps;
+    pd.mass = p->mass_amu; pd.mass_h = p->mass_h_amu > 0.f ? p->mass_h_amu : 0.f;
     pd.x = x_dev; pd.f = f_dev; pd.species = species_dev; pd.st = st;
+    pd.report_g0 = h->rep.g;
+    if (h->rep.interval > 0) h->rep.g += n_steps;
     return enqueue_md_steps(h, 0, false);
 }
 
@@ -1835,7 +1912,99 @@ int32_t gamd_md_run_nhc(gamd_handle* h, float* x_dev, float* v_dev, float* f_dev
     MdPending& pd = h->pending;
     pd.active = true; pd.kind = 1; pd.a = a; pd.first_step = 0; pd.n_steps = n_steps;
     pd.x = x_dev; pd.f = f_dev; pd.species = species_dev; pd.st = st;
+    pd.report_g0 = h->rep.g;
+    if (h->rep.interval > 0) h->rep.g += n_steps;
     return enqueue_md_steps(h, 0, false);
+}
+
+static_assert(sizeof(gamd_report_params) == 40 && offsetof(gamd_report_params, ndf) == 16 && offsetof(gamd_report_params, rdf_rmax) == 28,
+              "gamd_report_params layout is part of the C ABI (gamd_amd/_lib.py mirrors it)");
+
+// clear the reporter's step count, log and histogram (on the init stream, landed before it returns)
+static int report_clear(gamd_handle* h) {
+    Reporter& rp = h->rep;
+    rp.g = 0;
+    DevBuf* bufs[] = {&rp.steps, &rp.ke, &rp.counts};
+    for (DevBuf* b : bufs)
+        if (b->p) HIP_TRY(hipMemsetAsync(b->p, 0, b->bytes, tl_init_stream));
+    HIP_TRY(hipStreamSynchronize(tl_init_stream));
+    return 0;
+}
+
+int32_t gamd_report_configure(gamd_handle* h, const gamd_report_params* p) {
+    // the parameter block is checked first: these answers need no device
+    if (!p) return fail(-22, "null argument");
+    if (p->interval < 0) return fail(-22, "interval = %lld is negative", (long long)p->interval);
+    if (p->max_samples < 0 || p->max_samples > (1ll << 24)) return fail(-22, "max_samples = %lld outside [0, 2^24]", (long long)p->max_samples);
+    if (p->rdf_bins < 0 || p->rdf_bins > 1024) return fail(-22, "rdf_bins = %d outside [0, 1024]", (int)p->rdf_bins);
+    if (!(p->rdf_rmax >= 0.f)) return fail(-22, "rdf_rmax = %g is negative", (double)p->rdf_rmax);
+    if (!(p->ndf >= 0.0)) return fail(-22, "ndf = %g is negative", p->ndf);
+    if (!h) return fail(-22, "null handle");
+    if (p->rdf_rmax > h->cfg.cutoff)
+        return fail(-22, "rdf_rmax = %g exceeds the cutoff %g: pairs beyond it are not in the edge list", (double)p->rdf_rmax, (double)h->cfg.cutoff);
+    Reporter& rp = h->rep;
+    if (h->pending.active) return fail(-22, "an MD run is still enqueued: call gamd_sync_status before gamd_report_configure");
+    if (p->interval == 0) { rp.interval = 0; return 0; }        // off: what was recorded stays readable
+    DeviceGuard guard(h->dev);
+    InitStream init(h->init_stream);
+    rp.interval = 0;
+    rp.max_samples = p->max_samples > 0 ? p->max_samples : 4096;
+    rp.ndf = p->ndf > 0.0 ? p->ndf : 3.0 * (double)h->n_per_box;
+    rp.bins = p->rdf_bins;
+    rp.pairs = h->cfg.kind == GAMD_KIND_WATER ? 3 : 1;
+    rp.rmax = p->rdf_rmax > 0.f ? p->rdf_rmax : h->cfg.cutoff;
+    rp.exclude = p->exclude_same_molecule ? 1 : 0;
+    const size_t nb = (size_t)h->n_boxes;
+    // exact sizes (a smaller configuration after a larger one re-allocates: report_clear and gamd_report_read go by bytes)
+    DevBuf* bufs[] = {&rp.steps, &rp.ke, &rp.counts, &rp.partial};
+    const size_t want[] = {sizeof(long long) * (size_t)rp.max_samples, sizeof(double) * (size_t)rp.max_samples * nb,
+                           sizeof(unsigned long long) * nb * (size_t)rp.pairs * (size_t)rp.bins,
+                           sizeof(double) * nb * (size_t)report_ke_blocks(h)};
+    for (int k = 0; k < 4; ++k) {
+        if (bufs[k]->bytes != want[k]) bufs[k]->release();
+        if (want[k] && bufs[k]->ensure(want[k], true)) return fail(-12, "reporter allocation failed");
+    }
+    int r;
+    if ((r = report_clear(h))) return r;
+    rp.interval = rp.sample_interval = p->interval;
+    return 0;
+}
+
+int32_t gamd_report_reset(gamd_handle* h) {
+    if (!h) return fail(-22, "null handle");
+    if (h->pending.active) return fail(-22, "an MD run is still enqueued: call gamd_sync_status before gamd_report_reset");
+    DeviceGuard guard(h->dev);
+    InitStream init(h->init_stream);
+    return report_clear(h);
+}
+
+int32_t gamd_report_read(gamd_handle* h, void* stream, int64_t* steps, double* ke, double* temperature, int64_t max_rows,
+                         int64_t* n_rows, uint64_t* counts, int64_t count_elems, int64_t* frames, int64_t* dropped,
+                         int32_t dims[3]) {
+    if (!h) return fail(-22, "null handle");
+    if (max_rows < 0) return fail(-22, "max_rows is negative");
+    const Reporter& rp = h->rep;
+    DeviceGuard guard(h->dev);
+    hipStream_t st = (hipStream_t)stream;
+    const long long nb = h->n_boxes;
+    const long long taken = (rp.sample_interval > 0 && rp.steps.p) ? rp.g / rp.sample_interval : 0;
+    const long long rows = std::min<long long>(taken, rp.max_samples);
+    const long long n_copy = std::min<long long>(rows, max_rows);
+    const long long elems = nb * (long long)rp.pairs * (long long)rp.bins;
+    if (counts && rp.counts.p && count_elems < elems) return fail(-22, "counts has room for %lld elements, the histogram has %lld", (long long)count_elems, elems);
+    if (n_copy > 0 && steps) HIP_TRY(hipMemcpyAsync(steps, rp.steps.p, sizeof(int64_t) * (size_t)n_copy, hipMemcpyDeviceToHost, st));
+    if (n_copy > 0 && ke) HIP_TRY(hipMemcpyAsync(ke, rp.ke.p, sizeof(double) * (size_t)(n_copy * nb), hipMemcpyDeviceToHost, st));
+    if (n_copy > 0 && temperature && !ke) return fail(-22, "temperature needs ke");
+    if (counts && rp.counts.p && elems > 0) HIP_TRY(hipMemcpyAsync(counts, rp.counts.p, sizeof(uint64_t) * (size_t)elems, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (int t = check_traps(h)) return t;
+    if (temperature)
+        for (long long k = 0; k < n_copy * nb; ++k) temperature[k] = 2.0 * ke[k] / (rp.ndf * 0.00831446261815324);
+    if (n_rows) *n_rows = rows;
+    if (frames) *frames = (rp.bins > 0 && rp.counts.p) ? taken : 0;
+    if (dropped) *dropped = taken - rows;
+    if (dims) { dims[0] = (int32_t)nb; dims[1] = rp.pairs; dims[2] = rp.counts.p ? rp.bins : 0; }
+    return 0;
 }
 
 int32_t gamd_profile(gamd_handle* h, const float* pos_dev, const uint8_t* species_dev, const float* box,

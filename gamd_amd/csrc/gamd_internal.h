@@ -418,3 +418,41 @@ int launch_com_partial(const MdCom& com, const float* v, const uint8_t* species,
                        const BoxRef& bx, const int* devflags, int by_molecule, hipStream_t st);
 int launch_nhc_first(const NhcArgs& a, hipStream_t st);     // propagateNHC; v *= scale; v += dt/2 f/m; x += dt v
 int launch_nhc_second(const NhcArgs& a, hipStream_t st);    // v += dt/2 f/m; propagateNHC; v *= scale
+
+// ---- run reporter (report.hip) ------------------------------------------------------------------
+// One sample of an enqueued MD run (gamd_report_configure): the kinetic-energy log row `slot` and / or the pair-distance
+// histogram of the frame.  Slot and step number come from the host (the sample's ordinal), so a sample that is enqueued
+// again after a freeze writes the same row; the histogram is protected by the freeze gate alone (a kernel that returned
+// added nothing).
+enum { GAMD_CHK_REPORT_SRC = 141, GAMD_CHK_REPORT_DST = 142, GAMD_CHK_REPORT_PERM = 143, GAMD_CHK_REPORT_ROW = 144 };
+struct ReportArgs {
+    int n;                     // atoms of all boxes
+    BoxRef bx;
+    const int* devflags;       // DEVFLAG_FROZEN set: every reporter kernel returns at once
+    int* sticky;               // host-mapped (checked build)
+    // kinetic energy
+    const float* v;            // [n][3] length unit / ps
+    const uint8_t* species;    // [n] or null
+    double mass, mass_h;       // amu; species-0 atoms use mass_h when it is > 0
+    double len;                // length units per nm
+    double* partial;           // [n_boxes][blocks] per-block sums of m v^2
+    int blocks;                // blocks per box
+    long long* steps;          // [max_samples]
+    double* ke;                // [max_samples][n_boxes]
+    long long slot;            // log row of this sample, -1: the log is full (no kinetic-energy launch)
+    long long g;               // completed MD steps at this sample
+    // g(r)
+    const int* counters;
+    const float4* pos_s;
+    const int* col; const int* erow; const int* row_ptr; const int* perm;
+    long long e_cap;
+    float box[3], half[3];
+    int n_bins, n_pairs;       // n_bins == 0: no histogram
+    float r_max, bin_scale;    // bin_scale = n_bins (as float): bin = (int)(r * bin_scale / r_max)
+    int all_edges;             // r_max == cutoff: the edge list IS the set r < r_max (no second test against a rounded sqrt)
+    int exclude_same_molecule;
+    unsigned long long* counts;// [n_boxes][n_pairs][n_bins]
+    int rdf_blocks;            // workgroups per box
+};
+int launch_report_ke(const ReportArgs& a, hipStream_t st);
+int launch_report_rdf(const ReportArgs& a, hipStream_t st);

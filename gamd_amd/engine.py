@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import GamdConfig, GamdMdParams, GamdNhcParams, check
+from ._lib import GamdReportParams, GamdConfig, GamdMdParams, GamdNhcParams, check
 from .weights import ModelConfig, infer_config, validate_state_dict
 
 ArrayLike = Union[np.ndarray, torch.Tensor]
@@ -49,6 +49,59 @@ def _boxes(box, n_boxes: int) -> np.ndarray:
     if (b.ndim == 1 and b.size == n_boxes) or (b.ndim == 2 and b.shape == (n_boxes, 1)):
         return np.repeat(b.reshape(-1).astype(np.float32)[:, None], 3, axis=1)
     raise ValueError(f"box must be a scalar, 3 values, [{n_boxes}, 1] or [{n_boxes}, 3] ({n_boxes} boxes)")
+
+
+class RunReport:
+    """What the run reporter recorded (GamdForce.report_read).
+
+    steps [S] int64: completed MD steps g at each sample; ke, temperature [S, n_boxes] float64 (kJ/mol, K);
+    rdf_counts [n_boxes, P, bins] uint64: directed pair counts per distance bin, P = 1 (LJ) or 3 (water: O-O, O-H in both
+    directions, H-H); frames: frames in the histogram; dropped: samples that found the log full.
+    r_max / volumes: upper edge of the last bin and the box volumes, for ``rdf``."""
+
+    def __init__(self, steps, ke, temperature, rdf_counts, frames: int, dropped: int, r_max: float = 0.0, volumes=None):
+        self.steps = np.asarray(steps, dtype=np.int64)
+        self.ke = np.atleast_2d(np.asarray(ke, dtype=np.float64))              # [S, n_boxes]
+        self.temperature = np.atleast_2d(np.asarray(temperature, dtype=np.float64))
+        self.rdf_counts = np.asarray(rdf_counts, dtype=np.uint64)
+        self.frames, self.dropped = int(frames), int(dropped)
+        self.r_max = float(r_max)
+        self.volumes = None if volumes is None else np.asarray(volumes, dtype=np.float64).reshape(-1)
+
+    def rdf(self, box: int, n_by_class, volume: Optional[float] = None):
+        """(r_mid [bins], g [P, bins]) of box ``box``: g_ab(k) = c_ab[k] / (frames * m_ab * V_shell(k) / V) with
+        m_aa = N_a^2 and m_ab = 2 N_a N_b for the directed counts.  ``n_by_class``: N for one pair class, (N_O, N_H) for
+        three."""
+        c = self.rdf_counts[box].astype(np.float64)
+        n_pairs, bins = c.shape
+        if bins == 0 or self.frames == 0:
+            raise ValueError("no histogram was recorded")
+        vol = float(volume) if volume is not None else float(self.volumes[box])
+        nn = np.atleast_1d(np.asarray(n_by_class, dtype=np.float64))
+        if n_pairs == 1:
+            m = np.array([nn[0] ** 2])
+        else:
+            if nn.shape[0] != 2:
+                raise ValueError("three pair classes need n_by_class = (N_O, N_H)")
+            m = np.array([nn[0] ** 2, 2.0 * nn[0] * nn[1], nn[1] ** 2])
+        edges = np.arange(bins + 1, dtype=np.float64) * (self.r_max / bins)
+        shell = 4.0 / 3.0 * np.pi * (edges[1:] ** 3 - edges[:-1] ** 3)
+        g = c / (self.frames * m[:, None] * shell[None, :] / vol)
+        return 0.5 * (edges[1:] + edges[:-1]), g
+
+    def write_state_data(self, path, dt_ps: float, separator: str = "\t", driver_step_convention: bool = False,
+                         box: int = 0) -> None:
+        """The log file OpenMM's StateDataReporter(step=True, time=True, kineticEnergy=True, temperature=True) writes.
+        ``driver_step_convention``: Step and Time count the two ``simulation.step(1)`` calls per iteration of the
+        reference drivers (Step = 2 g, Time = 2 g dt), as their own logs do; otherwise Step = g, Time = g dt."""
+        k = 2 if driver_step_convention else 1
+        head = ['"Step"', '"Time (ps)"', '"Kinetic Energy (kJ/mole)"', '"Temperature (K)"']
+        with open(path, "w") as fh:
+            fh.write("#" + separator.join(head) + "\n")
+            for i, g in enumerate(self.steps):
+                row = [str(k * int(g)), str(k * int(g) * float(dt_ps)), str(float(self.ke[i, box])),
+                       str(float(self.temperature[i, box]))]
+                fh.write(separator.join(row) + "\n")
 
 
 class GamdForce:
@@ -451,6 +504,49 @@ class GamdForce:
         if sync:
             self.last_status = check(self._lib.gamd_sync_status(self._h, self._stream()), "gamd_sync_status")
         return chain_state
+
+    # -- run reporter (the drivers' StateDataReporter log and a g(r) histogram, taken inside enqueued runs) ----------
+    def report_configure(self, interval: int, max_samples: int = 0, ndf: Optional[float] = None, rdf_bins: int = 0,
+                         rdf_rmax: float = 0.0, exclude_same_molecule: bool = False, rigid_water: bool = False,
+                         remove_cm_motion: Optional[bool] = None) -> None:
+        """While configured, every ``interval``-th completed step of md_run / md_run_nhc (counted across calls) logs the
+        kinetic energy per box on the device and, with ``rdf_bins`` > 0, adds the frame's pair distances below ``rdf_rmax``
+        (default and at most: the cutoff) to a histogram; ``report_read`` fetches both.  ``interval`` = 0 switches it off.
+        ``ndf`` (degrees of freedom per box, for the temperature) defaults as md_run_nhc's does: 3 per atom, 6 per rigid
+        molecule (``rigid_water``), 3 fewer with ``remove_cm_motion`` (default: True with ``rigid_water``).
+        Replaces ``simulation.reporters.append(StateDataReporter(file, 100, step=True, time=True, kineticEnergy=True,
+        temperature=True))`` of the rollout drivers (LJ/test_script/test_langevin.py:79-83)."""
+        if remove_cm_motion is None:
+            remove_cm_motion = bool(rigid_water)
+        if ndf is None:
+            ndf = (2 * self.n if rigid_water else 3 * self.n) - (3 if remove_cm_motion else 0)
+        p = GamdReportParams(int(interval), int(max_samples), float(ndf), int(rdf_bins), float(rdf_rmax),
+                             int(bool(exclude_same_molecule)), 0)
+        check(self._lib.gamd_report_configure(self._h, C.byref(p)), "gamd_report_configure")
+        if interval:
+            self._report_rmax = float(np.float32(rdf_rmax)) if rdf_rmax else float(np.float32(self.cutoff))
+
+    def report_reset(self) -> None:
+        """Step count, log and histogram back to zero; the configuration stays."""
+        check(self._lib.gamd_report_reset(self._h), "gamd_report_reset")
+
+    def report_read(self) -> "RunReport":
+        """Synchronise and fetch what the reporter has recorded since it was configured or reset."""
+        n_rows, frames, dropped = C.c_int64(), C.c_int64(), C.c_int64()
+        dims = (C.c_int32 * 3)()
+        rd = self._lib.gamd_report_read
+        check(rd(self._h, self._stream(), None, None, None, 0, C.byref(n_rows), None, 0, C.byref(frames), C.byref(dropped), dims),
+              "gamd_report_read")
+        rows, (nb, npair, nbins) = n_rows.value, dims
+        steps = np.zeros(rows, dtype=np.int64)
+        ke = np.zeros((rows, nb), dtype=np.float64)
+        temp = np.zeros((rows, nb), dtype=np.float64)
+        counts = np.zeros((nb, npair, nbins), dtype=np.uint64)
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)
+        check(rd(self._h, self._stream(), vp(steps), vp(ke), vp(temp), rows, C.byref(n_rows), vp(counts), counts.size,
+                 C.byref(frames), C.byref(dropped), dims), "gamd_report_read")
+        return RunReport(steps, ke, temp, counts, frames.value, dropped.value, getattr(self, "_report_rmax", 0.0),
+                         np.prod(_boxes(self.box, self.n_boxes).astype(np.float64), axis=1))
 
     def sync_status(self) -> int:
         """0, or 1 when an enqueued MD run overflowed a neighbour buffer, froze on the device and was resumed."""

@@ -278,6 +278,50 @@ typedef struct gamd_nhc_params {
 int32_t gamd_md_run_nhc(gamd_handle* h, float* x_dev, float* v_dev, float* f_dev, const uint8_t* species_dev,
                         const float* box, const gamd_nhc_params* p, double* chain_state_dev, int64_t n_steps, void* stream);
 
+/* Run reporter: the log the reference's rollout drivers keep with OpenMM's
+ *   StateDataReporter(file, 100 | 250, step=True, time=True, kineticEnergy=True, temperature=True, separator='\t')
+ * (LJ/test_script/test_langevin.py:79-83, LJ/test_script/test_nosehoover.py:82-87, water/test_script/test_langevin.py:89-94,
+ * water/test_script/test_nosehoover.py:91-96, the _hb drivers alike), kept ON THE DEVICE while gamd_md_run / gamd_md_run_nhc
+ * are enqueued, plus the pair-distance histogram of a radial distribution function over the sampled frames.
+ * The reporter counts the completed MD steps g of the handle since it was configured or reset (across calls).  Step g is
+ * sampled when g % interval == 0, behind its second half (HackHalfVelocityIntegrator / HackHalfNoseHooverIntegrator and, for
+ * rigid water, the velocity constraint behind the kick): where the drivers' reporter fires, since they call
+ * simulation.step(1) twice per iteration and the report interval is even.  A sample is
+ *   - one log row {g, KE per box}: KE = sum_i 1/2 m_i |v_i|^2 in kJ/mol (OpenMM's m*v*v/2 of a CustomIntegrator), v converted
+ *     to nm/ps with the run's length_per_nm, m_i the run's mass_amu / mass_h_amu (the fp32 values of the parameter block),
+ *     summed in double in a fixed order: the same bits run after run.  Row number = g / interval - 1; rows beyond
+ *     max_samples are dropped and counted;
+ *   - rdf_bins > 0: every directed edge src -> dst of that step's force evaluation with src != dst (the frame's exact pair
+ *     list, in skin mode too) adds 1 to the 64-bit counter [box][pair class][bin], bin = min((int)(r * rdf_bins / rdf_rmax),
+ *     rdf_bins - 1) of the fp32 min-image distance r < rdf_rmax (rdf_rmax == cutoff: every edge).  Pair classes: one for
+ *     GAMD_KIND_LJ handles; three for GAMD_KIND_WATER: O-O, O-H (both directions), H-H, O = node feature != 0 (the
+ *     species flag).  exclude_same_molecule: pairs whose caller-order atom ids share id / 3 (O,H,H triples) are skipped.
+ * Nothing synchronises or returns to the host inside a run; a run that froze on a neighbour-buffer overflow and was resumed
+ * by gamd_sync_status gives the log and the counts of an ample buffer.  A handle whose reporter is off enqueues exactly what
+ * it enqueues without one; with it on, skin-mode runs launch the second half of a SAMPLED step on its own. */
+typedef struct gamd_report_params {
+    int64_t interval;        /* 0 = reporter off (buffers are kept); > 0: sample every interval-th completed step */
+    int64_t max_samples;     /* log rows allocated by gamd_report_configure; 0 = 4096 */
+    double ndf;              /* degrees of freedom per box for the temperature; 0 = 3 * n_atoms */
+    int32_t rdf_bins;        /* 0 = no histogram; at most 1024 */
+    float rdf_rmax;          /* upper edge of the last bin, 0 < rdf_rmax <= cutoff (0 with rdf_bins > 0: the cutoff) */
+    int32_t exclude_same_molecule;
+    int32_t reserved;        /* 0 */
+} gamd_report_params;
+/* p: HOST.  Allocates and clears the log and the histogram (drains nothing: call it between runs, after gamd_sync_status);
+ * -22 for a negative interval or max_samples, rdf_bins outside [0, 1024], rdf_rmax < 0 or above the cutoff. */
+int32_t gamd_report_configure(gamd_handle* h, const gamd_report_params* p);
+/* Step count g = 0, log and histogram cleared; the configuration stays. */
+int32_t gamd_report_reset(gamd_handle* h);
+/* Synchronises `stream` once (it does NOT resume a frozen run: call gamd_sync_status first) and copies to HOST arrays, any
+ * of which may be NULL: steps int64 [max_rows], ke and temperature double [max_rows][n_boxes] (T = 2 KE / (ndf kB), kB =
+ * 0.00831446261815324 kJ/mol/K), counts uint64 [n_boxes][pair classes][rdf_bins] (count_elems = room in elements; fewer
+ * than that product is -22).  *n_rows = rows in the log (at most max_rows are written), *frames = frames in the histogram,
+ * *dropped = samples that found the log full, dims[0..2] = n_boxes, pair classes, rdf_bins. */
+int32_t gamd_report_read(gamd_handle* h, void* stream, int64_t* steps, double* ke, double* temperature, int64_t max_rows,
+                         int64_t* n_rows, uint64_t* counts, int64_t count_elems, int64_t* frames, int64_t* dropped,
+                         int32_t dims[3]);
+
 /* Event-timed replay of one force evaluation: per-kernel milliseconds of the last gamd_profile call.
  * names: newline-separated kernel labels; ms: one float per label.  For bench.py's roofline block. */
 int32_t gamd_profile(gamd_handle* h, const float* pos_dev, const uint8_t* species_dev, const float* box,
