@@ -45,6 +45,14 @@ class GamdReportParams(C.Structure):
                 ("rdf_rmax", C.c_float), ("exclude_same_molecule", C.c_int32), ("reserved", C.c_int32)]
 
 
+class GamdTrajParams(C.Structure):
+    _fields_ = [("interval", C.c_int64), ("max_frames", C.c_int64), ("fields", C.c_int32), ("n_lags", C.c_int32),
+                ("subtract_com", C.c_int32), ("reserved", C.c_int32)]
+
+
+TRAJ_FIELDS = {"x": 1, "v": 2, "f": 4, "image": 8}          # GAMD_TRAJ_*
+
+
 # every symbol include/gamd_hip.h declares: name -> (restype, argtypes)
 _vp, _i32, _i64 = C.c_void_p, C.c_int32, C.c_int64
 SYMBOLS = {
@@ -73,6 +81,10 @@ SYMBOLS = {
     "gamd_report_reset": (_i32, [_vp]),
     "gamd_report_read": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, C.POINTER(_i64), _vp, _i64, C.POINTER(_i64), C.POINTER(_i64),
                                 C.POINTER(_i32)]),
+    "gamd_traj_configure": (_i32, [_vp, C.POINTER(GamdTrajParams)]),
+    "gamd_traj_reset": (_i32, [_vp]),
+    "gamd_traj_read_frames": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64)]),
+    "gamd_traj_read_dynamics": (_i32, [_vp, _vp, _vp, _vp, _i64, C.POINTER(_i64), C.POINTER(C.c_uint64), _vp, C.POINTER(_i32)]),
     "gamd_profile": (_i32, [_vp, _vp, _vp, C.POINTER(C.c_float), _vp, _vp, C.c_char_p, C.c_size_t,
                             C.POINTER(C.c_float), _i32, C.POINTER(_i32)]),
     "gamd_timing_enable": (_i32, [_vp, _i32]),

@@ -118,6 +118,8 @@ struct MdPending {
     const uint8_t* species = nullptr;
     hipStream_t st = nullptr;
     long long report_g0 = 0;           // run reporter: completed MD steps in front of this run's first step
+    long long traj_g0 = 0;             // run recorder: the same, by its own counter
+    int traj_classes = 1;              // run recorder: 2 = water with species (O, H), else 1
 };
 
 // run reporter (gamd_report_*, report.hip): configuration, step count and the device-resident log / histogram
@@ -130,6 +132,20 @@ struct Reporter {
     float rmax = 0.f;
     long long g = 0;                   // completed MD steps since configure / reset, runs still in the stream included
     DevBuf steps, ke, counts, partial;
+};
+
+// run recorder (gamd_traj_*, traj.hip): configuration, step count, frames, image counters, ring and running sums
+struct Recorder {
+    long long interval = 0;            // 0: off — nothing is enqueued
+    long long sample_interval = 0;     // the interval g was counted with (stays when the recorder is switched off)
+    long long max_frames = 0;
+    int fields = 0, n_lags = 0, subtract_com = 0;
+    int classes = 0;                   // 0: no run since configure / reset; else the classes of the first run
+    long long g = 0;                   // completed MD steps since configure / reset, runs still in the stream included
+    std::vector<float> box0;           // [n_boxes][3] of the first run since configure / reset (empty: none yet)
+    DevBuf steps, fx, fv, ff, fimg;    // frames
+    DevBuf x_prev, image, ambiguous;
+    DevBuf ring_x, ring_img, ring_v, ring_com, com_partial, corr_partial, msd, vacf, class_atoms;
 };
 
 }  // namespace
@@ -201,6 +217,7 @@ struct gamd_handle {
     const uint8_t* rigid_checked = nullptr;   // species pointer whose O,H,H layout has been validated
     MdPending pending;
     Reporter rep;
+    Recorder rec;
     bool has_bonds = false;
 
     // Verlet-skin reuse (cfg.neighbor_skin > 0)
@@ -848,6 +865,70 @@ bool report_sampled(const gamd_handle* h, long long s) {
     return h->rep.interval > 0 && (h->pending.report_g0 + s + 1) % h->rep.interval == 0;
 }
 
+int enqueue_report_sample(gamd_handle* h, long long s);
+
+// run recorder: blocks per box of k_traj_corr / k_traj_com (fixed per handle: the summation tree never changes)
+int traj_corr_blocks(const gamd_handle* h) { return std::max(1, std::min(16, (h->n_per_box + 1023) / 1024)); }
+
+// run recorder: does step s of the pending run carry a sample?
+bool traj_sampled(const gamd_handle* h, long long s) {
+    return h->rec.interval > 0 && (h->pending.traj_g0 + s + 1) % h->rec.interval == 0;
+}
+
+// this step carries a reporter sample or a recorder sample: its second half must be complete in front of them
+bool step_sampled(const gamd_handle* h, long long s) { return report_sampled(h, s) || traj_sampled(h, s); }
+
+// the recorder's sample of step s of the pending run, behind its second half
+int enqueue_traj_sample(gamd_handle* h, long long s) {
+    const MdPending& p = h->pending;
+    const Recorder& rc = h->rec;
+    TrajArgs a{};
+    a.n = h->n;
+    a.bx = box_ref(h);
+    for (int d = 0; d < 3; ++d) a.box[d] = h->box[d];
+    a.devflags = h->devflags.as<int>();
+    a.x = p.x; a.f = p.f;
+    if (p.kind == 0) {
+        a.v = p.m.v; a.species = p.m.species;
+        a.mass = (double)p.mass; a.mass_h = (double)p.mass_h;
+    } else {
+        a.v = p.a.v; a.species = p.a.species;
+        a.mass = (double)p.a.mass; a.mass_h = (double)p.a.mass_h;
+    }
+    a.g = p.traj_g0 + s + 1;
+    a.q = a.g / rc.interval - 1;                        // the sample's ordinal, chosen here like the reporter's row
+    a.frame = a.q < rc.max_frames ? a.q : -1;
+    a.steps = rc.steps.as<long long>();
+    a.fx = rc.fx.as<float>(); a.fv = rc.fv.as<float>(); a.ff = rc.ff.as<float>(); a.fimg = rc.fimg.as<int>();
+    a.x_prev = rc.x_prev.as<float>();
+    a.image = rc.image.as<int>();
+    a.ambiguous = rc.ambiguous.as<unsigned long long>();
+    a.n_lags = rc.n_lags;
+    a.classes = p.traj_classes;
+    if (rc.n_lags > 0) {
+        a.slot = (int)(a.q % rc.n_lags);
+        a.active = (int)std::min<long long>(a.q, rc.n_lags - 1) + 1;
+        a.subtract_com = rc.subtract_com;
+        a.ring_x = rc.ring_x.as<float>(); a.ring_img = rc.ring_img.as<int>(); a.ring_v = rc.ring_v.as<float>();
+        a.ring_com = rc.ring_com.as<double>();
+        a.com_partial = rc.com_partial.as<double>();
+        a.com_blocks = a.corr_blocks = traj_corr_blocks(h);
+        a.corr_partial = rc.corr_partial.as<double>();
+        a.msd = rc.msd.as<double>(); a.vacf = rc.vacf.as<double>();
+        a.class_atoms = rc.class_atoms.as<long long>();
+    }
+    if (int r = launch_traj_sample(a, p.st)) return fail(-1, "recorder launch failed (%d)", r);
+    return 0;
+}
+
+// the samples of step s, behind its second half
+int enqueue_samples(gamd_handle* h, long long s) {
+    int r;
+    if (report_sampled(h, s) && (r = enqueue_report_sample(h, s))) return r;
+    if (traj_sampled(h, s) && (r = enqueue_traj_sample(h, s))) return r;
+    return 0;
+}
+
 // the sample of step s of the pending run, behind its second half: the kinetic-energy row and the frame's pair histogram
 int enqueue_report_sample(gamd_handle* h, long long s) {
     const MdPending& p = h->pending;
@@ -902,8 +983,8 @@ int enqueue_md_steps(gamd_handle* h, long long s_begin, bool skip_first) {
             if ((r = step_event(h, p.st))) return r;
             p.m.step = p.first_step + (unsigned long long)s;
             p.m.step_index = (int)s;
-            // (the B of a step that carries a reporter sample has been launched on its own, in front of the sample)
-            int do_second = (s > s_begin && !report_sampled(h, s - 1)) ? 1 : 0;
+            // (the B of a step that carries a reporter or recorder sample has been launched on its own, in front of the sample)
+            int do_second = (s > s_begin && !step_sampled(h, s - 1)) ? 1 : 0;
             const int do_first = (skip_first && s == s_begin) ? 0 : 1;
             if (p.m.com.enabled) {
                 // COM motion removal sits between the B of step s-1 and the first half of step s and needs a sum over all
@@ -929,15 +1010,15 @@ int enqueue_md_steps(gamd_handle* h, long long s_begin, bool skip_first) {
             if ((r = enqueue_forward(h, p.x, p.species, nullptr, p.f, p.st, nullptr, nullptr, nullptr, nullptr, &fuse,
                                      s + 1 == p.n_steps, s > s_begin)))
                 return r;
-            if (s + 1 < p.n_steps && report_sampled(h, s)) {      // a sampled step completes its B before the sample
+            if (s + 1 < p.n_steps && step_sampled(h, s)) {        // a sampled step completes its B before the sample
                 if ((r = launch_baoab_second(p.m, p.st))) return fail(-1, "integrator launch failed (%d)", r);
-                if ((r = enqueue_report_sample(h, s))) return r;
+                if ((r = enqueue_samples(h, s))) return r;
             }
         }
         if (p.n_steps > s_begin) {
             p.m.step_index = (int)(p.n_steps - 1);
             if ((r = launch_baoab_second(p.m, p.st))) return fail(-1, "integrator launch failed (%d)", r);
-            if (report_sampled(h, p.n_steps - 1) && (r = enqueue_report_sample(h, p.n_steps - 1))) return r;
+            if ((r = enqueue_samples(h, p.n_steps - 1))) return r;
         }
         return step_event(h, p.st, true);
     }
@@ -957,9 +1038,37 @@ int enqueue_md_steps(gamd_handle* h, long long s_begin, bool skip_first) {
             if ((r = enqueue_forward(h, p.x, p.species, nullptr, p.f, p.st, nullptr, nullptr, nullptr, nullptr, nullptr, last, s > s_begin))) return r;
             if ((r = launch_nhc_second(p.a, p.st))) return fail(-1, "integrator launch failed (%d)", r);
         }
-        if (report_sampled(h, s) && (r = enqueue_report_sample(h, s))) return r;
+        if ((r = enqueue_samples(h, s))) return r;
     }
     return step_event(h, p.st, true);
+}
+
+// run recorder, at the top of gamd_md_run / gamd_md_run_nhc: the image counters and the ring are only meaningful in one box
+// and with one set of classes
+int traj_run_classes(const gamd_handle* h, const uint8_t* species_dev) {
+    return (h->cfg.kind == GAMD_KIND_WATER && species_dev) ? 2 : 1;
+}
+int traj_check_run(gamd_handle* h, const float* box, const uint8_t* species_dev) {
+    const Recorder& rc = h->rec;
+    if (rc.interval <= 0) return 0;
+    if (rc.n_lags > 0 && rc.classes && rc.classes != traj_run_classes(h, species_dev))
+        return fail(-22, "run recorder: species given in one run and not in another since gamd_traj_configure / gamd_traj_reset");
+    if ((rc.n_lags > 0 || (rc.fields & GAMD_TRAJ_IMAGE)) && !rc.box0.empty())
+        for (size_t k = 0; k < rc.box0.size(); ++k)
+            if (rc.box0[k] != box[k])
+                return fail(-22, "run recorder: the box differs from the box of the first run since gamd_traj_configure / "
+                                 "gamd_traj_reset (image counters and correlation functions need one box; call gamd_traj_reset)");
+    return 0;
+}
+// ... and once the run is certain to be enqueued
+void traj_begin_run(gamd_handle* h, const float* box, const uint8_t* species_dev, long long n_steps) {
+    Recorder& rc = h->rec;
+    h->pending.traj_g0 = rc.g;
+    h->pending.traj_classes = traj_run_classes(h, species_dev);
+    if (rc.interval <= 0) return;
+    if (rc.box0.empty()) rc.box0.assign(box, box + 3 * (size_t)h->n_boxes);
+    if (!rc.classes) rc.classes = h->pending.traj_classes;
+    rc.g += n_steps;
 }
 
 }  // namespace
@@ -1146,6 +1255,9 @@ int32_t gamd_destroy(gamd_handle* h) {
                       &h->cell_cnt, &h->cell_fill, &h->cell_start, &h->col, &h->erow, &h->chunk_piece,
                       &h->chunk_mask, &h->e_frag, &h->e_emb, &h->e_frag2, &h->partial, &h->feat_dbg, &h->counters, &h->tdbg, &h->tmp_eid, &h->ke_partial, &h->com_partial,
                       &h->rep.steps, &h->rep.ke, &h->rep.counts, &h->rep.partial,
+                      &h->rec.steps, &h->rec.fx, &h->rec.fv, &h->rec.ff, &h->rec.fimg, &h->rec.x_prev, &h->rec.image, &h->rec.ambiguous,
+                      &h->rec.ring_x, &h->rec.ring_img, &h->rec.ring_v, &h->rec.ring_com, &h->rec.com_partial, &h->rec.corr_partial,
+                      &h->rec.msd, &h->rec.vacf, &h->rec.class_atoms,
                       &h->ref_pos, &h->cand_deg, &h->cand_ptr, &h->cand_col};
     for (DevBuf* b : bufs) b->release();
     h->pos_in.release();
@@ -1827,6 +1939,7 @@ int32_t gamd_md_run(gamd_handle* h, float* x_dev, float* v_dev, float* f_dev, co
     if (!x_dev || !v_dev || !f_dev || !box || !p) return fail(-22, "null argument");
     if (n_steps < 0 || n_steps > 0x3fffffff) return fail(-22, "n_steps out of range");
     if ((r = check_model_inputs(h, species_dev))) return r;
+    if ((r = traj_check_run(h, box, species_dev))) return r;
     DeviceGuard guard(h->dev);
     InitStream init((hipStream_t)stream);
     if ((r = set_box(h, box, (hipStream_t)stream))) return r;
@@ -1857,6 +1970,7 @@ int32_t gamd_md_run(gamd_handle* h, float* x_dev, float* v_dev, float* f_dev, co
     pd.x = x_dev; pd.f = f_dev; pd.species = species_dev; pd.st = st;
     pd.report_g0 = h->rep.g;
     if (h->rep.interval > 0) h->rep.g += n_steps;
+    traj_begin_run(h, box, species_dev, n_steps);
     return enqueue_md_steps(h, 0, false);
 }
 
@@ -1874,6 +1988,7 @@ int32_t gamd_md_run_nhc(gamd_handle* h, float* x_dev, float* v_dev, float* f_dev
                                  0.2967324292201065};                       // hack_integrator.py:183-187
     const double* ys = p->num_yoshidasuzuki == 1 ? YS1 : p->num_yoshidasuzuki == 3 ? YS3 : p->num_yoshidasuzuki == 5 ? YS5 : nullptr;
     if (!ys) return fail(-22, "Invalid Yoshida-Suzuki value. Allowed values are: 1,3,5");
+    if ((r = traj_check_run(h, box, species_dev))) return r;
     DeviceGuard guard(h->dev);
     InitStream init((hipStream_t)stream);
     if ((r = set_box(h, box, (hipStream_t)stream))) return r;
@@ -1914,6 +2029,7 @@ int32_t gamd_md_run_nhc(gamd_handle* h, float* x_dev, float* v_dev, float* f_dev
     pd.x = x_dev; pd.f = f_dev; pd.species = species_dev; pd.st = st;
     pd.report_g0 = h->rep.g;
     if (h->rep.interval > 0) h->rep.g += n_steps;
+    traj_begin_run(h, box, species_dev, n_steps);
     return enqueue_md_steps(h, 0, false);
 }
 
@@ -2004,6 +2120,123 @@ int32_t gamd_report_read(gamd_handle* h, void* stream, int64_t* steps, double* k
     if (frames) *frames = (rp.bins > 0 && rp.counts.p) ? taken : 0;
     if (dropped) *dropped = taken - rows;
     if (dims) { dims[0] = (int32_t)nb; dims[1] = rp.pairs; dims[2] = rp.counts.p ? rp.bins : 0; }
+    return 0;
+}
+
+static_assert(sizeof(gamd_traj_params) == 32 && offsetof(gamd_traj_params, fields) == 16 && offsetof(gamd_traj_params, n_lags) == 20 &&
+              offsetof(gamd_traj_params, subtract_com) == 24,
+              "gamd_traj_params layout is part of the C ABI (gamd_amd/_lib.py mirrors it)");
+
+// clear the recorder's step count, frames, image counters, ring and sums (on the init stream, landed before it returns)
+static int traj_clear(gamd_handle* h) {
+    Recorder& rc = h->rec;
+    rc.g = 0;
+    rc.classes = 0;
+    rc.box0.clear();
+    DevBuf* bufs[] = {&rc.steps, &rc.fx, &rc.fv, &rc.ff, &rc.fimg, &rc.x_prev, &rc.image, &rc.ambiguous, &rc.ring_x, &rc.ring_img,
+                      &rc.ring_v, &rc.ring_com, &rc.msd, &rc.vacf, &rc.class_atoms};
+    for (DevBuf* b : bufs)
+        if (b->p) HIP_TRY(hipMemsetAsync(b->p, 0, b->bytes, tl_init_stream));
+    HIP_TRY(hipStreamSynchronize(tl_init_stream));
+    return 0;
+}
+
+int32_t gamd_traj_configure(gamd_handle* h, const gamd_traj_params* p) {
+    if (!p) return fail(-22, "null argument");
+    if (p->interval < 0) return fail(-22, "interval = %lld is negative", (long long)p->interval);
+    if (p->max_frames < 0 || p->max_frames > (1ll << 24)) return fail(-22, "max_frames = %lld outside [0, 2^24]", (long long)p->max_frames);
+    if (p->fields & ~(GAMD_TRAJ_X | GAMD_TRAJ_V | GAMD_TRAJ_F | GAMD_TRAJ_IMAGE)) return fail(-22, "fields = %d has unknown bits", (int)p->fields);
+    if (p->n_lags < 0 || p->n_lags > 4096) return fail(-22, "n_lags = %d outside [0, 4096]", (int)p->n_lags);
+    if (!h) return fail(-22, "null handle");
+    if (p->n_lags > 0 && h->n_boxes > 65535) return fail(-22, "correlation functions need n_boxes <= 65535");
+    Recorder& rc = h->rec;
+    if (h->pending.active) return fail(-22, "an MD run is still enqueued: call gamd_sync_status before gamd_traj_configure");
+    if (p->interval == 0) { rc.interval = 0; return 0; }        // off: what was recorded stays readable
+    DeviceGuard guard(h->dev);
+    InitStream init(h->init_stream);
+    rc.interval = 0;
+    rc.max_frames = p->max_frames;
+    rc.fields = p->fields;
+    rc.n_lags = p->n_lags;
+    rc.subtract_com = (p->subtract_com && p->n_lags > 0) ? 1 : 0;
+    const size_t nb = (size_t)h->n_boxes, n3 = 3 * (size_t)h->n, fr = (size_t)rc.max_frames, lags = (size_t)rc.n_lags;
+    const size_t cls = h->cfg.kind == GAMD_KIND_WATER ? 2 : 1, blocks = (size_t)traj_corr_blocks(h);
+    // exact sizes (a smaller configuration after a larger one re-allocates: traj_clear and the read calls go by bytes)
+    DevBuf* bufs[] = {&rc.steps, &rc.fx, &rc.fv, &rc.ff, &rc.fimg, &rc.x_prev, &rc.image, &rc.ambiguous, &rc.ring_x, &rc.ring_img,
+                      &rc.ring_v, &rc.ring_com, &rc.com_partial, &rc.corr_partial, &rc.msd, &rc.vacf, &rc.class_atoms};
+    const size_t want[] = {sizeof(long long) * fr,
+                           (rc.fields & GAMD_TRAJ_X) ? sizeof(float) * fr * n3 : 0, (rc.fields & GAMD_TRAJ_V) ? sizeof(float) * fr * n3 : 0,
+                           (rc.fields & GAMD_TRAJ_F) ? sizeof(float) * fr * n3 : 0, (rc.fields & GAMD_TRAJ_IMAGE) ? sizeof(int) * fr * n3 : 0,
+                           sizeof(float) * n3, sizeof(int) * n3, sizeof(unsigned long long),
+                           sizeof(float) * lags * n3, sizeof(int) * lags * n3, sizeof(float) * lags * n3,
+                           rc.subtract_com ? sizeof(double) * lags * nb * 3 : 0, rc.subtract_com ? sizeof(double) * nb * blocks * 4 : 0,
+                           sizeof(double) * nb * lags * blocks * cls * 2, sizeof(double) * nb * cls * lags, sizeof(double) * nb * cls * lags,
+                           lags ? sizeof(long long) * nb * cls : 0};
+    for (int k = 0; k < 17; ++k) {
+        if (bufs[k]->bytes != want[k]) bufs[k]->release();
+        if (want[k] && bufs[k]->ensure(want[k], true)) return fail(-12, "recorder allocation failed");
+    }
+    int r;
+    if ((r = traj_clear(h))) return r;
+    rc.interval = rc.sample_interval = p->interval;
+    return 0;
+}
+
+int32_t gamd_traj_reset(gamd_handle* h) {
+    if (!h) return fail(-22, "null handle");
+    if (h->pending.active) return fail(-22, "an MD run is still enqueued: call gamd_sync_status before gamd_traj_reset");
+    DeviceGuard guard(h->dev);
+    InitStream init(h->init_stream);
+    return traj_clear(h);
+}
+
+int32_t gamd_traj_read_frames(gamd_handle* h, void* stream, int64_t first, int64_t count, int64_t* steps, float* x, float* v,
+                              float* f, int32_t* image, int64_t* n_frames, int64_t* dropped) {
+    if (!h) return fail(-22, "null handle");
+    if (first < 0 || count < 0) return fail(-22, "first / count is negative");
+    const Recorder& rc = h->rec;
+    DeviceGuard guard(h->dev);
+    hipStream_t st = (hipStream_t)stream;
+    const long long taken = (rc.sample_interval > 0 && rc.x_prev.p) ? rc.g / rc.sample_interval : 0;
+    const long long kept = std::min<long long>(taken, rc.max_frames);
+    const long long n_copy = std::max<long long>(0, std::min<long long>(kept - first, count));
+    const size_t n3 = 3 * (size_t)h->n;
+    if (n_copy > 0) {
+        const size_t off = (size_t)first * n3, elems = (size_t)n_copy * n3;
+        if (steps) HIP_TRY(hipMemcpyAsync(steps, rc.steps.as<long long>() + first, sizeof(int64_t) * (size_t)n_copy, hipMemcpyDeviceToHost, st));
+        if (x && rc.fx.p) HIP_TRY(hipMemcpyAsync(x, rc.fx.as<float>() + off, sizeof(float) * elems, hipMemcpyDeviceToHost, st));
+        if (v && rc.fv.p) HIP_TRY(hipMemcpyAsync(v, rc.fv.as<float>() + off, sizeof(float) * elems, hipMemcpyDeviceToHost, st));
+        if (f && rc.ff.p) HIP_TRY(hipMemcpyAsync(f, rc.ff.as<float>() + off, sizeof(float) * elems, hipMemcpyDeviceToHost, st));
+        if (image && rc.fimg.p) HIP_TRY(hipMemcpyAsync(image, rc.fimg.as<int>() + off, sizeof(int32_t) * elems, hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    if (int t = check_traps(h)) return t;
+    if (n_frames) *n_frames = kept;
+    if (dropped) *dropped = taken - kept;
+    return 0;
+}
+
+int32_t gamd_traj_read_dynamics(gamd_handle* h, void* stream, double* msd_sum, double* vacf_sum, int64_t elems, int64_t* n_samples,
+                                uint64_t* ambiguous, int64_t* class_atoms, int32_t dims[3]) {
+    if (!h) return fail(-22, "null handle");
+    const Recorder& rc = h->rec;
+    DeviceGuard guard(h->dev);
+    hipStream_t st = (hipStream_t)stream;
+    const long long nb = h->n_boxes, cls = rc.msd.p ? rc.classes : 0, lags = rc.msd.p ? rc.n_lags : 0;
+    const long long taken = (rc.sample_interval > 0 && rc.x_prev.p) ? rc.g / rc.sample_interval : 0;
+    const long long need = nb * cls * lags;
+    if ((msd_sum || vacf_sum) && elems < need) return fail(-22, "msd_sum / vacf_sum have room for %lld elements, the sums have %lld", (long long)elems, need);
+    if (need > 0 && msd_sum) HIP_TRY(hipMemcpyAsync(msd_sum, rc.msd.p, sizeof(double) * (size_t)need, hipMemcpyDeviceToHost, st));
+    if (need > 0 && vacf_sum) HIP_TRY(hipMemcpyAsync(vacf_sum, rc.vacf.p, sizeof(double) * (size_t)need, hipMemcpyDeviceToHost, st));
+    if (ambiguous) {
+        *ambiguous = 0;
+        if (rc.ambiguous.p) HIP_TRY(hipMemcpyAsync(ambiguous, rc.ambiguous.p, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    }
+    if (class_atoms && nb * cls > 0) HIP_TRY(hipMemcpyAsync(class_atoms, rc.class_atoms.p, sizeof(int64_t) * (size_t)(nb * cls), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (int t = check_traps(h)) return t;
+    if (n_samples) *n_samples = taken;
+    if (dims) { dims[0] = (int32_t)nb; dims[1] = (int32_t)cls; dims[2] = (int32_t)lags; }
     return 0;
 }
 

@@ -456,3 +456,44 @@ struct ReportArgs {
 };
 int launch_report_ke(const ReportArgs& a, hipStream_t st);
 int launch_report_rdf(const ReportArgs& a, hipStream_t st);
+
+// ---- run recorder (traj.hip) --------------------------------------------------------------------
+// One sample of an enqueued MD run (gamd_traj_configure): trajectory frame q, the periodic-image counters, and the
+// MSD / VACF sums over the ring of the last n_lags samples.  Sample ordinal, frame slot and ring slot come from the host;
+// the image counters, x_prev, the ring and the running sums are updated in place and rely on the freeze gate alone (a
+// kernel that returned changed nothing, and a sample runs exactly once unfrozen).
+// (No recorder kernel uses a value it read from memory as an address: the checked build has nothing to range-check here.)
+struct TrajArgs {
+    int n;                     // atoms of all boxes
+    BoxRef bx;
+    float box[3];              // n_boxes <= 1
+    const int* devflags;       // DEVFLAG_FROZEN set: every recorder kernel returns at once
+    const float* x; const float* v; const float* f;    // [n][3] the caller's buffers
+    const uint8_t* species;    // [n] or null
+    double mass, mass_h;       // amu; species-0 atoms use mass_h when it is > 0 (the COM of subtract_com)
+    long long q;               // sample ordinal (g / interval - 1)
+    long long g;               // completed MD steps at this sample
+    // frames
+    long long frame;           // q when q < max_frames, else -1
+    long long* steps;          // [max_frames]
+    float* fx; float* fv; float* ff; int* fimg;        // [max_frames][n][3] or null (field not recorded)
+    // image bookkeeping
+    float* x_prev;             // [n][3] positions at the previous sample
+    int* image;                // [n][3]
+    unsigned long long* ambiguous;
+    // correlation functions
+    int n_lags;                // 0: none
+    int slot;                  // q % n_lags
+    int active;                // min(q, n_lags - 1) + 1 lags have an origin in the ring
+    int classes;               // 1, or 2 (O, H)
+    int subtract_com;
+    float* ring_x; int* ring_img; float* ring_v;       // [n_lags][n][3]
+    double* ring_com;          // [n_lags][n_boxes][3] mass-weighted mean of the unwrapped positions
+    double* com_partial;       // [n_boxes][com_blocks][4]
+    int com_blocks;
+    double* corr_partial;      // [n_boxes][n_lags][corr_blocks][classes][2]
+    int corr_blocks;           // workgroups per box and lag (fixed per handle)
+    double* msd; double* vacf; // [n_boxes][classes][n_lags] running sums
+    long long* class_atoms;    // [n_boxes][classes]
+};
+int launch_traj_sample(const TrajArgs& a, hipStream_t st);     // frame, images, ring; with n_lags > 0 also COM and the sums

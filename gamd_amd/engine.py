@@ -9,13 +9,14 @@ is in libgamd_hip.so.
 from __future__ import annotations
 
 import ctypes as C
+import os
 from typing import Dict, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
 
 from . import _lib
-from ._lib import GamdReportParams, GamdConfig, GamdMdParams, GamdNhcParams, check
+from ._lib import GamdReportParams, GamdTrajParams, GamdConfig, GamdMdParams, GamdNhcParams, TRAJ_FIELDS, check
 from .weights import ModelConfig, infer_config, validate_state_dict
 
 ArrayLike = Union[np.ndarray, torch.Tensor]
@@ -102,6 +103,102 @@ class RunReport:
                 row = [str(k * int(g)), str(k * int(g) * float(dt_ps)), str(float(self.ke[i, box])),
                        str(float(self.temperature[i, box]))]
                 fh.write(separator.join(row) + "\n")
+
+
+class RunTrajectory:
+    """What the run recorder kept (GamdForce.traj_read).  Host-only: plain arrays in, plain arrays out.
+
+    steps [F] int64: completed MD steps g of each kept frame; x, v, f float32 and image int32 [F, B, n, 3] in the caller's
+    atom order, or None when the field was not recorded; dropped: samples that found the frame buffer full; ambiguous:
+    (atom, sample) pairs that moved more than a quarter of a box edge between two samples (the image counters assume less
+    than half); n_samples: samples taken = time origins Q; class_atoms [B, classes]; msd_sum, vacf_sum [B, classes, n_lags]:
+    the device's sums over origins and atoms; interval: MD steps between two samples (one lag)."""
+
+    def __init__(self, steps=None, x=None, v=None, f=None, image=None, dropped: int = 0, ambiguous: int = 0,
+                 n_samples: int = 0, class_atoms=None, msd_sum=None, vacf_sum=None, interval: int = 1):
+        def arr(a, dt):
+            return None if a is None else np.asarray(a, dtype=dt)
+        self.steps = np.zeros(0, dtype=np.int64) if steps is None else np.asarray(steps, dtype=np.int64)
+        self.x, self.v, self.f = arr(x, np.float32), arr(v, np.float32), arr(f, np.float32)
+        self.image = arr(image, np.int32)
+        self.dropped, self.ambiguous, self.n_samples = int(dropped), int(ambiguous), int(n_samples)
+        self.class_atoms = None if class_atoms is None else np.atleast_2d(np.asarray(class_atoms, dtype=np.int64))
+        self.msd_sum, self.vacf_sum = arr(msd_sum, np.float64), arr(vacf_sum, np.float64)
+        self.interval = int(interval)
+
+    @property
+    def n_lags(self) -> int:
+        return 0 if self.msd_sum is None else int(self.msd_sum.shape[-1])
+
+    def unwrapped(self, box) -> np.ndarray:
+        """float64 [F, B, n, 3] unwrapped positions x + image * L.  ``box``: scalar, [3], [B, 1] or [B, 3] edge lengths
+        (used as their fp32 values, like the library)."""
+        if self.x is None or self.image is None:
+            raise ValueError("unwrapped needs the fields x and image")
+        L = _boxes(box, self.x.shape[1]).astype(np.float64)
+        return self.x.astype(np.float64) + self.image.astype(np.float64) * L[None, :, None, :]
+
+    def _normalised(self, sums, box: int) -> np.ndarray:
+        if sums is None or self.n_lags == 0:
+            raise ValueError("no correlation functions were recorded (n_lags = 0)")
+        origins = (self.n_samples - np.arange(self.n_lags)).astype(np.float64)             # Q - j
+        den = np.where(origins > 0, origins, np.nan)[None, :] * self.class_atoms[box].astype(np.float64)[:, None]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return np.where(den > 0, sums[box] / den, np.nan)
+
+    def msd(self, box: int = 0) -> np.ndarray:
+        """[classes, n_lags] mean-squared displacement of box ``box`` in (length unit)^2: msd_sum / ((Q - j) class_atoms);
+        NaN where no origin has that lag yet."""
+        return self._normalised(self.msd_sum, box)
+
+    def vacf(self, box: int = 0) -> np.ndarray:
+        """[classes, n_lags] <v(t) . v(0)> of box ``box`` in (length unit / ps)^2, normalised like ``msd``."""
+        return self._normalised(self.vacf_sum, box)
+
+    def lag_times(self, dt_ps: float) -> np.ndarray:
+        return np.arange(self.n_lags, dtype=np.float64) * (self.interval * float(dt_ps))
+
+    def diffusion_msd(self, box: int, cls: int, dt_ps: float, fit: Tuple[int, int], length_per_nm: float = 0.0) -> float:
+        """Einstein relation: the unweighted least-squares slope (with an intercept) of MSD against time over the lags
+        fit = (lo, hi), both included, divided by 6.  In (length unit)^2 / ps, or nm^2 / ps when ``length_per_nm`` is given."""
+        lo, hi = int(fit[0]), int(fit[1])
+        if not 0 <= lo < hi < self.n_lags:
+            raise ValueError(f"fit = ({lo}, {hi}) must satisfy 0 <= lo < hi < n_lags = {self.n_lags}")
+        t = self.lag_times(dt_ps)[lo:hi + 1]
+        y = self.msd(box)[cls, lo:hi + 1]
+        tc = t - t.mean()
+        d = float((tc * (y - y.mean())).sum() / (tc * tc).sum()) / 6.0
+        return d / float(length_per_nm) ** 2 if length_per_nm else d
+
+    def diffusion_green_kubo(self, box: int, cls: int, dt_ps: float, upto: int, length_per_nm: float = 0.0) -> float:
+        """Green-Kubo: the trapezoid integral of the VACF over the lags 0 .. upto (included), divided by 3."""
+        upto = int(upto)
+        if not 0 < upto < self.n_lags:
+            raise ValueError(f"upto = {upto} must satisfy 0 < upto < n_lags = {self.n_lags}")
+        c = self.vacf(box)[cls, :upto + 1]
+        h = self.interval * float(dt_ps)
+        d = float(h * (0.5 * c[0] + c[1:-1].sum() + 0.5 * c[-1])) / 3.0
+        return d / float(length_per_nm) ** 2 if length_per_nm else d
+
+    def write_dataset(self, dir, seed: int, prefix: str = "data_", length_per_nm: float = 0.0) -> list:
+        """One ``{prefix}{seed}_{t}.npz`` per kept frame t of box 0, in the layout and units of the reference's data
+        generators (dataset/generate_lj_data.py:100-106), which train_utils.LJDataNew / WaterDataNew open: ``pos`` in
+        Angstrom, ``vel`` in m/s (Angstrom/ps x 100; when recorded), ``forces`` in kJ/mol/nm (when recorded); float32,
+        caller order.  ``length_per_nm``: the run's length unit (0 or 10 = Angstrom, 18.8972613 = bohr).  Returns the paths."""
+        if self.x is None:
+            raise ValueError("write_dataset needs the field x")
+        to_angstrom = np.float64(10.0) / np.float64(np.float32(length_per_nm)) if length_per_nm else np.float64(1.0)
+        os.makedirs(dir, exist_ok=True)
+        paths = []
+        for t in range(self.x.shape[0]):
+            out = {"pos": (self.x[t, 0].astype(np.float64) * to_angstrom).astype(np.float32)}
+            if self.v is not None:
+                out["vel"] = (self.v[t, 0].astype(np.float64) * (to_angstrom * 100.0)).astype(np.float32)
+            if self.f is not None:
+                out["forces"] = self.f[t, 0].astype(np.float32)
+            paths.append(os.path.join(dir, f"{prefix}{seed}_{t}.npz"))
+            np.savez(paths[-1], **out)
+        return paths
 
 
 class GamdForce:
@@ -547,6 +644,54 @@ class GamdForce:
                  C.byref(frames), C.byref(dropped), dims), "gamd_report_read")
         return RunReport(steps, ke, temp, counts, frames.value, dropped.value, getattr(self, "_report_rmax", 0.0),
                          np.prod(_boxes(self.box, self.n_boxes).astype(np.float64), axis=1))
+
+    # -- run recorder (trajectory frames, image counters, MSD / VACF, taken inside enqueued runs) ---------------------
+    def traj_configure(self, interval: int, max_frames: int = 0, fields: Sequence[str] = ("x",), n_lags: int = 0,
+                       subtract_com: bool = False) -> None:
+        """While configured, every ``interval``-th completed step of md_run / md_run_nhc (counted across calls) keeps a
+        frame of the ``fields`` (any of "x", "v", "f", "image") on the device, up to ``max_frames`` frames, and with
+        ``n_lags`` > 0 adds to the mean-squared-displacement and velocity-autocorrelation sums for the lags
+        0 .. n_lags - 1 (in units of ``interval``), every sample a time origin; ``traj_read`` fetches both.
+        ``subtract_com``: displacements relative to the box's centre of mass.  ``interval`` = 0 switches it off.
+        Replaces the ``getState`` / ``np.savez`` loop of the data generators (dataset/generate_lj_data.py:93-107)."""
+        bits = 0
+        for name in ((fields,) if isinstance(fields, str) else fields):
+            if name not in TRAJ_FIELDS:
+                raise ValueError(f"fields must be among {sorted(TRAJ_FIELDS)}, got {name!r}")
+            bits |= TRAJ_FIELDS[name]
+        p = GamdTrajParams(int(interval), int(max_frames), bits, int(n_lags), int(bool(subtract_com)), 0)
+        check(self._lib.gamd_traj_configure(self._h, C.byref(p)), "gamd_traj_configure")
+        if interval:
+            self._traj_cfg = (int(interval), bits)
+
+    def traj_reset(self) -> None:
+        """Step count, frames, image counters, ring and sums back to zero; the configuration stays."""
+        check(self._lib.gamd_traj_reset(self._h), "gamd_traj_reset")
+
+    def traj_read(self) -> "RunTrajectory":
+        """Synchronise and fetch what the recorder has kept since it was configured or reset."""
+        interval, bits = getattr(self, "_traj_cfg", (1, 0))
+        n_frames, dropped, n_samples, amb = C.c_int64(), C.c_int64(), C.c_int64(), C.c_uint64()
+        dims = (C.c_int32 * 3)()
+        st = self._stream()
+        check(self._lib.gamd_traj_read_frames(self._h, st, 0, 0, None, None, None, None, None, C.byref(n_frames), C.byref(dropped)),
+              "gamd_traj_read_frames")
+        check(self._lib.gamd_traj_read_dynamics(self._h, st, None, None, 0, C.byref(n_samples), C.byref(amb), None, dims),
+              "gamd_traj_read_dynamics")
+        fr, (nb, ncls, nlags) = n_frames.value, dims
+        vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        shape = (fr, self.n_boxes, self.n, 3)
+        steps = np.zeros(fr, dtype=np.int64)
+        x, v, f = (np.zeros(shape, dtype=np.float32) if bits & TRAJ_FIELDS[k] else None for k in ("x", "v", "f"))
+        image = np.zeros(shape, dtype=np.int32) if bits & TRAJ_FIELDS["image"] else None
+        check(self._lib.gamd_traj_read_frames(self._h, st, 0, fr, vp(steps), vp(x), vp(v), vp(f), vp(image), C.byref(n_frames),
+                                              C.byref(dropped)), "gamd_traj_read_frames")
+        msd = np.zeros((nb, ncls, nlags), dtype=np.float64)
+        vacf = np.zeros((nb, ncls, nlags), dtype=np.float64)
+        cls_atoms = np.zeros((nb, ncls), dtype=np.int64)
+        check(self._lib.gamd_traj_read_dynamics(self._h, st, vp(msd), vp(vacf), msd.size, C.byref(n_samples), C.byref(amb),
+                                                vp(cls_atoms), dims), "gamd_traj_read_dynamics")
+        return RunTrajectory(steps, x, v, f, image, dropped.value, amb.value, n_samples.value, cls_atoms, msd, vacf, interval)
 
     def sync_status(self) -> int:
         """0, or 1 when an enqueued MD run overflowed a neighbour buffer, froze on the device and was resumed."""

@@ -322,6 +322,62 @@ int32_t gamd_report_read(gamd_handle* h, void* stream, int64_t* steps, double* k
                          int64_t* n_rows, uint64_t* counts, int64_t count_elems, int64_t* frames, int64_t* dropped,
                          int32_t dims[3]);
 
+/* Run recorder: the trajectory the reference's data generators dump every 50 steps (pos / vel / forces,
+ * dataset/generate_lj_data.py:93-106, read back by train_utils.LJDataNew / WaterDataNew) and the dynamical observables that
+ * need the UNWRAPPED displacement, kept ON THE DEVICE while gamd_md_run / gamd_md_run_nhc are enqueued.
+ * The recorder counts the completed MD steps g of the handle since it was configured or reset (across calls, with a counter
+ * of its own: its interval is independent of the reporter's).  Step g is sampled when g % interval == 0, behind its second
+ * half (for rigid water: behind the velocity constraint), where the reporter samples.  Sample ordinal q = g / interval - 1.
+ *   - Frame: a sample with q < max_frames stores the selected fields in the caller's atom order: x, v, f fp32
+ *     [n_boxes][n][3], the bits of the caller's buffers at that point; image int32 [n_boxes][n][3]; and the step number g.
+ *     Later samples are counted as dropped (the sums below still cover them).
+ *   - Image counters: the integrators wrap positions into the box every step, so the recorder keeps the positions of the
+ *     previous sample and an int32 count per atom and component: image = 0 at q = 0; afterwards d = x - x_prev,
+ *     k = rint(d / L) in double, image -= k, so that u = (double)x + (double)image * (double)L is the unwrapped coordinate
+ *     (L: the fp32 edge of the atom's box).  Exact as long as no atom moves L / 2 or more between two samples; every
+ *     (atom, sample) with a component where |d - k L| > L / 4 is counted in a 64-bit `ambiguous` counter.  Rigid water needs
+ *     nothing special (a molecule is re-wrapped by a lattice vector).  The counters belong to ONE box geometry: while n_lags > 0
+ *     or GAMD_TRAJ_IMAGE is set, a run whose box differs from the box of the first run since configure / reset returns -22.
+ *   - Correlation functions (n_lags > 0): every sample is a time origin; a device ring of n_lags slots holds each origin's
+ *     x, image, v.  At sample q, for every lag j = 0 .. min(q, n_lags - 1) with origin o = q - j, per box b and class c:
+ *       msd_sum[b][c][j]  += sum_i |du_i|^2,   du_i = (x_q - x_o) + (image_q - image_o) L   (every operand widened to double)
+ *       vacf_sum[b][c][j] += sum_i v_i(q) . v_i(o)
+ *     in (length unit of the run)^2 and (length unit / ps)^2.  subtract_com: du_i is taken relative to the displacement of
+ *     the box's mass-weighted mean of u (masses: the run's mass_amu / mass_h_amu).  Classes: one for GAMD_KIND_LJ handles
+ *     or a NULL species_dev; two for water: species flag != 0 (O) is class 0, H is class 1 (the same in every run since
+ *     configure / reset, or -22).  The host normalises with (Q - j) * class_atoms[b][c], Q = number of samples.  Double sums
+ *     in a fixed order, no floating-point atomics: the same bits run after run.
+ * Nothing synchronises or returns to the host inside a run; a run that froze on a neighbour-buffer overflow and was resumed
+ * by gamd_sync_status gives the frames and sums of an ample buffer.  A handle whose recorder is off (the default) enqueues
+ * exactly what it enqueues without one; with it on, skin-mode runs launch the second half of a SAMPLED step on its own. */
+enum { GAMD_TRAJ_X = 1, GAMD_TRAJ_V = 2, GAMD_TRAJ_F = 4, GAMD_TRAJ_IMAGE = 8 };
+typedef struct gamd_traj_params {
+    int64_t interval;      /* 0 = recorder off (buffers kept); > 0: sample every interval-th completed step */
+    int64_t max_frames;    /* frames kept (first max_frames samples; later ones are counted as dropped); 0 = keep no frames */
+    int32_t fields;        /* GAMD_TRAJ_* bit mask of what a kept frame holds */
+    int32_t n_lags;        /* 0 = no correlation functions; else lags 0 .. n_lags-1 in units of interval, at most 4096 */
+    int32_t subtract_com;  /* 1 = MSD of displacements relative to the box's mass-weighted centre-of-mass displacement */
+    int32_t reserved;      /* 0 */
+} gamd_traj_params;
+/* p: HOST.  Allocates and clears frames, image counters, ring and sums (drains nothing: call it between runs, after
+ * gamd_sync_status).  Device memory: 24 B per atom, 12 B per atom, field and frame, 36 B per atom and lag.  -22 for a negative
+ * interval or max_frames, unknown field bits, n_lags outside [0, 4096], or while a run is pending; -12 when an allocation fails. */
+int32_t gamd_traj_configure(gamd_handle* h, const gamd_traj_params* p);
+/* Step count g = 0; frames, image counters, ring and sums cleared (the next run may use another box); the configuration stays. */
+int32_t gamd_traj_reset(gamd_handle* h);
+/* Synchronises `stream` once (it does NOT resume a frozen run: call gamd_sync_status first) and copies frames
+ * [first, first + count) that exist to HOST arrays, any of which may be NULL (a field that was not recorded is left
+ * untouched): steps int64 [count], x / v / f float and image int32 [count][n_boxes][n][3].  *n_frames = frames kept in all,
+ * *dropped = samples that found the frame buffer full. */
+int32_t gamd_traj_read_frames(gamd_handle* h, void* stream, int64_t first, int64_t count, int64_t* steps,
+                              float* x, float* v, float* f, int32_t* image, int64_t* n_frames, int64_t* dropped);
+/* Synchronises `stream` once and copies to HOST arrays, any of which may be NULL: msd_sum and vacf_sum double
+ * [n_boxes][classes][n_lags] (elems = room in elements of each; fewer than that product is -22), *n_samples = samples taken
+ * (time origins Q), *ambiguous = the counter above, class_atoms int64 [n_boxes][classes], dims[0..2] = n_boxes, classes,
+ * n_lags (classes is 0 until the first run since configure / reset). */
+int32_t gamd_traj_read_dynamics(gamd_handle* h, void* stream, double* msd_sum, double* vacf_sum, int64_t elems,
+                                int64_t* n_samples, uint64_t* ambiguous, int64_t* class_atoms, int32_t dims[3]);
+
 /* Event-timed replay of one force evaluation: per-kernel milliseconds of the last gamd_profile call.
  * names: newline-separated kernel labels; ms: one float per label.  For bench.py's roofline block. */
 int32_t gamd_profile(gamd_handle* h, const float* pos_dev, const uint8_t* species_dev, const float* box,
