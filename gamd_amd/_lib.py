@@ -50,6 +50,11 @@ class GamdTrajParams(C.Structure):
                 ("subtract_com", C.c_int32), ("reserved", C.c_int32)]
 
 
+class GamdStructParams(C.Structure):
+    _fields_ = [("interval", C.c_int64), ("rdf_bins", C.c_int32), ("rdf_rmax", C.c_float), ("exclude_same_molecule", C.c_int32),
+                ("sk_n2max", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
 TRAJ_FIELDS = {"x": 1, "v": 2, "f": 4, "image": 8}          # GAMD_TRAJ_*
 
 
@@ -85,6 +90,9 @@ SYMBOLS = {
     "gamd_traj_reset": (_i32, [_vp]),
     "gamd_traj_read_frames": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64)]),
     "gamd_traj_read_dynamics": (_i32, [_vp, _vp, _vp, _vp, _i64, C.POINTER(_i64), C.POINTER(C.c_uint64), _vp, C.POINTER(_i32)]),
+    "gamd_struct_configure": (_i32, [_vp, C.POINTER(GamdStructParams)]),
+    "gamd_struct_reset": (_i32, [_vp]),
+    "gamd_struct_read": (_i32, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, C.POINTER(_i64), C.POINTER(_i32)]),
     "gamd_profile": (_i32, [_vp, _vp, _vp, C.POINTER(C.c_float), _vp, _vp, C.c_char_p, C.c_size_t,
                             C.POINTER(C.c_float), _i32, C.POINTER(_i32)]),
     "gamd_timing_enable": (_i32, [_vp, _i32]),

@@ -4,6 +4,7 @@
 #include "gamd_internal.h"
 
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdarg>
 #include <cstddef>
@@ -120,6 +121,7 @@ struct MdPending {
     long long report_g0 = 0;           // run reporter: completed MD steps in front of this run's first step
     long long traj_g0 = 0;             // run recorder: the same, by its own counter
     int traj_classes = 1;              // run recorder: 2 = water with species (O, H), else 1
+    long long struct_g0 = 0;           // structure sampler: completed MD steps in front of this run's first step, by its own counter
 };
 
 // run reporter (gamd_report_*, report.hip): configuration, step count and the device-resident log / histogram
@@ -146,6 +148,18 @@ struct Recorder {
     DevBuf steps, fx, fv, ff, fimg;    // frames
     DevBuf x_prev, image, ambiguous;
     DevBuf ring_x, ring_img, ring_v, ring_com, com_partial, corr_partial, msd, vacf, class_atoms;
+};
+
+// structure sampler (gamd_struct_*, structure.hip): configuration, step count, k-vector list, histogram and S(k) sums
+struct StructSampler {
+    long long interval = 0;            // 0: off — nothing is enqueued
+    long long sample_interval = 0;     // the interval g was counted with (stays when the sampler is switched off)
+    int bins = 0, pairs = 1, exclude = 0;
+    float rmax = 0.f;
+    int n_k = 0;
+    std::vector<int> kvec_host;        // [n_k][3]
+    long long g = 0;                   // completed MD steps since configure / reset, runs still in the stream included
+    DevBuf counts, kvec, rho_partial, sk_sum;
 };
 
 }  // namespace
@@ -218,6 +232,7 @@ struct gamd_handle {
     MdPending pending;
     Reporter rep;
     Recorder rec;
+    StructSampler ss;
     bool has_bonds = false;
 
     // Verlet-skin reuse (cfg.neighbor_skin > 0)
@@ -875,8 +890,53 @@ bool traj_sampled(const gamd_handle* h, long long s) {
     return h->rec.interval > 0 && (h->pending.traj_g0 + s + 1) % h->rec.interval == 0;
 }
 
-// this step carries a reporter sample or a recorder sample: its second half must be complete in front of them
-bool step_sampled(const gamd_handle* h, long long s) { return report_sampled(h, s) || traj_sampled(h, s); }
+// structure sampler: blocks per box of k_struct_rho (fixed per handle: the summation tree never changes)
+int struct_rho_blocks(const gamd_handle* h) { return std::max(1, std::min(64, (h->n_per_box + 255) / 256)); }
+
+// structure sampler: does step s of the pending run carry a sample?
+bool struct_sampled(const gamd_handle* h, long long s) {
+    return h->ss.interval > 0 && (h->pending.struct_g0 + s + 1) % h->ss.interval == 0;
+}
+
+// this step carries a reporter, recorder or structure sample: its second half must be complete in front of them
+bool step_sampled(const gamd_handle* h, long long s) { return report_sampled(h, s) || traj_sampled(h, s) || struct_sampled(h, s); }
+
+// the structure sampler's sample of step s of the pending run, behind its second half
+int enqueue_struct_sample(gamd_handle* h, long long s) {
+    const MdPending& p = h->pending;
+    const StructSampler& sp = h->ss;
+    StructArgs a{};
+    a.n = h->n;
+    a.bx = box_ref(h);
+    a.devflags = h->devflags.as<int>();
+    a.sticky = h->sticky_dev;
+    for (int d = 0; d < 3; ++d) { a.box[d] = h->box[d]; a.half[d] = 0.5f * h->box[d]; }
+    a.n_pairs = sp.pairs;
+    (void)s;                                                // no row of its own: the host counts the frames
+    int r;
+    if (sp.bins > 0) {
+        a.pos_s = h->pos_s.as<float4>();
+        a.perm = h->perm.as<int>();
+        a.n_bins = sp.bins;
+        a.r_max = sp.rmax; a.bin_scale = (float)sp.bins;
+        a.exclude_same_molecule = sp.exclude;
+        a.tiles = (h->n_per_box + 255) / 256;
+        a.counts = sp.counts.as<unsigned long long>();
+        if ((r = launch_struct_pairs(a, p.st))) return fail(-1, "structure sampler launch failed (%d)", r);
+    }
+    if (sp.n_k > 0) {
+        a.x = p.x;
+        a.species = p.species;
+        a.classes = sp.pairs == 3 ? 2 : 1;
+        a.n_k = sp.n_k;
+        a.kvec = sp.kvec.as<int>();
+        a.rho_blocks = struct_rho_blocks(h);
+        a.rho_partial = sp.rho_partial.as<double>();
+        a.sk_sum = sp.sk_sum.as<double>();
+        if ((r = launch_struct_sk(a, p.st))) return fail(-1, "structure sampler launch failed (%d)", r);
+    }
+    return 0;
+}
 
 // the recorder's sample of step s of the pending run, behind its second half
 int enqueue_traj_sample(gamd_handle* h, long long s) {
@@ -926,6 +986,7 @@ int enqueue_samples(gamd_handle* h, long long s) {
     int r;
     if (report_sampled(h, s) && (r = enqueue_report_sample(h, s))) return r;
     if (traj_sampled(h, s) && (r = enqueue_traj_sample(h, s))) return r;
+    if (struct_sampled(h, s) && (r = enqueue_struct_sample(h, s))) return r;
     return 0;
 }
 
@@ -1069,6 +1130,26 @@ void traj_begin_run(gamd_handle* h, const float* box, const uint8_t* species_dev
     if (rc.box0.empty()) rc.box0.assign(box, box + 3 * (size_t)h->n_boxes);
     if (!rc.classes) rc.classes = h->pending.traj_classes;
     rc.g += n_steps;
+}
+
+// structure sampler, at the top of gamd_md_run / gamd_md_run_nhc: the minimum image is the nearest image only inside the
+// sphere of half the shortest edge, and the S(k) classes need the species in the caller's order
+int struct_check_run(gamd_handle* h, const float* box, const uint8_t* species_dev) {
+    const StructSampler& sp = h->ss;
+    if (sp.interval <= 0) return 0;
+    if (sp.bins > 0)
+        for (int k = 0; k < 3 * h->n_boxes; ++k)
+            if (!(2.0f * sp.rmax <= box[k]))
+                return fail(-22, "structure sampler: rdf_rmax = %g exceeds half of box[%d][%d] = %g (the minimum image is the nearest "
+                                 "image only below that)", (double)sp.rmax, k / 3, k % 3, (double)box[k]);
+    if (sp.n_k > 0 && sp.pairs == 3 && !species_dev)
+        return fail(-22, "structure sampler: the partial structure factors of a water handle need species");
+    return 0;
+}
+// ... and once the run is certain to be enqueued
+void struct_begin_run(gamd_handle* h, long long n_steps) {
+    h->pending.struct_g0 = h->ss.g;
+    if (h->ss.interval > 0) h->ss.g += n_steps;
 }
 
 }  // namespace
@@ -1258,6 +1339,7 @@ int32_t gamd_destroy(gamd_handle* h) {
                       &h->rec.steps, &h->rec.fx, &h->rec.fv, &h->rec.ff, &h->rec.fimg, &h->rec.x_prev, &h->rec.image, &h->rec.ambiguous,
                       &h->rec.ring_x, &h->rec.ring_img, &h->rec.ring_v, &h->rec.ring_com, &h->rec.com_partial, &h->rec.corr_partial,
                       &h->rec.msd, &h->rec.vacf, &h->rec.class_atoms,
+                      &h->ss.counts, &h->ss.kvec, &h->ss.rho_partial, &h->ss.sk_sum,
                       &h->ref_pos, &h->cand_deg, &h->cand_ptr, &h->cand_col};
     for (DevBuf* b : bufs) b->release();
     h->pos_in.release();
@@ -1940,6 +2022,7 @@ int32_t gamd_md_run(gamd_handle* h, float* x_dev, float* v_dev, float* f_dev, co
     if (n_steps < 0 || n_steps > 0x3fffffff) return fail(-22, "n_steps out of range");
     if ((r = check_model_inputs(h, species_dev))) return r;
     if ((r = traj_check_run(h, box, species_dev))) return r;
+    if ((r = struct_check_run(h, box, species_dev))) return r;
     DeviceGuard guard(h->dev);
     InitStream init((hipStream_t)stream);
     if ((r = set_box(h, box, (hipStream_t)stream))) return r;
@@ -1971,6 +2054,7 @@ int32_t gamd_md_run(gamd_handle* h, float* x_dev, float* v_dev, float* f_dev, co
     pd.report_g0 = h->rep.g;
     if (h->rep.interval > 0) h->rep.g += n_steps;
     traj_begin_run(h, box, species_dev, n_steps);
+    struct_begin_run(h, n_steps);
     return enqueue_md_steps(h, 0, false);
 }
 
@@ -1989,6 +2073,7 @@ int32_t gamd_md_run_nhc(gamd_handle* h, float* x_dev, float* v_dev, float* f_dev
     const double* ys = p->num_yoshidasuzuki == 1 ? YS1 : p->num_yoshidasuzuki == 3 ? YS3 : p->num_yoshidasuzuki == 5 ? YS5 : nullptr;
     if (!ys) return fail(-22, "Invalid Yoshida-Suzuki value. Allowed values are: 1,3,5");
     if ((r = traj_check_run(h, box, species_dev))) return r;
+    if ((r = struct_check_run(h, box, species_dev))) return r;
     DeviceGuard guard(h->dev);
     InitStream init((hipStream_t)stream);
     if ((r = set_box(h, box, (hipStream_t)stream))) return r;
@@ -2030,6 +2115,7 @@ int32_t gamd_md_run_nhc(gamd_handle* h, float* x_dev, float* v_dev, float* f_dev
     pd.report_g0 = h->rep.g;
     if (h->rep.interval > 0) h->rep.g += n_steps;
     traj_begin_run(h, box, species_dev, n_steps);
+    struct_begin_run(h, n_steps);
     return enqueue_md_steps(h, 0, false);
 }
 
@@ -2237,6 +2323,112 @@ int32_t gamd_traj_read_dynamics(gamd_handle* h, void* stream, double* msd_sum, d
     if (int t = check_traps(h)) return t;
     if (n_samples) *n_samples = taken;
     if (dims) { dims[0] = (int32_t)nb; dims[1] = (int32_t)cls; dims[2] = (int32_t)lags; }
+    return 0;
+}
+
+static_assert(sizeof(gamd_struct_params) == 32 && offsetof(gamd_struct_params, rdf_bins) == 8 && offsetof(gamd_struct_params, rdf_rmax) == 12 &&
+              offsetof(gamd_struct_params, sk_n2max) == 20,
+              "gamd_struct_params layout is part of the C ABI (gamd_amd/_lib.py mirrors it)");
+
+// clear the structure sampler's step count, histogram and sums (on the init stream, landed before it returns)
+static int struct_clear(gamd_handle* h) {
+    StructSampler& sp = h->ss;
+    sp.g = 0;
+    DevBuf* bufs[] = {&sp.counts, &sp.sk_sum};
+    for (DevBuf* b : bufs)
+        if (b->p) HIP_TRY(hipMemsetAsync(b->p, 0, b->bytes, tl_init_stream));
+    HIP_TRY(hipStreamSynchronize(tl_init_stream));
+    return 0;
+}
+
+// one of each +-n with 0 < |n|^2 <= n2max (the one whose first non-zero component is positive), sorted by (|n|^2, nx, ny, nz)
+static std::vector<int> struct_kvectors(int n2max) {
+    int m = 0;
+    while ((m + 1) * (m + 1) <= n2max) ++m;
+    std::vector<std::array<int, 4>> v;
+    for (int x = 0; x <= m; ++x)
+        for (int y = -m; y <= m; ++y)
+            for (int z = -m; z <= m; ++z) {
+                const int n2 = x * x + y * y + z * z;
+                if (n2 == 0 || n2 > n2max) continue;
+                const int lead = x != 0 ? x : (y != 0 ? y : z);
+                if (lead > 0) v.push_back({n2, x, y, z});
+            }
+    std::sort(v.begin(), v.end());
+    std::vector<int> out;
+    for (const auto& e : v) { out.push_back(e[1]); out.push_back(e[2]); out.push_back(e[3]); }
+    return out;
+}
+
+int32_t gamd_struct_configure(gamd_handle* h, const gamd_struct_params* p) {
+    if (!p) return fail(-22, "null argument");
+    if (p->interval < 0) return fail(-22, "interval = %lld is negative", (long long)p->interval);
+    if (p->rdf_bins < 0 || p->rdf_bins > 1024) return fail(-22, "rdf_bins = %d outside [0, 1024]", (int)p->rdf_bins);
+    if (p->rdf_bins > 0 && !(p->rdf_rmax > 0.f)) return fail(-22, "rdf_rmax = %g is not positive", (double)p->rdf_rmax);
+    // K grows as (2 pi / 3) n2max^1.5: 4096 is passed near n2max = 156
+    if (p->sk_n2max < 0 || p->sk_n2max > 256) return fail(-22, "sk_n2max = %d gives more than 4096 k-vectors (or is negative)", (int)p->sk_n2max);
+    std::vector<int> kv = p->sk_n2max > 0 ? struct_kvectors(p->sk_n2max) : std::vector<int>();
+    if (kv.size() / 3 > 4096) return fail(-22, "sk_n2max = %d gives %zu k-vectors, more than 4096", (int)p->sk_n2max, kv.size() / 3);
+    if (!h) return fail(-22, "null handle");
+    if (h->n_boxes > 65535) return fail(-22, "the structure sampler needs n_boxes <= 65535");
+    {
+        const long long T = (h->n_per_box + 255) / 256;
+        if (p->rdf_bins > 0 && T * (T + 1) / 2 > 0xffffffll) return fail(-22, "the pair histogram needs at most 5791 tiles of 256 atoms per box");
+    }
+    StructSampler& sp = h->ss;
+    if (h->pending.active) return fail(-22, "an MD run is still enqueued: call gamd_sync_status before gamd_struct_configure");
+    if (p->interval == 0) { sp.interval = 0; return 0; }        // off: what was sampled stays readable
+    DeviceGuard guard(h->dev);
+    InitStream init(h->init_stream);
+    sp.interval = 0;
+    sp.bins = p->rdf_bins;
+    sp.pairs = h->cfg.kind == GAMD_KIND_WATER ? 3 : 1;
+    sp.rmax = p->rdf_rmax;
+    sp.exclude = p->exclude_same_molecule ? 1 : 0;
+    sp.n_k = (int)(kv.size() / 3);
+    sp.kvec_host = kv;
+    const size_t nb = (size_t)h->n_boxes, K = (size_t)sp.n_k, cls = sp.pairs == 3 ? 2 : 1;
+    // exact sizes (a smaller configuration after a larger one re-allocates: struct_clear and gamd_struct_read go by bytes)
+    DevBuf* bufs[] = {&sp.counts, &sp.kvec, &sp.rho_partial, &sp.sk_sum};
+    const size_t want[] = {sizeof(unsigned long long) * nb * (size_t)sp.pairs * (size_t)sp.bins, sizeof(int) * 3 * K,
+                           sizeof(double) * 2 * nb * (size_t)struct_rho_blocks(h) * cls * K, sizeof(double) * nb * (size_t)sp.pairs * K};
+    for (int k = 0; k < 4; ++k) {
+        if (bufs[k]->bytes != want[k]) bufs[k]->release();
+        if (want[k] && bufs[k]->ensure(want[k], true)) return fail(-12, "structure sampler allocation failed");
+    }
+    if (K) HIP_TRY(init_upload(sp.kvec.p, kv.data(), sizeof(int) * 3 * K));
+    int r;
+    if ((r = struct_clear(h))) return r;
+    sp.interval = sp.sample_interval = p->interval;
+    return 0;
+}
+
+int32_t gamd_struct_reset(gamd_handle* h) {
+    if (!h) return fail(-22, "null handle");
+    if (h->pending.active) return fail(-22, "an MD run is still enqueued: call gamd_sync_status before gamd_struct_reset");
+    DeviceGuard guard(h->dev);
+    InitStream init(h->init_stream);
+    return struct_clear(h);
+}
+
+int32_t gamd_struct_read(gamd_handle* h, void* stream, uint64_t* counts, int64_t count_elems, double* sk_sum, int64_t sk_elems,
+                         int32_t* kvec, int64_t kvec_elems, int64_t* frames, int32_t dims[4]) {
+    if (!h) return fail(-22, "null handle");
+    const StructSampler& sp = h->ss;
+    DeviceGuard guard(h->dev);
+    hipStream_t st = (hipStream_t)stream;
+    const long long nb = h->n_boxes, bins = sp.counts.p ? sp.bins : 0, K = sp.sk_sum.p ? sp.n_k : 0;
+    const long long c_elems = nb * (long long)sp.pairs * bins, s_elems = nb * (long long)sp.pairs * K;
+    if (counts && count_elems < c_elems) return fail(-22, "counts has room for %lld elements, the histogram has %lld", (long long)count_elems, c_elems);
+    if (sk_sum && sk_elems < s_elems) return fail(-22, "sk_sum has room for %lld elements, the sums have %lld", (long long)sk_elems, s_elems);
+    if (kvec && kvec_elems < 3 * K) return fail(-22, "kvec has room for %lld elements, the list has %lld", (long long)kvec_elems, 3 * K);
+    if (counts && c_elems > 0) HIP_TRY(hipMemcpyAsync(counts, sp.counts.p, sizeof(uint64_t) * (size_t)c_elems, hipMemcpyDeviceToHost, st));
+    if (sk_sum && s_elems > 0) HIP_TRY(hipMemcpyAsync(sk_sum, sp.sk_sum.p, sizeof(double) * (size_t)s_elems, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (int t = check_traps(h)) return t;
+    if (kvec && K > 0) std::memcpy(kvec, sp.kvec_host.data(), sizeof(int32_t) * 3 * (size_t)K);
+    if (frames) *frames = (sp.sample_interval > 0 && (bins > 0 || K > 0)) ? sp.g / sp.sample_interval : 0;
+    if (dims) { dims[0] = (int32_t)nb; dims[1] = sp.pairs; dims[2] = (int32_t)bins; dims[3] = (int32_t)K; }
     return 0;
 }
 

@@ -497,3 +497,36 @@ struct TrajArgs {
     long long* class_atoms;    // [n_boxes][classes]
 };
 int launch_traj_sample(const TrajArgs& a, hipStream_t st);     // frame, images, ring; with n_lags > 0 also COM and the sums
+
+// ---- structure sampler (structure.hip) ------------------------------------------------------------
+// One sample of an enqueued MD run (gamd_struct_configure): the all-pairs distance histogram of the frame out to r_max
+// (any r_max up to half the shortest box edge: the edge list of the force evaluation cannot serve beyond the cutoff) and / or
+// the partial structure-factor sums over the handle's k-vector list.  The integer counts commute; the S(k) sums are updated
+// in place and rely on the freeze gate alone (a kernel that returned changed nothing, and a sample runs exactly once unfrozen).
+enum { GAMD_CHK_STRUCT_PERM_I = 145, GAMD_CHK_STRUCT_PERM_J = 146 };
+struct StructArgs {
+    int n;                     // atoms of all boxes
+    BoxRef bx;
+    const int* devflags;       // DEVFLAG_FROZEN set: every sampler kernel returns at once
+    int* sticky;               // host-mapped (checked build)
+    float box[3], half[3];     // n_boxes <= 1
+    // pair histogram: the wrapped positions of the force evaluation that has just run, sorted order (box-contiguous)
+    const float4* pos_s;       // .w = species flag
+    const int* perm;           // sorted -> caller order (exclude_same_molecule)
+    int n_bins, n_pairs;       // n_bins == 0: no histogram
+    float r_max, bin_scale;    // bin = (int)(r * bin_scale / r_max), bin_scale = n_bins as float
+    int exclude_same_molecule;
+    int tiles;                 // 256-atom tiles per box
+    unsigned long long* counts;// [n_boxes][n_pairs][n_bins]
+    // structure factors: the caller's positions in the caller's order (the sorted order is not the same run after run)
+    const float* x;            // [n][3]
+    const uint8_t* species;    // [n], classes == 2 only
+    int n_k;                   // k-vectors, 0: none
+    const int* kvec;           // [n_k][3] integer triples n
+    int classes;               // 1, or 2 (O, H)
+    int rho_blocks;            // workgroups per box and 64 k-vectors (fixed per handle: the summation tree never changes)
+    double* rho_partial;       // [n_boxes][rho_blocks][classes][n_k][2] (re, im)
+    double* sk_sum;            // [n_boxes][n_pairs][n_k] running sums of Re(rho_a conj(rho_b))
+};
+int launch_struct_pairs(const StructArgs& a, hipStream_t st);
+int launch_struct_sk(const StructArgs& a, hipStream_t st);

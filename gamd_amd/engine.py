@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import GamdReportParams, GamdTrajParams, GamdConfig, GamdMdParams, GamdNhcParams, TRAJ_FIELDS, check
+from ._lib import GamdReportParams, GamdStructParams, GamdTrajParams, GamdConfig, GamdMdParams, GamdNhcParams, TRAJ_FIELDS, check
 from .weights import ModelConfig, infer_config, validate_state_dict
 
 ArrayLike = Union[np.ndarray, torch.Tensor]
@@ -52,6 +52,96 @@ def _boxes(box, n_boxes: int) -> np.ndarray:
     raise ValueError(f"box must be a scalar, 3 values, [{n_boxes}, 1] or [{n_boxes}, 3] ({n_boxes} boxes)")
 
 
+def _rdf_from_counts(counts, frames: int, r_max: float, n_by_class, vol: float):
+    """(r_mid [bins], g [P, bins]) from DIRECTED pair counts [P, bins]: g_ab(k) = c_ab[k] / (frames * m_ab * V_shell(k) / V)
+    with m_aa = N_a^2 and m_ab = 2 N_a N_b.  Shared by the run reporter and the structure sampler."""
+    c = np.asarray(counts).astype(np.float64)
+    n_pairs, bins = c.shape
+    if bins == 0 or frames == 0:
+        raise ValueError("no histogram was recorded")
+    nn = np.atleast_1d(np.asarray(n_by_class, dtype=np.float64))
+    if n_pairs == 1:
+        m = np.array([nn[0] ** 2])
+    else:
+        if nn.shape[0] != 2:
+            raise ValueError("three pair classes need n_by_class = (N_O, N_H)")
+        m = np.array([nn[0] ** 2, 2.0 * nn[0] * nn[1], nn[1] ** 2])
+    edges = np.arange(bins + 1, dtype=np.float64) * (r_max / bins)
+    shell = 4.0 / 3.0 * np.pi * (edges[1:] ** 3 - edges[:-1] ** 3)
+    g = c / (frames * m[:, None] * shell[None, :] / vol)
+    return 0.5 * (edges[1:] + edges[:-1]), g
+
+
+def structure_kvectors(n2max: int) -> np.ndarray:
+    """The structure sampler's wave-vector list as the library builds it: the integer triples n with 0 < |n|^2 <= n2max, one of
+    each +-n (the one whose first non-zero component is positive), sorted by (|n|^2, n_x, n_y, n_z).  int32 [K, 3]."""
+    n2max = int(n2max)
+    if n2max <= 0:
+        return np.zeros((0, 3), dtype=np.int32)
+    m = int(np.floor(np.sqrt(n2max)))
+    while (m + 1) * (m + 1) <= n2max:
+        m += 1
+    r = np.arange(-m, m + 1)
+    n = np.stack(np.meshgrid(r, r, r, indexing="ij"), axis=-1).reshape(-1, 3)
+    n2 = (n * n).sum(axis=1)
+    lead = np.where(n[:, 0] != 0, n[:, 0], np.where(n[:, 1] != 0, n[:, 1], n[:, 2]))
+    keep = (n2 > 0) & (n2 <= n2max) & (lead > 0)
+    n, n2 = n[keep], n2[keep]
+    order = np.lexsort((n[:, 2], n[:, 1], n[:, 0], n2))
+    return n[order].astype(np.int32)
+
+
+class RunStructure:
+    """What the structure sampler accumulated (GamdForce.structure_read).  Host-only: plain arrays in, plain arrays out.
+
+    rdf_counts [n_boxes, P, bins] uint64: directed pair counts per distance bin out to ``r_max`` (every unordered pair adds
+    2), P = 1 (LJ) or 3 (water: O-O, O-H, H-H); sk_sum [n_boxes, P, K] float64: sums over the frames of Re(rho_a conj(rho_b));
+    kvectors [K, 3] int32: the integer triples n of k = 2 pi n / L; frames: samples taken; boxes [n_boxes, 3]: box edges."""
+
+    def __init__(self, rdf_counts, sk_sum, kvectors, frames: int, r_max: float = 0.0, boxes=None):
+        self.rdf_counts = np.asarray(rdf_counts, dtype=np.uint64)
+        self.sk_sum = np.asarray(sk_sum, dtype=np.float64)
+        self.kvectors = np.asarray(kvectors, dtype=np.int32).reshape(-1, 3)
+        self.frames = int(frames)
+        self.r_max = float(r_max)
+        self.boxes = None if boxes is None else np.asarray(boxes, dtype=np.float64).reshape(-1, 3)
+
+    def rdf(self, box: int, n_by_class, volume: Optional[float] = None):
+        """(r_mid [bins], g [P, bins]) of box ``box``, normalised as RunReport.rdf: ``n_by_class`` is N for one pair class,
+        (N_O, N_H) for three."""
+        vol = float(volume) if volume is not None else float(np.prod(self.boxes[box]))
+        return _rdf_from_counts(self.rdf_counts[box], self.frames, self.r_max, n_by_class, vol)
+
+    def sk(self, box: int, n_by_class, shell_average: bool = False):
+        """(|k| [K], S [P, K]) of box ``box``: S_ab(k) = sk_sum / (frames * sqrt(N_a N_b)) (Ashcroft-Langreth), |k| from the
+        box edges.  ``shell_average``: one value per |n|^2, the mean over its vectors ([shells], [P, shells]); cubic boxes
+        only (vectors of equal |n|^2 have different |k| otherwise)."""
+        s = self.sk_sum[box]
+        n_pairs, K = s.shape
+        if K == 0 or self.frames == 0:
+            raise ValueError("no structure factor was sampled")
+        nn = np.atleast_1d(np.asarray(n_by_class, dtype=np.float64))
+        if n_pairs == 1:
+            m = np.array([nn[0]])
+        else:
+            if nn.shape[0] != 2:
+                raise ValueError("three pair classes need n_by_class = (N_O, N_H)")
+            m = np.array([nn[0], np.sqrt(nn[0] * nn[1]), nn[1]])
+        edges = self.boxes[box]
+        kk = 2.0 * np.pi * np.sqrt(((self.kvectors.astype(np.float64) / edges[None, :]) ** 2).sum(axis=1))
+        val = s / (self.frames * m[:, None])
+        if not shell_average:
+            return kk, val
+        if not (edges[0] == edges[1] == edges[2]):
+            raise ValueError("shell_average needs a cubic box")
+        n2 = (self.kvectors.astype(np.int64) ** 2).sum(axis=1)
+        shells, inv, cnt = np.unique(n2, return_inverse=True, return_counts=True)
+        out = np.zeros((n_pairs, shells.shape[0]), dtype=np.float64)
+        for c in range(n_pairs):
+            out[c] = np.bincount(inv, weights=val[c], minlength=shells.shape[0]) / cnt
+        return 2.0 * np.pi * np.sqrt(shells.astype(np.float64)) / edges[0], out
+
+
 class RunReport:
     """What the run reporter recorded (GamdForce.report_read).
 
@@ -73,22 +163,11 @@ class RunReport:
         """(r_mid [bins], g [P, bins]) of box ``box``: g_ab(k) = c_ab[k] / (frames * m_ab * V_shell(k) / V) with
         m_aa = N_a^2 and m_ab = 2 N_a N_b for the directed counts.  ``n_by_class``: N for one pair class, (N_O, N_H) for
         three."""
-        c = self.rdf_counts[box].astype(np.float64)
-        n_pairs, bins = c.shape
-        if bins == 0 or self.frames == 0:
+        c = self.rdf_counts[box]
+        if c.shape[1] == 0 or self.frames == 0:
             raise ValueError("no histogram was recorded")
         vol = float(volume) if volume is not None else float(self.volumes[box])
-        nn = np.atleast_1d(np.asarray(n_by_class, dtype=np.float64))
-        if n_pairs == 1:
-            m = np.array([nn[0] ** 2])
-        else:
-            if nn.shape[0] != 2:
-                raise ValueError("three pair classes need n_by_class = (N_O, N_H)")
-            m = np.array([nn[0] ** 2, 2.0 * nn[0] * nn[1], nn[1] ** 2])
-        edges = np.arange(bins + 1, dtype=np.float64) * (self.r_max / bins)
-        shell = 4.0 / 3.0 * np.pi * (edges[1:] ** 3 - edges[:-1] ** 3)
-        g = c / (self.frames * m[:, None] * shell[None, :] / vol)
-        return 0.5 * (edges[1:] + edges[:-1]), g
+        return _rdf_from_counts(c, self.frames, self.r_max, n_by_class, vol)
 
     def write_state_data(self, path, dt_ps: float, separator: str = "\t", driver_step_convention: bool = False,
                          box: int = 0) -> None:
@@ -692,6 +771,42 @@ class GamdForce:
         check(self._lib.gamd_traj_read_dynamics(self._h, st, vp(msd), vp(vacf), msd.size, C.byref(n_samples), C.byref(amb),
                                                 vp(cls_atoms), dims), "gamd_traj_read_dynamics")
         return RunTrajectory(steps, x, v, f, image, dropped.value, amb.value, n_samples.value, cls_atoms, msd, vacf, interval)
+
+    # -- structure sampler (all-pairs g(r) out to half the box and S(k), taken inside enqueued runs) --------------------
+    def structure_configure(self, interval: int, rdf_bins: int = 0, rdf_rmax: Optional[float] = None,
+                            exclude_same_molecule: bool = False, sk_n2max: int = 0) -> None:
+        """While configured, every ``interval``-th completed step of md_run / md_run_nhc (counted across calls, by a counter
+        of its own) adds every pair distance of the frame below ``rdf_rmax`` to a histogram of ``rdf_bins`` bins (default
+        ``rdf_rmax``: half the shortest edge of the engine's box, which is also the most a run accepts) and, with
+        ``sk_n2max`` > 0, Re(rho_a conj(rho_b)) at every wave vector 2 pi n / L with 0 < |n|^2 <= ``sk_n2max``;
+        ``structure_read`` fetches both.  O(N^2) pair distances per sample and box.  ``interval`` = 0 switches it off."""
+        if rdf_rmax is None:
+            rdf_rmax = float(np.float32(0.5) * self.box.min())
+        p = GamdStructParams(int(interval), int(rdf_bins), float(rdf_rmax), int(bool(exclude_same_molecule)), int(sk_n2max))
+        check(self._lib.gamd_struct_configure(self._h, C.byref(p)), "gamd_struct_configure")
+        if interval:
+            self._struct_rmax = float(np.float32(rdf_rmax))
+
+    def structure_reset(self) -> None:
+        """Step count, histogram and sums back to zero; the configuration stays."""
+        check(self._lib.gamd_struct_reset(self._h), "gamd_struct_reset")
+
+    def structure_read(self, box=None) -> "RunStructure":
+        """Synchronise and fetch what the structure sampler has accumulated since it was configured or reset.  ``box``: the
+        box edges the runs used when they differ from the constructor's (|k| and the g(r) volume are taken from them)."""
+        frames = C.c_int64()
+        dims = (C.c_int32 * 4)()
+        rd = self._lib.gamd_struct_read
+        check(rd(self._h, self._stream(), None, 0, None, 0, None, 0, C.byref(frames), dims), "gamd_struct_read")
+        nb, npair, nbins, nk = dims
+        counts = np.zeros((nb, npair, nbins), dtype=np.uint64)
+        sk = np.zeros((nb, npair, nk), dtype=np.float64)
+        kvec = np.zeros((nk, 3), dtype=np.int32)
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)
+        check(rd(self._h, self._stream(), vp(counts), counts.size, vp(sk), sk.size, vp(kvec), kvec.size, C.byref(frames), dims),
+              "gamd_struct_read")
+        boxes = _boxes(self.box if box is None else box, self.n_boxes).astype(np.float64)
+        return RunStructure(counts, sk, kvec, frames.value, getattr(self, "_struct_rmax", 0.0), boxes)
 
     def sync_status(self) -> int:
         """0, or 1 when an enqueued MD run overflowed a neighbour buffer, froze on the device and was resumed."""

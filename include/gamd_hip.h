@@ -378,6 +378,57 @@ int32_t gamd_traj_read_frames(gamd_handle* h, void* stream, int64_t first, int64
 int32_t gamd_traj_read_dynamics(gamd_handle* h, void* stream, double* msd_sum, double* vacf_sum, int64_t elems,
                                 int64_t* n_samples, uint64_t* ambiguous, int64_t* class_atoms, int32_t dims[3]);
 
+/* Structure sampler: the pair-distance histogram of a radial distribution function out to ANY rdf_rmax up to half the
+ * shortest box edge (the reporter's g(r) above walks the edge list and ends at the cutoff) and the partial static structure
+ * factors S_ab(k), kept ON THE DEVICE while gamd_md_run / gamd_md_run_nhc are enqueued.
+ * The sampler counts the completed MD steps g of the handle since it was configured or reset (across calls, with a counter of
+ * its own: its interval is independent of the reporter's and the recorder's).  Step g is sampled when g % interval == 0,
+ * behind its second half (for rigid water: behind the velocity constraint), where the other two sample.  A sample is
+ *   - rdf_bins > 0: for every box, every unordered pair {i, j}, i != j, of that box's atoms is evaluated ONCE: the fp32
+ *     min-image distance r of the wrapped positions of that step's force evaluation (per component d = x_i - x_j or
+ *     x_j - x_i, t = d + L/2, t += L if t < 0, t -= L if t >= L, d' = t - L/2; r = sqrtf((dx*dx + dy*dy) + dz*dz), no
+ *     contraction).  A pair with r < rdf_rmax adds 2 to the 64-bit counter [box][pair class][bin], bin = min((int)(r *
+ *     rdf_bins / rdf_rmax), rdf_bins - 1): the reporter's directed-count convention, so the same normalisation applies
+ *     (m_aa = N_a^2, m_ab = 2 N_a N_b).  Pair classes as the reporter's: one for GAMD_KIND_LJ handles; O-O, O-H, H-H for
+ *     GAMD_KIND_WATER, O = node feature != 0.  exclude_same_molecule: pairs whose caller-order atom ids share id / 3 are
+ *     skipped.  (d + L/2) - L/2 does not round symmetrically in d: against the reporter's histogram only pairs that sit on a
+ *     bin edge to fp32 rounding may differ.
+ *     Cost: N (N - 1) / 2 distances per box and sample — O(N^2), meant for up to about 10^5 atoms per box.
+ *     Precondition: 2 * rdf_rmax <= the shortest edge of every box of the run; otherwise gamd_md_run / gamd_md_run_nhc return
+ *     -22 (the message names rdf_rmax) before anything is enqueued.
+ *   - sk_n2max > 0: wave vectors k = 2 pi (n_x / L_x, n_y / L_y, n_z / L_z) for the integer triples with 0 < |n|^2 <= sk_n2max,
+ *     one of each +-n (the one whose first non-zero component is positive), sorted by (|n|^2, n_x, n_y, n_z): K = 61 / 128 /
+ *     462 for sk_n2max = 9 / 16 / 36; at most 4096.  Per box and class c, rho_c(n) = sum_i exp(-2 pi i n.s_i), s_i = (double)x_i
+ *     / (double)L per component from the caller's position buffer, the phase n_x s_x + n_y s_y + n_z s_z and sincospi(2 phase)
+ *     in double, the atoms summed in a fixed assignment and order.  Then sk_sum[box][pair][k] += Re(rho_a conj(rho_b)) for the
+ *     pair classes above (LJ: |rho|^2; classes O, H by species_dev != 0, which a water handle must then be given).  The same
+ *     bits run after run.  The host normalises S_ab(k) = sk_sum / (frames * sqrt(N_a N_b)) (Ashcroft-Langreth).
+ * Device memory: 8 B per box, pair class and bin; 8 B per box, pair class and k-vector; 16 B per box, class, k-vector and
+ * block of 256 atoms (at most 64 blocks).
+ * Nothing synchronises or returns to the host inside a run; a run that froze on a neighbour-buffer overflow and was resumed
+ * by gamd_sync_status gives the counts and sums of an ample buffer.  A handle whose sampler is off (the default) enqueues
+ * exactly what it enqueues without one; with it on, skin-mode runs launch the second half of a SAMPLED step on its own. */
+typedef struct gamd_struct_params {
+    int64_t interval;        /* 0 = sampler off (buffers are kept); > 0: sample every interval-th completed step */
+    int32_t rdf_bins;        /* 0 = no histogram; at most 1024 */
+    float rdf_rmax;          /* upper edge of the last bin, > 0 when rdf_bins > 0 (no default: half the shortest box edge at most) */
+    int32_t exclude_same_molecule;
+    int32_t sk_n2max;        /* 0 = no structure factors; else every n with 0 < |n|^2 <= sk_n2max (K <= 4096) */
+    int32_t reserved[2];     /* 0 */
+} gamd_struct_params;
+/* p: HOST.  Builds the k-vector list, allocates and clears histogram and sums (drains nothing: call it between runs, after
+ * gamd_sync_status).  -22 for a negative interval, rdf_bins outside [0, 1024], rdf_bins > 0 without rdf_rmax > 0, an sk_n2max
+ * with more than 4096 k-vectors, or while a run is pending; -12 when an allocation fails. */
+int32_t gamd_struct_configure(gamd_handle* h, const gamd_struct_params* p);
+/* Step count g = 0, histogram and sums cleared; the configuration and the k-vector list stay. */
+int32_t gamd_struct_reset(gamd_handle* h);
+/* Synchronises `stream` once (it does NOT resume a frozen run: call gamd_sync_status first) and copies to HOST arrays, any
+ * of which may be NULL: counts uint64 [n_boxes][pair classes][rdf_bins], sk_sum double [n_boxes][pair classes][K], kvec int32
+ * [K][3] (count_elems / sk_elems / kvec_elems = room in elements; fewer than needed is -22).  *frames = samples taken,
+ * dims[0..3] = n_boxes, pair classes, rdf_bins, K. */
+int32_t gamd_struct_read(gamd_handle* h, void* stream, uint64_t* counts, int64_t count_elems, double* sk_sum, int64_t sk_elems,
+                         int32_t* kvec, int64_t kvec_elems, int64_t* frames, int32_t dims[4]);
+
 /* Event-timed replay of one force evaluation: per-kernel milliseconds of the last gamd_profile call.
  * names: newline-separated kernel labels; ms: one float per label.  For bench.py's roofline block. */
 int32_t gamd_profile(gamd_handle* h, const float* pos_dev, const uint8_t* species_dev, const float* box,
