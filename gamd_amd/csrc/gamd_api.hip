@@ -1,276 +1,21 @@
-// gamd_api.hip — handle, weight packing and the extern "C" entry points of include/gamd_hip.h.
-#include "../../include/gamd_hip.h"
-#include "gamd_common.h"
-#include "gamd_internal.h"
+// gamd_api.hip — weight packing, the force evaluation, the MD driver and their extern "C" entry points of include/gamd_hip.h
+// (the handle itself is in gamd_host.h; the run observers' entry points are in observe.hip).
+#include "gamd_host.h"
 
 #include <algorithm>
-#include <array>
 #include <cmath>
-#include <cstdarg>
 #include <cstddef>
-#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <deque>
-#include <map>
-#include <string>
-#include <vector>
-
-namespace {
-
-thread_local char g_err[512] = "";
-
-int fail(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-#define HIP_TRY(expr)                                                                              \
-    do {                                                                                           \
-        hipError_t e__ = (expr);                                                                   \
-        if (e__ != hipSuccess) return fail(-1000 - (int)e__, "%s: %s", #expr, hipGetErrorString(e__)); \
-    } while (0)
-
-struct HostTensor {
-    std::vector<int64_t> shape;
-    std::vector<float> data;
-};
-
-// Initialising work — zeroing a fresh buffer, uploading a small table — goes to ONE stream and is waited for on THAT stream
-// before the call returns: the caller's stream inside the entry points that take one, the handle's private non-blocking
-// stream everywhere else (gamd_create, gamd_finalize_weights, gamd_set_bonds).  Nothing is ordered on, or waits for, the NULL
-// stream: a hipMemset / hipMemcpy there is asynchronous to the host for device memory and not ordered with a non-blocking
-// stream at all (round 5: the momentum sums of a run's first step, com_partial, were wiped after k_com_partial on the caller's
-// non-blocking stream had written them, once in ~300 runs), and a NULL-stream synchronise inside a library stalls every
-// blocking stream of the process.  InitStream is set by every entry point (RAII, per thread: different handles may be driven
-// from different threads).
-thread_local hipStream_t tl_init_stream = nullptr;
-struct InitStream {
-    hipStream_t prev;
-    explicit InitStream(hipStream_t st) : prev(tl_init_stream) { tl_init_stream = st; }
-    ~InitStream() { tl_init_stream = prev; }
-    InitStream(const InitStream&) = delete;
-    InitStream& operator=(const InitStream&) = delete;
-};
-// host -> device upload of a small table from pageable memory, landed before it returns
-hipError_t init_upload(void* dst, const void* src, size_t bytes) {
-    hipError_t e = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, tl_init_stream);
-    return e != hipSuccess ? e : hipStreamSynchronize(tl_init_stream);
-}
-
-struct DevBuf {
-    void* p = nullptr;
-    size_t bytes = 0;
-    int ensure(size_t want, bool zero) {
-        if (want <= bytes && p) return 0;
-        if (p) { hipError_t e = hipFree(p); if (e != hipSuccess) return (int)e; p = nullptr; bytes = 0; }
-        hipError_t e = hipMalloc(&p, want);
-        if (e != hipSuccess) return (int)e;
-        bytes = want;
-        if (zero) {
-            // on the call's stream (InitStream) and waited for there: allocations are rare, and what a call allocates and
-            // initialises has landed before it returns whatever stream the next call comes on
-            e = hipMemsetAsync(p, 0, want, tl_init_stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(tl_init_stream);
-            if (e != hipSuccess) return (int)e;
-        }
-        return 0;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
-    template <typename T> T* as() const { return reinterpret_cast<T*>(p); }
-};
-
-struct LayerDev {
-    // edge side
-    const float *w1p, *w2p, *w3p, *w4p, *b1, *b3, *b4;
-    const float *w16p = nullptr;                        // generic-width fp32: the blocks again, packed for wide16.hip
-    const float *e_ln_g = nullptr, *e_ln_b = nullptr;   // update_edge_emb: this layer's edge_layer_norm
-    const float *w3p_l0 = nullptr, *b3_l0 = nullptr;    // layer-0 form (gamd_handle::l0_hoist): W3, b3 in the F2 output order
-    NodeLayerW node;
-};
-
-// every entry point runs on the handle's device and leaves the caller's current device as it found it
-struct DeviceGuard {
-    int prev = -1;
-    bool changed = false;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) == hipSuccess && prev != dev) changed = hipSetDevice(dev) == hipSuccess;
-    }
-    ~DeviceGuard() { if (changed) (void)hipSetDevice(prev); }
-    DeviceGuard(const DeviceGuard&) = delete;
-    DeviceGuard& operator=(const DeviceGuard&) = delete;
-};
-
-// the gamd_md_run / gamd_md_run_nhc call whose steps are still in the stream: what gamd_sync_status needs to finish the
-// run after a neighbour-buffer overflow froze it
-struct MdPending {
-    bool active = false;
-    int kind = 0;                      // 0: split BAOAB, 1: split Nose-Hoover chain
-    MdArgs m{};
-    NhcArgs a{};
-    unsigned long long first_step = 0;
-    float mass = 0.f, mass_h = 0.f;    // BAOAB: mass_amu / mass_h_amu as given (MdArgs keeps their reciprocals)
-    long long n_steps = 0;
-    float* x = nullptr;
-    float* f = nullptr;
-    const uint8_t* species = nullptr;
-    hipStream_t st = nullptr;
-    long long report_g0 = 0;           // run reporter: completed MD steps in front of this run's first step
-    long long traj_g0 = 0;             // run recorder: the same, by its own counter
-    int traj_classes = 1;              // run recorder: 2 = water with species (O, H), else 1
-    long long struct_g0 = 0;           // structure sampler: completed MD steps in front of this run's first step, by its own counter
-};
-
-// run reporter (gamd_report_*, report.hip): configuration, step count and the device-resident log / histogram
-struct Reporter {
-    long long interval = 0;            // 0: off — nothing is enqueued, nothing is allocated
-    long long sample_interval = 0;     // the interval g was counted with (stays when the reporter is switched off: the log stays readable)
-    long long max_samples = 0;
-    double ndf = 0.0;
-    int bins = 0, pairs = 1, exclude = 0;
-    float rmax = 0.f;
-    long long g = 0;                   // completed MD steps since configure / reset, runs still in the stream included
-    DevBuf steps, ke, counts, partial;
-};
-
-// run recorder (gamd_traj_*, traj.hip): configuration, step count, frames, image counters, ring and running sums
-struct Recorder {
-    long long interval = 0;            // 0: off — nothing is enqueued
-    long long sample_interval = 0;     // the interval g was counted with (stays when the recorder is switched off)
-    long long max_frames = 0;
-    int fields = 0, n_lags = 0, subtract_com = 0;
-    int classes = 0;                   // 0: no run since configure / reset; else the classes of the first run
-    long long g = 0;                   // completed MD steps since configure / reset, runs still in the stream included
-    std::vector<float> box0;           // [n_boxes][3] of the first run since configure / reset (empty: none yet)
-    DevBuf steps, fx, fv, ff, fimg;    // frames
-    DevBuf x_prev, image, ambiguous;
-    DevBuf ring_x, ring_img, ring_v, ring_com, com_partial, corr_partial, msd, vacf, class_atoms;
-};
-
-// structure sampler (gamd_struct_*, structure.hip): configuration, step count, k-vector list, histogram and S(k) sums
-struct StructSampler {
-    long long interval = 0;            // 0: off — nothing is enqueued
-    long long sample_interval = 0;     // the interval g was counted with (stays when the sampler is switched off)
-    int bins = 0, pairs = 1, exclude = 0;
-    float rmax = 0.f;
-    int n_k = 0;
-    std::vector<int> kvec_host;        // [n_k][3]
-    long long g = 0;                   // completed MD steps since configure / reset, runs still in the stream included
-    DevBuf counts, kvec, rho_partial, sk_sum;
-};
-
-}  // namespace
 
 static_assert(sizeof(gamd_config) == 96 && offsetof(gamd_config, n_boxes) == 88 && offsetof(gamd_config, edge_capacity) == 40,
               "gamd_config layout is part of the C ABI (gamd_amd/_lib.py mirrors it)");
-
-struct gamd_handle {
-    gamd_config cfg{};
-    int dev = 0;
-    int n = 0, L = 0, n_feat = 44, n_cu = 256;   // n: atoms of ALL boxes together (n_boxes * n_per_box)
-    int n_boxes = 1, n_per_box = 0;              // gamd_config.n_boxes: independent boxes evaluated in one set of launches
-    bool use_small = false;                      // skin mode: the single-workgroup small-system path of neighbor.hip (decided once)
-    DevBuf boxes_dev, box_shift;                 // n_boxes > 1: per-box dimensions (BoxRef::boxes), scratch of the row scan
-    std::vector<float> boxes_host;               // [n_boxes][3] as last set
-    int H = 128, Eh = 128, HT = 1, EHT = 1;      // node width, edge-embedding width (PADDED to 128-blocks) and their block counts
-    int H_true = 128, Eh_true = 128, D_true = 128;   // encoding_size, edge_embedding_dim, hidden_dim as given (<= the padded ones)
-    int Dp = 128, DT = 1;                        // hidden_dim padded to 128-blocks; DT = 2: the kernels of wide_d.hip (fp32)
-    int norm_bn = 0;                             // graph_conv.norm_layers are BatchNorm1d (running statistics in the state_dict)
-    bool update_edge = false;                    // update_edge_emb=True: conv.<l>.edge_layer_norm keys in the state_dict
-    bool node_f16 = false;                       // node.hip's GEMMs in split-fp16 (reduced-precision edge modes, 128-wide kernels)
-    bool wide_enc = false, wide_conv = false;    // generic-width kernels of wide.hip
-    bool l0_hoist = false;                       // LJ, fp32, 128-wide: layer 0 in its three-GEMM form (conv_edge.hip, node.hip post(0))
-    long long small_tile_limit = 512;            // fp32 path: at most this many 32-edge tiles -> conv_edge_small.hip
-    std::map<std::string, HostTensor> host_w;
-    bool finalized = false;
-    double scaler_mean = 0.0, scaler_var = 1.0;
-
-    // packed weights on device
-    DevBuf wblob;
-    std::vector<LayerDev> layers;
-    const float *enc_w1p = nullptr, *enc_w2p = nullptr, *enc_w3p = nullptr, *enc_b1 = nullptr, *enc_b2 = nullptr,
-                *enc_b3 = nullptr, *enc_lng = nullptr, *enc_lnb = nullptr, *centers = nullptr;
-    const float *node_emb = nullptr, *nenc_w = nullptr, *nenc_b = nullptr;
-    const float *dec_w1p = nullptr, *dec_b1 = nullptr, *dec_w2 = nullptr, *dec_b2 = nullptr;
-    float length_mean = 0.f, length_std = 1.f;
-    RbfGrid rbf{};                               // set when edge_expand.centers is a uniform grid
-
-    // per-atom buffers
-    DevBuf pos_w, pos_s, cell_of, perm, inv_perm, deg, row_ptr, na_excl, bond_nbr;
-    DevBuf hbuf, hn, S, D, P, f_norm, f_den;
-    // Layer-0 node tables of their own (skin mode): h0 and pre(0)'s hn / S / D / P depend on the species and the weights only,
-    // not on the positions — in sorted atom order they change when the candidate list is rebuilt (the atoms are renumbered), not
-    // otherwise.  Inside an enqueued MD run the first node launch of a step therefore returns at once unless that step rebuilt
-    // (NodeArgs::l0_gate): the other layers' tables are overwritten layer by layer, these are not.
-    DevBuf l0_h, l0_hn, l0_S, l0_D, l0_P;
-    // cells
-    DevBuf cell_cnt, cell_fill, cell_start;
-    int ncell_cap = 0;
-    // edges
-    long long e_cap = 0;
-    long long piece_cap = 0;        // rows of `partial`
-    DevBuf col, erow, chunk_piece, chunk_mask, e_frag, partial, feat_dbg, e_emb, e_frag2;
-    DevBuf counters, tdbg, tmp_eid, ke_partial, com_partial;
-    DevBuf cnt2;                    // small systems in skin mode: two counter blocks used alternately (no per-call memset)
-    int cnt_parity = 0;
-    long long skin_calls = 0;       // skin-mode force evaluations so far (rebuild-frequency estimate)
-    int* cur_counters = nullptr;    // the counter block of the call being enqueued
-    int* counters_host = nullptr;   // pinned
-    // gamd_forces_host: pinned staging buffers ([n][3] floats each) and the device copy of the positions, allocated on first use
-    float* host_in = nullptr;
-    float* host_out = nullptr;
-    DevBuf pos_in;
-    int* sticky_host = nullptr;     // pinned + mapped: overflow flags and rebuild count, written by kernels directly
-    int* sticky_dev = nullptr;
-    hipStream_t init_stream = nullptr;   // private non-blocking stream: initialising memsets / uploads of the entry points without a stream argument
-    DevBuf devflags;                // [DEVFLAG_COUNT] device-resident freeze flag + where an MD run stopped
-    const float* feat_dev = nullptr;   // gamd_set_node_features
-    const uint8_t* rigid_checked = nullptr;   // species pointer whose O,H,H layout has been validated
-    MdPending pending;
-    Reporter rep;
-    Recorder rec;
-    StructSampler ss;
-    bool has_bonds = false;
-
-    // Verlet-skin reuse (cfg.neighbor_skin > 0)
-    float skin = 0.f;
-    DevBuf ref_pos, cand_deg, cand_ptr, cand_col;
-    long long cand_cap = 0;
-    bool cand_valid = false;
-
-    float box[3] = {0, 0, 0};
-    int nc[3] = {1, 1, 1};
-    int ncell = 1;                  // cells of all boxes together
-
-    // live timing of the conv-edge kernel (gamd_timing_*)
-    bool timing = false;
-    std::vector<hipEvent_t> tev;     // pairs (start, stop)
-    std::vector<int> tev_kind;       // per pair: 0 = conv-layer edge kernel(s) of layer l, 1 = edge encoder; -(l+1) coded below
-    size_t tev_used = 0;
-    // one event at the top of every MD step of an enqueued run (and one behind the last): gamd_timing_read_steps
-    std::vector<hipEvent_t> sev;
-    std::vector<uint8_t> sev_closes; // per event: 1 = recorded BEHIND the last step of an enqueue (the interval to the next event
-                                     // is the host's gap between two runs, not a step)
-    size_t sev_used = 0;
-    static constexpr size_t EVENT_POOL_CAP = 1u << 16;   // timing left on across a long run: recording stops here (never unbounded)
-};
 
 namespace {
 
 // batches never take the single-workgroup small-system path of neighbor.hip (k_step_small / k_filter_fill_small)
 bool small_path(const gamd_handle* h) { return h->use_small; }
-
-BoxRef box_ref(const gamd_handle* h) {
-    BoxRef r{};
-    r.n_boxes = h->n_boxes;
-    r.n_per_box = h->n_per_box;
-    r.inv_npb = 1.0f / (float)h->n_per_box;
-    r.boxes = h->n_boxes > 1 ? h->boxes_dev.as<float4>() : nullptr;
-    return r;
-}
 
 // centre-of-mass motion removal (MdCom): per-box, per-block momentum sums
 int fill_com(gamd_handle* h, int enabled, MdCom* c) {
@@ -816,15 +561,6 @@ int enqueue_forward(gamd_handle* h, const float* pos_dev, const uint8_t* species
     return 0;
 }
 
-// checked build: a device-side range check (GAMD_CHK_RANGE) failed in some kernel since the last report
-int check_traps(gamd_handle* h) {
-    const int code = h->sticky_host[STICKY_CHECK_CODE];
-    if (!code) return 0;
-    const int value = h->sticky_host[STICKY_CHECK_VALUE], line = h->sticky_host[STICKY_CHECK_LINE];
-    h->sticky_host[STICKY_CHECK_CODE] = 0;
-    return fail(-35, "checked build: device-side range check %d failed (value %d, source line %d)", code, value, line);
-}
-
 int check_ready(gamd_handle* h) {
     if (!h) return fail(-22, "null handle");
     if (!h->finalized) return fail(-22, "weights not finalized (call gamd_finalize_weights)");
@@ -872,167 +608,6 @@ int step_event(gamd_handle* h, hipStream_t st, bool closes = false) {
     return 0;
 }
 
-// run reporter: blocks per box of k_report_ke (fixed per handle: the summation tree never changes)
-int report_ke_blocks(const gamd_handle* h) { return std::max(1, std::min(64, (h->n_per_box + 1023) / 1024)); }
-
-// run reporter: does step s of the pending run carry a sample?  (g counts completed steps: step s completes as g0 + s + 1)
-bool report_sampled(const gamd_handle* h, long long s) {
-    return h->rep.interval > 0 && (h->pending.report_g0 + s + 1) % h->rep.interval == 0;
-}
-
-int enqueue_report_sample(gamd_handle* h, long long s);
-
-// run recorder: blocks per box of k_traj_corr / k_traj_com (fixed per handle: the summation tree never changes)
-int traj_corr_blocks(const gamd_handle* h) { return std::max(1, std::min(16, (h->n_per_box + 1023) / 1024)); }
-
-// run recorder: does step s of the pending run carry a sample?
-bool traj_sampled(const gamd_handle* h, long long s) {
-    return h->rec.interval > 0 && (h->pending.traj_g0 + s + 1) % h->rec.interval == 0;
-}
-
-// structure sampler: blocks per box of k_struct_rho (fixed per handle: the summation tree never changes)
-int struct_rho_blocks(const gamd_handle* h) { return std::max(1, std::min(64, (h->n_per_box + 255) / 256)); }
-
-// structure sampler: does step s of the pending run carry a sample?
-bool struct_sampled(const gamd_handle* h, long long s) {
-    return h->ss.interval > 0 && (h->pending.struct_g0 + s + 1) % h->ss.interval == 0;
-}
-
-// this step carries a reporter, recorder or structure sample: its second half must be complete in front of them
-bool step_sampled(const gamd_handle* h, long long s) { return report_sampled(h, s) || traj_sampled(h, s) || struct_sampled(h, s); }
-
-// the structure sampler's sample of step s of the pending run, behind its second half
-int enqueue_struct_sample(gamd_handle* h, long long s) {
-    const MdPending& p = h->pending;
-    const StructSampler& sp = h->ss;
-    StructArgs a{};
-    a.n = h->n;
-    a.bx = box_ref(h);
-    a.devflags = h->devflags.as<int>();
-    a.sticky = h->sticky_dev;
-    for (int d = 0; d < 3; ++d) { a.box[d] = h->box[d]; a.half[d] = 0.5f * h->box[d]; }
-    a.n_pairs = sp.pairs;
-    (void)s;                                                // no row of its own: the host counts the frames
-    int r;
-    if (sp.bins > 0) {
-        a.pos_s = h->pos_s.as<float4>();
-        a.perm = h->perm.as<int>();
-        a.n_bins = sp.bins;
-        a.r_max = sp.rmax; a.bin_scale = (float)sp.bins;
-        a.exclude_same_molecule = sp.exclude;
-        a.tiles = (h->n_per_box + 255) / 256;
-        a.counts = sp.counts.as<unsigned long long>();
-        if ((r = launch_struct_pairs(a, p.st))) return fail(-1, "structure sampler launch failed (%d)", r);
-    }
-    if (sp.n_k > 0) {
-        a.x = p.x;
-        a.species = p.species;
-        a.classes = sp.pairs == 3 ? 2 : 1;
-        a.n_k = sp.n_k;
-        a.kvec = sp.kvec.as<int>();
-        a.rho_blocks = struct_rho_blocks(h);
-        a.rho_partial = sp.rho_partial.as<double>();
-        a.sk_sum = sp.sk_sum.as<double>();
-        if ((r = launch_struct_sk(a, p.st))) return fail(-1, "structure sampler launch failed (%d)", r);
-    }
-    return 0;
-}
-
-// the recorder's sample of step s of the pending run, behind its second half
-int enqueue_traj_sample(gamd_handle* h, long long s) {
-    const MdPending& p = h->pending;
-    const Recorder& rc = h->rec;
-    TrajArgs a{};
-    a.n = h->n;
-    a.bx = box_ref(h);
-    for (int d = 0; d < 3; ++d) a.box[d] = h->box[d];
-    a.devflags = h->devflags.as<int>();
-    a.x = p.x; a.f = p.f;
-    if (p.kind == 0) {
-        a.v = p.m.v; a.species = p.m.species;
-        a.mass = (double)p.mass; a.mass_h = (double)p.mass_h;
-    } else {
-        a.v = p.a.v; a.species = p.a.species;
-        a.mass = (double)p.a.mass; a.mass_h = (double)p.a.mass_h;
-    }
-    a.g = p.traj_g0 + s + 1;
-    a.q = a.g / rc.interval - 1;                        // the sample's ordinal, chosen here like the reporter's row
-    a.frame = a.q < rc.max_frames ? a.q : -1;
-    a.steps = rc.steps.as<long long>();
-    a.fx = rc.fx.as<float>(); a.fv = rc.fv.as<float>(); a.ff = rc.ff.as<float>(); a.fimg = rc.fimg.as<int>();
-    a.x_prev = rc.x_prev.as<float>();
-    a.image = rc.image.as<int>();
-    a.ambiguous = rc.ambiguous.as<unsigned long long>();
-    a.n_lags = rc.n_lags;
-    a.classes = p.traj_classes;
-    if (rc.n_lags > 0) {
-        a.slot = (int)(a.q % rc.n_lags);
-        a.active = (int)std::min<long long>(a.q, rc.n_lags - 1) + 1;
-        a.subtract_com = rc.subtract_com;
-        a.ring_x = rc.ring_x.as<float>(); a.ring_img = rc.ring_img.as<int>(); a.ring_v = rc.ring_v.as<float>();
-        a.ring_com = rc.ring_com.as<double>();
-        a.com_partial = rc.com_partial.as<double>();
-        a.com_blocks = a.corr_blocks = traj_corr_blocks(h);
-        a.corr_partial = rc.corr_partial.as<double>();
-        a.msd = rc.msd.as<double>(); a.vacf = rc.vacf.as<double>();
-        a.class_atoms = rc.class_atoms.as<long long>();
-    }
-    if (int r = launch_traj_sample(a, p.st)) return fail(-1, "recorder launch failed (%d)", r);
-    return 0;
-}
-
-// the samples of step s, behind its second half
-int enqueue_samples(gamd_handle* h, long long s) {
-    int r;
-    if (report_sampled(h, s) && (r = enqueue_report_sample(h, s))) return r;
-    if (traj_sampled(h, s) && (r = enqueue_traj_sample(h, s))) return r;
-    if (struct_sampled(h, s) && (r = enqueue_struct_sample(h, s))) return r;
-    return 0;
-}
-
-// the sample of step s of the pending run, behind its second half: the kinetic-energy row and the frame's pair histogram
-int enqueue_report_sample(gamd_handle* h, long long s) {
-    const MdPending& p = h->pending;
-    const Reporter& rp = h->rep;
-    ReportArgs a{};
-    a.n = h->n;
-    a.bx = box_ref(h);
-    a.devflags = h->devflags.as<int>();
-    a.sticky = h->sticky_dev;
-    if (p.kind == 0) {
-        a.v = p.m.v; a.species = p.m.species; a.len = (double)p.m.len;
-        a.mass = (double)p.mass; a.mass_h = (double)p.mass_h;
-    } else {
-        a.v = p.a.v; a.species = p.a.species; a.len = (double)p.a.len;
-        a.mass = (double)p.a.mass; a.mass_h = (double)p.a.mass_h;
-    }
-    a.partial = rp.partial.as<double>();
-    a.blocks = report_ke_blocks(h);
-    a.steps = rp.steps.as<long long>();
-    a.ke = rp.ke.as<double>();
-    a.g = p.report_g0 + s + 1;
-    a.slot = a.g / rp.interval - 1;
-    int r;
-    // the row is the sample's ordinal, chosen here: a sample enqueued again after a freeze writes the same row
-    if (a.slot < rp.max_samples && (r = launch_report_ke(a, p.st))) return fail(-1, "reporter launch failed (%d)", r);
-    if (rp.bins > 0) {
-        a.counters = h->cur_counters;
-        a.pos_s = h->pos_s.as<float4>();
-        a.col = h->col.as<int>(); a.erow = h->erow.as<int>(); a.row_ptr = h->row_ptr.as<int>(); a.perm = h->perm.as<int>();
-        a.e_cap = h->e_cap;
-        for (int d = 0; d < 3; ++d) { a.box[d] = h->box[d]; a.half[d] = 0.5f * h->box[d]; }
-        a.n_bins = rp.bins; a.n_pairs = rp.pairs;
-        a.r_max = rp.rmax; a.bin_scale = (float)rp.bins;
-        a.all_edges = rp.rmax >= h->cfg.cutoff ? 1 : 0;
-        a.exclude_same_molecule = rp.exclude;
-        a.counts = rp.counts.as<unsigned long long>();
-        // ~16 edge slots per thread; every workgroup flushes its non-zero bins with one atomic each
-        a.rdf_blocks = (int)std::max<long long>(1, std::min<long long>(h->n_cu, h->e_cap / h->n_boxes / 4096));
-        if ((r = launch_report_rdf(a, p.st))) return fail(-1, "reporter launch failed (%d)", r);
-    }
-    return 0;
-}
-
 // steps [s_begin, n_steps) of the pending MD run; skip_first: the first half of step s_begin has already been done
 int enqueue_md_steps(gamd_handle* h, long long s_begin, bool skip_first) {
     MdPending& p = h->pending;
@@ -1044,8 +619,8 @@ int enqueue_md_steps(gamd_handle* h, long long s_begin, bool skip_first) {
             if ((r = step_event(h, p.st))) return r;
             p.m.step = p.first_step + (unsigned long long)s;
             p.m.step_index = (int)s;
-            // (the B of a step that carries a reporter or recorder sample has been launched on its own, in front of the sample)
-            int do_second = (s > s_begin && !step_sampled(h, s - 1)) ? 1 : 0;
+            // (the B of a step that carries an observer's sample has been launched on its own, in front of the sample)
+            int do_second = (s > s_begin && !observers_sampled(h, s - 1)) ? 1 : 0;
             const int do_first = (skip_first && s == s_begin) ? 0 : 1;
             if (p.m.com.enabled) {
                 // COM motion removal sits between the B of step s-1 and the first half of step s and needs a sum over all
@@ -1071,15 +646,15 @@ int enqueue_md_steps(gamd_handle* h, long long s_begin, bool skip_first) {
             if ((r = enqueue_forward(h, p.x, p.species, nullptr, p.f, p.st, nullptr, nullptr, nullptr, nullptr, &fuse,
                                      s + 1 == p.n_steps, s > s_begin)))
                 return r;
-            if (s + 1 < p.n_steps && step_sampled(h, s)) {        // a sampled step completes its B before the sample
+            if (s + 1 < p.n_steps && observers_sampled(h, s)) {        // a sampled step completes its B before the sample
                 if ((r = launch_baoab_second(p.m, p.st))) return fail(-1, "integrator launch failed (%d)", r);
-                if ((r = enqueue_samples(h, s))) return r;
+                if ((r = observers_enqueue(h, s))) return r;
             }
         }
         if (p.n_steps > s_begin) {
             p.m.step_index = (int)(p.n_steps - 1);
             if ((r = launch_baoab_second(p.m, p.st))) return fail(-1, "integrator launch failed (%d)", r);
-            if ((r = enqueue_samples(h, p.n_steps - 1))) return r;
+            if ((r = observers_enqueue(h, p.n_steps - 1))) return r;
         }
         return step_event(h, p.st, true);
     }
@@ -1099,57 +674,34 @@ int enqueue_md_steps(gamd_handle* h, long long s_begin, bool skip_first) {
             if ((r = enqueue_forward(h, p.x, p.species, nullptr, p.f, p.st, nullptr, nullptr, nullptr, nullptr, nullptr, last, s > s_begin))) return r;
             if ((r = launch_nhc_second(p.a, p.st))) return fail(-1, "integrator launch failed (%d)", r);
         }
-        if ((r = enqueue_samples(h, s))) return r;
+        if ((r = observers_enqueue(h, s))) return r;
     }
     return step_event(h, p.st, true);
 }
 
-// run recorder, at the top of gamd_md_run / gamd_md_run_nhc: the image counters and the ring are only meaningful in one box
-// and with one set of classes
-int traj_run_classes(const gamd_handle* h, const uint8_t* species_dev) {
-    return (h->cfg.kind == GAMD_KIND_WATER && species_dev) ? 2 : 1;
-}
-int traj_check_run(gamd_handle* h, const float* box, const uint8_t* species_dev) {
-    const Recorder& rc = h->rec;
-    if (rc.interval <= 0) return 0;
-    if (rc.n_lags > 0 && rc.classes && rc.classes != traj_run_classes(h, species_dev))
-        return fail(-22, "run recorder: species given in one run and not in another since gamd_traj_configure / gamd_traj_reset");
-    if ((rc.n_lags > 0 || (rc.fields & GAMD_TRAJ_IMAGE)) && !rc.box0.empty())
-        for (size_t k = 0; k < rc.box0.size(); ++k)
-            if (rc.box0[k] != box[k])
-                return fail(-22, "run recorder: the box differs from the box of the first run since gamd_traj_configure / "
-                                 "gamd_traj_reset (image counters and correlation functions need one box; call gamd_traj_reset)");
+// gamd_md_run / gamd_md_run_nhc (p: gamd_md_params / gamd_nhc_params, a: MdArgs / NhcArgs): atoms, units, rigid water, box,
+// centre-of-mass motion removal and the freeze flags of the integrator's argument block
+template <typename Params, typename Args>
+int fill_run_args(gamd_handle* h, const Params* p, const float* box, const uint8_t* species_dev, hipStream_t st, Args* a) {
+    int r;
+    a->n = h->n; a->species = species_dev; a->dt = p->dt_ps;
+    a->len = p->length_per_nm > 0.f ? p->length_per_nm : 10.0f;
+    if ((r = fill_rigid(h, p->rigid_water, p->mass_amu, p->mass_h_amu, p->r_oh, p->r_hh, &a->use_rigid, &a->rigid))) return r;
+    if (a->use_rigid && (r = check_rigid_layout(h, species_dev, st))) return r;
+    for (int d = 0; d < 3; ++d) a->box[d] = box[d];
+    a->bx = box_ref(h);
+    if ((r = fill_com(h, p->remove_cm_motion, &a->com))) return r;
+    a->devflags = h->devflags.as<int>();
     return 0;
-}
-// ... and once the run is certain to be enqueued
-void traj_begin_run(gamd_handle* h, const float* box, const uint8_t* species_dev, long long n_steps) {
-    Recorder& rc = h->rec;
-    h->pending.traj_g0 = rc.g;
-    h->pending.traj_classes = traj_run_classes(h, species_dev);
-    if (rc.interval <= 0) return;
-    if (rc.box0.empty()) rc.box0.assign(box, box + 3 * (size_t)h->n_boxes);
-    if (!rc.classes) rc.classes = h->pending.traj_classes;
-    rc.g += n_steps;
 }
 
-// structure sampler, at the top of gamd_md_run / gamd_md_run_nhc: the minimum image is the nearest image only inside the
-// sphere of half the shortest edge, and the S(k) classes need the species in the caller's order
-int struct_check_run(gamd_handle* h, const float* box, const uint8_t* species_dev) {
-    const StructSampler& sp = h->ss;
-    if (sp.interval <= 0) return 0;
-    if (sp.bins > 0)
-        for (int k = 0; k < 3 * h->n_boxes; ++k)
-            if (!(2.0f * sp.rmax <= box[k]))
-                return fail(-22, "structure sampler: rdf_rmax = %g exceeds half of box[%d][%d] = %g (the minimum image is the nearest "
-                                 "image only below that)", (double)sp.rmax, k / 3, k % 3, (double)box[k]);
-    if (sp.n_k > 0 && sp.pairs == 3 && !species_dev)
-        return fail(-22, "structure sampler: the partial structure factors of a water handle need species");
-    return 0;
-}
-// ... and once the run is certain to be enqueued
-void struct_begin_run(gamd_handle* h, long long n_steps) {
-    h->pending.struct_g0 = h->ss.g;
-    if (h->ss.interval > 0) h->ss.g += n_steps;
+// ... and once the run is certain to be enqueued (pending.kind and its argument block are set)
+int start_run(gamd_handle* h, float* x_dev, float* f_dev, const uint8_t* species_dev, const float* box, long long n_steps, hipStream_t st) {
+    MdPending& pd = h->pending;
+    pd.active = true; pd.n_steps = n_steps;
+    pd.x = x_dev; pd.f = f_dev; pd.species = species_dev; pd.st = st;
+    observers_begin_run(h, box, species_dev, n_steps);
+    return enqueue_md_steps(h, 0, false);
 }
 
 }  // namespace
@@ -1210,6 +762,7 @@ int32_t gamd_create(const gamd_config* cfg, gamd_handle** out) {
     if (cfg->edge_dtype != GAMD_EDGE_F32 && H == 256 && (long long)cfg->n_atoms * n_boxes > (1ll << 22) - 2)
         return fail(-22, "bf16 / split-fp16 with encoding_size > 128: at most 2^22 - 2 atoms per handle (32-bit byte offsets into hn)");
     gamd_handle* h = new gamd_handle();
+    h->obs = observers_new();
     h->cfg = *cfg;
     h->dev = cfg->device;
     if (hipStreamCreateWithFlags(&h->init_stream, hipStreamNonBlocking) != hipSuccess) {
@@ -1335,13 +888,9 @@ int32_t gamd_destroy(gamd_handle* h) {
                       &h->na_excl, &h->bond_nbr, &h->hbuf, &h->hn, &h->S, &h->D, &h->P, &h->l0_h, &h->l0_hn, &h->l0_S, &h->l0_D, &h->l0_P, &h->f_norm, &h->f_den,
                       &h->cell_cnt, &h->cell_fill, &h->cell_start, &h->col, &h->erow, &h->chunk_piece,
                       &h->chunk_mask, &h->e_frag, &h->e_emb, &h->e_frag2, &h->partial, &h->feat_dbg, &h->counters, &h->tdbg, &h->tmp_eid, &h->ke_partial, &h->com_partial,
-                      &h->rep.steps, &h->rep.ke, &h->rep.counts, &h->rep.partial,
-                      &h->rec.steps, &h->rec.fx, &h->rec.fv, &h->rec.ff, &h->rec.fimg, &h->rec.x_prev, &h->rec.image, &h->rec.ambiguous,
-                      &h->rec.ring_x, &h->rec.ring_img, &h->rec.ring_v, &h->rec.ring_com, &h->rec.com_partial, &h->rec.corr_partial,
-                      &h->rec.msd, &h->rec.vacf, &h->rec.class_atoms,
-                      &h->ss.counts, &h->ss.kvec, &h->ss.rho_partial, &h->ss.sk_sum,
                       &h->ref_pos, &h->cand_deg, &h->cand_ptr, &h->cand_col};
     for (DevBuf* b : bufs) b->release();
+    observers_free(h);
     h->pos_in.release();
     if (h->host_in) (void)hipHostFree(h->host_in);
     if (h->host_out) (void)hipHostFree(h->host_out);
@@ -2021,41 +1570,26 @@ int32_t gamd_md_run(gamd_handle* h, float* x_dev, float* v_dev, float* f_dev, co
     if (!x_dev || !v_dev || !f_dev || !box || !p) return fail(-22, "null argument");
     if (n_steps < 0 || n_steps > 0x3fffffff) return fail(-22, "n_steps out of range");
     if ((r = check_model_inputs(h, species_dev))) return r;
-    if ((r = traj_check_run(h, box, species_dev))) return r;
-    if ((r = struct_check_run(h, box, species_dev))) return r;
+    if ((r = observers_check_run(h, box, species_dev))) return r;
     DeviceGuard guard(h->dev);
     InitStream init((hipStream_t)stream);
     if ((r = set_box(h, box, (hipStream_t)stream))) return r;
     hipStream_t st = (hipStream_t)stream;
     MdArgs m{};
-    m.n = h->n; m.x = x_dev; m.v = v_dev; m.f = f_dev;
+    m.x = x_dev; m.v = v_dev; m.f = f_dev;
     if (!(p->mass_amu > 0.f)) return fail(-22, "mass_amu must be positive");
-    m.species = species_dev;
     m.inv_mass = 1.0f / p->mass_amu;
     m.inv_mass_h = p->mass_h_amu > 0.f ? 1.0f / p->mass_h_amu : 0.f;
-    m.len = p->length_per_nm > 0.f ? p->length_per_nm : 10.0f;
-    m.dt = p->dt_ps;
+    if ((r = fill_run_args(h, p, box, species_dev, st, &m))) return r;
     const double kB = 0.00831446261815324;                       // kJ/mol/K
     const double a = std::exp(-(double)p->gamma_per_ps * p->dt_ps);
     m.a = (float)a;
     m.b_len_kT = (float)(std::sqrt(1.0 - a * a) * (double)m.len * std::sqrt(kB * p->temperature_k));
-    if ((r = fill_rigid(h, p->rigid_water, p->mass_amu, p->mass_h_amu, p->r_oh, p->r_hh, &m.use_rigid, &m.rigid)))
-        return r;
-    if (m.use_rigid && (r = check_rigid_layout(h, species_dev, st))) return r;
-    for (int d = 0; d < 3; ++d) m.box[d] = box[d];
-    m.bx = box_ref(h);
-    if ((r = fill_com(h, p->remove_cm_motion, &m.com))) return r;
     m.seed = p->seed;
-    m.devflags = h->devflags.as<int>();
     MdPending& pd = h->pending;
-    pd.active = true; pd.kind = 0; pd.m = m; pd.first_step = p->first_step; pd.n_steps = n_steps;
+    pd.kind = 0; pd.m = m; pd.first_step = p->first_step;
     pd.mass = p->mass_amu; pd.mass_h = p->mass_h_amu > 0.f ? p->mass_h_amu : 0.f;
-    pd.x = x_dev; pd.f = f_dev; pd.species = species_dev; pd.st = st;
-    pd.report_g0 = h->rep.g;
-    if (h->rep.interval > 0) h->rep.g += n_steps;
-    traj_begin_run(h, box, species_dev, n_steps);
-    struct_begin_run(h, n_steps);
-    return enqueue_md_steps(h, 0, false);
+    return start_run(h, x_dev, f_dev, species_dev, box, n_steps, st);
 }
 
 int32_t gamd_md_run_nhc(gamd_handle* h, float* x_dev, float* v_dev, float* f_dev, const uint8_t* species_dev,
@@ -2072,25 +1606,16 @@ int32_t gamd_md_run_nhc(gamd_handle* h, float* x_dev, float* v_dev, float* f_dev
                                  0.2967324292201065};                       // hack_integrator.py:183-187
     const double* ys = p->num_yoshidasuzuki == 1 ? YS1 : p->num_yoshidasuzuki == 3 ? YS3 : p->num_yoshidasuzuki == 5 ? YS5 : nullptr;
     if (!ys) return fail(-22, "Invalid Yoshida-Suzuki value. Allowed values are: 1,3,5");
-    if ((r = traj_check_run(h, box, species_dev))) return r;
-    if ((r = struct_check_run(h, box, species_dev))) return r;
+    if ((r = observers_check_run(h, box, species_dev))) return r;
     DeviceGuard guard(h->dev);
     InitStream init((hipStream_t)stream);
     if ((r = set_box(h, box, (hipStream_t)stream))) return r;
     hipStream_t st = (hipStream_t)stream;
     NhcArgs a{};
-    a.n = h->n; a.x = x_dev; a.v = v_dev; a.f = f_dev;
+    a.x = x_dev; a.v = v_dev; a.f = f_dev;
     if (!(p->mass_amu > 0.f)) return fail(-22, "mass_amu must be positive");
-    a.species = species_dev;
     a.mass = p->mass_amu; a.mass_h = p->mass_h_amu > 0.f ? p->mass_h_amu : 0.f;
-    a.len = p->length_per_nm > 0.f ? p->length_per_nm : 10.0f;
-    a.dt = p->dt_ps;
-    if ((r = fill_rigid(h, p->rigid_water, p->mass_amu, p->mass_h_amu, p->r_oh, p->r_hh, &a.use_rigid, &a.rigid)))
-        return r;
-    if (a.use_rigid && (r = check_rigid_layout(h, species_dev, st))) return r;
-    for (int d = 0; d < 3; ++d) a.box[d] = box[d];
-    a.bx = box_ref(h);
-    if ((r = fill_com(h, p->remove_cm_motion, &a.com))) return r;
+    if ((r = fill_run_args(h, p, box, species_dev, st, &a))) return r;
     a.kT = 0.00831446261815324 * (double)p->temperature_k;
     a.freq = p->frequency_per_ps;
     a.ndf = p->ndf;
@@ -2100,7 +1625,6 @@ int32_t gamd_md_run_nhc(gamd_handle* h, float* x_dev, float* v_dev, float* f_dev
     a.n_blocks = std::min(256, (3 * h->n_per_box + 255) / 256);       // per box
     if (h->ke_partial.ensure(sizeof(double) * 256 * (size_t)h->n_boxes, true)) return fail(-12, "allocation failed");
     a.partial = h->ke_partial.as<double>();
-    a.devflags = h->devflags.as<int>();
     if (p->reset) {
         const size_t stride = 3 * (size_t)a.M + 2;
         std::vector<double> init(stride * (size_t)h->n_boxes, 0.0);
@@ -2110,326 +1634,8 @@ int32_t gamd_md_run_nhc(gamd_handle* h, float* x_dev, float* v_dev, float* f_dev
         HIP_TRY(hipStreamSynchronize(st));
     }
     MdPending& pd = h->pending;
-    pd.active = true; pd.kind = 1; pd.a = a; pd.first_step = 0; pd.n_steps = n_steps;
-    pd.x = x_dev; pd.f = f_dev; pd.species = species_dev; pd.st = st;
-    pd.report_g0 = h->rep.g;
-    if (h->rep.interval > 0) h->rep.g += n_steps;
-    traj_begin_run(h, box, species_dev, n_steps);
-    struct_begin_run(h, n_steps);
-    return enqueue_md_steps(h, 0, false);
-}
-
-static_assert(sizeof(gamd_report_params) == 40 && offsetof(gamd_report_params, ndf) == 16 && offsetof(gamd_report_params, rdf_rmax) == 28,
-              "gamd_report_params layout is part of the C ABI (gamd_amd/_lib.py mirrors it)");
-
-// clear the reporter's step count, log and histogram (on the init stream, landed before it returns)
-static int report_clear(gamd_handle* h) {
-    Reporter& rp = h->rep;
-    rp.g = 0;
-    DevBuf* bufs[] = {&rp.steps, &rp.ke, &rp.counts};
-    for (DevBuf* b : bufs)
-        if (b->p) HIP_TRY(hipMemsetAsync(b->p, 0, b->bytes, tl_init_stream));
-    HIP_TRY(hipStreamSynchronize(tl_init_stream));
-    return 0;
-}
-
-int32_t gamd_report_configure(gamd_handle* h, const gamd_report_params* p) {
-    // the parameter block is checked first: these answers need no device
-    if (!p) return fail(-22, "null argument");
-    if (p->interval < 0) return fail(-22, "interval = %lld is negative", (long long)p->interval);
-    if (p->max_samples < 0 || p->max_samples > (1ll << 24)) return fail(-22, "max_samples = %lld outside [0, 2^24]", (long long)p->max_samples);
-    if (p->rdf_bins < 0 || p->rdf_bins > 1024) return fail(-22, "rdf_bins = %d outside [0, 1024]", (int)p->rdf_bins);
-    if (!(p->rdf_rmax >= 0.f)) return fail(-22, "rdf_rmax = %g is negative", (double)p->rdf_rmax);
-    if (!(p->ndf >= 0.0)) return fail(-22, "ndf = %g is negative", p->ndf);
-    if (!h) return fail(-22, "null handle");
-    if (p->rdf_rmax > h->cfg.cutoff)
-        return fail(-22, "rdf_rmax = %g exceeds the cutoff %g: pairs beyond it are not in the edge list", (double)p->rdf_rmax, (double)h->cfg.cutoff);
-    Reporter& rp = h->rep;
-    if (h->pending.active) return fail(-22, "an MD run is still enqueued: call gamd_sync_status before gamd_report_configure");
-    if (p->interval == 0) { rp.interval = 0; return 0; }        // off: what was recorded stays readable
-    DeviceGuard guard(h->dev);
-    InitStream init(h->init_stream);
-    rp.interval = 0;
-    rp.max_samples = p->max_samples > 0 ? p->max_samples : 4096;
-    rp.ndf = p->ndf > 0.0 ? p->ndf : 3.0 * (double)h->n_per_box;
-    rp.bins = p->rdf_bins;
-    rp.pairs = h->cfg.kind == GAMD_KIND_WATER ? 3 : 1;
-    rp.rmax = p->rdf_rmax > 0.f ? p->rdf_rmax : h->cfg.cutoff;
-    rp.exclude = p->exclude_same_molecule ? 1 : 0;
-    const size_t nb = (size_t)h->n_boxes;
-    // exact sizes (a smaller configuration after a larger one re-allocates: report_clear and gamd_report_read go by bytes)
-    DevBuf* bufs[] = {&rp.steps, &rp.ke, &rp.counts, &rp.partial};
-    const size_t want[] = {sizeof(long long) * (size_t)rp.max_samples, sizeof(double) * (size_t)rp.max_samples * nb,
-                           sizeof(unsigned long long) * nb * (size_t)rp.pairs * (size_t)rp.bins,
-                           sizeof(double) * nb * (size_t)report_ke_blocks(h)};
-    for (int k = 0; k < 4; ++k) {
-        if (bufs[k]->bytes != want[k]) bufs[k]->release();
-        if (want[k] && bufs[k]->ensure(want[k], true)) return fail(-12, "reporter allocation failed");
-    }
-    int r;
-    if ((r = report_clear(h))) return r;
-    rp.interval = rp.sample_interval = p->interval;
-    return 0;
-}
-
-int32_t gamd_report_reset(gamd_handle* h) {
-    if (!h) return fail(-22, "null handle");
-    if (h->pending.active) return fail(-22, "an MD run is still enqueued: call gamd_sync_status before gamd_report_reset");
-    DeviceGuard guard(h->dev);
-    InitStream init(h->init_stream);
-    return report_clear(h);
-}
-
-int32_t gamd_report_read(gamd_handle* h, void* stream, int64_t* steps, double* ke, double* temperature, int64_t max_rows,
-                         int64_t* n_rows, uint64_t* counts, int64_t count_elems, int64_t* frames, int64_t* dropped,
-                         int32_t dims[3]) {
-    if (!h) return fail(-22, "null handle");
-    if (max_rows < 0) return fail(-22, "max_rows is negative");
-    const Reporter& rp = h->rep;
-    DeviceGuard guard(h->dev);
-    hipStream_t st = (hipStream_t)stream;
-    const long long nb = h->n_boxes;
-    const long long taken = (rp.sample_interval > 0 && rp.steps.p) ? rp.g / rp.sample_interval : 0;
-    const long long rows = std::min<long long>(taken, rp.max_samples);
-    const long long n_copy = std::min<long long>(rows, max_rows);
-    const long long elems = nb * (long long)rp.pairs * (long long)rp.bins;
-    if (counts && rp.counts.p && count_elems < elems) return fail(-22, "counts has room for %lld elements, the histogram has %lld", (long long)count_elems, elems);
-    if (n_copy > 0 && steps) HIP_TRY(hipMemcpyAsync(steps, rp.steps.p, sizeof(int64_t) * (size_t)n_copy, hipMemcpyDeviceToHost, st));
-    if (n_copy > 0 && ke) HIP_TRY(hipMemcpyAsync(ke, rp.ke.p, sizeof(double) * (size_t)(n_copy * nb), hipMemcpyDeviceToHost, st));
-    if (n_copy > 0 && temperature && !ke) return fail(-22, "temperature needs ke");
-    if (counts && rp.counts.p && elems > 0) HIP_TRY(hipMemcpyAsync(counts, rp.counts.p, sizeof(uint64_t) * (size_t)elems, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (int t = check_traps(h)) return t;
-    if (temperature)
-        for (long long k = 0; k < n_copy * nb; ++k) temperature[k] = 2.0 * ke[k] / (rp.ndf * 0.00831446261815324);
-    if (n_rows) *n_rows = rows;
-    if (frames) *frames = (rp.bins > 0 && rp.counts.p) ? taken : 0;
-    if (dropped) *dropped = taken - rows;
-    if (dims) { dims[0] = (int32_t)nb; dims[1] = rp.pairs; dims[2] = rp.counts.p ? rp.bins : 0; }
-    return 0;
-}
-
-static_assert(sizeof(gamd_traj_params) == 32 && offsetof(gamd_traj_params, fields) == 16 && offsetof(gamd_traj_params, n_lags) == 20 &&
-              offsetof(gamd_traj_params, subtract_com) == 24,
-              "gamd_traj_params layout is part of the C ABI (gamd_amd/_lib.py mirrors it)");
-
-// clear the recorder's step count, frames, image counters, ring and sums (on the init stream, landed before it returns)
-static int traj_clear(gamd_handle* h) {
-    Recorder& rc = h->rec;
-    rc.g = 0;
-    rc.classes = 0;
-    rc.box0.clear();
-    DevBuf* bufs[] = {&rc.steps, &rc.fx, &rc.fv, &rc.ff, &rc.fimg, &rc.x_prev, &rc.image, &rc.ambiguous, &rc.ring_x, &rc.ring_img,
-                      &rc.ring_v, &rc.ring_com, &rc.msd, &rc.vacf, &rc.class_atoms};
-    for (DevBuf* b : bufs)
-        if (b->p) HIP_TRY(hipMemsetAsync(b->p, 0, b->bytes, tl_init_stream));
-    HIP_TRY(hipStreamSynchronize(tl_init_stream));
-    return 0;
-}
-
-int32_t gamd_traj_configure(gamd_handle* h, const gamd_traj_params* p) {
-    if (!p) return fail(-22, "null argument");
-    if (p->interval < 0) return fail(-22, "interval = %lld is negative", (long long)p->interval);
-    if (p->max_frames < 0 || p->max_frames > (1ll << 24)) return fail(-22, "max_frames = %lld outside [0, 2^24]", (long long)p->max_frames);
-    if (p->fields & ~(GAMD_TRAJ_X | GAMD_TRAJ_V | GAMD_TRAJ_F | GAMD_TRAJ_IMAGE)) return fail(-22, "fields = %d has unknown bits", (int)p->fields);
-    if (p->n_lags < 0 || p->n_lags > 4096) return fail(-22, "n_lags = %d outside [0, 4096]", (int)p->n_lags);
-    if (!h) return fail(-22, "null handle");
-    if (p->n_lags > 0 && h->n_boxes > 65535) return fail(-22, "correlation functions need n_boxes <= 65535");
-    Recorder& rc = h->rec;
-    if (h->pending.active) return fail(-22, "an MD run is still enqueued: call gamd_sync_status before gamd_traj_configure");
-    if (p->interval == 0) { rc.interval = 0; return 0; }        // off: what was recorded stays readable
-    DeviceGuard guard(h->dev);
-    InitStream init(h->init_stream);
-    rc.interval = 0;
-    rc.max_frames = p->max_frames;
-    rc.fields = p->fields;
-    rc.n_lags = p->n_lags;
-    rc.subtract_com = (p->subtract_com && p->n_lags > 0) ? 1 : 0;
-    const size_t nb = (size_t)h->n_boxes, n3 = 3 * (size_t)h->n, fr = (size_t)rc.max_frames, lags = (size_t)rc.n_lags;
-    const size_t cls = h->cfg.kind == GAMD_KIND_WATER ? 2 : 1, blocks = (size_t)traj_corr_blocks(h);
-    // exact sizes (a smaller configuration after a larger one re-allocates: traj_clear and the read calls go by bytes)
-    DevBuf* bufs[] = {&rc.steps, &rc.fx, &rc.fv, &rc.ff, &rc.fimg, &rc.x_prev, &rc.image, &rc.ambiguous, &rc.ring_x, &rc.ring_img,
-                      &rc.ring_v, &rc.ring_com, &rc.com_partial, &rc.corr_partial, &rc.msd, &rc.vacf, &rc.class_atoms};
-    const size_t want[] = {sizeof(long long) * fr,
-                           (rc.fields & GAMD_TRAJ_X) ? sizeof(float) * fr * n3 : 0, (rc.fields & GAMD_TRAJ_V) ? sizeof(float) * fr * n3 : 0,
-                           (rc.fields & GAMD_TRAJ_F) ? sizeof(float) * fr * n3 : 0, (rc.fields & GAMD_TRAJ_IMAGE) ? sizeof(int) * fr * n3 : 0,
-                           sizeof(float) * n3, sizeof(int) * n3, sizeof(unsigned long long),
-                           sizeof(float) * lags * n3, sizeof(int) * lags * n3, sizeof(float) * lags * n3,
-                           rc.subtract_com ? sizeof(double) * lags * nb * 3 : 0, rc.subtract_com ? sizeof(double) * nb * blocks * 4 : 0,
-                           sizeof(double) * nb * lags * blocks * cls * 2, sizeof(double) * nb * cls * lags, sizeof(double) * nb * cls * lags,
-                           lags ? sizeof(long long) * nb * cls : 0};
-    for (int k = 0; k < 17; ++k) {
-        if (bufs[k]->bytes != want[k]) bufs[k]->release();
-        if (want[k] && bufs[k]->ensure(want[k], true)) return fail(-12, "recorder allocation failed");
-    }
-    int r;
-    if ((r = traj_clear(h))) return r;
-    rc.interval = rc.sample_interval = p->interval;
-    return 0;
-}
-
-int32_t gamd_traj_reset(gamd_handle* h) {
-    if (!h) return fail(-22, "null handle");
-    if (h->pending.active) return fail(-22, "an MD run is still enqueued: call gamd_sync_status before gamd_traj_reset");
-    DeviceGuard guard(h->dev);
-    InitStream init(h->init_stream);
-    return traj_clear(h);
-}
-
-int32_t gamd_traj_read_frames(gamd_handle* h, void* stream, int64_t first, int64_t count, int64_t* steps, float* x, float* v,
-                              float* f, int32_t* image, int64_t* n_frames, int64_t* dropped) {
-    if (!h) return fail(-22, "null handle");
-    if (first < 0 || count < 0) return fail(-22, "first / count is negative");
-    const Recorder& rc = h->rec;
-    DeviceGuard guard(h->dev);
-    hipStream_t st = (hipStream_t)stream;
-    const long long taken = (rc.sample_interval > 0 && rc.x_prev.p) ? rc.g / rc.sample_interval : 0;
-    const long long kept = std::min<long long>(taken, rc.max_frames);
-    const long long n_copy = std::max<long long>(0, std::min<long long>(kept - first, count));
-    const size_t n3 = 3 * (size_t)h->n;
-    if (n_copy > 0) {
-        const size_t off = (size_t)first * n3, elems = (size_t)n_copy * n3;
-        if (steps) HIP_TRY(hipMemcpyAsync(steps, rc.steps.as<long long>() + first, sizeof(int64_t) * (size_t)n_copy, hipMemcpyDeviceToHost, st));
-        if (x && rc.fx.p) HIP_TRY(hipMemcpyAsync(x, rc.fx.as<float>() + off, sizeof(float) * elems, hipMemcpyDeviceToHost, st));
-        if (v && rc.fv.p) HIP_TRY(hipMemcpyAsync(v, rc.fv.as<float>() + off, sizeof(float) * elems, hipMemcpyDeviceToHost, st));
-        if (f && rc.ff.p) HIP_TRY(hipMemcpyAsync(f, rc.ff.as<float>() + off, sizeof(float) * elems, hipMemcpyDeviceToHost, st));
-        if (image && rc.fimg.p) HIP_TRY(hipMemcpyAsync(image, rc.fimg.as<int>() + off, sizeof(int32_t) * elems, hipMemcpyDeviceToHost, st));
-    }
-    HIP_TRY(hipStreamSynchronize(st));
-    if (int t = check_traps(h)) return t;
-    if (n_frames) *n_frames = kept;
-    if (dropped) *dropped = taken - kept;
-    return 0;
-}
-
-int32_t gamd_traj_read_dynamics(gamd_handle* h, void* stream, double* msd_sum, double* vacf_sum, int64_t elems, int64_t* n_samples,
-                                uint64_t* ambiguous, int64_t* class_atoms, int32_t dims[3]) {
-    if (!h) return fail(-22, "null handle");
-    const Recorder& rc = h->rec;
-    DeviceGuard guard(h->dev);
-    hipStream_t st = (hipStream_t)stream;
-    const long long nb = h->n_boxes, cls = rc.msd.p ? rc.classes : 0, lags = rc.msd.p ? rc.n_lags : 0;
-    const long long taken = (rc.sample_interval > 0 && rc.x_prev.p) ? rc.g / rc.sample_interval : 0;
-    const long long need = nb * cls * lags;
-    if ((msd_sum || vacf_sum) && elems < need) return fail(-22, "msd_sum / vacf_sum have room for %lld elements, the sums have %lld", (long long)elems, need);
-    if (need > 0 && msd_sum) HIP_TRY(hipMemcpyAsync(msd_sum, rc.msd.p, sizeof(double) * (size_t)need, hipMemcpyDeviceToHost, st));
-    if (need > 0 && vacf_sum) HIP_TRY(hipMemcpyAsync(vacf_sum, rc.vacf.p, sizeof(double) * (size_t)need, hipMemcpyDeviceToHost, st));
-    if (ambiguous) {
-        *ambiguous = 0;
-        if (rc.ambiguous.p) HIP_TRY(hipMemcpyAsync(ambiguous, rc.ambiguous.p, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    }
-    if (class_atoms && nb * cls > 0) HIP_TRY(hipMemcpyAsync(class_atoms, rc.class_atoms.p, sizeof(int64_t) * (size_t)(nb * cls), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (int t = check_traps(h)) return t;
-    if (n_samples) *n_samples = taken;
-    if (dims) { dims[0] = (int32_t)nb; dims[1] = (int32_t)cls; dims[2] = (int32_t)lags; }
-    return 0;
-}
-
-static_assert(sizeof(gamd_struct_params) == 32 && offsetof(gamd_struct_params, rdf_bins) == 8 && offsetof(gamd_struct_params, rdf_rmax) == 12 &&
-              offsetof(gamd_struct_params, sk_n2max) == 20,
-              "gamd_struct_params layout is part of the C ABI (gamd_amd/_lib.py mirrors it)");
-
-// clear the structure sampler's step count, histogram and sums (on the init stream, landed before it returns)
-static int struct_clear(gamd_handle* h) {
-    StructSampler& sp = h->ss;
-    sp.g = 0;
-    DevBuf* bufs[] = {&sp.counts, &sp.sk_sum};
-    for (DevBuf* b : bufs)
-        if (b->p) HIP_TRY(hipMemsetAsync(b->p, 0, b->bytes, tl_init_stream));
-    HIP_TRY(hipStreamSynchronize(tl_init_stream));
-    return 0;
-}
-
-// one of each +-n with 0 < |n|^2 <= n2max (the one whose first non-zero component is positive), sorted by (|n|^2, nx, ny, nz)
-static std::vector<int> struct_kvectors(int n2max) {
-    int m = 0;
-    while ((m + 1) * (m + 1) <= n2max) ++m;
-    std::vector<std::array<int, 4>> v;
-    for (int x = 0; x <= m; ++x)
-        for (int y = -m; y <= m; ++y)
-            for (int z = -m; z <= m; ++z) {
-                const int n2 = x * x + y * y + z * z;
-                if (n2 == 0 || n2 > n2max) continue;
-                const int lead = x != 0 ? x : (y != 0 ? y : z);
-                if (lead > 0) v.push_back({n2, x, y, z});
-            }
-    std::sort(v.begin(), v.end());
-    std::vector<int> out;
-    for (const auto& e : v) { out.push_back(e[1]); out.push_back(e[2]); out.push_back(e[3]); }
-    return out;
-}
-
-int32_t gamd_struct_configure(gamd_handle* h, const gamd_struct_params* p) {
-    if (!p) return fail(-22, "null argument");
-    if (p->interval < 0) return fail(-22, "interval = %lld is negative", (long long)p->interval);
-    if (p->rdf_bins < 0 || p->rdf_bins > 1024) return fail(-22, "rdf_bins = %d outside [0, 1024]", (int)p->rdf_bins);
-    if (p->rdf_bins > 0 && !(p->rdf_rmax > 0.f)) return fail(-22, "rdf_rmax = %g is not positive", (double)p->rdf_rmax);
-    // K grows as (2 pi / 3) n2max^1.5: 4096 is passed near n2max = 156
-    if (p->sk_n2max < 0 || p->sk_n2max > 256) return fail(-22, "sk_n2max = %d gives more than 4096 k-vectors (or is negative)", (int)p->sk_n2max);
-    std::vector<int> kv = p->sk_n2max > 0 ? struct_kvectors(p->sk_n2max) : std::vector<int>();
-    if (kv.size() / 3 > 4096) return fail(-22, "sk_n2max = %d gives %zu k-vectors, more than 4096", (int)p->sk_n2max, kv.size() / 3);
-    if (!h) return fail(-22, "null handle");
-    if (h->n_boxes > 65535) return fail(-22, "the structure sampler needs n_boxes <= 65535");
-    {
-        const long long T = (h->n_per_box + 255) / 256;
-        if (p->rdf_bins > 0 && T * (T + 1) / 2 > 0xffffffll) return fail(-22, "the pair histogram needs at most 5791 tiles of 256 atoms per box");
-    }
-    StructSampler& sp = h->ss;
-    if (h->pending.active) return fail(-22, "an MD run is still enqueued: call gamd_sync_status before gamd_struct_configure");
-    if (p->interval == 0) { sp.interval = 0; return 0; }        // off: what was sampled stays readable
-    DeviceGuard guard(h->dev);
-    InitStream init(h->init_stream);
-    sp.interval = 0;
-    sp.bins = p->rdf_bins;
-    sp.pairs = h->cfg.kind == GAMD_KIND_WATER ? 3 : 1;
-    sp.rmax = p->rdf_rmax;
-    sp.exclude = p->exclude_same_molecule ? 1 : 0;
-    sp.n_k = (int)(kv.size() / 3);
-    sp.kvec_host = kv;
-    const size_t nb = (size_t)h->n_boxes, K = (size_t)sp.n_k, cls = sp.pairs == 3 ? 2 : 1;
-    // exact sizes (a smaller configuration after a larger one re-allocates: struct_clear and gamd_struct_read go by bytes)
-    DevBuf* bufs[] = {&sp.counts, &sp.kvec, &sp.rho_partial, &sp.sk_sum};
-    const size_t want[] = {sizeof(unsigned long long) * nb * (size_t)sp.pairs * (size_t)sp.bins, sizeof(int) * 3 * K,
-                           sizeof(double) * 2 * nb * (size_t)struct_rho_blocks(h) * cls * K, sizeof(double) * nb * (size_t)sp.pairs * K};
-    for (int k = 0; k < 4; ++k) {
-        if (bufs[k]->bytes != want[k]) bufs[k]->release();
-        if (want[k] && bufs[k]->ensure(want[k], true)) return fail(-12, "structure sampler allocation failed");
-    }
-    if (K) HIP_TRY(init_upload(sp.kvec.p, kv.data(), sizeof(int) * 3 * K));
-    int r;
-    if ((r = struct_clear(h))) return r;
-    sp.interval = sp.sample_interval = p->interval;
-    return 0;
-}
-
-int32_t gamd_struct_reset(gamd_handle* h) {
-    if (!h) return fail(-22, "null handle");
-    if (h->pending.active) return fail(-22, "an MD run is still enqueued: call gamd_sync_status before gamd_struct_reset");
-    DeviceGuard guard(h->dev);
-    InitStream init(h->init_stream);
-    return struct_clear(h);
-}
-
-int32_t gamd_struct_read(gamd_handle* h, void* stream, uint64_t* counts, int64_t count_elems, double* sk_sum, int64_t sk_elems,
-                         int32_t* kvec, int64_t kvec_elems, int64_t* frames, int32_t dims[4]) {
-    if (!h) return fail(-22, "null handle");
-    const StructSampler& sp = h->ss;
-    DeviceGuard guard(h->dev);
-    hipStream_t st = (hipStream_t)stream;
-    const long long nb = h->n_boxes, bins = sp.counts.p ? sp.bins : 0, K = sp.sk_sum.p ? sp.n_k : 0;
-    const long long c_elems = nb * (long long)sp.pairs * bins, s_elems = nb * (long long)sp.pairs * K;
-    if (counts && count_elems < c_elems) return fail(-22, "counts has room for %lld elements, the histogram has %lld", (long long)count_elems, c_elems);
-    if (sk_sum && sk_elems < s_elems) return fail(-22, "sk_sum has room for %lld elements, the sums have %lld", (long long)sk_elems, s_elems);
-    if (kvec && kvec_elems < 3 * K) return fail(-22, "kvec has room for %lld elements, the list has %lld", (long long)kvec_elems, 3 * K);
-    if (counts && c_elems > 0) HIP_TRY(hipMemcpyAsync(counts, sp.counts.p, sizeof(uint64_t) * (size_t)c_elems, hipMemcpyDeviceToHost, st));
-    if (sk_sum && s_elems > 0) HIP_TRY(hipMemcpyAsync(sk_sum, sp.sk_sum.p, sizeof(double) * (size_t)s_elems, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (int t = check_traps(h)) return t;
-    if (kvec && K > 0) std::memcpy(kvec, sp.kvec_host.data(), sizeof(int32_t) * 3 * (size_t)K);
-    if (frames) *frames = (sp.sample_interval > 0 && (bins > 0 || K > 0)) ? sp.g / sp.sample_interval : 0;
-    if (dims) { dims[0] = (int32_t)nb; dims[1] = sp.pairs; dims[2] = (int32_t)bins; dims[3] = (int32_t)K; }
-    return 0;
+    pd.kind = 1; pd.a = a; pd.first_step = 0;
+    return start_run(h, x_dev, f_dev, species_dev, box, n_steps, st);
 }
 
 int32_t gamd_profile(gamd_handle* h, const float* pos_dev, const uint8_t* species_dev, const float* box,

@@ -102,6 +102,43 @@ __device__ __forceinline__ BoxDims gamd_box_dims(const BoxRef& r, const float (&
     return BoxDims{b.x, b.y, b.z, h.x, h.y, h.z};
 }
 
+// ---- pair-distance histogram of a frame (k_report_rdf over the edge list, k_struct_pairs over all pairs): one binning, 32-bit
+// bins in LDS per workgroup, one 64-bit integer atomic per non-zero bin per workgroup (exact whatever the arrival order) -----
+constexpr int GAMD_HIST_MAX_BINS = 1024;       // per pair class (rdf_bins of gamd_report_params / gamd_struct_params)
+constexpr int GAMD_HIST_MAX_PAIRS = 3;         // O-O, O-H, H-H
+// Count the pair (p, q) of a box with dimensions B: its distance to a bin, its species flags (.w, O != 0) to a pair class, and
+// `inc` onto that LDS bin — or nothing when the pair lies outside r_max.  accept_all: the caller's pair list IS the set
+// r < r_max (no second test against a rounded sqrt).  (The add is in here: a slot handed back into the kernel's loop costs an
+// exec-mask close and reopen in front of it.)
+__device__ __forceinline__ void gamd_hist_add(unsigned* bins, float4 p, float4 q, const BoxDims& B, float r_max, float bin_scale,
+                                              int n_bins, int n_pairs, int accept_all, unsigned inc) {
+    float r;
+    {
+#pragma clang fp contract(off)
+        const float rx = gamd_min_image_wrapped(p.x - q.x, B.bx, B.hx);
+        const float ry = gamd_min_image_wrapped(p.y - q.y, B.by, B.hy);
+        const float rz = gamd_min_image_wrapped(p.z - q.z, B.bz, B.hz);
+        r = sqrtf((rx * rx + ry * ry) + rz * rz);
+    }
+    if (!(accept_all || r < r_max)) return;
+    int bin = (int)(r * bin_scale / r_max);
+    bin = bin < n_bins - 1 ? bin : n_bins - 1;
+    bin = bin < 0 ? 0 : bin;
+    int pair = 0;
+    if (n_pairs == 3) {
+        const bool po = p.w != 0.f, qo = q.w != 0.f;
+        pair = (po && qo) ? 0 : ((po || qo) ? 1 : 2);
+    }
+    atomicAdd(&bins[pair * n_bins + bin], inc);
+}
+__device__ __forceinline__ void gamd_hist_zero(unsigned* bins, int n_slots) { for (int k = threadIdx.x; k < n_slots; k += blockDim.x) bins[k] = 0u; }
+__device__ __forceinline__ void gamd_hist_flush(const unsigned* bins, unsigned long long* out, int n_slots) {
+    for (int k = threadIdx.x; k < n_slots; k += blockDim.x) {
+        const unsigned c = bins[k];
+        if (c) atomicAdd(&out[k], (unsigned long long)c);
+    }
+}
+
 // ---- neighbour build --------------------------------------------------------------------------
 struct NbrArgs {
     int n;                 // atoms (all boxes together)

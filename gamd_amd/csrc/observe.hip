@@ -1,0 +1,566 @@
+// observe.hip — host side of the run observers, the consumers at the sample point of an enqueued gamd_md_run / gamd_md_run_nhc
+// (behind the second half of every interval-th step): the run reporter (gamd_report_*, report.hip), the run recorder
+// (gamd_traj_*, traj.hip) and the structure sampler (gamd_struct_*, structure.hip).  Each is its configuration plus a SampleClock,
+// a buffer table and an entry in observer_list(), through which the MD driver of gamd_api.hip sees it (observers_*, gamd_host.h).
+#include "gamd_host.h"
+
+#include <algorithm>
+#include <array>
+#include <cstring>
+
+namespace {
+
+// Every observer counts the completed MD steps of the runs it was armed for by itself and samples the multiples of its interval.
+struct SampleClock {
+    long long interval = 0;            // 0: off — nothing is enqueued
+    long long sample_interval = 0;     // the interval g was counted with (stays when the observer is switched off: what it took stays readable)
+    long long g = 0;                   // completed MD steps since configure / reset, runs still in the stream included
+    long long g0 = 0;                  // the same in front of the pending run's first step
+    long long completed(long long s) const { return g0 + s + 1; }          // step s of the pending run completes as ...
+    bool sampled(long long s) const { return interval > 0 && completed(s) % interval == 0; }
+    // the sample's ordinal, chosen on the host: a sample enqueued again after a freeze writes the same row
+    long long ordinal(long long s) const { return completed(s) / interval - 1; }
+    void begin_run(long long n_steps) { g0 = g; if (interval > 0) g += n_steps; }
+    // samples since configure / reset; readable: the observer still holds what it took (each has its own test)
+    long long taken(bool readable) const { return (sample_interval > 0 && readable) ? g / sample_interval : 0; }
+    void clear() { g = 0; }
+};
+
+// buffer table entry: want = bytes under the current configuration (0: not needed); cleared: zeroed by configure / reset
+// (the partial-sum scratch and uploaded tables are not)
+struct ObsBuf { DevBuf* buf; size_t want; bool cleared; };
+using ObsBufs = std::vector<ObsBuf>;
+
+// exact sizes (a smaller configuration after a larger one re-allocates: observer_clear and the read calls go by bytes)
+int bufs_resize(const ObsBufs& bufs) {
+    for (const ObsBuf& b : bufs) {
+        if (b.buf->bytes != b.want) b.buf->release();
+        if (b.want && b.buf->ensure(b.want, true)) return -12;
+    }
+    return 0;
+}
+
+// run reporter: configuration and the device-resident log / histogram
+struct Reporter {
+    SampleClock clock;
+    long long max_samples = 0;
+    double ndf = 0.0;
+    int bins = 0, pairs = 1, exclude = 0;
+    float rmax = 0.f;
+    DevBuf steps, ke, counts, partial;
+};
+
+// run recorder: configuration, frames, image counters, ring and running sums
+struct Recorder {
+    SampleClock clock;
+    long long max_frames = 0;
+    int fields = 0, n_lags = 0, subtract_com = 0;
+    int classes = 0;                   // 0: no run since configure / reset; else the classes of the first run
+    std::vector<float> box0;           // [n_boxes][3] of the first run since configure / reset (empty: none yet)
+    DevBuf steps, fx, fv, ff, fimg;    // frames
+    DevBuf x_prev, image, ambiguous;
+    DevBuf ring_x, ring_img, ring_v, ring_com, com_partial, corr_partial, msd, vacf, class_atoms;
+};
+
+// structure sampler: configuration, k-vector list, histogram and S(k) sums
+struct StructSampler {
+    SampleClock clock;
+    int bins = 0, pairs = 1, exclude = 0, n_k = 0;
+    float rmax = 0.f;
+    std::vector<int> kvec_host;        // [n_k][3]
+    DevBuf counts, kvec, rho_partial, sk_sum;
+};
+
+}  // namespace
+
+struct Observers { Reporter rep; Recorder rec; StructSampler ss; };
+
+namespace {
+
+// blocks per box of k_report_ke, of k_traj_corr / k_traj_com and of k_struct_rho (fixed per handle: the summation trees never change)
+int report_ke_blocks(const gamd_handle* h) { return std::max(1, std::min(64, (h->n_per_box + 1023) / 1024)); }
+int traj_corr_blocks(const gamd_handle* h) { return std::max(1, std::min(16, (h->n_per_box + 1023) / 1024)); }
+int struct_rho_blocks(const gamd_handle* h) { return std::max(1, std::min(64, (h->n_per_box + 255) / 256)); }
+
+ObsBufs report_bufs(gamd_handle* h) {
+    Reporter& rp = h->obs->rep;
+    const size_t nb = (size_t)h->n_boxes, rows = (size_t)rp.max_samples;
+    return {{&rp.steps, sizeof(long long) * rows, true}, {&rp.ke, sizeof(double) * rows * nb, true},
+            {&rp.counts, sizeof(unsigned long long) * nb * (size_t)rp.pairs * (size_t)rp.bins, true},
+            {&rp.partial, sizeof(double) * nb * (size_t)report_ke_blocks(h), false}};
+}
+
+ObsBufs traj_bufs(gamd_handle* h) {
+    Recorder& rc = h->obs->rec;
+    const size_t nb = (size_t)h->n_boxes, n3 = 3 * (size_t)h->n, fr = (size_t)rc.max_frames, lags = (size_t)rc.n_lags;
+    const size_t cls = h->cfg.kind == GAMD_KIND_WATER ? 2 : 1, blocks = (size_t)traj_corr_blocks(h);
+    auto frames = [&](int field, size_t elem) { return (rc.fields & field) ? elem * fr * n3 : 0; };
+    return {{&rc.steps, sizeof(long long) * fr, true},
+            {&rc.fx, frames(GAMD_TRAJ_X, sizeof(float)), true}, {&rc.fv, frames(GAMD_TRAJ_V, sizeof(float)), true},
+            {&rc.ff, frames(GAMD_TRAJ_F, sizeof(float)), true}, {&rc.fimg, frames(GAMD_TRAJ_IMAGE, sizeof(int)), true},
+            {&rc.x_prev, sizeof(float) * n3, true}, {&rc.image, sizeof(int) * n3, true}, {&rc.ambiguous, sizeof(unsigned long long), true},
+            {&rc.ring_x, sizeof(float) * lags * n3, true}, {&rc.ring_img, sizeof(int) * lags * n3, true}, {&rc.ring_v, sizeof(float) * lags * n3, true},
+            {&rc.ring_com, rc.subtract_com ? sizeof(double) * lags * nb * 3 : 0, true},
+            {&rc.com_partial, rc.subtract_com ? sizeof(double) * nb * blocks * 4 : 0, false},
+            {&rc.corr_partial, sizeof(double) * nb * lags * blocks * cls * 2, false},
+            {&rc.msd, sizeof(double) * nb * cls * lags, true}, {&rc.vacf, sizeof(double) * nb * cls * lags, true},
+            {&rc.class_atoms, lags ? sizeof(long long) * nb * cls : 0, true}};
+}
+
+ObsBufs struct_bufs(gamd_handle* h) {
+    StructSampler& sp = h->obs->ss;
+    const size_t nb = (size_t)h->n_boxes, K = (size_t)sp.n_k, cls = sp.pairs == 3 ? 2 : 1;
+    return {{&sp.counts, sizeof(unsigned long long) * nb * (size_t)sp.pairs * (size_t)sp.bins, true},
+            {&sp.kvec, sizeof(int) * 3 * K, false},                 // uploaded by gamd_struct_configure
+            {&sp.rho_partial, sizeof(double) * 2 * nb * (size_t)struct_rho_blocks(h) * cls * K, false},
+            {&sp.sk_sum, sizeof(double) * nb * (size_t)sp.pairs * K, true}};
+}
+
+// what every observer's argument block starts with
+template <typename Args>
+void sample_args(const gamd_handle* h, Args& a) { a.n = h->n; a.bx = box_ref(h); a.devflags = h->devflags.as<int>(); }
+
+// v, species, masses (amu) and length unit of the pending run, whichever integrator carries it
+struct Particles { const float* v; const uint8_t* species; double mass, mass_h, len; };
+Particles pending_particles(const MdPending& p) {
+    if (p.kind == 0) return {p.m.v, p.m.species, (double)p.mass, (double)p.mass_h, (double)p.m.len};
+    return {p.a.v, p.a.species, (double)p.a.mass, (double)p.a.mass_h, (double)p.a.len};
+}
+
+// the reporter's sample of step s of the pending run, behind its second half: the kinetic-energy row and the frame's pair histogram
+int enqueue_report_sample(gamd_handle* h, long long s) {
+    const MdPending& p = h->pending;
+    const Reporter& rp = h->obs->rep;
+    const Particles pt = pending_particles(p);
+    ReportArgs a{};
+    sample_args(h, a);
+    a.sticky = h->sticky_dev;
+    a.v = pt.v; a.species = pt.species; a.len = pt.len; a.mass = pt.mass; a.mass_h = pt.mass_h;
+    a.partial = rp.partial.as<double>();
+    a.blocks = report_ke_blocks(h);
+    a.steps = rp.steps.as<long long>();
+    a.ke = rp.ke.as<double>();
+    a.g = rp.clock.completed(s);
+    a.slot = rp.clock.ordinal(s);
+    int r;
+    if (a.slot < rp.max_samples && (r = launch_report_ke(a, p.st))) return fail(-1, "reporter launch failed (%d)", r);
+    if (rp.bins > 0) {
+        a.counters = h->cur_counters;
+        a.pos_s = h->pos_s.as<float4>();
+        a.col = h->col.as<int>(); a.erow = h->erow.as<int>(); a.row_ptr = h->row_ptr.as<int>(); a.perm = h->perm.as<int>();
+        a.e_cap = h->e_cap;
+        for (int d = 0; d < 3; ++d) { a.box[d] = h->box[d]; a.half[d] = 0.5f * h->box[d]; }
+        a.n_bins = rp.bins; a.n_pairs = rp.pairs;
+        a.r_max = rp.rmax; a.bin_scale = (float)rp.bins;
+        a.all_edges = rp.rmax >= h->cfg.cutoff ? 1 : 0;
+        a.exclude_same_molecule = rp.exclude;
+        a.counts = rp.counts.as<unsigned long long>();
+        // ~16 edge slots per thread; every workgroup flushes its non-zero bins with one atomic each
+        a.rdf_blocks = (int)std::max<long long>(1, std::min<long long>(h->n_cu, h->e_cap / h->n_boxes / 4096));
+        if ((r = launch_report_rdf(a, p.st))) return fail(-1, "reporter launch failed (%d)", r);
+    }
+    return 0;
+}
+
+// the recorder's classes in a run: 2 = water with species (O, H), else 1
+int traj_run_classes(const gamd_handle* h, const uint8_t* species_dev) { return (h->cfg.kind == GAMD_KIND_WATER && species_dev) ? 2 : 1; }
+
+// the recorder's sample of step s of the pending run, behind its second half
+int enqueue_traj_sample(gamd_handle* h, long long s) {
+    const MdPending& p = h->pending;
+    const Recorder& rc = h->obs->rec;
+    const Particles pt = pending_particles(p);
+    TrajArgs a{};
+    sample_args(h, a);
+    for (int d = 0; d < 3; ++d) a.box[d] = h->box[d];
+    a.x = p.x; a.f = p.f;
+    a.v = pt.v; a.species = pt.species; a.mass = pt.mass; a.mass_h = pt.mass_h;
+    a.g = rc.clock.completed(s);
+    a.q = rc.clock.ordinal(s);
+    a.frame = a.q < rc.max_frames ? a.q : -1;
+    a.steps = rc.steps.as<long long>();
+    a.fx = rc.fx.as<float>(); a.fv = rc.fv.as<float>(); a.ff = rc.ff.as<float>(); a.fimg = rc.fimg.as<int>();
+    a.x_prev = rc.x_prev.as<float>();
+    a.image = rc.image.as<int>();
+    a.ambiguous = rc.ambiguous.as<unsigned long long>();
+    a.n_lags = rc.n_lags;
+    a.classes = traj_run_classes(h, p.species);
+    if (rc.n_lags > 0) {
+        a.slot = (int)(a.q % rc.n_lags);
+        a.active = (int)std::min<long long>(a.q, rc.n_lags - 1) + 1;
+        a.subtract_com = rc.subtract_com;
+        a.ring_x = rc.ring_x.as<float>(); a.ring_img = rc.ring_img.as<int>(); a.ring_v = rc.ring_v.as<float>();
+        a.ring_com = rc.ring_com.as<double>();
+        a.com_partial = rc.com_partial.as<double>();
+        a.com_blocks = a.corr_blocks = traj_corr_blocks(h);
+        a.corr_partial = rc.corr_partial.as<double>();
+        a.msd = rc.msd.as<double>(); a.vacf = rc.vacf.as<double>();
+        a.class_atoms = rc.class_atoms.as<long long>();
+    }
+    if (int r = launch_traj_sample(a, p.st)) return fail(-1, "recorder launch failed (%d)", r);
+    return 0;
+}
+
+// the structure sampler's sample of the pending run, behind a second half (no row of its own: the host counts the frames)
+int enqueue_struct_sample(gamd_handle* h, long long) {
+    const MdPending& p = h->pending;
+    const StructSampler& sp = h->obs->ss;
+    StructArgs a{};
+    sample_args(h, a);
+    a.sticky = h->sticky_dev;
+    for (int d = 0; d < 3; ++d) { a.box[d] = h->box[d]; a.half[d] = 0.5f * h->box[d]; }
+    a.n_pairs = sp.pairs;
+    int r;
+    if (sp.bins > 0) {
+        a.pos_s = h->pos_s.as<float4>();
+        a.perm = h->perm.as<int>();
+        a.n_bins = sp.bins;
+        a.r_max = sp.rmax; a.bin_scale = (float)sp.bins;
+        a.exclude_same_molecule = sp.exclude;
+        a.tiles = (h->n_per_box + 255) / 256;
+        a.counts = sp.counts.as<unsigned long long>();
+        if ((r = launch_struct_pairs(a, p.st))) return fail(-1, "structure sampler launch failed (%d)", r);
+    }
+    if (sp.n_k > 0) {
+        a.x = p.x;
+        a.species = p.species;
+        a.classes = sp.pairs == 3 ? 2 : 1;
+        a.n_k = sp.n_k;
+        a.kvec = sp.kvec.as<int>();
+        a.rho_blocks = struct_rho_blocks(h);
+        a.rho_partial = sp.rho_partial.as<double>();
+        a.sk_sum = sp.sk_sum.as<double>();
+        if ((r = launch_struct_sk(a, p.st))) return fail(-1, "structure sampler launch failed (%d)", r);
+    }
+    return 0;
+}
+
+// run recorder: image counters and ring are only meaningful in one box and with one set of classes
+int traj_check_run(gamd_handle* h, const float* box, const uint8_t* species_dev) {
+    const Recorder& rc = h->obs->rec;
+    if (rc.n_lags > 0 && rc.classes && rc.classes != traj_run_classes(h, species_dev))
+        return fail(-22, "run recorder: species given in one run and not in another since gamd_traj_configure / gamd_traj_reset");
+    if ((rc.n_lags > 0 || (rc.fields & GAMD_TRAJ_IMAGE)) && !rc.box0.empty())
+        for (size_t k = 0; k < rc.box0.size(); ++k)
+            if (rc.box0[k] != box[k])
+                return fail(-22, "run recorder: the box differs from the box of the first run since gamd_traj_configure / "
+                                 "gamd_traj_reset (image counters and correlation functions need one box; call gamd_traj_reset)");
+    return 0;
+}
+void traj_begin_run(gamd_handle* h, const float* box, const uint8_t* species_dev) {
+    Recorder& rc = h->obs->rec;
+    if (rc.clock.interval <= 0) return;
+    if (rc.box0.empty()) rc.box0.assign(box, box + 3 * (size_t)h->n_boxes);
+    if (!rc.classes) rc.classes = traj_run_classes(h, species_dev);
+}
+void traj_forget(gamd_handle* h) { h->obs->rec.classes = 0; h->obs->rec.box0.clear(); }
+
+// structure sampler: the minimum image is the nearest image only inside the sphere of half the shortest edge, and the S(k)
+// classes need the species in the caller's order
+int struct_check_run(gamd_handle* h, const float* box, const uint8_t* species_dev) {
+    const StructSampler& sp = h->obs->ss;
+    if (sp.bins > 0)
+        for (int k = 0; k < 3 * h->n_boxes; ++k)
+            if (!(2.0f * sp.rmax <= box[k]))
+                return fail(-22, "structure sampler: rdf_rmax = %g exceeds half of box[%d][%d] = %g (the minimum image is the nearest "
+                                 "image only below that)", (double)sp.rmax, k / 3, k % 3, (double)box[k]);
+    if (sp.n_k > 0 && sp.pairs == 3 && !species_dev)
+        return fail(-22, "structure sampler: the partial structure factors of a water handle need species");
+    return 0;
+}
+
+// What an observer supplies.  The order of the list is the order of the samples on the stream and of the run checks.
+struct Observer {
+    SampleClock* clock;
+    ObsBufs (*bufs)(gamd_handle*);
+    int (*sample)(gamd_handle*, long long s);                                        // armed and clock->sampled(s)
+    int (*check_run)(gamd_handle*, const float* box, const uint8_t* species_dev);    // armed; may be null
+    void (*begin_run)(gamd_handle*, const float* box, const uint8_t* species_dev);   // what it keeps of a run besides the clock; may be null
+    void (*forget)(gamd_handle*);                                                    // ... and how configure / reset drop it; may be null
+};
+enum { OBS_REPORT = 0, OBS_TRAJ = 1, OBS_STRUCT = 2, OBS_COUNT = 3 };
+std::array<Observer, OBS_COUNT> observer_list(const gamd_handle* h) {
+    Observers& o = *h->obs;
+    return {{{&o.rep.clock, report_bufs, enqueue_report_sample, nullptr, nullptr, nullptr},
+             {&o.rec.clock, traj_bufs, enqueue_traj_sample, traj_check_run, traj_begin_run, traj_forget},
+             {&o.ss.clock, struct_bufs, enqueue_struct_sample, struct_check_run, nullptr, nullptr}}};
+}
+
+// clear an observer's step count and what it took (configuration and scratch stay): on the init stream, landed on return
+int observer_clear(gamd_handle* h, const Observer& ob) {
+    ob.clock->clear();
+    if (ob.forget) ob.forget(h);
+    for (const ObsBuf& b : ob.bufs(h))
+        if (b.cleared && b.buf->p) HIP_TRY(hipMemsetAsync(b.buf->p, 0, b.buf->bytes, tl_init_stream));
+    HIP_TRY(hipStreamSynchronize(tl_init_stream));
+    return 0;
+}
+
+// The common part of gamd_*_configure behind the checks of the parameter block.  apply() writes the new configuration into the
+// observer's state, sizes its buffers (bufs_resize) and uploads what it needs on the device.
+template <typename Apply>
+int observer_configure(gamd_handle* h, int which, long long interval, const char* entry, Apply apply) {
+    const Observer ob = observer_list(h)[which];
+    if (h->pending.active) return fail(-22, "an MD run is still enqueued: call gamd_sync_status before %s", entry);
+    if (interval == 0) { ob.clock->interval = 0; return 0; }        // off: what was recorded stays readable
+    DeviceGuard guard(h->dev);
+    InitStream init(h->init_stream);
+    ob.clock->interval = 0;                                          // off, should anything below fail
+    if (int r = apply()) return r;
+    if (int r = observer_clear(h, ob)) return r;
+    ob.clock->interval = ob.clock->sample_interval = interval;
+    return 0;
+}
+
+int observer_reset(gamd_handle* h, int which, const char* entry) {
+    if (!h) return fail(-22, "null handle");
+    if (h->pending.active) return fail(-22, "an MD run is still enqueued: call gamd_sync_status before %s", entry);
+    DeviceGuard guard(h->dev);
+    InitStream init(h->init_stream);
+    return observer_clear(h, observer_list(h)[which]);
+}
+
+// one of each +-n with 0 < |n|^2 <= n2max (the one whose first non-zero component is positive), sorted by (|n|^2, nx, ny, nz)
+std::vector<int> struct_kvectors(int n2max) {
+    int m = 0;
+    while ((m + 1) * (m + 1) <= n2max) ++m;
+    std::vector<std::array<int, 4>> v;
+    for (int x = 0; x <= m; ++x)
+        for (int y = -m; y <= m; ++y)
+            for (int z = -m; z <= m; ++z) {
+                const int n2 = x * x + y * y + z * z;
+                if (n2 == 0 || n2 > n2max) continue;
+                const int lead = x != 0 ? x : (y != 0 ? y : z);
+                if (lead > 0) v.push_back({n2, x, y, z});
+            }
+    std::sort(v.begin(), v.end());
+    std::vector<int> out;
+    for (const auto& e : v) { out.push_back(e[1]); out.push_back(e[2]); out.push_back(e[3]); }
+    return out;
+}
+
+}  // namespace
+
+// ---- towards the MD driver (gamd_host.h) ------------------------------------------------------------------------------------
+Observers* observers_new() { return new Observers(); }
+
+void observers_free(gamd_handle* h) {
+    for (const Observer& ob : observer_list(h))
+        for (const ObsBuf& b : ob.bufs(h)) b.buf->release();
+    delete h->obs; h->obs = nullptr;
+}
+
+int observers_check_run(gamd_handle* h, const float* box, const uint8_t* species_dev) {
+    for (const Observer& ob : observer_list(h))
+        if (ob.check_run && ob.clock->interval > 0)
+            if (int r = ob.check_run(h, box, species_dev)) return r;
+    return 0;
+}
+
+void observers_begin_run(gamd_handle* h, const float* box, const uint8_t* species_dev, long long n_steps) {
+    for (const Observer& ob : observer_list(h)) {
+        if (ob.begin_run) ob.begin_run(h, box, species_dev);
+        ob.clock->begin_run(n_steps);
+    }
+}
+
+bool observers_sampled(const gamd_handle* h, long long s) {
+    for (const Observer& ob : observer_list(h))
+        if (ob.clock->sampled(s)) return true;
+    return false;
+}
+
+int observers_enqueue(gamd_handle* h, long long s) {
+    for (const Observer& ob : observer_list(h))
+        if (ob.clock->sampled(s))
+            if (int r = ob.sample(h, s)) return r;
+    return 0;
+}
+
+static_assert(sizeof(gamd_report_params) == 40 && offsetof(gamd_report_params, ndf) == 16 && offsetof(gamd_report_params, rdf_rmax) == 28,
+              "gamd_report_params layout is part of the C ABI (gamd_amd/_lib.py mirrors it)");
+static_assert(sizeof(gamd_traj_params) == 32 && offsetof(gamd_traj_params, fields) == 16 && offsetof(gamd_traj_params, n_lags) == 20 &&
+              offsetof(gamd_traj_params, subtract_com) == 24,
+              "gamd_traj_params layout is part of the C ABI (gamd_amd/_lib.py mirrors it)");
+static_assert(sizeof(gamd_struct_params) == 32 && offsetof(gamd_struct_params, rdf_bins) == 8 && offsetof(gamd_struct_params, rdf_rmax) == 12 &&
+              offsetof(gamd_struct_params, sk_n2max) == 20,
+              "gamd_struct_params layout is part of the C ABI (gamd_amd/_lib.py mirrors it)");
+
+extern "C" {
+
+int32_t gamd_report_configure(gamd_handle* h, const gamd_report_params* p) {
+    // the parameter block is checked first: these answers need no device
+    if (!p) return fail(-22, "null argument");
+    if (p->interval < 0) return fail(-22, "interval = %lld is negative", (long long)p->interval);
+    if (p->max_samples < 0 || p->max_samples > (1ll << 24)) return fail(-22, "max_samples = %lld outside [0, 2^24]", (long long)p->max_samples);
+    if (p->rdf_bins < 0 || p->rdf_bins > GAMD_HIST_MAX_BINS) return fail(-22, "rdf_bins = %d outside [0, %d]", (int)p->rdf_bins, GAMD_HIST_MAX_BINS);
+    if (!(p->rdf_rmax >= 0.f)) return fail(-22, "rdf_rmax = %g is negative", (double)p->rdf_rmax);
+    if (!(p->ndf >= 0.0)) return fail(-22, "ndf = %g is negative", p->ndf);
+    if (!h) return fail(-22, "null handle");
+    if (p->rdf_rmax > h->cfg.cutoff)
+        return fail(-22, "rdf_rmax = %g exceeds the cutoff %g: pairs beyond it are not in the edge list", (double)p->rdf_rmax, (double)h->cfg.cutoff);
+    return observer_configure(h, OBS_REPORT, p->interval, "gamd_report_configure", [&]() {
+        Reporter& rp = h->obs->rep;
+        rp.max_samples = p->max_samples > 0 ? p->max_samples : 4096;
+        rp.ndf = p->ndf > 0.0 ? p->ndf : 3.0 * (double)h->n_per_box;
+        rp.bins = p->rdf_bins;
+        rp.pairs = h->cfg.kind == GAMD_KIND_WATER ? 3 : 1;
+        rp.rmax = p->rdf_rmax > 0.f ? p->rdf_rmax : h->cfg.cutoff;
+        rp.exclude = p->exclude_same_molecule ? 1 : 0;
+        return bufs_resize(report_bufs(h)) ? fail(-12, "reporter allocation failed") : 0;
+    });
+}
+
+int32_t gamd_report_reset(gamd_handle* h) { return observer_reset(h, OBS_REPORT, "gamd_report_reset"); }
+
+int32_t gamd_report_read(gamd_handle* h, void* stream, int64_t* steps, double* ke, double* temperature, int64_t max_rows,
+                         int64_t* n_rows, uint64_t* counts, int64_t count_elems, int64_t* frames, int64_t* dropped,
+                         int32_t dims[3]) {
+    if (!h) return fail(-22, "null handle");
+    if (max_rows < 0) return fail(-22, "max_rows is negative");
+    const Reporter& rp = h->obs->rep;
+    DeviceGuard guard(h->dev);
+    hipStream_t st = (hipStream_t)stream;
+    const long long nb = h->n_boxes;
+    const long long taken = rp.clock.taken(rp.steps.p != nullptr);
+    const long long rows = std::min<long long>(taken, rp.max_samples);
+    const long long n_copy = std::min<long long>(rows, max_rows);
+    const long long elems = nb * (long long)rp.pairs * (long long)rp.bins;
+    if (counts && rp.counts.p && count_elems < elems) return fail(-22, "counts has room for %lld elements, the histogram has %lld", (long long)count_elems, elems);
+    if (n_copy > 0 && steps) HIP_TRY(hipMemcpyAsync(steps, rp.steps.p, sizeof(int64_t) * (size_t)n_copy, hipMemcpyDeviceToHost, st));
+    if (n_copy > 0 && ke) HIP_TRY(hipMemcpyAsync(ke, rp.ke.p, sizeof(double) * (size_t)(n_copy * nb), hipMemcpyDeviceToHost, st));
+    if (n_copy > 0 && temperature && !ke) return fail(-22, "temperature needs ke");
+    if (counts && rp.counts.p && elems > 0) HIP_TRY(hipMemcpyAsync(counts, rp.counts.p, sizeof(uint64_t) * (size_t)elems, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (int t = check_traps(h)) return t;
+    if (temperature)
+        for (long long k = 0; k < n_copy * nb; ++k) temperature[k] = 2.0 * ke[k] / (rp.ndf * 0.00831446261815324);
+    if (n_rows) *n_rows = rows;
+    if (frames) *frames = (rp.bins > 0 && rp.counts.p) ? taken : 0;
+    if (dropped) *dropped = taken - rows;
+    if (dims) { dims[0] = (int32_t)nb; dims[1] = rp.pairs; dims[2] = rp.counts.p ? rp.bins : 0; }
+    return 0;
+}
+
+int32_t gamd_traj_configure(gamd_handle* h, const gamd_traj_params* p) {
+    if (!p) return fail(-22, "null argument");
+    if (p->interval < 0) return fail(-22, "interval = %lld is negative", (long long)p->interval);
+    if (p->max_frames < 0 || p->max_frames > (1ll << 24)) return fail(-22, "max_frames = %lld outside [0, 2^24]", (long long)p->max_frames);
+    if (p->fields & ~(GAMD_TRAJ_X | GAMD_TRAJ_V | GAMD_TRAJ_F | GAMD_TRAJ_IMAGE)) return fail(-22, "fields = %d has unknown bits", (int)p->fields);
+    if (p->n_lags < 0 || p->n_lags > 4096) return fail(-22, "n_lags = %d outside [0, 4096]", (int)p->n_lags);
+    if (!h) return fail(-22, "null handle");
+    if (p->n_lags > 0 && h->n_boxes > 65535) return fail(-22, "correlation functions need n_boxes <= 65535");
+    return observer_configure(h, OBS_TRAJ, p->interval, "gamd_traj_configure", [&]() {
+        Recorder& rc = h->obs->rec;
+        rc.max_frames = p->max_frames;
+        rc.fields = p->fields;
+        rc.n_lags = p->n_lags;
+        rc.subtract_com = (p->subtract_com && p->n_lags > 0) ? 1 : 0;
+        return bufs_resize(traj_bufs(h)) ? fail(-12, "recorder allocation failed") : 0;
+    });
+}
+
+int32_t gamd_traj_reset(gamd_handle* h) { return observer_reset(h, OBS_TRAJ, "gamd_traj_reset"); }
+
+int32_t gamd_traj_read_frames(gamd_handle* h, void* stream, int64_t first, int64_t count, int64_t* steps, float* x, float* v,
+                              float* f, int32_t* image, int64_t* n_frames, int64_t* dropped) {
+    if (!h) return fail(-22, "null handle");
+    if (first < 0 || count < 0) return fail(-22, "first / count is negative");
+    const Recorder& rc = h->obs->rec;
+    DeviceGuard guard(h->dev);
+    hipStream_t st = (hipStream_t)stream;
+    const long long taken = rc.clock.taken(rc.x_prev.p != nullptr);
+    const long long kept = std::min<long long>(taken, rc.max_frames);
+    const long long n_copy = std::max<long long>(0, std::min<long long>(kept - first, count));
+    const size_t n3 = 3 * (size_t)h->n;
+    if (n_copy > 0) {
+        const size_t off = (size_t)first * n3, elems = (size_t)n_copy * n3;
+        if (steps) HIP_TRY(hipMemcpyAsync(steps, rc.steps.as<long long>() + first, sizeof(int64_t) * (size_t)n_copy, hipMemcpyDeviceToHost, st));
+        if (x && rc.fx.p) HIP_TRY(hipMemcpyAsync(x, rc.fx.as<float>() + off, sizeof(float) * elems, hipMemcpyDeviceToHost, st));
+        if (v && rc.fv.p) HIP_TRY(hipMemcpyAsync(v, rc.fv.as<float>() + off, sizeof(float) * elems, hipMemcpyDeviceToHost, st));
+        if (f && rc.ff.p) HIP_TRY(hipMemcpyAsync(f, rc.ff.as<float>() + off, sizeof(float) * elems, hipMemcpyDeviceToHost, st));
+        if (image && rc.fimg.p) HIP_TRY(hipMemcpyAsync(image, rc.fimg.as<int>() + off, sizeof(int32_t) * elems, hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    if (int t = check_traps(h)) return t;
+    if (n_frames) *n_frames = kept;
+    if (dropped) *dropped = taken - kept;
+    return 0;
+}
+
+int32_t gamd_traj_read_dynamics(gamd_handle* h, void* stream, double* msd_sum, double* vacf_sum, int64_t elems, int64_t* n_samples,
+                                uint64_t* ambiguous, int64_t* class_atoms, int32_t dims[3]) {
+    if (!h) return fail(-22, "null handle");
+    const Recorder& rc = h->obs->rec;
+    DeviceGuard guard(h->dev);
+    hipStream_t st = (hipStream_t)stream;
+    const long long nb = h->n_boxes, cls = rc.msd.p ? rc.classes : 0, lags = rc.msd.p ? rc.n_lags : 0;
+    const long long need = nb * cls * lags;
+    if ((msd_sum || vacf_sum) && elems < need) return fail(-22, "msd_sum / vacf_sum have room for %lld elements, the sums have %lld", (long long)elems, need);
+    if (need > 0 && msd_sum) HIP_TRY(hipMemcpyAsync(msd_sum, rc.msd.p, sizeof(double) * (size_t)need, hipMemcpyDeviceToHost, st));
+    if (need > 0 && vacf_sum) HIP_TRY(hipMemcpyAsync(vacf_sum, rc.vacf.p, sizeof(double) * (size_t)need, hipMemcpyDeviceToHost, st));
+    if (ambiguous) {
+        *ambiguous = 0;
+        if (rc.ambiguous.p) HIP_TRY(hipMemcpyAsync(ambiguous, rc.ambiguous.p, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    }
+    if (class_atoms && nb * cls > 0) HIP_TRY(hipMemcpyAsync(class_atoms, rc.class_atoms.p, sizeof(int64_t) * (size_t)(nb * cls), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (int t = check_traps(h)) return t;
+    if (n_samples) *n_samples = rc.clock.taken(rc.x_prev.p != nullptr);
+    if (dims) { dims[0] = (int32_t)nb; dims[1] = (int32_t)cls; dims[2] = (int32_t)lags; }
+    return 0;
+}
+
+int32_t gamd_struct_configure(gamd_handle* h, const gamd_struct_params* p) {
+    if (!p) return fail(-22, "null argument");
+    if (p->interval < 0) return fail(-22, "interval = %lld is negative", (long long)p->interval);
+    if (p->rdf_bins < 0 || p->rdf_bins > GAMD_HIST_MAX_BINS) return fail(-22, "rdf_bins = %d outside [0, %d]", (int)p->rdf_bins, GAMD_HIST_MAX_BINS);
+    if (p->rdf_bins > 0 && !(p->rdf_rmax > 0.f)) return fail(-22, "rdf_rmax = %g is not positive", (double)p->rdf_rmax);
+    // K grows as (2 pi / 3) n2max^1.5: 4096 is passed near n2max = 156
+    if (p->sk_n2max < 0 || p->sk_n2max > 256) return fail(-22, "sk_n2max = %d gives more than 4096 k-vectors (or is negative)", (int)p->sk_n2max);
+    std::vector<int> kv = p->sk_n2max > 0 ? struct_kvectors(p->sk_n2max) : std::vector<int>();
+    if (kv.size() / 3 > 4096) return fail(-22, "sk_n2max = %d gives %zu k-vectors, more than 4096", (int)p->sk_n2max, kv.size() / 3);
+    if (!h) return fail(-22, "null handle");
+    if (h->n_boxes > 65535) return fail(-22, "the structure sampler needs n_boxes <= 65535");
+    {
+        const long long T = (h->n_per_box + 255) / 256;
+        if (p->rdf_bins > 0 && T * (T + 1) / 2 > 0xffffffll) return fail(-22, "the pair histogram needs at most 5791 tiles of 256 atoms per box");
+    }
+    return observer_configure(h, OBS_STRUCT, p->interval, "gamd_struct_configure", [&]() {
+        StructSampler& sp = h->obs->ss;
+        sp.bins = p->rdf_bins;
+        sp.pairs = h->cfg.kind == GAMD_KIND_WATER ? 3 : 1;
+        sp.rmax = p->rdf_rmax;
+        sp.exclude = p->exclude_same_molecule ? 1 : 0;
+        sp.n_k = (int)(kv.size() / 3);
+        sp.kvec_host = kv;
+        if (bufs_resize(struct_bufs(h))) return fail(-12, "structure sampler allocation failed");
+        if (sp.n_k) HIP_TRY(init_upload(sp.kvec.p, kv.data(), sizeof(int) * kv.size()));
+        return 0;
+    });
+}
+
+int32_t gamd_struct_reset(gamd_handle* h) { return observer_reset(h, OBS_STRUCT, "gamd_struct_reset"); }
+
+int32_t gamd_struct_read(gamd_handle* h, void* stream, uint64_t* counts, int64_t count_elems, double* sk_sum, int64_t sk_elems,
+                         int32_t* kvec, int64_t kvec_elems, int64_t* frames, int32_t dims[4]) {
+    if (!h) return fail(-22, "null handle");
+    const StructSampler& sp = h->obs->ss;
+    DeviceGuard guard(h->dev);
+    hipStream_t st = (hipStream_t)stream;
+    const long long nb = h->n_boxes, bins = sp.counts.p ? sp.bins : 0, K = sp.sk_sum.p ? sp.n_k : 0;
+    const long long c_elems = nb * (long long)sp.pairs * bins, s_elems = nb * (long long)sp.pairs * K;
+    if (counts && count_elems < c_elems) return fail(-22, "counts has room for %lld elements, the histogram has %lld", (long long)count_elems, c_elems);
+    if (sk_sum && sk_elems < s_elems) return fail(-22, "sk_sum has room for %lld elements, the sums have %lld", (long long)sk_elems, s_elems);
+    if (kvec && kvec_elems < 3 * K) return fail(-22, "kvec has room for %lld elements, the list has %lld", (long long)kvec_elems, 3 * K);
+    if (counts && c_elems > 0) HIP_TRY(hipMemcpyAsync(counts, sp.counts.p, sizeof(uint64_t) * (size_t)c_elems, hipMemcpyDeviceToHost, st));
+    if (sk_sum && s_elems > 0) HIP_TRY(hipMemcpyAsync(sk_sum, sp.sk_sum.p, sizeof(double) * (size_t)s_elems, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (int t = check_traps(h)) return t;
+    if (kvec && K > 0) std::memcpy(kvec, sp.kvec_host.data(), sizeof(int32_t) * 3 * (size_t)K);
+    if (frames) *frames = sp.clock.taken(bins > 0 || K > 0);
+    if (dims) { dims[0] = (int32_t)nb; dims[1] = sp.pairs; dims[2] = (int32_t)bins; dims[3] = (int32_t)K; }
+    return 0;
+}
+
+}  // extern "C"

@@ -19,9 +19,6 @@
 
 namespace {
 
-constexpr int REPORT_MAX_BINS = 1024;          // per pair class (gamd_report_params.rdf_bins)
-constexpr int REPORT_MAX_PAIRS = 3;            // O-O, O-H, H-H
-
 __global__ void __launch_bounds__(256) k_report_ke(ReportArgs a) {
     if (a.devflags[DEVFLAG_FROZEN]) return;
     __shared__ double red[4];
@@ -53,9 +50,9 @@ __global__ void k_report_ke_final(ReportArgs a) {
 
 __global__ void __launch_bounds__(256) k_report_rdf(ReportArgs a) {
     if (a.devflags[DEVFLAG_FROZEN]) return;                 // truncated CSR, or a frame that will be evaluated again
-    __shared__ unsigned bins[REPORT_MAX_PAIRS * REPORT_MAX_BINS];
+    __shared__ unsigned bins[GAMD_HIST_MAX_PAIRS * GAMD_HIST_MAX_BINS];
     const int n_slots = a.n_pairs * a.n_bins;               // <= 3072 (checked by gamd_report_configure)
-    for (int k = threadIdx.x; k < n_slots; k += blockDim.x) bins[k] = 0u;
+    gamd_hist_zero(bins, n_slots);
     __syncthreads();
 
     const int box = blockIdx.y;
@@ -78,32 +75,10 @@ __global__ void __launch_bounds__(256) k_report_rdf(ReportArgs a) {
             const int id = GAMD_CHK_RANGE(a.sticky, a.perm[dst], 0, a.n - 1, GAMD_CHK_REPORT_PERM);
             if (is / 3 == id / 3) continue;
         }
-        const float4 ps = a.pos_s[src], pd = a.pos_s[dst];
-        float r;
-        {
-#pragma clang fp contract(off)
-            const float rx = gamd_min_image_wrapped(ps.x - pd.x, B.bx, B.hx);
-            const float ry = gamd_min_image_wrapped(ps.y - pd.y, B.by, B.hy);
-            const float rz = gamd_min_image_wrapped(ps.z - pd.z, B.bz, B.hz);
-            r = sqrtf((rx * rx + ry * ry) + rz * rz);
-        }
-        if (!(a.all_edges || r < a.r_max)) continue;
-        int bin = (int)(r * a.bin_scale / a.r_max);
-        bin = bin < a.n_bins - 1 ? bin : a.n_bins - 1;
-        bin = bin < 0 ? 0 : bin;
-        int pair = 0;
-        if (a.n_pairs == 3) {
-            const bool so = ps.w != 0.f, d_o = pd.w != 0.f;
-            pair = (so && d_o) ? 0 : ((so || d_o) ? 1 : 2);
-        }
-        atomicAdd(&bins[pair * a.n_bins + bin], 1u);
+        gamd_hist_add(bins, a.pos_s[src], a.pos_s[dst], B, a.r_max, a.bin_scale, a.n_bins, a.n_pairs, a.all_edges, 1u);
     }
     __syncthreads();
-    unsigned long long* out = a.counts + (size_t)box * n_slots;
-    for (int k = threadIdx.x; k < n_slots; k += blockDim.x) {
-        const unsigned c = bins[k];
-        if (c) atomicAdd(&out[k], (unsigned long long)c);
-    }
+    gamd_hist_flush(bins, a.counts + (size_t)box * n_slots, n_slots);
 }
 
 }  // namespace
@@ -117,7 +92,7 @@ int launch_report_ke(const ReportArgs& a, hipStream_t st) {
 
 int launch_report_rdf(const ReportArgs& a, hipStream_t st) {
     const int nb = a.bx.n_boxes > 1 ? a.bx.n_boxes : 1;
-    if (a.n_bins < 1 || a.n_bins > REPORT_MAX_BINS || a.n_pairs < 1 || a.n_pairs > REPORT_MAX_PAIRS) return -1;
+    if (a.n_bins < 1 || a.n_bins > GAMD_HIST_MAX_BINS || a.n_pairs < 1 || a.n_pairs > GAMD_HIST_MAX_PAIRS) return -1;
     hipLaunchKernelGGL(k_report_rdf, dim3(a.rdf_blocks, nb), dim3(256), 0, st, a); GAMD_CHECK_LAUNCH();
     return 0;
 }

@@ -25,18 +25,16 @@
 
 namespace {
 
-constexpr int STRUCT_MAX_BINS = 1024;          // per pair class (gamd_struct_params.rdf_bins)
-constexpr int STRUCT_MAX_PAIRS = 3;            // O-O, O-H, H-H
 constexpr int STRUCT_TILE = 256;
 
 __global__ void __launch_bounds__(256) k_struct_pairs(StructArgs a) {
     if (a.devflags[DEVFLAG_FROZEN]) return;                 // a frame that will be evaluated again
-    __shared__ unsigned bins[STRUCT_MAX_PAIRS * STRUCT_MAX_BINS];
+    __shared__ unsigned bins[GAMD_HIST_MAX_PAIRS * GAMD_HIST_MAX_BINS];
     __shared__ float4 tj[STRUCT_TILE];
     __shared__ int mj[STRUCT_TILE];
     const int tid = threadIdx.x;
     const int n_slots = a.n_pairs * a.n_bins;               // <= 3072 (checked by gamd_struct_configure)
-    for (int k = tid; k < n_slots; k += blockDim.x) bins[k] = 0u;
+    gamd_hist_zero(bins, n_slots);
 
     // tile pair p = J (J + 1) / 2 + I, I <= J < tiles
     const long long p = (long long)blockIdx.x;
@@ -70,36 +68,15 @@ __global__ void __launch_bounds__(256) k_struct_pairs(StructArgs a) {
     // on one LDS address
     const bool diag = I == J;
     const int first = diag ? tid + 1 : 0;
-    const bool io = pi.w != 0.f;
     for (int jj = diag ? (tid & ~63) + 1 : 0; jj < nj; ++jj) {
         const float4 pj = tj[jj];
         if (!vi || jj < first) continue;
         if (a.exclude_same_molecule && mj[jj] == mi) continue;
-        float r;
-        {
-#pragma clang fp contract(off)
-            const float rx = gamd_min_image_wrapped(pi.x - pj.x, B.bx, B.hx);
-            const float ry = gamd_min_image_wrapped(pi.y - pj.y, B.by, B.hy);
-            const float rz = gamd_min_image_wrapped(pi.z - pj.z, B.bz, B.hz);
-            r = sqrtf((rx * rx + ry * ry) + rz * rz);
-        }
-        if (!(r < a.r_max)) continue;
-        int bin = (int)(r * a.bin_scale / a.r_max);
-        bin = bin < a.n_bins - 1 ? bin : a.n_bins - 1;
-        bin = bin < 0 ? 0 : bin;
-        int pair = 0;
-        if (a.n_pairs == 3) {
-            const bool jo = pj.w != 0.f;
-            pair = (io && jo) ? 0 : ((io || jo) ? 1 : 2);
-        }
-        atomicAdd(&bins[pair * a.n_bins + bin], 2u);        // both directions of the pair (at most 2 * 256 * 256 per workgroup)
+        // r < r_max only; both directions of the pair (at most 2 * 256 * 256 per workgroup)
+        gamd_hist_add(bins, pi, pj, B, a.r_max, a.bin_scale, a.n_bins, a.n_pairs, 0, 2u);
     }
     __syncthreads();
-    unsigned long long* out = a.counts + (size_t)box * n_slots;
-    for (int k = tid; k < n_slots; k += blockDim.x) {
-        const unsigned c = bins[k];
-        if (c) atomicAdd(&out[k], (unsigned long long)c);
-    }
+    gamd_hist_flush(bins, a.counts + (size_t)box * n_slots, n_slots);
 }
 
 // fp32 edge `c` of box `box`
@@ -186,7 +163,7 @@ __global__ void __launch_bounds__(64) k_struct_sk(StructArgs a) {
 
 int launch_struct_pairs(const StructArgs& a, hipStream_t st) {
     const int nb = a.bx.n_boxes > 1 ? a.bx.n_boxes : 1, npb = a.bx.n_boxes > 1 ? a.bx.n_per_box : a.n;
-    if (a.n_bins < 1 || a.n_bins > STRUCT_MAX_BINS || a.n_pairs < 1 || a.n_pairs > STRUCT_MAX_PAIRS || nb > 65535) return -1;
+    if (a.n_bins < 1 || a.n_bins > GAMD_HIST_MAX_BINS || a.n_pairs < 1 || a.n_pairs > GAMD_HIST_MAX_PAIRS || nb > 65535) return -1;
     const long long T = (npb + STRUCT_TILE - 1) / STRUCT_TILE, grid = T * (T + 1) / 2;
     if (a.tiles != (int)T || grid > 0xffffffll) return -1;          // grid.x * 256 threads must stay below 2^32
     hipLaunchKernelGGL(k_struct_pairs, dim3((unsigned)grid, nb), dim3(256), 0, st, a); GAMD_CHECK_LAUNCH();
