@@ -538,7 +538,11 @@ class GamdForce:
 
     def debug_partial(self) -> np.ndarray:
         """[pieces, H] partial-sum pieces of the LAST conv layer (one row per run of edges with the same destination inside a
-        16-edge chunk), CSR order."""
+        16-edge chunk), CSR order; H padded to whole 128-blocks.  A piece holds the sum of its edges' messages hn[src] * e_emb
+        -- always in the bf16 and split-fp16 modes, and in fp32 for every layer but one: layer 0 in its hoisted form (the
+        library's l0_hoist: an LJ model, fp32 edge MLP, 128 / 128 / 128 widths, no update_edge_emb, not under
+        KSEL_NO_LAYER0_HOIST), which is the LAST layer only in a one-layer model.  There the pieces hold sums of T3 rows, the
+        third GEMM's activated output, and phi_edge's part is applied per atom by the node kernel (M0 sum T3 + d_i c0)."""
         return self._dbg(6, (self.counts()[1], 128 * ((self.cfg.encoding_size + 127) // 128)), np.float32)
 
     def debug_perm(self) -> np.ndarray:

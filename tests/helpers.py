@@ -59,3 +59,21 @@ def edge_set(edge_idx):
     e = np.asarray(edge_idx).astype(np.int64)
     key = e[0] * (e.max() + 1) + e[1]
     return np.sort(key)
+
+
+def pieces_of_csr(row_ptr, chunk=16):
+    """Which partial-sum piece of the conv edge kernels (GamdForce.debug_partial) each CSR slot adds to, from the CSR alone:
+    (piece [E] per slot, destination row [pieces] per piece, pieces).  A piece is a run of edges with the same destination
+    inside a `chunk`-edge chunk, numbered in CSR order: a new one starts at every chunk boundary and at every row start, so
+    slot x sits in piece x // chunk + #{non-empty rows r: row_ptr[r] % chunk != 0 and row_ptr[r] <= x}."""
+    rp = np.asarray(row_ptr, dtype=np.int64)
+    n_edges = int(rp[-1])
+    deg = np.diff(rp)
+    starts = np.sort(rp[:-1][(deg > 0) & (rp[:-1] % chunk != 0)])
+    x = np.arange(n_edges, dtype=np.int64)
+    piece = x // chunk + np.searchsorted(starts, x, side="right")
+    n_pieces = int(piece[-1]) + 1 if n_edges else 0
+    row = np.repeat(np.arange(deg.shape[0], dtype=np.int64), deg)
+    piece_row = np.zeros(n_pieces, dtype=np.int64)
+    piece_row[piece] = row                         # every slot of a piece has the same row
+    return piece, piece_row, n_pieces
