@@ -1,0 +1,181 @@
+// classical.hip — the classical observer: the switched, shifted Lennard-Jones potential the reference's LJ data generators and
+// rollout drivers evaluate with OpenMM (potentialEnergy / totalEnergy of dataset/generate_lj_data.py:87-90; gt_force of
+// LJ/test_script/test_langevin.py:102-106), on the device behind the second half of every interval-th step of an enqueued
+// gamd_md_run / gamd_md_run_nhc, and the same kernels on given positions outside a run (gamd_classical_eval).  r_cut (3 sigma)
+// lies beyond the network's cutoff, so the edge list of the force evaluation cannot be walked: every ordered pair of a box is
+// evaluated, N (N - 1) pair terms per box and sample, in double, from the caller's fp32 positions in the CALLER's atom order (the
+// sorted order depends on the arrival order of the cell-fill atomics).
+//
+//   k_classical_pairs   grid (T * slices, boxes), T = 256-atom row tiles per box: workgroup (I, s) keeps atom t of tile I in
+//                       the registers of thread t and walks the atoms [s * chunk, (s + 1) * chunk) of the box, staged 256 at a
+//                       time in LDS as doubles (every lane of a wave reads the same LDS address).  FULL rows (j != i, both
+//                       i < j and i > j): an atom's force is the sum of its own row, no atomics.  Per atom and slice one
+//                       partial row {Fx, Fy, Fz, e_i, w_i, pairs_i}, summed over j in ascending order from 0.
+//   k_classical_atoms   grid (blocks per box, boxes): per atom, the slices' partial rows added in order from 0, f_cl = F * len;
+//                       with f given, the atom's terms of the five force-error sums; per-thread sums over the thread's atoms
+//                       (fixed assignment), then the fixed tree of k_report_ke (shuffle 32 .. 1, (w0 + w1) + (w2 + w3)).
+//   k_classical_final   one thread per box adds the block rows in order and writes the row the HOST chose: E = sum e_i / 2,
+//                       W = sum w_i / 2, pairs = sum pairs_i / 2 (halving is exact), the five sums, the atoms left out.
+// The arithmetic of a pair term is spelled out in DESIGN.md section 4.9 (tests/classical_ref.py mirrors it).  d_ij = -d_ji bit
+// for bit (rint is odd), so u_ij = u_ji and F_ij = -F_ji bit for bit.  Fixed atom-to-thread assignment, fixed slices and
+// blocks per handle, no floating-point atomics, contraction off: the same bits run after run.  Every kernel returns while
+// DEVFLAG_FROZEN is set; nothing is updated in place, so a sample that runs twice writes the same bits twice.
+#include "gamd_common.h"
+#include "gamd_internal.h"
+
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int CL_TILE = 256;
+
+// fp32 edge `c` of box `box`, widened
+__device__ __forceinline__ double classical_box_edge(const ClassicalArgs& a, int box, int c) {
+    if (a.box_edges) return (double)a.box_edges[3 * box + c];
+    if (a.bx.n_boxes <= 1) return (double)a.box[c];
+    const float4 b = a.bx.boxes[3 * box];
+    return (double)(c == 0 ? b.x : (c == 1 ? b.y : b.z));
+}
+
+__global__ void __launch_bounds__(256) k_classical_pairs(ClassicalArgs a) {
+    if (a.devflags[DEVFLAG_FROZEN]) return;                 // a frame that will be evaluated again
+    __shared__ double sx[CL_TILE], sy[CL_TILE], sz[CL_TILE];
+    const int tid = threadIdx.x;
+    const int I = (int)(blockIdx.x / (unsigned)a.slices), s = (int)(blockIdx.x % (unsigned)a.slices);
+    const int box = blockIdx.y;
+    const int npb = a.bx.n_boxes > 1 ? a.bx.n_per_box : a.n;
+    const size_t a0 = (size_t)box * (size_t)npb;            // the caller's order is box-major
+    if (I >= a.tiles) return;                               // (uniform; cannot happen with the launcher's grid)
+    const int il = I * CL_TILE + tid;                       // atom of this thread inside its box
+    const bool vi = il < npb;
+    const long long jb = (long long)s * a.chunk;
+    const int je = (int)(jb + a.chunk < (long long)npb ? jb + a.chunk : (long long)npb);
+    const double Lx = classical_box_edge(a, box, 0), Ly = classical_box_edge(a, box, 1), Lz = classical_box_edge(a, box, 2);
+
+    double xi = 0.0, yi = 0.0, zi = 0.0;
+    if (vi) {
+        const float* p = a.x + 3 * (a0 + (size_t)il);
+        xi = (double)p[0]; yi = (double)p[1]; zi = (double)p[2];
+    }
+    double fx = 0.0, fy = 0.0, fz = 0.0, e = 0.0, w = 0.0, cnt = 0.0;
+    for (long long base = jb; base < je; base += CL_TILE) {
+        __syncthreads();                                    // the previous chunk has been read
+        const int nj = (int)(je - base < CL_TILE ? je - base : CL_TILE);
+        if (tid < nj) {
+            const float* p = a.x + 3 * (a0 + (size_t)base + (size_t)tid);
+            sx[tid] = (double)p[0]; sy[tid] = (double)p[1]; sz[tid] = (double)p[2];
+        }
+        __syncthreads();
+        if (!vi) continue;
+        const int self = (int)((long long)il - base);       // this atom's own slot in the chunk, if it is there
+        for (int jj = 0; jj < nj; ++jj) {
+            double dx = xi - sx[jj], dy = yi - sy[jj], dz = zi - sz[jj];
+            dx = dx - Lx * rint(dx / Lx);
+            dy = dy - Ly * rint(dy / Ly);
+            dz = dz - Lz * rint(dz / Lz);
+            const double r2 = (dx * dx + dy * dy) + dz * dz;
+            if (jj == self || !(r2 < a.rc2)) continue;
+            const double ir2 = 1.0 / r2;
+            const double s2 = a.sig2 * ir2;
+            const double s6 = (s2 * s2) * s2;
+            const double s12 = s6 * s6;
+            double u = a.eps4 * (s12 - s6) - a.u0;          // u_LJ - u0
+            double ru = -(a.eps24 * ((s12 + s12) - s6));    // r u_LJ'(r)
+            if (a.rs >= 0.0) {
+                const double r = sqrt(r2);
+                if (r > a.rs) {
+                    const double t = (r - a.rs) * a.inv_w;
+                    const double t2 = t * t, tm = t - 1.0;
+                    const double S = 1.0 - (t2 * t) * ((6.0 * t - 15.0) * t + 10.0);
+                    const double dS = ((-30.0 * t2) * (tm * tm)) * a.inv_w;
+                    ru = ru * S + ((u * dS) * r);           // r u'(r), u = (u_LJ - u0) S
+                    u = u * S;
+                }
+            }
+            const double fs = -(ru * ir2);                  // F_ij = -u'(r) d / r = fs d
+            fx += fs * dx; fy += fs * dy; fz += fs * dz;
+            e += u;
+            w += -ru;                                       // d . F_ij = -r u'(r)
+            cnt += 1.0;
+        }
+    }
+    if (vi) {
+        double* out = a.part + (((size_t)box * (size_t)a.slices + (size_t)s) * (size_t)npb + (size_t)il) * CLASSICAL_PART;
+        out[0] = fx; out[1] = fy; out[2] = fz; out[3] = e; out[4] = w; out[5] = cnt;
+    }
+}
+
+__global__ void __launch_bounds__(256) k_classical_atoms(ClassicalArgs a) {
+    if (a.devflags[DEVFLAG_FROZEN]) return;
+    __shared__ double red[4][CLASSICAL_ROW];
+    const int box = blockIdx.y;
+    const int npb = a.bx.n_boxes > 1 ? a.bx.n_per_box : a.n;
+    const size_t a0 = (size_t)box * (size_t)npb;
+    double acc[CLASSICAL_ROW];
+#pragma unroll
+    for (int q = 0; q < CLASSICAL_ROW; ++q) acc[q] = 0.0;
+    for (int il = blockIdx.x * blockDim.x + threadIdx.x; il < npb; il += gridDim.x * blockDim.x) {
+        double t[CLASSICAL_PART];
+#pragma unroll
+        for (int q = 0; q < CLASSICAL_PART; ++q) t[q] = 0.0;
+        for (int s = 0; s < a.slices; ++s) {
+            const double* p = a.part + (((size_t)box * (size_t)a.slices + (size_t)s) * (size_t)npb + (size_t)il) * CLASSICAL_PART;
+#pragma unroll
+            for (int q = 0; q < CLASSICAL_PART; ++q) t[q] += p[q];
+        }
+        const size_t i = a0 + (size_t)il;
+        const double cx = t[0] * a.len, cy = t[1] * a.len, cz = t[2] * a.len;      // kJ/mol/nm
+        a.f_cl[3 * i] = cx; a.f_cl[3 * i + 1] = cy; a.f_cl[3 * i + 2] = cz;
+        acc[0] += t[3]; acc[1] += t[4]; acc[2] += t[5];
+        if (a.f) {
+            const double gx = (double)a.f[3 * i], gy = (double)a.f[3 * i + 1], gz = (double)a.f[3 * i + 2];
+            const double dx = gx - cx, dy = gy - cy, dz = gz - cz;
+            acc[3] += (fabs(dx) + fabs(dy)) + fabs(dz);
+            acc[4] += (dx * dx + dy * dy) + dz * dz;
+            const double nc = sqrt((cx * cx + cy * cy) + cz * cz), ng = sqrt((gx * gx + gy * gy) + gz * gz);
+            if (nc == 0.0 || ng == 0.0) acc[8] += 1.0;
+            else acc[5] += ((gx * cx + gy * cy) + gz * cz) / (ng * nc);
+            acc[6] += nc; acc[7] += ng;
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < CLASSICAL_ROW; ++q) {
+        double v = acc[q];
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) v += __shfl_down(v, d, 64);
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][q] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < CLASSICAL_ROW) {
+        const int q = threadIdx.x;
+        a.blk[((size_t)box * (size_t)a.blocks + blockIdx.x) * CLASSICAL_ROW + q] = (red[0][q] + red[1][q]) + (red[2][q] + red[3][q]);
+    }
+}
+
+__global__ void k_classical_final(ClassicalArgs a) {
+    if (a.devflags[DEVFLAG_FROZEN]) return;
+    const int nb = a.bx.n_boxes > 1 ? a.bx.n_boxes : 1;
+    const int box = blockIdx.x * blockDim.x + threadIdx.x;  // one thread per box
+    if (box >= nb) return;
+    double* row = a.rows + ((size_t)a.slot * (size_t)nb + (size_t)box) * CLASSICAL_ROW;
+    for (int q = 0; q < CLASSICAL_ROW; ++q) {
+        double s = 0.0;
+        for (int b = 0; b < a.blocks; ++b) s += a.blk[((size_t)box * (size_t)a.blocks + b) * CLASSICAL_ROW + q];
+        row[q] = q < 3 ? 0.5 * s : s;                       // every pair sits in two rows
+    }
+    if (box == 0 && a.steps) a.steps[a.slot] = a.g;
+}
+
+}  // namespace
+
+int launch_classical(const ClassicalArgs& a, hipStream_t st) {
+    const int nb = a.bx.n_boxes > 1 ? a.bx.n_boxes : 1, npb = a.bx.n_boxes > 1 ? a.bx.n_per_box : a.n;
+    const long long T = (npb + CL_TILE - 1) / CL_TILE;
+    if (npb < 1 || nb > 65535 || a.tiles != (int)T || a.slices < 1 || a.chunk < 1 || a.blocks < 1 || a.blocks > 65535 || a.slot < 0) return -1;
+    if ((long long)a.slices * a.chunk < npb || T * a.slices > 0x7fffffll) return -1;   // the slices cover a row; grid.x * 256 threads stay below 2^31
+    if (!a.x || !a.part || !a.f_cl || !a.blk || !a.rows || !a.devflags) return -1;
+    hipLaunchKernelGGL(k_classical_pairs, dim3((unsigned)(T * a.slices), nb), dim3(256), 0, st, a); GAMD_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_classical_atoms, dim3(a.blocks, nb), dim3(256), 0, st, a); GAMD_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_classical_final, dim3((nb + 63) / 64), dim3(64), 0, st, a); GAMD_CHECK_LAUNCH();
+    return 0;
+}

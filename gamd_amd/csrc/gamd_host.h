@@ -115,7 +115,7 @@ struct MdPending {
     hipStream_t st = nullptr;
 };
 
-// ---- run observers (observe.hip: reporter, recorder, structure sampler) as the MD driver sees them ----------------------------
+// ---- run observers (observe.hip: reporter, recorder, structure sampler, classical observer) as the MD driver sees them --------
 struct Observers;
 Observers* observers_new();
 void observers_free(gamd_handle* h);           // releases their device buffers (under the caller's DeviceGuard)

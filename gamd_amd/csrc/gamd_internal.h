@@ -567,3 +567,36 @@ struct StructArgs {
 };
 int launch_struct_pairs(const StructArgs& a, hipStream_t st);
 int launch_struct_sk(const StructArgs& a, hipStream_t st);
+
+// ---- classical potential (classical.hip) ----------------------------------------------------------
+// One sample of an enqueued MD run (gamd_classical_configure) or one gamd_classical_eval call: the switched, shifted
+// Lennard-Jones potential of include/gamd_hip.h on every pair of every box in double, from the caller's fp32 positions in the
+// caller's atom order: per-atom forces f_cl, per-box energy, virial and pair count, and (f != null) the force-error sums of f
+// against f_cl.  Row number and step number come from the host (the sample's ordinal), so a sample that is enqueued again after
+// a freeze writes the same row with the same bits; nothing is updated in place.
+// (No kernel uses a value it read from memory as an address: the checked build has nothing to range-check here.)
+enum { CLASSICAL_PART = 6,     // per atom and slice: Fx, Fy, Fz (per length unit), e_i, w_i, pairs of the atom's row
+       CLASSICAL_ROW = 9 };    // per box: E, W, pairs, sum |D_ic|, sum |D_i|^2, sum cos, sum |f_cl,i|, sum |f_i|, atoms left out of cos
+struct ClassicalArgs {
+    int n;                     // atoms of all boxes
+    BoxRef bx;
+    const int* devflags;       // DEVFLAG_FROZEN set: every kernel returns at once
+    float box[3];              // n_boxes <= 1 and box_edges == null
+    const float* box_edges;    // device [n_boxes][3] (gamd_classical_eval), or null: box / bx.boxes of the run
+    const float* x;            // [n][3] positions, length unit, any periodic image
+    const float* f;            // [n][3] kJ/mol/nm to compare f_cl with, or null
+    double sig2, eps4, eps24;  // sigma^2, 4 epsilon, 24 epsilon
+    double rc2, u0;            // r_cut^2, u_LJ(r_cut) or 0
+    double rs, inv_w;          // r_switch and 1 / (r_cut - r_switch); rs < 0: no switching
+    double len;                // length units per nm
+    int tiles, slices, chunk;  // 256-atom row tiles per box; J slices per row; atoms per slice
+    int blocks;                // workgroups per box of the per-atom pass (fixed per handle: the summation tree never changes)
+    double* part;              // [n_boxes][slices][n_per_box][CLASSICAL_PART]
+    double* f_cl;              // [n][3] kJ/mol/nm
+    double* blk;               // [n_boxes][blocks][CLASSICAL_ROW]
+    double* rows;              // [...][n_boxes][CLASSICAL_ROW]
+    long long* steps;          // [...] or null
+    long long slot;            // row of this sample
+    long long g;               // completed MD steps at this sample
+};
+int launch_classical(const ClassicalArgs& a, hipStream_t st);

@@ -1,11 +1,13 @@
 // observe.hip — host side of the run observers, the consumers at the sample point of an enqueued gamd_md_run / gamd_md_run_nhc
 // (behind the second half of every interval-th step): the run reporter (gamd_report_*, report.hip), the run recorder
-// (gamd_traj_*, traj.hip) and the structure sampler (gamd_struct_*, structure.hip).  Each is its configuration plus a SampleClock,
+// (gamd_traj_*, traj.hip), the structure sampler (gamd_struct_*, structure.hip) and the classical observer (gamd_classical_*,
+// classical.hip; gamd_classical_eval runs its kernels outside a run).  Each is its configuration plus a SampleClock,
 // a buffer table and an entry in observer_list(), through which the MD driver of gamd_api.hip sees it (observers_*, gamd_host.h).
 #include "gamd_host.h"
 
 #include <algorithm>
 #include <array>
+#include <cmath>
 #include <cstring>
 
 namespace {
@@ -71,9 +73,23 @@ struct StructSampler {
     DevBuf counts, kvec, rho_partial, sk_sum;
 };
 
+// classical observer: the potential's parameters (taken by every gamd_classical_configure, armed or not), the log rows and
+// the work buffers of one evaluation
+struct Classical {
+    SampleClock clock;
+    long long max_samples = 0;
+    bool params_set = false;           // gamd_classical_eval needs parameters, not an armed observer
+    bool evaluated = false;            // f_cl holds the forces of a sample or a gamd_classical_eval call
+    double sigma = 0.0, epsilon = 0.0, r_cut = 0.0, r_switch = 0.0;
+    int shift = 0;
+    DevBuf steps, rows;                // log
+    DevBuf part, f_cl, blk;            // one evaluation
+    DevBuf eval_rows, eval_box;        // gamd_classical_eval: its row and its box edges
+};
+
 }  // namespace
 
-struct Observers { Reporter rep; Recorder rec; StructSampler ss; };
+struct Observers { Reporter rep; Recorder rec; StructSampler ss; Classical cl; };
 
 namespace {
 
@@ -114,6 +130,23 @@ ObsBufs struct_bufs(gamd_handle* h) {
             {&sp.kvec, sizeof(int) * 3 * K, false},                 // uploaded by gamd_struct_configure
             {&sp.rho_partial, sizeof(double) * 2 * nb * (size_t)struct_rho_blocks(h) * cls * K, false},
             {&sp.sk_sum, sizeof(double) * nb * (size_t)sp.pairs * K, true}};
+}
+
+// classical observer: J slices per row (258 atoms still fill more than two workgroups), atoms per slice, blocks of the
+// per-atom pass — fixed per handle: the summation order never changes
+int classical_tiles(const gamd_handle* h) { return (h->n_per_box + 255) / 256; }
+int classical_slices(const gamd_handle* h) { const int T = classical_tiles(h); return std::max(1, std::min(32, (1024 + T - 1) / T)); }
+int classical_chunk(const gamd_handle* h) { const int S = classical_slices(h); return (h->n_per_box + S - 1) / S; }
+int classical_blocks(const gamd_handle* h) { return std::max(1, std::min(64, (h->n_per_box + 255) / 256)); }
+
+ObsBufs classical_bufs(gamd_handle* h) {
+    Classical& cl = h->obs->cl;
+    const size_t nb = (size_t)h->n_boxes, rows = (size_t)cl.max_samples, n = (size_t)h->n;
+    return {{&cl.steps, sizeof(long long) * rows, true}, {&cl.rows, sizeof(double) * CLASSICAL_ROW * nb * rows, true},
+            {&cl.part, sizeof(double) * CLASSICAL_PART * n * (size_t)classical_slices(h), false},
+            {&cl.f_cl, sizeof(double) * 3 * n, false},
+            {&cl.blk, sizeof(double) * CLASSICAL_ROW * nb * (size_t)classical_blocks(h), false},
+            {&cl.eval_rows, sizeof(double) * CLASSICAL_ROW * nb, false}, {&cl.eval_box, sizeof(float) * 3 * nb, false}};
 }
 
 // what every observer's argument block starts with
@@ -235,6 +268,55 @@ int enqueue_struct_sample(gamd_handle* h, long long) {
     return 0;
 }
 
+// the classical observer's argument block but for positions, forces, box and output row
+ClassicalArgs classical_args(gamd_handle* h, double len) {
+    const Classical& cl = h->obs->cl;
+    ClassicalArgs a{};
+    sample_args(h, a);
+    a.sig2 = cl.sigma * cl.sigma;
+    a.eps4 = 4.0 * cl.epsilon; a.eps24 = 24.0 * cl.epsilon;
+    a.rc2 = cl.r_cut * cl.r_cut;
+    a.u0 = 0.0;
+    if (cl.shift) {                                         // u_LJ(r_cut) by the kernel's own operations
+        const double s2 = a.sig2 * (1.0 / a.rc2), s6 = (s2 * s2) * s2;
+        a.u0 = a.eps4 * (s6 * s6 - s6);
+    }
+    const bool sw = cl.r_switch > 0.0 && cl.r_switch < cl.r_cut;
+    a.rs = sw ? cl.r_switch : -1.0;
+    a.inv_w = sw ? 1.0 / (cl.r_cut - cl.r_switch) : 0.0;
+    a.len = len;
+    a.tiles = classical_tiles(h); a.slices = classical_slices(h); a.chunk = classical_chunk(h); a.blocks = classical_blocks(h);
+    a.part = cl.part.as<double>(); a.f_cl = cl.f_cl.as<double>(); a.blk = cl.blk.as<double>();
+    return a;
+}
+
+// the classical observer's sample of step s of the pending run, behind its second half: f holds the network forces at x
+int enqueue_classical_sample(gamd_handle* h, long long s) {
+    const MdPending& p = h->pending;
+    Classical& cl = h->obs->cl;
+    if (cl.clock.ordinal(s) >= cl.max_samples) return 0;    // the log is full: counted as dropped by gamd_classical_read
+    ClassicalArgs a = classical_args(h, pending_particles(p).len);
+    for (int d = 0; d < 3; ++d) a.box[d] = h->box[d];
+    a.x = p.x; a.f = p.f;
+    a.rows = cl.rows.as<double>(); a.steps = cl.steps.as<long long>();
+    a.g = cl.clock.completed(s);
+    a.slot = cl.clock.ordinal(s);
+    if (int r = launch_classical(a, p.st)) return fail(-1, "classical observer launch failed (%d)", r);
+    cl.evaluated = true;
+    return 0;
+}
+
+// classical observer: the minimum image is the nearest image only inside the sphere of half the shortest edge
+int classical_check_box(const gamd_handle* h, const float* box) {
+    const Classical& cl = h->obs->cl;
+    for (int k = 0; k < 3 * h->n_boxes; ++k)
+        if (!(2.0 * cl.r_cut <= (double)box[k]))
+            return fail(-22, "classical potential: r_cut = %g exceeds half of box[%d][%d] = %g (the minimum image is the nearest "
+                             "image only below that)", cl.r_cut, k / 3, k % 3, (double)box[k]);
+    return 0;
+}
+int classical_check_run(gamd_handle* h, const float* box, const uint8_t*) { return classical_check_box(h, box); }
+
 // run recorder: image counters and ring are only meaningful in one box and with one set of classes
 int traj_check_run(gamd_handle* h, const float* box, const uint8_t* species_dev) {
     const Recorder& rc = h->obs->rec;
@@ -278,12 +360,13 @@ struct Observer {
     void (*begin_run)(gamd_handle*, const float* box, const uint8_t* species_dev);   // what it keeps of a run besides the clock; may be null
     void (*forget)(gamd_handle*);                                                    // ... and how configure / reset drop it; may be null
 };
-enum { OBS_REPORT = 0, OBS_TRAJ = 1, OBS_STRUCT = 2, OBS_COUNT = 3 };
+enum { OBS_REPORT = 0, OBS_TRAJ = 1, OBS_STRUCT = 2, OBS_CLASSICAL = 3, OBS_COUNT = 4 };
 std::array<Observer, OBS_COUNT> observer_list(const gamd_handle* h) {
     Observers& o = *h->obs;
     return {{{&o.rep.clock, report_bufs, enqueue_report_sample, nullptr, nullptr, nullptr},
              {&o.rec.clock, traj_bufs, enqueue_traj_sample, traj_check_run, traj_begin_run, traj_forget},
-             {&o.ss.clock, struct_bufs, enqueue_struct_sample, struct_check_run, nullptr, nullptr}}};
+             {&o.ss.clock, struct_bufs, enqueue_struct_sample, struct_check_run, nullptr, nullptr},
+             {&o.cl.clock, classical_bufs, enqueue_classical_sample, classical_check_run, nullptr, nullptr}}};
 }
 
 // clear an observer's step count and what it took (configuration and scratch stay): on the init stream, landed on return
@@ -385,6 +468,10 @@ static_assert(sizeof(gamd_traj_params) == 32 && offsetof(gamd_traj_params, field
 static_assert(sizeof(gamd_struct_params) == 32 && offsetof(gamd_struct_params, rdf_bins) == 8 && offsetof(gamd_struct_params, rdf_rmax) == 12 &&
               offsetof(gamd_struct_params, sk_n2max) == 20,
               "gamd_struct_params layout is part of the C ABI (gamd_amd/_lib.py mirrors it)");
+static_assert(sizeof(gamd_classical_params) == 56 && offsetof(gamd_classical_params, sigma) == 16 && offsetof(gamd_classical_params, r_switch) == 40 &&
+              offsetof(gamd_classical_params, shift) == 48,
+              "gamd_classical_params layout is part of the C ABI (gamd_amd/_lib.py mirrors it)");
+static_assert(GAMD_CLASSICAL_ROW == CLASSICAL_ROW, "the row of gamd_classical_read is the kernels' row");
 
 extern "C" {
 
@@ -560,6 +647,96 @@ int32_t gamd_struct_read(gamd_handle* h, void* stream, uint64_t* counts, int64_t
     if (kvec && K > 0) std::memcpy(kvec, sp.kvec_host.data(), sizeof(int32_t) * 3 * (size_t)K);
     if (frames) *frames = sp.clock.taken(bins > 0 || K > 0);
     if (dims) { dims[0] = (int32_t)nb; dims[1] = sp.pairs; dims[2] = (int32_t)bins; dims[3] = (int32_t)K; }
+    return 0;
+}
+
+int32_t gamd_classical_configure(gamd_handle* h, const gamd_classical_params* p) {
+    if (!p) return fail(-22, "null argument");
+    if (p->interval < 0) return fail(-22, "interval = %lld is negative", (long long)p->interval);
+    if (p->max_samples < 0 || p->max_samples > (1ll << 24)) return fail(-22, "max_samples = %lld outside [0, 2^24]", (long long)p->max_samples);
+    if (!(p->sigma > 0.0) || !std::isfinite(p->sigma)) return fail(-22, "sigma = %g is not positive", p->sigma);
+    if (!std::isfinite(p->epsilon)) return fail(-22, "epsilon = %g is not finite", p->epsilon);
+    if (!(p->r_cut > 0.0) || !std::isfinite(p->r_cut)) return fail(-22, "r_cut = %g is not positive", p->r_cut);
+    if (!(p->r_switch >= 0.0)) return fail(-22, "r_switch = %g is negative", p->r_switch);
+    if (!h) return fail(-22, "null handle");
+    if (h->cfg.kind != GAMD_KIND_LJ)
+        return fail(-22, "classical potential: a GAMD_KIND_WATER handle needs electrostatics, which are not implemented (Lennard-Jones, "
+                         "GAMD_KIND_LJ handles only)");
+    if (h->n_boxes > 65535) return fail(-22, "the classical observer needs n_boxes <= 65535");
+    {
+        const long long T = (h->n_per_box + 255) / 256;
+        if (T * (T + 1) / 2 > 0xffffffll) return fail(-22, "the classical observer needs at most 5791 tiles of 256 atoms per box");
+    }
+    if (h->pending.active) return fail(-22, "an MD run is still enqueued: call gamd_sync_status before gamd_classical_configure");
+    Classical& cl = h->obs->cl;
+    cl.sigma = p->sigma; cl.epsilon = p->epsilon; cl.r_cut = p->r_cut; cl.r_switch = p->r_switch; cl.shift = p->shift ? 1 : 0;
+    cl.params_set = true;
+    return observer_configure(h, OBS_CLASSICAL, p->interval, "gamd_classical_configure", [&]() {
+        cl.max_samples = p->max_samples > 0 ? p->max_samples : 4096;
+        return bufs_resize(classical_bufs(h)) ? fail(-12, "classical observer allocation failed") : 0;
+    });
+}
+
+int32_t gamd_classical_reset(gamd_handle* h) { return observer_reset(h, OBS_CLASSICAL, "gamd_classical_reset"); }
+
+int32_t gamd_classical_read(gamd_handle* h, void* stream, int64_t* steps, double* rows, int64_t max_rows, int64_t* n_rows,
+                            int64_t* dropped, double* f_cl, int64_t f_cl_elems) {
+    if (!h) return fail(-22, "null handle");
+    if (max_rows < 0) return fail(-22, "max_rows is negative");
+    const Classical& cl = h->obs->cl;
+    DeviceGuard guard(h->dev);
+    hipStream_t st = (hipStream_t)stream;
+    const long long nb = h->n_boxes;
+    const long long taken = cl.clock.taken(cl.steps.p != nullptr);
+    const long long kept = std::min<long long>(taken, cl.max_samples);
+    const long long n_copy = std::min<long long>(kept, max_rows);
+    if (f_cl && f_cl_elems < 3ll * h->n) return fail(-22, "f_cl has room for %lld elements, the forces have %lld", (long long)f_cl_elems, 3ll * h->n);
+    if (n_copy > 0 && steps) HIP_TRY(hipMemcpyAsync(steps, cl.steps.p, sizeof(int64_t) * (size_t)n_copy, hipMemcpyDeviceToHost, st));
+    if (n_copy > 0 && rows) HIP_TRY(hipMemcpyAsync(rows, cl.rows.p, sizeof(double) * (size_t)(n_copy * nb * CLASSICAL_ROW), hipMemcpyDeviceToHost, st));
+    if (f_cl && cl.evaluated && cl.f_cl.p) HIP_TRY(hipMemcpyAsync(f_cl, cl.f_cl.p, sizeof(double) * 3 * (size_t)h->n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (int t = check_traps(h)) return t;
+    if (n_rows) *n_rows = kept;
+    if (dropped) *dropped = taken - kept;
+    return 0;
+}
+
+int32_t gamd_classical_eval(gamd_handle* h, const float* pos_dev, const float* box, float length_per_nm, double* f_out_dev,
+                            double* energy, double* virial, double* pairs, void* stream) {
+    if (!h) return fail(-22, "null handle");
+    if (!pos_dev || !box) return fail(-22, "null argument");
+    Classical& cl = h->obs->cl;
+    if (!cl.params_set) return fail(-22, "gamd_classical_eval needs the parameters of a gamd_classical_configure call (interval 0 will do)");
+    if (h->pending.active) return fail(-22, "an MD run is still enqueued: call gamd_sync_status before gamd_classical_eval");
+    for (int k = 0; k < 3 * h->n_boxes; ++k)
+        if (!(box[k] > 0.f)) return fail(-22, "box[%d][%d] = %g is not positive", k / 3, k % 3, (double)box[k]);
+    if (int r = classical_check_box(h, box)) return r;
+    DeviceGuard guard(h->dev);
+    hipStream_t st = (hipStream_t)stream;
+    InitStream init(st);
+    for (const ObsBuf& b : classical_bufs(h))               // the work buffers; the log is gamd_classical_configure's
+        if (!b.cleared && b.buf->ensure(b.want, true)) return fail(-12, "classical potential allocation failed");
+    const size_t nb = (size_t)h->n_boxes;
+    HIP_TRY(init_upload(cl.eval_box.p, box, sizeof(float) * 3 * nb));
+    // a frozen handle's kernels return at once: the row would be what the last call left
+    HIP_TRY(hipMemsetAsync(cl.eval_rows.p, 0xff, sizeof(double) * CLASSICAL_ROW * nb, st));
+    ClassicalArgs a = classical_args(h, length_per_nm > 0.f ? (double)length_per_nm : 10.0);
+    a.box_edges = cl.eval_box.as<float>();
+    a.x = pos_dev; a.f = nullptr;
+    a.rows = cl.eval_rows.as<double>(); a.steps = nullptr; a.slot = 0; a.g = 0;
+    if (int r = launch_classical(a, st)) return fail(-1, "classical potential launch failed (%d)", r);
+    cl.evaluated = true;
+    if (f_out_dev) HIP_TRY(hipMemcpyAsync(f_out_dev, cl.f_cl.p, sizeof(double) * 3 * (size_t)h->n, hipMemcpyDeviceToDevice, st));
+    std::vector<double> row(CLASSICAL_ROW * nb);
+    HIP_TRY(hipMemcpyAsync(row.data(), cl.eval_rows.p, sizeof(double) * row.size(), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (int t = check_traps(h)) return t;
+    for (size_t b = 0; b < nb; ++b) {
+        if (std::isnan(row[CLASSICAL_ROW * b + 2])) return fail(-1, "gamd_classical_eval: the handle is frozen by a neighbour-buffer overflow (call gamd_sync_status)");
+        if (energy) energy[b] = row[CLASSICAL_ROW * b];
+        if (virial) virial[b] = row[CLASSICAL_ROW * b + 1];
+        if (pairs) pairs[b] = row[CLASSICAL_ROW * b + 2];
+    }
     return 0;
 }
 

@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import GamdReportParams, GamdStructParams, GamdTrajParams, GamdConfig, GamdMdParams, GamdNhcParams, TRAJ_FIELDS, check
+from ._lib import GamdClassicalParams, GamdReportParams, GamdStructParams, GamdTrajParams, GamdConfig, GamdMdParams, GamdNhcParams, TRAJ_FIELDS, check
 from .weights import ModelConfig, infer_config, validate_state_dict
 
 ArrayLike = Union[np.ndarray, torch.Tensor]
@@ -278,6 +278,70 @@ class RunTrajectory:
             paths.append(os.path.join(dir, f"{prefix}{seed}_{t}.npz"))
             np.savez(paths[-1], **out)
         return paths
+
+
+KJ_PER_KCAL = 4.184
+BAR_PER_KJ_MOL_NM3 = 16.6053906717          # 1 kJ/mol/nm^3 = 1e3 / (6.02214076e23 * 1e-27) Pa = 16.6053906717 bar
+
+
+class RunClassical:
+    """What the classical observer logged (GamdForce.classical_read).  Host-only: plain arrays in, plain arrays out.
+
+    steps [S] int64: completed MD steps g at each sample; per sample and box, float64 [S, B]: energy (kJ/mol), virial
+    W = sum_{i<j} d . F_ij (kJ/mol), pairs (pairs inside r_cut), and the force-error sums of the run's forces f against the
+    classical forces f_cl (both kJ/mol/nm): sum_abs = sum_i sum_c |f - f_cl|, sum_sq = sum_i |f - f_cl|^2, sum_cos = sum_i
+    cos(f_i, f_cl,i), sum_norm_cl = sum_i |f_cl,i|, sum_norm = sum_i |f_i|, excluded = atoms left out of sum_cos because one
+    of the two forces is zero.  n_atoms: atoms per box; dropped: samples that found the log full; forces [B * n, 3] float64:
+    the classical forces of the last sample, or None."""
+
+    COLUMNS = ("energy", "virial", "pairs", "sum_abs", "sum_sq", "sum_cos", "sum_norm_cl", "sum_norm", "excluded")
+
+    def __init__(self, steps, rows, n_atoms: int, dropped: int = 0, forces=None):
+        self.steps = np.asarray(steps, dtype=np.int64)
+        rows = np.asarray(rows, dtype=np.float64)
+        if rows.ndim != 3 or rows.shape[0] != self.steps.shape[0] or rows.shape[2] != len(self.COLUMNS):
+            raise ValueError(f"rows must be [{self.steps.shape[0]}, n_boxes, {len(self.COLUMNS)}], got {rows.shape}")
+        for k, name in enumerate(self.COLUMNS):
+            setattr(self, name, rows[:, :, k].copy())
+        self.n_atoms, self.dropped = int(n_atoms), int(dropped)
+        self.forces = None if forces is None else np.asarray(forces, dtype=np.float64)
+
+    def force_errors(self, unit: float = 1.0) -> Dict[str, np.ndarray]:
+        """The accuracy figures of LJ/test_script/lj.ipynb cell 3 per sample and box, [S, B] each, network force against
+        classical force: ``mae`` = sum_abs / (3 N), ``rmse`` = sqrt(sum_sq / (3 N)), ``cosine`` = sum_cos / (N - excluded),
+        ``relative_mae`` = mae / (sum_norm_cl / N).  ``unit`` multiplies mae and rmse (the notebook's 0.0010364 turns
+        kJ/mol/nm into eV/Angstrom; the relative figure and the cosine do not depend on it)."""
+        n = float(self.n_atoms)
+        mae = self.sum_abs / (3.0 * n)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            cos = np.where(n - self.excluded > 0, self.sum_cos / (n - self.excluded), np.nan)
+            rel = np.where(self.sum_norm_cl > 0, mae / (self.sum_norm_cl / n), np.nan)
+        return {"mae": float(unit) * mae, "rmse": float(unit) * np.sqrt(self.sum_sq / (3.0 * n)), "cosine": cos, "relative_mae": rel}
+
+    def pressure(self, ke, volumes) -> np.ndarray:
+        """[S, B] virial pressure in bar: (2 KE + W) / (3 V) with KE [S, B] in kJ/mol (RunReport.ke of the same samples),
+        ``volumes`` scalar or [B] in nm^3; 1 kJ/mol/nm^3 = 16.6053906717 bar.  No long-range correction."""
+        ke = np.asarray(ke, dtype=np.float64).reshape(self.virial.shape)
+        vol = np.broadcast_to(np.asarray(volumes, dtype=np.float64).reshape(-1), (self.virial.shape[1],))
+        return BAR_PER_KJ_MOL_NM3 * (2.0 * ke + self.virial) / (3.0 * vol[None, :])
+
+    def write_state_data(self, report: "RunReport", path, dt_ps: float, separator: str = "\t",
+                         driver_step_convention: bool = False, box: int = 0) -> None:
+        """The log file OpenMM's StateDataReporter(step=True, time=True, potentialEnergy=True, kineticEnergy=True,
+        totalEnergy=True, temperature=True) writes, in its column order, from a RunReport taken at the same interval (the
+        two step columns must be equal).  ``driver_step_convention`` as in RunReport.write_state_data."""
+        if not np.array_equal(np.asarray(report.steps, dtype=np.int64), self.steps):
+            raise ValueError("the reporter's and the classical observer's step columns differ: configure both with one interval "
+                             "and enough rows, and reset them together")
+        k = 2 if driver_step_convention else 1
+        head = ['"Step"', '"Time (ps)"', '"Potential Energy (kJ/mole)"', '"Kinetic Energy (kJ/mole)"', '"Total Energy (kJ/mole)"',
+                '"Temperature (K)"']
+        with open(path, "w") as fh:
+            fh.write("#" + separator.join(head) + "\n")
+            for i, g in enumerate(self.steps):
+                pe, ke = float(self.energy[i, box]), float(report.ke[i, box])
+                row = [str(k * int(g)), str(k * int(g) * float(dt_ps)), str(pe), str(ke), str(pe + ke), str(float(report.temperature[i, box]))]
+                fh.write(separator.join(row) + "\n")
 
 
 class GamdForce:
@@ -811,6 +875,61 @@ class GamdForce:
               "gamd_struct_read")
         boxes = _boxes(self.box if box is None else box, self.n_boxes).astype(np.float64)
         return RunStructure(counts, sk, kvec, frames.value, getattr(self, "_struct_rmax", 0.0), boxes)
+
+    # -- classical observer (the LJ potential energy, virial and force error on sampled frames; classical force labels) ---
+    def classical_configure(self, interval: int, max_samples: int = 0, sigma: float = 3.4, epsilon: float = 0.238 * KJ_PER_KCAL,
+                            r_cut: Optional[float] = None, r_switch: Optional[float] = None, shift: bool = True) -> None:
+        """While configured, every ``interval``-th completed step of md_run / md_run_nhc (counted across calls, by a counter
+        of its own) evaluates the switched, shifted Lennard-Jones potential on all pairs of every box in double on the
+        device and logs the potential energy, the virial, the pair count and the error sums of the run's (network) forces
+        against the classical forces; ``classical_read`` fetches the rows.  ``interval`` = 0 switches the observer off but
+        still takes the parameters, which ``classical_forces`` uses.  LJ models only.
+
+        ``sigma``, ``r_cut``, ``r_switch`` are in the engine's length unit, ``epsilon`` in kJ/mol.  ``r_cut`` defaults to
+        3 sigma and ``r_switch`` to r_cut - sigma (0: no switching); ``shift`` subtracts u_LJ(r_cut).  The defaults (sigma =
+        3.4 Angstrom, epsilon = 0.238 kcal/mol, cutoff 3 sigma, switch width 3.4 Angstrom, shifted) are meant to be those of
+        openmmtools' ``LennardJonesFluid(shift=True)`` behind the reference's data generator, but they were written down from
+        memory and are UNVERIFIED: neither OpenMM nor openmmtools was available to compare against, and no long-range
+        dispersion correction is applied.  Check them against your OpenMM system before comparing energies."""
+        r_cut = 3.0 * float(sigma) if r_cut is None else float(r_cut)
+        r_switch = r_cut - float(sigma) if r_switch is None else float(r_switch)
+        p = GamdClassicalParams(int(interval), int(max_samples), float(sigma), float(epsilon), r_cut, r_switch, int(bool(shift)), 0)
+        check(self._lib.gamd_classical_configure(self._h, C.byref(p)), "gamd_classical_configure")
+        self._classical_set = True
+
+    def classical_reset(self) -> None:
+        """Step count and rows back to zero; parameters and configuration stay."""
+        check(self._lib.gamd_classical_reset(self._h), "gamd_classical_reset")
+
+    def classical_read(self, forces: bool = False) -> "RunClassical":
+        """Synchronise and fetch what the classical observer has logged since it was configured or reset; ``forces``: also
+        the classical forces of the last sample."""
+        n_rows, dropped = C.c_int64(), C.c_int64()
+        rd = self._lib.gamd_classical_read
+        check(rd(self._h, self._stream(), None, None, 0, C.byref(n_rows), C.byref(dropped), None, 0), "gamd_classical_read")
+        rows = n_rows.value
+        steps = np.zeros(rows, dtype=np.int64)
+        data = np.zeros((rows, self.n_boxes, _lib.CLASSICAL_ROW), dtype=np.float64)
+        fcl = np.full((self.n_total, 3), np.nan, dtype=np.float64) if forces else None
+        vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        check(rd(self._h, self._stream(), vp(steps), vp(data), rows, C.byref(n_rows), C.byref(dropped), vp(fcl),
+                 0 if fcl is None else fcl.size), "gamd_classical_read")
+        return RunClassical(steps, data, self.n, dropped.value, fcl)
+
+    def classical_forces(self, pos: ArrayLike, box=None, length_per_nm: float = 0.0):
+        """The classical potential of the last ``classical_configure`` (with the defaults and interval 0 when there was
+        none) on given positions, outside any run: (forces float64 [N, 3] on the device in kJ/mol/nm, energy [B], virial
+        [B], pairs [B] as float64 arrays).  ``pos`` [N, 3] in any periodic image, fp32 as the library reads it; ``box`` as
+        in ``forward``; ``length_per_nm`` the length unit (0 or 10 = Angstrom).  Synchronises once."""
+        if not getattr(self, "_classical_set", False):
+            self.classical_configure(0)
+        p = self._dev_pos(pos)
+        out = torch.empty((self.n_total, 3), dtype=torch.float64, device=self.device)
+        e, w, c = (np.zeros(self.n_boxes, dtype=np.float64) for _ in range(3))
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)
+        check(self._lib.gamd_classical_eval(self._h, C.c_void_p(p.data_ptr()), self._box_arg(box), float(length_per_nm),
+                                            C.c_void_p(out.data_ptr()), vp(e), vp(w), vp(c), self._stream()), "gamd_classical_eval")
+        return out, e, w, c
 
     def sync_status(self) -> int:
         """0, or 1 when an enqueued MD run overflowed a neighbour buffer, froze on the device and was resumed."""

@@ -429,6 +429,70 @@ int32_t gamd_struct_reset(gamd_handle* h);
 int32_t gamd_struct_read(gamd_handle* h, void* stream, uint64_t* counts, int64_t count_elems, double* sk_sum, int64_t sk_elems,
                          int32_t* kvec, int64_t kvec_elems, int64_t* frames, int32_t dims[4]);
 
+/* Classical observer: where a classical potential exists the reference judges a rollout by it — the potential energy of the
+ * GNN-driven run against the classical run (LJ/test_script/lj.ipynb cells 5-6; potentialEnergy / totalEnergy of
+ * dataset/generate_lj_data.py:87-90) and the network force against the classical force on every frame (gt_force,
+ * LJ/test_script/test_langevin.py:102-106; cosine, MAE, RMSE, relative MAE of lj.ipynb cell 3).  This observer evaluates the
+ * switched, shifted Lennard-Jones potential ON THE DEVICE while gamd_md_run / gamd_md_run_nhc are enqueued, and
+ * gamd_classical_eval evaluates it on given positions outside a run.  GAMD_KIND_LJ handles only, one pair class; no long-range
+ * dispersion correction, no electrostatics (a GAMD_KIND_WATER handle is refused with -22).
+ * The potential, for the minimum-image distance r of a pair (d = x_i - x_j, per component d - L rint(d / L) in double, L the
+ * fp32 box edge widened; r^2 = (dx^2 + dy^2) + dz^2):
+ *     u_LJ(r) = 4 epsilon [(sigma / r)^12 - (sigma / r)^6],   u0 = u_LJ(r_cut) with `shift`, else 0
+ *     S(r) = 1 for r <= r_switch;  1 - 6 t^5 + 15 t^4 - 10 t^3, t = (r - r_switch) / (r_cut - r_switch), beyond it (OpenMM's
+ *     switching function); r_switch = 0 or r_switch >= r_cut: no switching
+ *     u(r) = (u_LJ - u0) S for r^2 < r_cut^2, else 0;   F_ij = -u'(r) d / r
+ * Per box: E = sum_{i<j} u, the virial W = sum_{i<j} d . F_ij = -sum r u'(r), and the number of pairs inside r_cut.  sigma,
+ * r_cut, r_switch are in the handle's length unit (like gamd_config.cutoff), epsilon in kJ/mol, forces in kJ/mol/nm through the
+ * run's (or the call's) length_per_nm, like f; E and W in kJ/mol.  Everything is computed in double from the caller's fp32
+ * position buffer in the caller's atom order, every atom walks its full row (N (N - 1) pair terms per box and sample — O(N^2):
+ * meant for sampling intervals, not for every step), powers by multiplication, no contraction, no floating-point atomics, fixed
+ * summation order: the same bits run after run.
+ * The observer counts the completed MD steps g of the handle since it was configured or reset (across calls, with a counter of
+ * its own).  Step g is sampled when g % interval == 0, behind its second half, where the other observers sample: f then holds
+ * the network forces at the sampled positions.  A sample writes row g / interval - 1 (rows beyond max_samples are dropped and
+ * counted): {g; per box E, W, pairs, and the force-error sums of f (widened to double) against the classical force f_cl:
+ * sum_i sum_c |D_ic|, sum_i |D_i|^2, sum_i cos(f_i, f_cl,i), sum_i |f_cl,i|, sum_i |f_i| with D = f - f_cl, and the number of
+ * atoms left out of the cosine sum because f_i or f_cl,i is zero}.  The last sample's f_cl stays readable.
+ * Precondition: 2 * r_cut <= the shortest edge of every box (the minimum image is the nearest image only below that);
+ * otherwise gamd_md_run / gamd_md_run_nhc / gamd_classical_eval return -22 (the message names r_cut) before anything is enqueued.
+ * Device memory: 48 B per atom and slice (at most 32 slices per row), 24 B per atom, 72 B per box and row.
+ * Nothing synchronises or returns to the host inside a run; a run that froze on a neighbour-buffer overflow and was resumed by
+ * gamd_sync_status gives the rows of an ample buffer (a sample that runs twice writes the same bits twice).  A handle whose
+ * classical observer is off (the default) enqueues exactly what it enqueues without one; with it on, skin-mode runs launch the
+ * second half of a SAMPLED step on its own. */
+typedef struct gamd_classical_params {
+    int64_t interval;        /* 0 = observer off: the parameters below are still taken (gamd_classical_eval uses them), rows kept */
+    int64_t max_samples;     /* rows allocated by gamd_classical_configure with interval > 0; 0 = 4096 */
+    double sigma;            /* length unit of the handle, > 0 */
+    double epsilon;          /* kJ/mol, finite */
+    double r_cut;            /* length unit of the handle, > 0 */
+    double r_switch;         /* 0 or >= r_cut: no switching; else 0 < r_switch < r_cut */
+    int32_t shift;           /* 1: u0 = u_LJ(r_cut) */
+    int32_t reserved;        /* 0 */
+} gamd_classical_params;
+enum { GAMD_CLASSICAL_ROW = 9 };   /* doubles per box and row: E, W, pairs, the five sums in the order above, atoms left out */
+/* p: HOST.  Takes the parameters; with interval > 0 allocates and clears the rows (drains nothing: call it between runs, after
+ * gamd_sync_status).  -22 for a negative interval or max_samples, sigma or r_cut not positive, a non-finite epsilon, a negative
+ * r_switch, a GAMD_KIND_WATER handle, more than 65535 boxes, or while a run is pending; -12 when an allocation fails. */
+int32_t gamd_classical_configure(gamd_handle* h, const gamd_classical_params* p);
+/* Step count g = 0, rows cleared; parameters and configuration stay. */
+int32_t gamd_classical_reset(gamd_handle* h);
+/* Synchronises `stream` once (it does NOT resume a frozen run: call gamd_sync_status first) and copies to HOST arrays, any of
+ * which may be NULL: steps int64 [max_rows], rows double [max_rows][n_boxes][GAMD_CLASSICAL_ROW], f_cl double [n_boxes * n_atoms][3]
+ * (the classical forces of the last sample or gamd_classical_eval call; f_cl_elems = room in elements, fewer than 3 n is -22;
+ * left untouched when nothing was evaluated yet).  *n_rows = rows in the log (at most max_rows are written), *dropped = samples
+ * that found the log full. */
+int32_t gamd_classical_read(gamd_handle* h, void* stream, int64_t* steps, double* rows, int64_t max_rows, int64_t* n_rows,
+                            int64_t* dropped, double* f_cl, int64_t f_cl_elems);
+/* The same kernels on given positions, outside any run, with the parameters of the last gamd_classical_configure (interval 0
+ * will do): pos_dev float [n_boxes * n_atoms][3] DEVICE (any periodic image), box HOST [n_boxes][3], length_per_nm (0 = 10,
+ * Angstrom), f_out_dev double [n_boxes * n_atoms][3] DEVICE (kJ/mol/nm; may be NULL), energy / virial / pairs HOST double
+ * [n_boxes] (any may be NULL).  Enqueued on `stream`, which is synchronised once.  -22 before gamd_classical_configure, while a
+ * run is pending, or when 2 * r_cut exceeds a box edge. */
+int32_t gamd_classical_eval(gamd_handle* h, const float* pos_dev, const float* box, float length_per_nm, double* f_out_dev,
+                            double* energy, double* virial, double* pairs, void* stream);
+
 /* Event-timed replay of one force evaluation: per-kernel milliseconds of the last gamd_profile call.
  * names: newline-separated kernel labels; ms: one float per label.  For bench.py's roofline block. */
 int32_t gamd_profile(gamd_handle* h, const float* pos_dev, const uint8_t* species_dev, const float* box,
