@@ -60,7 +60,14 @@ class GamdClassicalParams(C.Structure):
                 ("r_cut", C.c_double), ("r_switch", C.c_double), ("shift", C.c_int32), ("reserved", C.c_int32)]
 
 
+class GamdWaterParams(C.Structure):
+    _fields_ = [("interval", C.c_int64), ("max_samples", C.c_int64), ("q_h", C.c_double), ("sigma_o", C.c_double),
+                ("epsilon_o", C.c_double), ("r_cut", C.c_double), ("r_switch", C.c_double), ("shift", C.c_int32),
+                ("reserved", C.c_int32), ("alpha", C.c_double), ("k_cut", C.c_double), ("coulomb_const", C.c_double)]
+
+
 CLASSICAL_ROW = 9                                           # GAMD_CLASSICAL_ROW: doubles per box and row of gamd_classical_read
+WATER_ROW = 12                                              # GAMD_WATER_ROW: doubles per box and row of gamd_water_read
 TRAJ_FIELDS = {"x": 1, "v": 2, "f": 4, "image": 8}          # GAMD_TRAJ_*
 
 
@@ -103,6 +110,10 @@ SYMBOLS = {
     "gamd_classical_reset": (_i32, [_vp]),
     "gamd_classical_read": (_i32, [_vp, _vp, _vp, _vp, _i64, C.POINTER(_i64), C.POINTER(_i64), _vp, _i64]),
     "gamd_classical_eval": (_i32, [_vp, _vp, C.POINTER(C.c_float), C.c_float, _vp, _vp, _vp, _vp, _vp]),
+    "gamd_water_configure": (_i32, [_vp, C.POINTER(GamdWaterParams)]),
+    "gamd_water_reset": (_i32, [_vp]),
+    "gamd_water_read": (_i32, [_vp, _vp, _vp, _vp, _i64, C.POINTER(_i64), C.POINTER(_i64), _vp, _i64]),
+    "gamd_water_eval": (_i32, [_vp, _vp, _vp, C.POINTER(C.c_float), C.c_float, _vp, _vp, _vp]),
     "gamd_profile": (_i32, [_vp, _vp, _vp, C.POINTER(C.c_float), _vp, _vp, C.c_char_p, C.c_size_t,
                             C.POINTER(C.c_float), _i32, C.POINTER(_i32)]),
     "gamd_timing_enable": (_i32, [_vp, _i32]),

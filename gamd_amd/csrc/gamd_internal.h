@@ -600,3 +600,52 @@ struct ClassicalArgs {
     long long g;               // completed MD steps at this sample
 };
 int launch_classical(const ClassicalArgs& a, hipStream_t st);
+
+// ---- water classical potential (water_classical.hip) ------------------------------------------------
+// One sample of an enqueued MD run (gamd_water_configure) or one gamd_water_eval call: 3-site water in the caller's order
+// O,H,H (molecule = index / 3, O = species != 0, q_O = -2 q_H), O-O Lennard-Jones as in classical.hip plus a plain Ewald sum
+// (real space with the same-molecule exclusion, reciprocal space over the handle's k-vector list, self term), all in double
+// (DESIGN.md section 4.10).  Rows, steps and the resume rule are those of ClassicalArgs: plain stores only.
+// (No kernel uses a value it read from memory as an address: the checked build has nothing to range-check here.)
+enum { WATER_PART = 6,         // per atom and pair slice: Fx, Fy, Fz (per length unit), u_LJ, u_real + u_excl, pairs of the atom's row
+       WATER_ACC = 11,         // per box and block: sum u_LJ, sum u_coul, sum pairs, the five sums, atoms left out, sum z, sum z^2
+       WATER_ROW = 12 };       // per box: U_LJ, U_real + U_excl, U_recip, U_self, pairs, the five sums, atoms left out, sum q
+struct WaterArgs {
+    int n;                     // atoms of all boxes
+    BoxRef bx;
+    const int* devflags;       // DEVFLAG_FROZEN set: every kernel returns at once
+    float box[3];              // n_boxes <= 1 and box_edges == null
+    const float* box_edges;    // device [n_boxes][3] (gamd_water_eval), or null: box / bx.boxes of the run
+    const float* x;            // [n][3] positions, length unit, any periodic image
+    const float* f;            // [n][3] kJ/mol/nm to compare f_cl with, or null
+    const uint8_t* species;    // [n] O != 0
+    double q_h, q_o;           // e; q_o = -2 q_h
+    double sig2, eps4;         // O-O Lennard-Jones: sigma^2, 4 epsilon (24 epsilon is 6 * eps4 on the device, the same double)
+    double rc2, u0;            // r_cut^2, u_LJ(r_cut) or 0
+    double rs, inv_w;          // r_switch and 1 / (r_cut - r_switch); rs < 0: no switching
+    double coul;               // C = coulomb_const * len: kJ/mol * length unit / e^2
+    double alpha, two_a_rpi;   // alpha and 2 alpha / sqrt(pi)
+    double kc2, inv_4a2;       // k_cut^2 and 1 / (4 alpha^2)
+    double two_pi;             // 2 pi
+    double coul4pi, coul8pi;   // 4 pi C and 8 pi C
+    double self_c;             // C alpha / sqrt(pi)
+    double len;                // length units per nm
+    int tiles, slices, chunk;  // 256-atom row tiles per box; J slices per row; atoms per slice
+    int blocks;                // workgroups per box of the per-atom pass (fixed per handle: the summation tree never changes)
+    int n_k, kslices, kchunk;  // k-vectors of the list; k slices per atom; k-vectors per slice
+    int kblocks;               // (n_k + 255) / 256: workgroups per box of k_water_sk
+    int rho_blocks;            // workgroups per box and 64 k-vectors of k_water_rho (fixed per handle)
+    const int* kvec;           // [n_k][3] integer triples n
+    double* part;              // [n_boxes][slices][n_per_box][WATER_PART]
+    double* rho_partial;       // [n_boxes][rho_blocks][n_k][2] (re, im)
+    double* sk;                // [n_boxes][n_k][3]: Re S, Im S, A
+    double* ublk;              // [n_boxes][kblocks]: block sums of A |S|^2
+    double* rpart;             // [n_boxes][kslices][n_per_box][3]: sum_k A (Re S sin + Im S cos) n per component
+    double* f_cl;              // [n][3] kJ/mol/nm
+    double* blk;               // [n_boxes][blocks][WATER_ACC]
+    double* rows;              // [...][n_boxes][WATER_ROW]
+    long long* steps;          // [...] or null
+    long long slot;            // row of this sample
+    long long g;               // completed MD steps at this sample
+};
+int launch_water_classical(const WaterArgs& a, hipStream_t st);

@@ -1,7 +1,8 @@
 // observe.hip — host side of the run observers, the consumers at the sample point of an enqueued gamd_md_run / gamd_md_run_nhc
 // (behind the second half of every interval-th step): the run reporter (gamd_report_*, report.hip), the run recorder
-// (gamd_traj_*, traj.hip), the structure sampler (gamd_struct_*, structure.hip) and the classical observer (gamd_classical_*,
-// classical.hip; gamd_classical_eval runs its kernels outside a run).  Each is its configuration plus a SampleClock,
+// (gamd_traj_*, traj.hip), the structure sampler (gamd_struct_*, structure.hip), the classical observer (gamd_classical_*,
+// classical.hip; gamd_classical_eval runs its kernels outside a run) and the water classical observer (gamd_water_*,
+// water_classical.hip; gamd_water_eval).  Each is its configuration plus a SampleClock,
 // a buffer table and an entry in observer_list(), through which the MD driver of gamd_api.hip sees it (observers_*, gamd_host.h).
 #include "gamd_host.h"
 
@@ -87,9 +88,26 @@ struct Classical {
     DevBuf eval_rows, eval_box;        // gamd_classical_eval: its row and its box edges
 };
 
+// water classical observer: the potential's parameters (taken by every gamd_water_configure, armed or not), the k-vector list
+// in force (built for the longest edge of the boxes of the last configure, run or gamd_water_eval), the log rows and the work
+// buffers of one evaluation
+struct WaterClassical {
+    SampleClock clock;
+    long long max_samples = 0;
+    bool params_set = false;           // gamd_water_eval needs parameters, not an armed observer
+    bool evaluated = false;            // f_cl holds the forces of a sample or a gamd_water_eval call
+    double q_h = 0.0, sigma = 0.0, epsilon = 0.0, r_cut = 0.0, r_switch = 0.0, alpha = 0.0, k_cut = 0.0, coulomb = 0.0;
+    int shift = 0;
+    int n2max = -1, n_k = 0;           // the list in force: every n with 0 < |n|^2 <= n2max (-1: none yet)
+    DevBuf steps, rows;                // log
+    DevBuf part, rpart, f_cl, blk;     // one evaluation: per atom
+    DevBuf kvec, rho_partial, sk, ublk;// ... per k-vector
+    DevBuf eval_rows, eval_box;        // gamd_water_eval: its row and its box edges
+};
+
 }  // namespace
 
-struct Observers { Reporter rep; Recorder rec; StructSampler ss; Classical cl; };
+struct Observers { Reporter rep; Recorder rec; StructSampler ss; Classical cl; WaterClassical wc; };
 
 namespace {
 
@@ -147,6 +165,25 @@ ObsBufs classical_bufs(gamd_handle* h) {
             {&cl.f_cl, sizeof(double) * 3 * n, false},
             {&cl.blk, sizeof(double) * CLASSICAL_ROW * nb * (size_t)classical_blocks(h), false},
             {&cl.eval_rows, sizeof(double) * CLASSICAL_ROW * nb, false}, {&cl.eval_box, sizeof(float) * 3 * nb, false}};
+}
+
+// water classical observer: the pair pass has the classical observer's tiles, slices and blocks; the k slices of the reciprocal
+// force pass are as many as the pair slices, the blocks of the rho(k) pass the structure sampler's
+int water_kchunk(const gamd_handle* h, int n_k) { const int S = classical_slices(h); return std::max(1, (n_k + S - 1) / S); }
+
+ObsBufs water_bufs(gamd_handle* h) {
+    WaterClassical& wc = h->obs->wc;
+    const size_t nb = (size_t)h->n_boxes, rows = (size_t)wc.max_samples, n = (size_t)h->n, K = (size_t)wc.n_k;
+    return {{&wc.steps, sizeof(long long) * rows, true}, {&wc.rows, sizeof(double) * WATER_ROW * nb * rows, true},
+            {&wc.part, sizeof(double) * WATER_PART * n * (size_t)classical_slices(h), false},
+            {&wc.rpart, sizeof(double) * 3 * n * (size_t)classical_slices(h), false},
+            {&wc.f_cl, sizeof(double) * 3 * n, false},
+            {&wc.blk, sizeof(double) * WATER_ACC * nb * (size_t)classical_blocks(h), false},
+            {&wc.kvec, sizeof(int) * 3 * K, false},                 // uploaded by water_klist_apply
+            {&wc.rho_partial, sizeof(double) * 2 * nb * (size_t)struct_rho_blocks(h) * K, false},
+            {&wc.sk, sizeof(double) * 3 * nb * K, false},
+            {&wc.ublk, sizeof(double) * nb * ((K + 255) / 256), false},
+            {&wc.eval_rows, sizeof(double) * WATER_ROW * nb, false}, {&wc.eval_box, sizeof(float) * 3 * nb, false}};
 }
 
 // what every observer's argument block starts with
@@ -306,6 +343,119 @@ int enqueue_classical_sample(gamd_handle* h, long long s) {
     return 0;
 }
 
+// one of each +-n with 0 < |n|^2 <= n2max, sorted by (|n|^2, nx, ny, nz) (defined below)
+std::vector<int> struct_kvectors(int n2max);
+
+enum { WATER_MAX_K = 131072 };
+
+// water classical observer: the integer triples the boxes `box` ([n_boxes][3]) need under k_cut — every n with 0 < |n|^2 <=
+// (k_cut Lmax / 2 pi)^2, Lmax the longest edge (a box gives the vectors beyond its own k_cut the weight zero on the device;
+// the bound is taken a few ulp up so that no vector a box's own test admits is missing).  Host only.
+int water_klist(double k_cut, const float* box, int n_boxes, int* n2max, std::vector<int>* kv) {
+    double lmax = 0.0;
+    for (int k = 0; k < 3 * n_boxes; ++k) lmax = std::max(lmax, (double)box[k]);
+    const double m = k_cut * lmax / 6.283185307179586;
+    const double m2 = m * m * (1.0 + 1e-12);
+    // K grows as (2 pi / 3) n2max^1.5: 131 072 is passed near n2max = 1576
+    if (!(m2 < 1700.0))
+        return fail(-22, "water classical potential: k_cut = %g gives more than %d k-vectors in a box with an edge of %g", k_cut, (int)WATER_MAX_K, lmax);
+    const int n2 = (int)std::floor(m2);
+    if (n2 == *n2max) return 0;                             // the list in force
+    std::vector<int> v = n2 > 0 ? struct_kvectors(n2) : std::vector<int>();
+    if (v.empty()) return fail(-22, "water classical potential: k_cut = %g admits no k-vector in a box with an edge of %g", k_cut, lmax);
+    if (v.size() / 3 > (size_t)WATER_MAX_K)
+        return fail(-22, "water classical potential: k_cut = %g gives %zu k-vectors in a box with an edge of %g, more than %d", k_cut,
+                    v.size() / 3, lmax, (int)WATER_MAX_K);
+    *n2max = n2; kv->swap(v);
+    return 0;
+}
+
+// ... and the list put in force: the k-dependent work buffers sized for it, the triples uploaded (on the handle's own stream,
+// landed on return).  No run is pending.
+int water_klist_apply(gamd_handle* h, int n2max, const std::vector<int>& kv) {
+    WaterClassical& wc = h->obs->wc;
+    if (n2max == wc.n2max) return 0;
+    DeviceGuard guard(h->dev);
+    InitStream init(h->init_stream);
+    wc.n2max = -1;                                          // none, should anything below fail
+    wc.n_k = (int)(kv.size() / 3);
+    for (DevBuf* b : {&wc.kvec, &wc.rho_partial, &wc.sk, &wc.ublk}) b->release();
+    for (const ObsBuf& b : water_bufs(h))
+        if (!b.cleared && b.buf->ensure(b.want, true)) return fail(-12, "water classical potential allocation failed");
+    HIP_TRY(init_upload(wc.kvec.p, kv.data(), sizeof(int) * kv.size()));
+    wc.n2max = n2max;
+    return 0;
+}
+
+// the water classical observer's argument block but for positions, species, forces, box and output row
+WaterArgs water_args(gamd_handle* h, double len) {
+    const WaterClassical& wc = h->obs->wc;
+    WaterArgs a{};
+    sample_args(h, a);
+    const double pi = 3.141592653589793;
+    a.q_h = wc.q_h; a.q_o = -2.0 * wc.q_h;
+    a.sig2 = wc.sigma * wc.sigma;
+    a.eps4 = 4.0 * wc.epsilon;
+    a.rc2 = wc.r_cut * wc.r_cut;
+    a.u0 = 0.0;
+    if (wc.shift) {                                         // u_LJ(r_cut) by the kernel's own operations
+        const double s2 = a.sig2 * (1.0 / a.rc2), s6 = (s2 * s2) * s2;
+        a.u0 = a.eps4 * (s6 * s6 - s6);
+    }
+    const bool sw = wc.r_switch > 0.0 && wc.r_switch < wc.r_cut;
+    a.rs = sw ? wc.r_switch : -1.0;
+    a.inv_w = sw ? 1.0 / (wc.r_cut - wc.r_switch) : 0.0;
+    a.coul = wc.coulomb * len;
+    a.alpha = wc.alpha; a.two_a_rpi = (2.0 * wc.alpha) / std::sqrt(pi);
+    a.kc2 = wc.k_cut * wc.k_cut; a.inv_4a2 = 1.0 / (4.0 * (wc.alpha * wc.alpha));
+    a.two_pi = 2.0 * pi;
+    a.coul4pi = (4.0 * pi) * a.coul; a.coul8pi = (8.0 * pi) * a.coul;
+    a.self_c = (a.coul * wc.alpha) / std::sqrt(pi);
+    a.len = len;
+    a.tiles = classical_tiles(h); a.slices = classical_slices(h); a.chunk = classical_chunk(h); a.blocks = classical_blocks(h);
+    a.n_k = wc.n_k; a.kslices = classical_slices(h); a.kchunk = water_kchunk(h, wc.n_k); a.kblocks = (wc.n_k + 255) / 256;
+    a.rho_blocks = struct_rho_blocks(h);
+    a.kvec = wc.kvec.as<int>();
+    a.part = wc.part.as<double>(); a.rho_partial = wc.rho_partial.as<double>(); a.sk = wc.sk.as<double>(); a.ublk = wc.ublk.as<double>();
+    a.rpart = wc.rpart.as<double>(); a.f_cl = wc.f_cl.as<double>(); a.blk = wc.blk.as<double>();
+    return a;
+}
+
+// the water classical observer's sample of step s of the pending run, behind its second half: f holds the network forces at x
+int enqueue_water_sample(gamd_handle* h, long long s) {
+    const MdPending& p = h->pending;
+    WaterClassical& wc = h->obs->wc;
+    if (wc.clock.ordinal(s) >= wc.max_samples) return 0;    // the log is full: counted as dropped by gamd_water_read
+    WaterArgs a = water_args(h, pending_particles(p).len);
+    for (int d = 0; d < 3; ++d) a.box[d] = h->box[d];
+    a.x = p.x; a.f = p.f; a.species = p.species;
+    a.rows = wc.rows.as<double>(); a.steps = wc.steps.as<long long>();
+    a.g = wc.clock.completed(s);
+    a.slot = wc.clock.ordinal(s);
+    if (int r = launch_water_classical(a, p.st)) return fail(-1, "water classical observer launch failed (%d)", r);
+    wc.evaluated = true;
+    return 0;
+}
+
+// water classical observer: what a run or gamd_water_eval must bring — species, 2 r_cut <= every edge, a k-vector list of at
+// most 131 072 triples for these boxes (built and uploaded here when the boxes need another one than the list in force)
+int water_check_box(gamd_handle* h, const float* box, const uint8_t* species_dev) {
+    WaterClassical& wc = h->obs->wc;
+    if (!species_dev) return fail(-22, "water classical potential: the charges need species (O = 1, H = 0, atoms ordered O,H,H)");
+    for (int k = 0; k < 3 * h->n_boxes; ++k)
+        if (!(2.0 * wc.r_cut <= (double)box[k]))
+            return fail(-22, "water classical potential: r_cut = %g exceeds half of box[%d][%d] = %g (the minimum image is the nearest "
+                             "image only below that)", wc.r_cut, k / 3, k % 3, (double)box[k]);
+    int n2max = wc.n2max;
+    std::vector<int> kv;
+    if (int r = water_klist(wc.k_cut, box, h->n_boxes, &n2max, &kv)) return r;
+    return water_klist_apply(h, n2max, kv);
+}
+int water_check_run(gamd_handle* h, const float* box, const uint8_t* species_dev) {
+    if (h->pending.active) return fail(-22, "an MD run is still enqueued: call gamd_sync_status before the next run of a handle whose water classical observer is on");
+    return water_check_box(h, box, species_dev);
+}
+
 // classical observer: the minimum image is the nearest image only inside the sphere of half the shortest edge
 int classical_check_box(const gamd_handle* h, const float* box) {
     const Classical& cl = h->obs->cl;
@@ -360,13 +510,14 @@ struct Observer {
     void (*begin_run)(gamd_handle*, const float* box, const uint8_t* species_dev);   // what it keeps of a run besides the clock; may be null
     void (*forget)(gamd_handle*);                                                    // ... and how configure / reset drop it; may be null
 };
-enum { OBS_REPORT = 0, OBS_TRAJ = 1, OBS_STRUCT = 2, OBS_CLASSICAL = 3, OBS_COUNT = 4 };
+enum { OBS_REPORT = 0, OBS_TRAJ = 1, OBS_STRUCT = 2, OBS_CLASSICAL = 3, OBS_WATER = 4, OBS_COUNT = 5 };
 std::array<Observer, OBS_COUNT> observer_list(const gamd_handle* h) {
     Observers& o = *h->obs;
     return {{{&o.rep.clock, report_bufs, enqueue_report_sample, nullptr, nullptr, nullptr},
              {&o.rec.clock, traj_bufs, enqueue_traj_sample, traj_check_run, traj_begin_run, traj_forget},
              {&o.ss.clock, struct_bufs, enqueue_struct_sample, struct_check_run, nullptr, nullptr},
-             {&o.cl.clock, classical_bufs, enqueue_classical_sample, classical_check_run, nullptr, nullptr}}};
+             {&o.cl.clock, classical_bufs, enqueue_classical_sample, classical_check_run, nullptr, nullptr},
+             {&o.wc.clock, water_bufs, enqueue_water_sample, water_check_run, nullptr, nullptr}}};
 }
 
 // clear an observer's step count and what it took (configuration and scratch stay): on the init stream, landed on return
@@ -472,6 +623,10 @@ static_assert(sizeof(gamd_classical_params) == 56 && offsetof(gamd_classical_par
               offsetof(gamd_classical_params, shift) == 48,
               "gamd_classical_params layout is part of the C ABI (gamd_amd/_lib.py mirrors it)");
 static_assert(GAMD_CLASSICAL_ROW == CLASSICAL_ROW, "the row of gamd_classical_read is the kernels' row");
+static_assert(sizeof(gamd_water_params) == 88 && offsetof(gamd_water_params, q_h) == 16 && offsetof(gamd_water_params, r_switch) == 48 &&
+              offsetof(gamd_water_params, shift) == 56 && offsetof(gamd_water_params, alpha) == 64 && offsetof(gamd_water_params, coulomb_const) == 80,
+              "gamd_water_params layout is part of the C ABI (gamd_amd/_lib.py mirrors it)");
+static_assert(GAMD_WATER_ROW == WATER_ROW, "the row of gamd_water_read is the kernels' row");
 
 extern "C" {
 
@@ -660,8 +815,8 @@ int32_t gamd_classical_configure(gamd_handle* h, const gamd_classical_params* p)
     if (!(p->r_switch >= 0.0)) return fail(-22, "r_switch = %g is negative", p->r_switch);
     if (!h) return fail(-22, "null handle");
     if (h->cfg.kind != GAMD_KIND_LJ)
-        return fail(-22, "classical potential: a GAMD_KIND_WATER handle needs electrostatics, which are not implemented (Lennard-Jones, "
-                         "GAMD_KIND_LJ handles only)");
+        return fail(-22, "classical potential: a GAMD_KIND_WATER handle needs electrostatics, which this Lennard-Jones potential does "
+                         "not have (GAMD_KIND_LJ handles only; gamd_water_configure evaluates 3-site water)");
     if (h->n_boxes > 65535) return fail(-22, "the classical observer needs n_boxes <= 65535");
     {
         const long long T = (h->n_per_box + 255) / 256;
@@ -737,6 +892,107 @@ int32_t gamd_classical_eval(gamd_handle* h, const float* pos_dev, const float* b
         if (virial) virial[b] = row[CLASSICAL_ROW * b + 1];
         if (pairs) pairs[b] = row[CLASSICAL_ROW * b + 2];
     }
+    return 0;
+}
+
+int32_t gamd_water_configure(gamd_handle* h, const gamd_water_params* p) {
+    if (!p) return fail(-22, "null argument");
+    if (p->interval < 0) return fail(-22, "interval = %lld is negative", (long long)p->interval);
+    if (p->max_samples < 0 || p->max_samples > (1ll << 24)) return fail(-22, "max_samples = %lld outside [0, 2^24]", (long long)p->max_samples);
+    if (!std::isfinite(p->q_h)) return fail(-22, "q_h = %g is not finite", p->q_h);
+    if (!(p->sigma_o > 0.0) || !std::isfinite(p->sigma_o)) return fail(-22, "sigma_o = %g is not positive", p->sigma_o);
+    if (!std::isfinite(p->epsilon_o)) return fail(-22, "epsilon_o = %g is not finite", p->epsilon_o);
+    if (!(p->r_cut > 0.0) || !std::isfinite(p->r_cut)) return fail(-22, "r_cut = %g is not positive", p->r_cut);
+    if (!(p->r_switch >= 0.0)) return fail(-22, "r_switch = %g is negative", p->r_switch);
+    if (!(p->alpha > 0.0) || !std::isfinite(p->alpha)) return fail(-22, "alpha = %g is not positive", p->alpha);
+    if (!(p->k_cut > 0.0) || !std::isfinite(p->k_cut)) return fail(-22, "k_cut = %g is not positive", p->k_cut);
+    if (!std::isfinite(p->coulomb_const)) return fail(-22, "coulomb_const = %g is not finite", p->coulomb_const);
+    if (!h) return fail(-22, "null handle");
+    if (h->cfg.kind != GAMD_KIND_WATER)
+        return fail(-22, "water classical potential: a GAMD_KIND_LJ handle has no molecules and no charges (GAMD_KIND_WATER handles only; "
+                         "gamd_classical_configure evaluates Lennard-Jones)");
+    if (h->n_per_box % 3) return fail(-22, "water classical potential: n_atoms = %d per box is not a multiple of 3 (atoms ordered O,H,H)", h->n_per_box);
+    if (h->n_boxes > 65535) return fail(-22, "the water classical observer needs n_boxes <= 65535");
+    {
+        const long long T = (h->n_per_box + 255) / 256;
+        if (T * (T + 1) / 2 > 0xffffffll) return fail(-22, "the water classical observer needs at most 5791 tiles of 256 atoms per box");
+    }
+    if (h->pending.active) return fail(-22, "an MD run is still enqueued: call gamd_sync_status before gamd_water_configure");
+    WaterClassical& wc = h->obs->wc;
+    // the k-vector list of the handle's current boxes, in front of anything that is taken: a refused block changes nothing
+    int n2max = wc.n2max;
+    std::vector<int> kv;
+    const bool have_box = h->boxes_host.size() == 3 * (size_t)h->n_boxes;
+    if (have_box)
+        if (int r = water_klist(p->k_cut, h->boxes_host.data(), h->n_boxes, &n2max, &kv)) return r;
+    wc.q_h = p->q_h; wc.sigma = p->sigma_o; wc.epsilon = p->epsilon_o; wc.r_cut = p->r_cut; wc.r_switch = p->r_switch;
+    wc.shift = p->shift ? 1 : 0; wc.alpha = p->alpha; wc.k_cut = p->k_cut; wc.coulomb = p->coulomb_const;
+    wc.params_set = true;
+    if (have_box)
+        if (int r = water_klist_apply(h, n2max, kv)) return r;
+    return observer_configure(h, OBS_WATER, p->interval, "gamd_water_configure", [&]() {
+        wc.max_samples = p->max_samples > 0 ? p->max_samples : 4096;
+        return bufs_resize(water_bufs(h)) ? fail(-12, "water classical observer allocation failed") : 0;
+    });
+}
+
+int32_t gamd_water_reset(gamd_handle* h) { return observer_reset(h, OBS_WATER, "gamd_water_reset"); }
+
+int32_t gamd_water_read(gamd_handle* h, void* stream, int64_t* steps, double* rows, int64_t max_rows, int64_t* n_rows,
+                        int64_t* dropped, double* f_cl, int64_t f_cl_elems) {
+    if (!h) return fail(-22, "null handle");
+    if (max_rows < 0) return fail(-22, "max_rows is negative");
+    const WaterClassical& wc = h->obs->wc;
+    DeviceGuard guard(h->dev);
+    hipStream_t st = (hipStream_t)stream;
+    const long long nb = h->n_boxes;
+    const long long taken = wc.clock.taken(wc.steps.p != nullptr);
+    const long long kept = std::min<long long>(taken, wc.max_samples);
+    const long long n_copy = std::min<long long>(kept, max_rows);
+    if (f_cl && f_cl_elems < 3ll * h->n) return fail(-22, "f_cl has room for %lld elements, the forces have %lld", (long long)f_cl_elems, 3ll * h->n);
+    if (n_copy > 0 && steps) HIP_TRY(hipMemcpyAsync(steps, wc.steps.p, sizeof(int64_t) * (size_t)n_copy, hipMemcpyDeviceToHost, st));
+    if (n_copy > 0 && rows) HIP_TRY(hipMemcpyAsync(rows, wc.rows.p, sizeof(double) * (size_t)(n_copy * nb * WATER_ROW), hipMemcpyDeviceToHost, st));
+    if (f_cl && wc.evaluated && wc.f_cl.p) HIP_TRY(hipMemcpyAsync(f_cl, wc.f_cl.p, sizeof(double) * 3 * (size_t)h->n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (int t = check_traps(h)) return t;
+    if (n_rows) *n_rows = kept;
+    if (dropped) *dropped = taken - kept;
+    return 0;
+}
+
+int32_t gamd_water_eval(gamd_handle* h, const float* pos_dev, const uint8_t* species_dev, const float* box, float length_per_nm,
+                        double* f_out_dev, double* rows, void* stream) {
+    if (!h) return fail(-22, "null handle");
+    if (!pos_dev || !box) return fail(-22, "null argument");
+    WaterClassical& wc = h->obs->wc;
+    if (!wc.params_set) return fail(-22, "gamd_water_eval needs the parameters of a gamd_water_configure call (interval 0 will do)");
+    if (h->pending.active) return fail(-22, "an MD run is still enqueued: call gamd_sync_status before gamd_water_eval");
+    for (int k = 0; k < 3 * h->n_boxes; ++k)
+        if (!(box[k] > 0.f)) return fail(-22, "box[%d][%d] = %g is not positive", k / 3, k % 3, (double)box[k]);
+    if (int r = water_check_box(h, box, species_dev)) return r;
+    DeviceGuard guard(h->dev);
+    hipStream_t st = (hipStream_t)stream;
+    InitStream init(st);
+    for (const ObsBuf& b : water_bufs(h))                   // the work buffers; the log is gamd_water_configure's
+        if (!b.cleared && b.buf->ensure(b.want, true)) return fail(-12, "water classical potential allocation failed");
+    const size_t nb = (size_t)h->n_boxes;
+    HIP_TRY(init_upload(wc.eval_box.p, box, sizeof(float) * 3 * nb));
+    // a frozen handle's kernels return at once: the row would be what the last call left
+    HIP_TRY(hipMemsetAsync(wc.eval_rows.p, 0xff, sizeof(double) * WATER_ROW * nb, st));
+    WaterArgs a = water_args(h, length_per_nm > 0.f ? (double)length_per_nm : 10.0);
+    a.box_edges = wc.eval_box.as<float>();
+    a.x = pos_dev; a.f = nullptr; a.species = species_dev;
+    a.rows = wc.eval_rows.as<double>(); a.steps = nullptr; a.slot = 0; a.g = 0;
+    if (int r = launch_water_classical(a, st)) return fail(-1, "water classical potential launch failed (%d)", r);
+    wc.evaluated = true;
+    if (f_out_dev) HIP_TRY(hipMemcpyAsync(f_out_dev, wc.f_cl.p, sizeof(double) * 3 * (size_t)h->n, hipMemcpyDeviceToDevice, st));
+    std::vector<double> row(WATER_ROW * nb);
+    HIP_TRY(hipMemcpyAsync(row.data(), wc.eval_rows.p, sizeof(double) * row.size(), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (int t = check_traps(h)) return t;
+    for (size_t b = 0; b < nb; ++b)
+        if (std::isnan(row[WATER_ROW * b + 4])) return fail(-1, "gamd_water_eval: the handle is frozen by a neighbour-buffer overflow (call gamd_sync_status)");
+    if (rows) std::memcpy(rows, row.data(), sizeof(double) * row.size());
     return 0;
 }
 

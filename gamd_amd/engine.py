@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import GamdClassicalParams, GamdReportParams, GamdStructParams, GamdTrajParams, GamdConfig, GamdMdParams, GamdNhcParams, TRAJ_FIELDS, check
+from ._lib import GamdClassicalParams, GamdWaterParams, GamdReportParams, GamdStructParams, GamdTrajParams, GamdConfig, GamdMdParams, GamdNhcParams, TRAJ_FIELDS, check
 from .weights import ModelConfig, infer_config, validate_state_dict
 
 ArrayLike = Union[np.ndarray, torch.Tensor]
@@ -342,6 +342,31 @@ class RunClassical:
                 pe, ke = float(self.energy[i, box]), float(report.ke[i, box])
                 row = [str(k * int(g)), str(k * int(g) * float(dt_ps)), str(pe), str(ke), str(pe + ke), str(float(report.temperature[i, box]))]
                 fh.write(separator.join(row) + "\n")
+
+
+COULOMB_KJ_NM = 138.935456                   # 1 / (4 pi eps0) in kJ nm / (mol e^2), as OpenMM's ONE_4PI_EPS0 is remembered (UNVERIFIED)
+
+
+class RunWaterClassical(RunClassical):
+    """What the water classical observer logged (GamdForce.water_classical_read).  Host-only: plain arrays in, plain arrays
+    out.
+
+    steps [S] int64; per sample and box, float64 [S, B], all energies in kJ/mol: u_lj (O-O Lennard-Jones), u_real (real-space
+    Ewald sum of the different-molecule pairs inside r_cut plus the same-molecule erf correction), u_recip, u_self, pairs
+    (different-molecule pairs inside r_cut), the force-error sums and ``excluded`` of RunClassical, and sum_q, the sum of the
+    charges in e: exactly 0.0 unless the species vector is not one O and two H per molecule.  ``energy`` is the sum of the four
+    Coulomb terms plus u_lj, added as ((u_real + u_recip) + u_self) + u_lj.  No virial and no pressure: with rigid
+    molecules the atomic virial is not the pressure.  ``force_errors`` and ``write_state_data`` are RunClassical's."""
+
+    COLUMNS = ("u_lj", "u_real", "u_recip", "u_self", "pairs", "sum_abs", "sum_sq", "sum_cos", "sum_norm_cl", "sum_norm",
+               "excluded", "sum_q")
+
+    def __init__(self, steps, rows, n_atoms: int, dropped: int = 0, forces=None):
+        super().__init__(steps, rows, n_atoms, dropped, forces)
+        self.energy = ((self.u_real + self.u_recip) + self.u_self) + self.u_lj
+
+    def pressure(self, ke, volumes):
+        raise NotImplementedError("the water classical observer logs no virial: with rigid molecules the atomic virial is not the pressure")
 
 
 class GamdForce:
@@ -930,6 +955,88 @@ class GamdForce:
         check(self._lib.gamd_classical_eval(self._h, C.c_void_p(p.data_ptr()), self._box_arg(box), float(length_per_nm),
                                             C.c_void_p(out.data_ptr()), vp(e), vp(w), vp(c), self._stream()), "gamd_classical_eval")
         return out, e, w, c
+
+    # -- water classical observer (3-site water: O-O Lennard-Jones plus an Ewald sum, on sampled frames; force labels) ------
+    def water_classical_configure(self, interval: int, max_samples: int = 0, q_h: float = 0.417, sigma_o: Optional[float] = None,
+                                  epsilon_o: float = 0.635968, r_cut: Optional[float] = None, r_switch: float = 0.0,
+                                  shift: bool = False, ewald_tol: float = 1e-10, alpha: Optional[float] = None,
+                                  k_cut: Optional[float] = None, coulomb_const: float = COULOMB_KJ_NM,
+                                  length_per_nm: float = 0.0) -> None:
+        """While configured, every ``interval``-th completed step of md_run / md_run_nhc (counted across calls, by a counter
+        of its own) evaluates the classical potential of 3-site water in double on the device — O-O Lennard-Jones plus
+        point charges q_H and q_O = -2 q_H by a plain Ewald sum (real space inside ``r_cut``, same-molecule exclusion,
+        reciprocal space out to ``k_cut``, self term; no PME grid) — and logs its terms, the pair count, the charge sum and
+        the error sums of the run's (network) forces against the classical forces; ``water_classical_read`` fetches the
+        rows.  ``interval`` = 0 switches the observer off but still takes the parameters, which ``water_classical_forces``
+        uses.  Water models only, atoms ordered O,H,H, runs with ``species``.  O(N^2) + O(N K) per sample and box.
+
+        ``sigma_o``, ``r_cut``, ``r_switch`` are in the engine's length unit (``alpha``, ``k_cut`` in its reciprocal),
+        ``epsilon_o`` in kJ/mol, ``q_h`` in e, ``coulomb_const`` in kJ nm / (mol e^2).  ``length_per_nm`` (0 or 10 =
+        Angstrom) only scales the DEFAULTS of ``sigma_o`` (3.15075 Angstrom) and ``r_cut`` (9.5 Angstrom) into the engine's unit.
+        Unless given, alpha = sqrt(-ln ewald_tol) / r_cut and k_cut = 2 alpha sqrt(-ln ewald_tol): both truncated tails
+        are then about ``ewald_tol`` of a term.  ``r_switch`` and ``shift`` act on the Lennard-Jones term only (default:
+        neither).  The defaults (q_H = 0.417 e, sigma_O = 3.15075 Angstrom, epsilon_O = 0.635968 kJ/mol, 138.935456 kJ nm /
+        (mol e^2), cutoff 9.5 Angstrom) are meant to be those of OpenMM's ``tip3p.xml`` and of the drivers'
+        ``WaterBox(cutoff=9.5 Angstrom)``, but they were written down from memory and are UNVERIFIED: neither OpenMM nor
+        openmmtools was available to compare against.  The sum is the limit OpenMM's PME approximates, not PME; no
+        long-range dispersion correction, no TIP4P M-site (a TIP4P handle evaluates the 3-site parameters it is given), no
+        virial.  Check the parameters against your OpenMM system before comparing energies."""
+        unit = float(np.float32(length_per_nm)) / 10.0 if length_per_nm else 1.0     # the fp32 value the library holds
+        sigma_o = 3.15075 * unit if sigma_o is None else float(sigma_o)
+        r_cut = 9.5 * unit if r_cut is None else float(r_cut)
+        if alpha is None or k_cut is None:
+            if not 0.0 < float(ewald_tol) < 1.0:
+                raise ValueError(f"ewald_tol = {ewald_tol} must lie in (0, 1)")
+            root = float(np.sqrt(-np.log(float(ewald_tol))))
+            alpha = root / r_cut if alpha is None else float(alpha)
+            k_cut = 2.0 * alpha * root if k_cut is None else float(k_cut)
+        p = GamdWaterParams(int(interval), int(max_samples), float(q_h), sigma_o, float(epsilon_o), r_cut, float(r_switch),
+                            int(bool(shift)), 0, float(alpha), float(k_cut), float(coulomb_const))
+        check(self._lib.gamd_water_configure(self._h, C.byref(p)), "gamd_water_configure")
+        self._water_set = True
+
+    def water_classical_reset(self) -> None:
+        """Step count and rows back to zero; parameters and configuration stay."""
+        check(self._lib.gamd_water_reset(self._h), "gamd_water_reset")
+
+    def water_classical_read(self, forces: bool = False) -> "RunWaterClassical":
+        """Synchronise and fetch what the water classical observer has logged since it was configured or reset; ``forces``:
+        also the classical forces of the last sample."""
+        n_rows, dropped = C.c_int64(), C.c_int64()
+        rd = self._lib.gamd_water_read
+        check(rd(self._h, self._stream(), None, None, 0, C.byref(n_rows), C.byref(dropped), None, 0), "gamd_water_read")
+        rows = n_rows.value
+        steps = np.zeros(rows, dtype=np.int64)
+        data = np.zeros((rows, self.n_boxes, _lib.WATER_ROW), dtype=np.float64)
+        fcl = np.full((self.n_total, 3), np.nan, dtype=np.float64) if forces else None
+        vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        check(rd(self._h, self._stream(), vp(steps), vp(data), rows, C.byref(n_rows), C.byref(dropped), vp(fcl),
+                 0 if fcl is None else fcl.size), "gamd_water_read")
+        return RunWaterClassical(steps, data, self.n, dropped.value, fcl)
+
+    def water_classical_forces(self, pos: ArrayLike, species, box=None, length_per_nm: float = 0.0):
+        """The water classical potential of the last ``water_classical_configure`` (with the defaults and interval 0 when
+        there was none) on given positions, outside any run: (forces float64 [N, 3] on the device in kJ/mol/nm, a
+        RunWaterClassical of one row with the terms per box; its force-error sums are 0).  ``pos`` [N, 3] in any periodic
+        image, fp32 as the library reads it; ``species`` [N] (or one box's), O != 0; ``box`` as in ``forward``;
+        ``length_per_nm`` the length unit (0 or 10 = Angstrom).  Synchronises once."""
+        if not getattr(self, "_water_set", False):
+            self.water_classical_configure(0, length_per_nm=length_per_nm)
+        p = self._dev_pos(pos)
+        flags = None
+        if species is not None:
+            s = torch.as_tensor(species).reshape(-1).to(device=self.device)
+            if s.numel() == self.n and self.n_boxes > 1:
+                s = s.repeat(self.n_boxes)
+            if s.numel() != self.n_total:
+                raise ValueError("species must have one entry per atom")
+            flags = (s != 0).to(torch.uint8).contiguous()
+        out = torch.empty((self.n_total, 3), dtype=torch.float64, device=self.device)
+        row = np.zeros((1, self.n_boxes, _lib.WATER_ROW), dtype=np.float64)
+        check(self._lib.gamd_water_eval(self._h, C.c_void_p(p.data_ptr()), C.c_void_p(flags.data_ptr()) if flags is not None else None,
+                                        self._box_arg(box), float(length_per_nm), C.c_void_p(out.data_ptr()),
+                                        row.ctypes.data_as(C.c_void_p), self._stream()), "gamd_water_eval")
+        return out, RunWaterClassical([0], row, self.n)
 
     def sync_status(self) -> int:
         """0, or 1 when an enqueued MD run overflowed a neighbour buffer, froze on the device and was resumed."""

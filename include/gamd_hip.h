@@ -435,7 +435,8 @@ int32_t gamd_struct_read(gamd_handle* h, void* stream, uint64_t* counts, int64_t
  * LJ/test_script/test_langevin.py:102-106; cosine, MAE, RMSE, relative MAE of lj.ipynb cell 3).  This observer evaluates the
  * switched, shifted Lennard-Jones potential ON THE DEVICE while gamd_md_run / gamd_md_run_nhc are enqueued, and
  * gamd_classical_eval evaluates it on given positions outside a run.  GAMD_KIND_LJ handles only, one pair class; no long-range
- * dispersion correction, no electrostatics (a GAMD_KIND_WATER handle is refused with -22).
+ * dispersion correction, no electrostatics (a GAMD_KIND_WATER handle is refused with -22; gamd_water_configure below evaluates
+ * 3-site water).
  * The potential, for the minimum-image distance r of a pair (d = x_i - x_j, per component d - L rint(d / L) in double, L the
  * fp32 box edge widened; r^2 = (dx^2 + dy^2) + dz^2):
  *     u_LJ(r) = 4 epsilon [(sigma / r)^12 - (sigma / r)^6],   u0 = u_LJ(r_cut) with `shift`, else 0
@@ -492,6 +493,69 @@ int32_t gamd_classical_read(gamd_handle* h, void* stream, int64_t* steps, double
  * run is pending, or when 2 * r_cut exceeds a box edge. */
 int32_t gamd_classical_eval(gamd_handle* h, const float* pos_dev, const float* box, float length_per_nm, double* f_out_dev,
                             double* energy, double* virial, double* pairs, void* stream);
+
+/* Water classical observer: the classical potential of 3-site water — the reference logs OpenMM's potential energy for its
+ * TIP3P data and trains on getForces (dataset/generate_tip3p_data.py:91-103), and its rollout driver fetches classical forces
+ * beside the network's (water/test_script/test_nosehoover_hb.py:107).  GAMD_KIND_WATER handles, atoms in the caller's order
+ * O,H,H: molecule = caller-order index / 3 (n_atoms must be a multiple of 3), O = species flag != 0, charges q_H and
+ * q_O = -2 q_H (every molecule neutral: no background term).  Electrostatics are a plain Ewald sum in double, exact to the
+ * stated truncation (no PME grid).  Per box, with d the minimum-image vector of a pair (per component d - L rint(d / L), L the
+ * fp32 edge widened), r = |d|, C = coulomb_const * length_per_nm, V = L_x L_y L_z:
+ *     U_LJ    = the switched, shifted 12-6 form of gamd_classical_params (sigma_o, epsilon_o, r_cut, r_switch, shift), O-O pairs
+ *               of different molecules with r^2 < r_cut^2
+ *     U_real  = C sum_{i<j, different molecules, r^2 < r_cut^2} q_i q_j erfc(alpha r) / r
+ *     U_excl  = -C sum_{i<j, same molecule} q_i q_j erf(alpha r) / r                 (minimum image, no cutoff)
+ *     U_recip = (4 pi C / V) sum_k A(k) |S(k)|^2,  A(k) = exp(-k^2 / 4 alpha^2) / k^2,  S(k) = sum_j q_j exp(-i k.r_j),
+ *               k = 2 pi (n_x / L_x, n_y / L_y, n_z / L_z) over one of each +-n with 0 < |k| <= k_cut
+ *     U_self  = -C alpha / sqrt(pi) sum_i q_i^2
+ * and the forces are the exact negative gradients of these terms times length_per_nm (kJ/mol/nm).  The integer triples are one
+ * list per handle, built for the longest edge of the boxes of the run or call and sorted by (|n|^2, n_x, n_y, n_z); a box gives
+ * the vectors beyond its own k_cut the weight A = 0.  At most 131 072 triples: a longer list is refused with -22 (the message
+ * names k_cut).  Not included: TIP4P M-sites (a TIP4P handle evaluates the 3-site parameters it is given), the long-range
+ * dispersion correction, and any virial or pressure (with rigid molecules the atomic virial is not the pressure).
+ * Sample point, step counter, rows, resume rule and the off state are those of the classical observer above.  A row holds, per
+ * box: U_LJ, U_real + U_excl, U_recip, U_self, the different-molecule pairs inside r_cut, the five force-error sums of f against
+ * the classical force in the order of gamd_classical_params, the atoms left out of the cosine, and sum_i q_i, which is exactly
+ * 0.0 for a species vector with one O and two H per molecule (the charges are summed as integers -2, +1 and scaled once).
+ * Precondition: 2 * r_cut <= the shortest edge of every box, and a species vector; otherwise gamd_md_run / gamd_md_run_nhc /
+ * gamd_water_eval return -22 before anything is enqueued.  Cost per sample and box: N (N - 1) pair terms and 2 N K reciprocal
+ * terms (K k-vectors), all in double.
+ * Device memory: 48 B per atom and pair slice, 24 B per atom and k slice (at most 32 slices each), 24 B per atom, 12 B + 24 B per
+ * k-vector (and box), 16 B per box, k-vector and block of 256 atoms (at most 64 blocks), 96 B per box and row. */
+typedef struct gamd_water_params {
+    int64_t interval;        /* 0 = observer off: the parameters below are still taken (gamd_water_eval uses them), rows kept */
+    int64_t max_samples;     /* rows allocated by gamd_water_configure with interval > 0; 0 = 4096 */
+    double q_h;              /* hydrogen charge in e, finite; q_O = -2 q_h */
+    double sigma_o;          /* length unit of the handle, > 0 */
+    double epsilon_o;        /* kJ/mol, finite */
+    double r_cut;            /* length unit of the handle, > 0: real-space Coulomb and Lennard-Jones cutoff */
+    double r_switch;         /* Lennard-Jones only; 0 or >= r_cut: no switching */
+    int32_t shift;           /* 1: u0 = u_LJ(r_cut) */
+    int32_t reserved;        /* 0 */
+    double alpha;            /* Ewald splitting parameter, 1 / length unit, > 0 */
+    double k_cut;            /* reciprocal cutoff, 1 / length unit, > 0 */
+    double coulomb_const;    /* 1 / (4 pi eps0) in kJ nm / (mol e^2), finite (138.935456) */
+} gamd_water_params;
+enum { GAMD_WATER_ROW = 12 };      /* doubles per box and row, in the order above */
+/* p: HOST.  Takes the parameters and builds the k-vector list for the handle's current boxes; with interval > 0 allocates and
+ * clears the rows (drains nothing: call it between runs, after gamd_sync_status).  -22 for a negative interval or max_samples,
+ * sigma_o, r_cut, alpha or k_cut not positive, a non-finite q_h, epsilon_o or coulomb_const, a negative r_switch, a k_cut with no
+ * or more than 131 072 k-vectors, a GAMD_KIND_LJ handle, n_atoms not a multiple of 3, more than 65535 boxes, or while a run is
+ * pending; -12 when an allocation fails. */
+int32_t gamd_water_configure(gamd_handle* h, const gamd_water_params* p);
+/* Step count g = 0, rows cleared; parameters and configuration stay. */
+int32_t gamd_water_reset(gamd_handle* h);
+/* As gamd_classical_read, with rows double [max_rows][n_boxes][GAMD_WATER_ROW]. */
+int32_t gamd_water_read(gamd_handle* h, void* stream, int64_t* steps, double* rows, int64_t max_rows, int64_t* n_rows,
+                        int64_t* dropped, double* f_cl, int64_t f_cl_elems);
+/* The same kernels on given positions, outside any run, with the parameters of the last gamd_water_configure (interval 0 will
+ * do): pos_dev float [n_boxes * n_atoms][3] DEVICE (any periodic image), species_dev uint8 [n_boxes * n_atoms] DEVICE, box HOST
+ * [n_boxes][3], length_per_nm (0 = 10, Angstrom), f_out_dev double [n_boxes * n_atoms][3] DEVICE (kJ/mol/nm; may be NULL), rows
+ * HOST double [n_boxes][GAMD_WATER_ROW] (may be NULL; the force-error sums are 0).  Enqueued on `stream`, which is synchronised
+ * once.  -22 before gamd_water_configure, without species, while a run is pending, when 2 * r_cut exceeds a box edge or the
+ * boxes need more than 131 072 k-vectors. */
+int32_t gamd_water_eval(gamd_handle* h, const float* pos_dev, const uint8_t* species_dev, const float* box, float length_per_nm,
+                        double* f_out_dev, double* rows, void* stream);
 
 /* Event-timed replay of one force evaluation: per-kernel milliseconds of the last gamd_profile call.
  * names: newline-separated kernel labels; ms: one float per label.  For bench.py's roofline block. */
