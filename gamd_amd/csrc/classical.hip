@@ -25,17 +25,11 @@
 
 #pragma clang fp contract(off)
 
+#include "gamd_potential_dev.h"
+
 namespace {
 
 constexpr int CL_TILE = 256;
-
-// fp32 edge `c` of box `box`, widened
-__device__ __forceinline__ double classical_box_edge(const ClassicalArgs& a, int box, int c) {
-    if (a.box_edges) return (double)a.box_edges[3 * box + c];
-    if (a.bx.n_boxes <= 1) return (double)a.box[c];
-    const float4 b = a.bx.boxes[3 * box];
-    return (double)(c == 0 ? b.x : (c == 1 ? b.y : b.z));
-}
 
 __global__ void __launch_bounds__(256) k_classical_pairs(ClassicalArgs a) {
     if (a.devflags[DEVFLAG_FROZEN]) return;                 // a frame that will be evaluated again
@@ -50,7 +44,7 @@ __global__ void __launch_bounds__(256) k_classical_pairs(ClassicalArgs a) {
     const bool vi = il < npb;
     const long long jb = (long long)s * a.chunk;
     const int je = (int)(jb + a.chunk < (long long)npb ? jb + a.chunk : (long long)npb);
-    const double Lx = classical_box_edge(a, box, 0), Ly = classical_box_edge(a, box, 1), Lz = classical_box_edge(a, box, 2);
+    const double Lx = gamd_box_edge(a, box, 0), Ly = gamd_box_edge(a, box, 1), Lz = gamd_box_edge(a, box, 2);
 
     double xi = 0.0, yi = 0.0, zi = 0.0;
     if (vi) {
@@ -76,20 +70,14 @@ __global__ void __launch_bounds__(256) k_classical_pairs(ClassicalArgs a) {
             const double r2 = (dx * dx + dy * dy) + dz * dz;
             if (jj == self || !(r2 < a.rc2)) continue;
             const double ir2 = 1.0 / r2;
-            const double s2 = a.sig2 * ir2;
-            const double s6 = (s2 * s2) * s2;
-            const double s12 = s6 * s6;
-            double u = a.eps4 * (s12 - s6) - a.u0;          // u_LJ - u0
-            double ru = -(a.eps24 * ((s12 + s12) - s6));    // r u_LJ'(r)
-            if (a.rs >= 0.0) {
+            const double2 lj = gamd_lj_term(a.sig2, a.eps4, a.eps24, a.u0, ir2);
+            double u = lj.x, ru = lj.y;                     // u_LJ - u0 and r u_LJ'(r)
+            if (a.rs >= 0.0) {                              // (the square root only where there is a switch)
                 const double r = sqrt(r2);
                 if (r > a.rs) {
-                    const double t = (r - a.rs) * a.inv_w;
-                    const double t2 = t * t, tm = t - 1.0;
-                    const double S = 1.0 - (t2 * t) * ((6.0 * t - 15.0) * t + 10.0);
-                    const double dS = ((-30.0 * t2) * (tm * tm)) * a.inv_w;
-                    ru = ru * S + ((u * dS) * r);           // r u'(r), u = (u_LJ - u0) S
-                    u = u * S;
+                    const double2 sw = gamd_lj_switch(a.rs, a.inv_w, r);
+                    ru = ru * sw.x + ((u * sw.y) * r);      // r u'(r), u = (u_LJ - u0) S
+                    u = u * sw.x;
                 }
             }
             const double fs = -(ru * ir2);                  // F_ij = -u'(r) d / r = fs d
@@ -128,19 +116,13 @@ __global__ void __launch_bounds__(256) k_classical_atoms(ClassicalArgs a) {
         a.f_cl[3 * i] = cx; a.f_cl[3 * i + 1] = cy; a.f_cl[3 * i + 2] = cz;
         acc[0] += t[3]; acc[1] += t[4]; acc[2] += t[5];
         if (a.f) {
-            const double gx = (double)a.f[3 * i], gy = (double)a.f[3 * i + 1], gz = (double)a.f[3 * i + 2];
-            const double dx = gx - cx, dy = gy - cy, dz = gz - cz;
-            acc[3] += (fabs(dx) + fabs(dy)) + fabs(dz);
-            acc[4] += (dx * dx + dy * dy) + dz * dz;
-            const double nc = sqrt((cx * cx + cy * cy) + cz * cz), ng = sqrt((gx * gx + gy * gy) + gz * gz);
-            if (nc == 0.0 || ng == 0.0) acc[8] += 1.0;
-            else acc[5] += ((gx * cx + gy * cy) + gz * cz) / (ng * nc);
-            acc[6] += nc; acc[7] += ng;
+            gamd_force_error((double)a.f[3 * i], (double)a.f[3 * i + 1], (double)a.f[3 * i + 2], cx, cy, cz, acc[3], acc[4], acc[5],
+                             acc[6], acc[7], acc[8]);
         }
     }
 #pragma unroll
     for (int q = 0; q < CLASSICAL_ROW; ++q) {
-        double v = acc[q];
+        double v = acc[q];                                  // gamd_wave_sum, spelled out: the call moves this kernel's registers
 #pragma unroll
         for (int d = 32; d >= 1; d >>= 1) v += __shfl_down(v, d, 64);
         if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][q] = v;

@@ -1,0 +1,57 @@
+// gamd_potential_dev.h — the device terms the kernels of the observers with a potential share (classical.hip,
+// water_classical.hip; DESIGN.md sections 4.9 and 4.10).  Every helper spells out one order of operations: the host computes
+// u_LJ(r_cut) by gamd_lj_term's (potential_args, observe.hip), and tests/classical_ref.py mirrors them.  Contraction is off from
+// here on, as in the files that include it.
+#pragma once
+#include "gamd_common.h"
+
+#pragma clang fp contract(off)
+
+// fp32 edge `c` of box `box`, widened: the eval call's edges, the run's one box, or the run's box table
+template <typename Args>
+__device__ __forceinline__ double gamd_box_edge(const Args& a, int box, int c) {
+    if (a.box_edges) return (double)a.box_edges[3 * box + c];
+    if (a.bx.n_boxes <= 1) return (double)a.box[c];
+    const float4 b = a.bx.boxes[3 * box];
+    return (double)(c == 0 ? b.x : (c == 1 ? b.y : b.z));
+}
+
+// one wave's part of the fixed tree of k_report_ke: shuffle-down 32 .. 1 (lane 0 holds the sum; the four waves of a
+// 256-thread workgroup are then added as (w0 + w1) + (w2 + w3))
+__device__ __forceinline__ double gamd_wave_sum(double v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_down(v, d, 64);
+    return v;
+}
+
+// Lennard-Jones at 1 / r^2 = ir2: (u_LJ - u0, r u_LJ'(r)); eps24 = 24 epsilon (6 * eps4 is the same double)
+__device__ __forceinline__ double2 gamd_lj_term(double sig2, double eps4, double eps24, double u0, double ir2) {
+    const double s2 = sig2 * ir2;
+    const double s6 = (s2 * s2) * s2;
+    const double s12 = s6 * s6;
+    return make_double2(eps4 * (s12 - s6) - u0, -(eps24 * ((s12 + s12) - s6)));
+}
+
+// the switch polynomial at r > rs, (S, dS / dr): S(t) = 1 - t^3 (6 t^2 - 15 t + 10), t = (r - rs) inv_w.  The caller applies it
+// to (u, r u'): r u' <- r u' S + (u dS) r, then u <- u S.  (Both helpers return by value: written through references,
+// k_classical_pairs orders its accumulators differently.)
+__device__ __forceinline__ double2 gamd_lj_switch(double rs, double inv_w, double r) {
+    const double t = (r - rs) * inv_w;
+    const double t2 = t * t, tm = t - 1.0;
+    const double S = 1.0 - (t2 * t) * ((6.0 * t - 15.0) * t + 10.0);
+    const double dS = ((-30.0 * t2) * (tm * tm)) * inv_w;
+    return make_double2(S, dS);
+}
+
+// one atom's terms of the force-error sums of the run's force g against the classical force c (both kJ/mol/nm):
+// sum |D_c|, sum |D|^2, sum cos, sum |c|, sum |g|, and the atoms left out of the cosine because one of the two is zero
+__device__ __forceinline__ void gamd_force_error(double gx, double gy, double gz, double cx, double cy, double cz, double& sum_abs,
+                                                 double& sum_sq, double& sum_cos, double& sum_norm_cl, double& sum_norm, double& excluded) {
+    const double dx = gx - cx, dy = gy - cy, dz = gz - cz;
+    sum_abs += (fabs(dx) + fabs(dy)) + fabs(dz);
+    sum_sq += (dx * dx + dy * dy) + dz * dz;
+    const double nc = sqrt((cx * cx + cy * cy) + cz * cz), ng = sqrt((gx * gx + gy * gy) + gz * gz);
+    if (nc == 0.0 || ng == 0.0) excluded += 1.0;
+    else sum_cos += ((gx * cx + gy * cy) + gz * cz) / (ng * nc);
+    sum_norm_cl += nc; sum_norm += ng;
+}

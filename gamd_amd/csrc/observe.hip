@@ -4,6 +4,8 @@
 // classical.hip; gamd_classical_eval runs its kernels outside a run) and the water classical observer (gamd_water_*,
 // water_classical.hip; gamd_water_eval).  Each is its configuration plus a SampleClock,
 // a buffer table and an entry in observer_list(), through which the MD driver of gamd_api.hip sees it (observers_*, gamd_host.h).
+// The last two are observers with a potential: a PotentialLog and a traits struct (LjPotential, WaterPotential) behind one
+// sample, one read call and one eval call (potential_*).
 #include "gamd_host.h"
 
 #include <algorithm>
@@ -74,35 +76,30 @@ struct StructSampler {
     DevBuf counts, kvec, rho_partial, sk_sum;
 };
 
-// classical observer: the potential's parameters (taken by every gamd_classical_configure, armed or not), the log rows and
-// the work buffers of one evaluation
-struct Classical {
+// What the observers with a potential share: the Lennard-Jones parameters (taken by every gamd_*_configure of theirs, armed or
+// not), the log rows and the work buffers of one evaluation
+struct PotentialLog {
     SampleClock clock;
     long long max_samples = 0;
-    bool params_set = false;           // gamd_classical_eval needs parameters, not an armed observer
-    bool evaluated = false;            // f_cl holds the forces of a sample or a gamd_classical_eval call
+    bool params_set = false;           // the eval call needs parameters, not an armed observer
+    bool evaluated = false;            // f_cl holds the forces of a sample or an eval call
     double sigma = 0.0, epsilon = 0.0, r_cut = 0.0, r_switch = 0.0;
     int shift = 0;
     DevBuf steps, rows;                // log
     DevBuf part, f_cl, blk;            // one evaluation
-    DevBuf eval_rows, eval_box;        // gamd_classical_eval: its row and its box edges
+    DevBuf eval_rows, eval_box;        // the eval call: its row and its box edges
 };
 
-// water classical observer: the potential's parameters (taken by every gamd_water_configure, armed or not), the k-vector list
-// in force (built for the longest edge of the boxes of the last configure, run or gamd_water_eval), the log rows and the work
-// buffers of one evaluation
-struct WaterClassical {
-    SampleClock clock;
-    long long max_samples = 0;
-    bool params_set = false;           // gamd_water_eval needs parameters, not an armed observer
-    bool evaluated = false;            // f_cl holds the forces of a sample or a gamd_water_eval call
-    double q_h = 0.0, sigma = 0.0, epsilon = 0.0, r_cut = 0.0, r_switch = 0.0, alpha = 0.0, k_cut = 0.0, coulomb = 0.0;
-    int shift = 0;
+// classical observer: Lennard-Jones and nothing else
+using Classical = PotentialLog;
+
+// water classical observer: O-O Lennard-Jones plus the Ewald parameters, the k-vector list in force (built for the longest edge
+// of the boxes of the last configure, run or gamd_water_eval) and the work buffers that go by it
+struct WaterClassical : PotentialLog {
+    double q_h = 0.0, alpha = 0.0, k_cut = 0.0, coulomb = 0.0;
     int n2max = -1, n_k = 0;           // the list in force: every n with 0 < |n|^2 <= n2max (-1: none yet)
-    DevBuf steps, rows;                // log
-    DevBuf part, rpart, f_cl, blk;     // one evaluation: per atom
+    DevBuf rpart;                      // one evaluation: per atom and k slice
     DevBuf kvec, rho_partial, sk, ublk;// ... per k-vector
-    DevBuf eval_rows, eval_box;        // gamd_water_eval: its row and its box edges
 };
 
 }  // namespace
@@ -150,22 +147,24 @@ ObsBufs struct_bufs(gamd_handle* h) {
             {&sp.sk_sum, sizeof(double) * nb * (size_t)sp.pairs * K, true}};
 }
 
-// classical observer: J slices per row (258 atoms still fill more than two workgroups), atoms per slice, blocks of the
+// observers with a potential: J slices per row (258 atoms still fill more than two workgroups), atoms per slice, blocks of the
 // per-atom pass — fixed per handle: the summation order never changes
 int classical_tiles(const gamd_handle* h) { return (h->n_per_box + 255) / 256; }
 int classical_slices(const gamd_handle* h) { const int T = classical_tiles(h); return std::max(1, std::min(32, (1024 + T - 1) / T)); }
 int classical_chunk(const gamd_handle* h) { const int S = classical_slices(h); return (h->n_per_box + S - 1) / S; }
 int classical_blocks(const gamd_handle* h) { return std::max(1, std::min(64, (h->n_per_box + 255) / 256)); }
 
-ObsBufs classical_bufs(gamd_handle* h) {
-    Classical& cl = h->obs->cl;
-    const size_t nb = (size_t)h->n_boxes, rows = (size_t)cl.max_samples, n = (size_t)h->n;
-    return {{&cl.steps, sizeof(long long) * rows, true}, {&cl.rows, sizeof(double) * CLASSICAL_ROW * nb * rows, true},
-            {&cl.part, sizeof(double) * CLASSICAL_PART * n * (size_t)classical_slices(h), false},
-            {&cl.f_cl, sizeof(double) * 3 * n, false},
-            {&cl.blk, sizeof(double) * CLASSICAL_ROW * nb * (size_t)classical_blocks(h), false},
-            {&cl.eval_rows, sizeof(double) * CLASSICAL_ROW * nb, false}, {&cl.eval_box, sizeof(float) * 3 * nb, false}};
+// ... and the rows of their buffer tables: doubles per log row, per atom and slice, per box and block
+ObsBufs potential_bufs(gamd_handle* h, PotentialLog& pl, size_t row, size_t part, size_t acc) {
+    const size_t nb = (size_t)h->n_boxes, rows = (size_t)pl.max_samples, n = (size_t)h->n;
+    return {{&pl.steps, sizeof(long long) * rows, true}, {&pl.rows, sizeof(double) * row * nb * rows, true},
+            {&pl.part, sizeof(double) * part * n * (size_t)classical_slices(h), false},
+            {&pl.f_cl, sizeof(double) * 3 * n, false},
+            {&pl.blk, sizeof(double) * acc * nb * (size_t)classical_blocks(h), false},
+            {&pl.eval_rows, sizeof(double) * row * nb, false}, {&pl.eval_box, sizeof(float) * 3 * nb, false}};
 }
+
+ObsBufs classical_bufs(gamd_handle* h) { return potential_bufs(h, h->obs->cl, CLASSICAL_ROW, CLASSICAL_PART, CLASSICAL_ROW); }
 
 // water classical observer: the pair pass has the classical observer's tiles, slices and blocks; the k slices of the reciprocal
 // force pass are as many as the pair slices, the blocks of the rho(k) pass the structure sampler's
@@ -173,17 +172,21 @@ int water_kchunk(const gamd_handle* h, int n_k) { const int S = classical_slices
 
 ObsBufs water_bufs(gamd_handle* h) {
     WaterClassical& wc = h->obs->wc;
-    const size_t nb = (size_t)h->n_boxes, rows = (size_t)wc.max_samples, n = (size_t)h->n, K = (size_t)wc.n_k;
-    return {{&wc.steps, sizeof(long long) * rows, true}, {&wc.rows, sizeof(double) * WATER_ROW * nb * rows, true},
-            {&wc.part, sizeof(double) * WATER_PART * n * (size_t)classical_slices(h), false},
-            {&wc.rpart, sizeof(double) * 3 * n * (size_t)classical_slices(h), false},
-            {&wc.f_cl, sizeof(double) * 3 * n, false},
-            {&wc.blk, sizeof(double) * WATER_ACC * nb * (size_t)classical_blocks(h), false},
-            {&wc.kvec, sizeof(int) * 3 * K, false},                 // uploaded by water_klist_apply
-            {&wc.rho_partial, sizeof(double) * 2 * nb * (size_t)struct_rho_blocks(h) * K, false},
-            {&wc.sk, sizeof(double) * 3 * nb * K, false},
-            {&wc.ublk, sizeof(double) * nb * ((K + 255) / 256), false},
-            {&wc.eval_rows, sizeof(double) * WATER_ROW * nb, false}, {&wc.eval_box, sizeof(float) * 3 * nb, false}};
+    const size_t nb = (size_t)h->n_boxes, n = (size_t)h->n, K = (size_t)wc.n_k;
+    ObsBufs t = potential_bufs(h, wc, WATER_ROW, WATER_PART, WATER_ACC);
+    t.insert(t.begin() + 3, {&wc.rpart, sizeof(double) * 3 * n * (size_t)classical_slices(h), false});      // behind part
+    t.insert(t.begin() + 6, {{&wc.kvec, sizeof(int) * 3 * K, false},                                         // behind blk; uploaded by water_klist_apply
+                             {&wc.rho_partial, sizeof(double) * 2 * nb * (size_t)struct_rho_blocks(h) * K, false},
+                             {&wc.sk, sizeof(double) * 3 * nb * K, false},
+                             {&wc.ublk, sizeof(double) * nb * ((K + 255) / 256), false}});
+    return t;
+}
+
+// the work buffers of a table only (the log is gamd_*_configure's)
+int bufs_ensure_work(const ObsBufs& bufs) {
+    for (const ObsBuf& b : bufs)
+        if (!b.cleared && b.buf->ensure(b.want, true)) return -12;
+    return 0;
 }
 
 // what every observer's argument block starts with
@@ -305,42 +308,26 @@ int enqueue_struct_sample(gamd_handle* h, long long) {
     return 0;
 }
 
-// the classical observer's argument block but for positions, forces, box and output row
-ClassicalArgs classical_args(gamd_handle* h, double len) {
-    const Classical& cl = h->obs->cl;
-    ClassicalArgs a{};
+// The fields the argument blocks of the observers with a potential share by name: the Lennard-Jones constants, the length
+// unit, the geometry of the pair and per-atom passes and their work buffers.  Positions, forces, species, box and output row
+// are the caller's.
+template <typename Args>
+void potential_args(const gamd_handle* h, const PotentialLog& pl, double len, Args& a) {
     sample_args(h, a);
-    a.sig2 = cl.sigma * cl.sigma;
-    a.eps4 = 4.0 * cl.epsilon; a.eps24 = 24.0 * cl.epsilon;
-    a.rc2 = cl.r_cut * cl.r_cut;
+    a.sig2 = pl.sigma * pl.sigma;
+    a.eps4 = 4.0 * pl.epsilon;
+    a.rc2 = pl.r_cut * pl.r_cut;
     a.u0 = 0.0;
-    if (cl.shift) {                                         // u_LJ(r_cut) by the kernel's own operations
+    if (pl.shift) {                                         // u_LJ(r_cut) by gamd_lj_term's own operations (gamd_potential_dev.h)
         const double s2 = a.sig2 * (1.0 / a.rc2), s6 = (s2 * s2) * s2;
         a.u0 = a.eps4 * (s6 * s6 - s6);
     }
-    const bool sw = cl.r_switch > 0.0 && cl.r_switch < cl.r_cut;
-    a.rs = sw ? cl.r_switch : -1.0;
-    a.inv_w = sw ? 1.0 / (cl.r_cut - cl.r_switch) : 0.0;
+    const bool sw = pl.r_switch > 0.0 && pl.r_switch < pl.r_cut;
+    a.rs = sw ? pl.r_switch : -1.0;
+    a.inv_w = sw ? 1.0 / (pl.r_cut - pl.r_switch) : 0.0;
     a.len = len;
     a.tiles = classical_tiles(h); a.slices = classical_slices(h); a.chunk = classical_chunk(h); a.blocks = classical_blocks(h);
-    a.part = cl.part.as<double>(); a.f_cl = cl.f_cl.as<double>(); a.blk = cl.blk.as<double>();
-    return a;
-}
-
-// the classical observer's sample of step s of the pending run, behind its second half: f holds the network forces at x
-int enqueue_classical_sample(gamd_handle* h, long long s) {
-    const MdPending& p = h->pending;
-    Classical& cl = h->obs->cl;
-    if (cl.clock.ordinal(s) >= cl.max_samples) return 0;    // the log is full: counted as dropped by gamd_classical_read
-    ClassicalArgs a = classical_args(h, pending_particles(p).len);
-    for (int d = 0; d < 3; ++d) a.box[d] = h->box[d];
-    a.x = p.x; a.f = p.f;
-    a.rows = cl.rows.as<double>(); a.steps = cl.steps.as<long long>();
-    a.g = cl.clock.completed(s);
-    a.slot = cl.clock.ordinal(s);
-    if (int r = launch_classical(a, p.st)) return fail(-1, "classical observer launch failed (%d)", r);
-    cl.evaluated = true;
-    return 0;
+    a.part = pl.part.as<double>(); a.f_cl = pl.f_cl.as<double>(); a.blk = pl.blk.as<double>();
 }
 
 // one of each +-n with 0 < |n|^2 <= n2max, sorted by (|n|^2, nx, ny, nz) (defined below)
@@ -380,92 +367,105 @@ int water_klist_apply(gamd_handle* h, int n2max, const std::vector<int>& kv) {
     wc.n2max = -1;                                          // none, should anything below fail
     wc.n_k = (int)(kv.size() / 3);
     for (DevBuf* b : {&wc.kvec, &wc.rho_partial, &wc.sk, &wc.ublk}) b->release();
-    for (const ObsBuf& b : water_bufs(h))
-        if (!b.cleared && b.buf->ensure(b.want, true)) return fail(-12, "water classical potential allocation failed");
+    if (bufs_ensure_work(water_bufs(h))) return fail(-12, "water classical potential allocation failed");
     HIP_TRY(init_upload(wc.kvec.p, kv.data(), sizeof(int) * kv.size()));
     wc.n2max = n2max;
     return 0;
 }
 
-// the water classical observer's argument block but for positions, species, forces, box and output row
-WaterArgs water_args(gamd_handle* h, double len) {
-    const WaterClassical& wc = h->obs->wc;
-    WaterArgs a{};
-    sample_args(h, a);
-    const double pi = 3.141592653589793;
-    a.q_h = wc.q_h; a.q_o = -2.0 * wc.q_h;
-    a.sig2 = wc.sigma * wc.sigma;
-    a.eps4 = 4.0 * wc.epsilon;
-    a.rc2 = wc.r_cut * wc.r_cut;
-    a.u0 = 0.0;
-    if (wc.shift) {                                         // u_LJ(r_cut) by the kernel's own operations
-        const double s2 = a.sig2 * (1.0 / a.rc2), s6 = (s2 * s2) * s2;
-        a.u0 = a.eps4 * (s6 * s6 - s6);
-    }
-    const bool sw = wc.r_switch > 0.0 && wc.r_switch < wc.r_cut;
-    a.rs = sw ? wc.r_switch : -1.0;
-    a.inv_w = sw ? 1.0 / (wc.r_cut - wc.r_switch) : 0.0;
-    a.coul = wc.coulomb * len;
-    a.alpha = wc.alpha; a.two_a_rpi = (2.0 * wc.alpha) / std::sqrt(pi);
-    a.kc2 = wc.k_cut * wc.k_cut; a.inv_4a2 = 1.0 / (4.0 * (wc.alpha * wc.alpha));
-    a.two_pi = 2.0 * pi;
-    a.coul4pi = (4.0 * pi) * a.coul; a.coul8pi = (8.0 * pi) * a.coul;
-    a.self_c = (a.coul * wc.alpha) / std::sqrt(pi);
-    a.len = len;
-    a.tiles = classical_tiles(h); a.slices = classical_slices(h); a.chunk = classical_chunk(h); a.blocks = classical_blocks(h);
-    a.n_k = wc.n_k; a.kslices = classical_slices(h); a.kchunk = water_kchunk(h, wc.n_k); a.kblocks = (wc.n_k + 255) / 256;
-    a.rho_blocks = struct_rho_blocks(h);
-    a.kvec = wc.kvec.as<int>();
-    a.part = wc.part.as<double>(); a.rho_partial = wc.rho_partial.as<double>(); a.sk = wc.sk.as<double>(); a.ublk = wc.ublk.as<double>();
-    a.rpart = wc.rpart.as<double>(); a.f_cl = wc.f_cl.as<double>(); a.blk = wc.blk.as<double>();
-    return a;
-}
-
-// the water classical observer's sample of step s of the pending run, behind its second half: f holds the network forces at x
-int enqueue_water_sample(gamd_handle* h, long long s) {
-    const MdPending& p = h->pending;
-    WaterClassical& wc = h->obs->wc;
-    if (wc.clock.ordinal(s) >= wc.max_samples) return 0;    // the log is full: counted as dropped by gamd_water_read
-    WaterArgs a = water_args(h, pending_particles(p).len);
-    for (int d = 0; d < 3; ++d) a.box[d] = h->box[d];
-    a.x = p.x; a.f = p.f; a.species = p.species;
-    a.rows = wc.rows.as<double>(); a.steps = wc.steps.as<long long>();
-    a.g = wc.clock.completed(s);
-    a.slot = wc.clock.ordinal(s);
-    if (int r = launch_water_classical(a, p.st)) return fail(-1, "water classical observer launch failed (%d)", r);
-    wc.evaluated = true;
+// the minimum image is the nearest image only inside the sphere of half the shortest edge
+int potential_check_box(const gamd_handle* h, const PotentialLog& pl, const char* who, const float* box) {
+    for (int k = 0; k < 3 * h->n_boxes; ++k)
+        if (!(2.0 * pl.r_cut <= (double)box[k]))
+            return fail(-22, "%s potential: r_cut = %g exceeds half of box[%d][%d] = %g (the minimum image is the nearest "
+                             "image only below that)", who, pl.r_cut, k / 3, k % 3, (double)box[k]);
     return 0;
 }
 
-// water classical observer: what a run or gamd_water_eval must bring — species, 2 r_cut <= every edge, a k-vector list of at
-// most 131 072 triples for these boxes (built and uploaded here when the boxes need another one than the list in force)
-int water_check_box(gamd_handle* h, const float* box, const uint8_t* species_dev) {
-    WaterClassical& wc = h->obs->wc;
-    if (!species_dev) return fail(-22, "water classical potential: the charges need species (O = 1, H = 0, atoms ordered O,H,H)");
-    for (int k = 0; k < 3 * h->n_boxes; ++k)
-        if (!(2.0 * wc.r_cut <= (double)box[k]))
-            return fail(-22, "water classical potential: r_cut = %g exceeds half of box[%d][%d] = %g (the minimum image is the nearest "
-                             "image only below that)", wc.r_cut, k / 3, k % 3, (double)box[k]);
-    int n2max = wc.n2max;
-    std::vector<int> kv;
-    if (int r = water_klist(wc.k_cut, box, h->n_boxes, &n2max, &kv)) return r;
-    return water_klist_apply(h, n2max, kv);
+// What an observer with a potential supplies besides its entry in observer_list(): its name in the error texts and in the C
+// ABI, the width of its log row and the column of it that only a frozen handle leaves NaN, its state, its argument block but
+// for positions, forces, species, box and output row (potential_args plus what is its own), its launcher, and check_box():
+// what a run or its eval call must bring, which may prepare the handle for these boxes (no run is pending).
+struct LjPotential {
+    using Args = ClassicalArgs;
+    static constexpr const char* who = "classical";
+    static constexpr const char* api = "gamd_classical";
+    enum { ROW = CLASSICAL_ROW, FROZEN_COL = 2 };
+    static Classical& state(const gamd_handle* h) { return h->obs->cl; }
+    static ObsBufs bufs(gamd_handle* h) { return classical_bufs(h); }
+    static Args args(gamd_handle* h, double len) {
+        Args a{};
+        potential_args(h, state(h), len, a);
+        a.eps24 = 24.0 * state(h).epsilon;
+        return a;
+    }
+    static void species(Args&, const uint8_t*) {}
+    static int launch(const Args& a, hipStream_t st) { return launch_classical(a, st); }
+    static int check_box(gamd_handle* h, const float* box, const uint8_t*) { return potential_check_box(h, state(h), who, box); }
+};
+
+struct WaterPotential {
+    using Args = WaterArgs;
+    static constexpr const char* who = "water classical";
+    static constexpr const char* api = "gamd_water";
+    enum { ROW = WATER_ROW, FROZEN_COL = 4 };
+    static WaterClassical& state(const gamd_handle* h) { return h->obs->wc; }
+    static ObsBufs bufs(gamd_handle* h) { return water_bufs(h); }
+    static Args args(gamd_handle* h, double len) {
+        const WaterClassical& wc = state(h);
+        Args a{};
+        potential_args(h, wc, len, a);
+        const double pi = 3.141592653589793;
+        a.q_h = wc.q_h; a.q_o = -2.0 * wc.q_h;
+        a.coul = wc.coulomb * len;
+        a.alpha = wc.alpha; a.two_a_rpi = (2.0 * wc.alpha) / std::sqrt(pi);
+        a.kc2 = wc.k_cut * wc.k_cut; a.inv_4a2 = 1.0 / (4.0 * (wc.alpha * wc.alpha));
+        a.two_pi = 2.0 * pi;
+        a.coul4pi = (4.0 * pi) * a.coul; a.coul8pi = (8.0 * pi) * a.coul;
+        a.self_c = (a.coul * wc.alpha) / std::sqrt(pi);
+        a.n_k = wc.n_k; a.kslices = classical_slices(h); a.kchunk = water_kchunk(h, wc.n_k); a.kblocks = (wc.n_k + 255) / 256;
+        a.rho_blocks = struct_rho_blocks(h);
+        a.kvec = wc.kvec.as<int>();
+        a.rho_partial = wc.rho_partial.as<double>(); a.sk = wc.sk.as<double>(); a.ublk = wc.ublk.as<double>();
+        a.rpart = wc.rpart.as<double>();
+        return a;
+    }
+    static void species(Args& a, const uint8_t* species_dev) { a.species = species_dev; }
+    static int launch(const Args& a, hipStream_t st) { return launch_water_classical(a, st); }
+    // species, 2 r_cut <= every edge, a k-vector list of at most 131 072 triples for these boxes (built and uploaded here when
+    // the boxes need another one than the list in force)
+    static int check_box(gamd_handle* h, const float* box, const uint8_t* species_dev) {
+        WaterClassical& wc = state(h);
+        if (!species_dev) return fail(-22, "water classical potential: the charges need species (O = 1, H = 0, atoms ordered O,H,H)");
+        if (int r = potential_check_box(h, wc, who, box)) return r;
+        int n2max = wc.n2max;
+        std::vector<int> kv;
+        if (int r = water_klist(wc.k_cut, box, h->n_boxes, &n2max, &kv)) return r;
+        return water_klist_apply(h, n2max, kv);
+    }
+};
+
+// the sample of step s of the pending run, behind its second half: f holds the network forces at x
+template <typename P>
+int potential_sample(gamd_handle* h, long long s) {
+    const MdPending& p = h->pending;
+    PotentialLog& pl = P::state(h);
+    if (pl.clock.ordinal(s) >= pl.max_samples) return 0;    // the log is full: counted as dropped by the read call
+    typename P::Args a = P::args(h, pending_particles(p).len);
+    for (int d = 0; d < 3; ++d) a.box[d] = h->box[d];
+    a.x = p.x; a.f = p.f; P::species(a, p.species);
+    a.rows = pl.rows.as<double>(); a.steps = pl.steps.as<long long>();
+    a.g = pl.clock.completed(s);
+    a.slot = pl.clock.ordinal(s);
+    if (int r = P::launch(a, p.st)) return fail(-1, "%s observer launch failed (%d)", P::who, r);
+    pl.evaluated = true;
+    return 0;
 }
+
 int water_check_run(gamd_handle* h, const float* box, const uint8_t* species_dev) {
     if (h->pending.active) return fail(-22, "an MD run is still enqueued: call gamd_sync_status before the next run of a handle whose water classical observer is on");
-    return water_check_box(h, box, species_dev);
+    return WaterPotential::check_box(h, box, species_dev);
 }
-
-// classical observer: the minimum image is the nearest image only inside the sphere of half the shortest edge
-int classical_check_box(const gamd_handle* h, const float* box) {
-    const Classical& cl = h->obs->cl;
-    for (int k = 0; k < 3 * h->n_boxes; ++k)
-        if (!(2.0 * cl.r_cut <= (double)box[k]))
-            return fail(-22, "classical potential: r_cut = %g exceeds half of box[%d][%d] = %g (the minimum image is the nearest "
-                             "image only below that)", cl.r_cut, k / 3, k % 3, (double)box[k]);
-    return 0;
-}
-int classical_check_run(gamd_handle* h, const float* box, const uint8_t*) { return classical_check_box(h, box); }
 
 // run recorder: image counters and ring are only meaningful in one box and with one set of classes
 int traj_check_run(gamd_handle* h, const float* box, const uint8_t* species_dev) {
@@ -516,8 +516,8 @@ std::array<Observer, OBS_COUNT> observer_list(const gamd_handle* h) {
     return {{{&o.rep.clock, report_bufs, enqueue_report_sample, nullptr, nullptr, nullptr},
              {&o.rec.clock, traj_bufs, enqueue_traj_sample, traj_check_run, traj_begin_run, traj_forget},
              {&o.ss.clock, struct_bufs, enqueue_struct_sample, struct_check_run, nullptr, nullptr},
-             {&o.cl.clock, classical_bufs, enqueue_classical_sample, classical_check_run, nullptr, nullptr},
-             {&o.wc.clock, water_bufs, enqueue_water_sample, water_check_run, nullptr, nullptr}}};
+             {&o.cl.clock, classical_bufs, potential_sample<LjPotential>, LjPotential::check_box, nullptr, nullptr},
+             {&o.wc.clock, water_bufs, potential_sample<WaterPotential>, water_check_run, nullptr, nullptr}}};
 }
 
 // clear an observer's step count and what it took (configuration and scratch stay): on the init stream, landed on return
@@ -552,6 +552,83 @@ int observer_reset(gamd_handle* h, int which, const char* entry) {
     DeviceGuard guard(h->dev);
     InitStream init(h->init_stream);
     return observer_clear(h, observer_list(h)[which]);
+}
+
+// the grids of the all-pairs kernels: boxes in grid.y, and (tiles_who given) the upper triangle of 256-atom tiles in 24 bits
+int check_boxes_tiles(const gamd_handle* h, const char* who, const char* tiles_who) {
+    if (h->n_boxes > 65535) return fail(-22, "the %s needs n_boxes <= 65535", who);
+    const long long T = (h->n_per_box + 255) / 256;
+    if (tiles_who && T * (T + 1) / 2 > 0xffffffll) return fail(-22, "the %s needs at most 5791 tiles of 256 atoms per box", tiles_who);
+    return 0;
+}
+
+// the tail of the gamd_*_configure of an observer with a potential, behind its parameters
+template <typename P>
+int potential_configure(gamd_handle* h, int which, long long interval, long long max_samples, const char* entry) {
+    return observer_configure(h, which, interval, entry, [&]() {
+        P::state(h).max_samples = max_samples > 0 ? max_samples : 4096;
+        return bufs_resize(P::bufs(h)) ? fail(-12, "%s observer allocation failed", P::who) : 0;
+    });
+}
+
+template <typename P>
+int potential_read(gamd_handle* h, void* stream, int64_t* steps, double* rows, int64_t max_rows, int64_t* n_rows, int64_t* dropped,
+                   double* f_cl, int64_t f_cl_elems) {
+    if (!h) return fail(-22, "null handle");
+    if (max_rows < 0) return fail(-22, "max_rows is negative");
+    const PotentialLog& pl = P::state(h);
+    DeviceGuard guard(h->dev);
+    hipStream_t st = (hipStream_t)stream;
+    const long long nb = h->n_boxes;
+    const long long taken = pl.clock.taken(pl.steps.p != nullptr);
+    const long long kept = std::min<long long>(taken, pl.max_samples);
+    const long long n_copy = std::min<long long>(kept, max_rows);
+    if (f_cl && f_cl_elems < 3ll * h->n) return fail(-22, "f_cl has room for %lld elements, the forces have %lld", (long long)f_cl_elems, 3ll * h->n);
+    if (n_copy > 0 && steps) HIP_TRY(hipMemcpyAsync(steps, pl.steps.p, sizeof(int64_t) * (size_t)n_copy, hipMemcpyDeviceToHost, st));
+    if (n_copy > 0 && rows) HIP_TRY(hipMemcpyAsync(rows, pl.rows.p, sizeof(double) * (size_t)(n_copy * nb * P::ROW), hipMemcpyDeviceToHost, st));
+    if (f_cl && pl.evaluated && pl.f_cl.p) HIP_TRY(hipMemcpyAsync(f_cl, pl.f_cl.p, sizeof(double) * 3 * (size_t)h->n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (int t = check_traps(h)) return t;
+    if (n_rows) *n_rows = kept;
+    if (dropped) *dropped = taken - kept;
+    return 0;
+}
+
+// the kernels of a sample on given positions, outside a run: the forces to f_out_dev (may be null), the row of every box to `row`
+template <typename P>
+int potential_eval(gamd_handle* h, const float* pos_dev, const uint8_t* species_dev, const float* box, float length_per_nm,
+                   double* f_out_dev, std::vector<double>& row, void* stream) {
+    if (!h) return fail(-22, "null handle");
+    if (!pos_dev || !box) return fail(-22, "null argument");
+    PotentialLog& pl = P::state(h);
+    if (!pl.params_set) return fail(-22, "%s_eval needs the parameters of a %s_configure call (interval 0 will do)", P::api, P::api);
+    if (h->pending.active) return fail(-22, "an MD run is still enqueued: call gamd_sync_status before %s_eval", P::api);
+    for (int k = 0; k < 3 * h->n_boxes; ++k)
+        if (!(box[k] > 0.f)) return fail(-22, "box[%d][%d] = %g is not positive", k / 3, k % 3, (double)box[k]);
+    if (int r = P::check_box(h, box, species_dev)) return r;
+    DeviceGuard guard(h->dev);
+    hipStream_t st = (hipStream_t)stream;
+    InitStream init(st);
+    if (bufs_ensure_work(P::bufs(h))) return fail(-12, "%s potential allocation failed", P::who);
+    const size_t nb = (size_t)h->n_boxes;
+    HIP_TRY(init_upload(pl.eval_box.p, box, sizeof(float) * 3 * nb));
+    // a frozen handle's kernels return at once: the row would be what the last call left
+    HIP_TRY(hipMemsetAsync(pl.eval_rows.p, 0xff, sizeof(double) * P::ROW * nb, st));
+    typename P::Args a = P::args(h, length_per_nm > 0.f ? (double)length_per_nm : 10.0);
+    a.box_edges = pl.eval_box.as<float>();
+    a.x = pos_dev; a.f = nullptr; P::species(a, species_dev);
+    a.rows = pl.eval_rows.as<double>(); a.steps = nullptr; a.slot = 0; a.g = 0;
+    if (int r = P::launch(a, st)) return fail(-1, "%s potential launch failed (%d)", P::who, r);
+    pl.evaluated = true;
+    if (f_out_dev) HIP_TRY(hipMemcpyAsync(f_out_dev, pl.f_cl.p, sizeof(double) * 3 * (size_t)h->n, hipMemcpyDeviceToDevice, st));
+    row = std::vector<double>(P::ROW * nb);
+    HIP_TRY(hipMemcpyAsync(row.data(), pl.eval_rows.p, sizeof(double) * row.size(), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (int t = check_traps(h)) return t;
+    for (size_t b = 0; b < nb; ++b)
+        if (std::isnan(row[P::ROW * b + P::FROZEN_COL]))
+            return fail(-1, "%s_eval: the handle is frozen by a neighbour-buffer overflow (call gamd_sync_status)", P::api);
+    return 0;
 }
 
 // one of each +-n with 0 < |n|^2 <= n2max (the one whose first non-zero component is positive), sorted by (|n|^2, nx, ny, nz)
@@ -763,11 +840,7 @@ int32_t gamd_struct_configure(gamd_handle* h, const gamd_struct_params* p) {
     std::vector<int> kv = p->sk_n2max > 0 ? struct_kvectors(p->sk_n2max) : std::vector<int>();
     if (kv.size() / 3 > 4096) return fail(-22, "sk_n2max = %d gives %zu k-vectors, more than 4096", (int)p->sk_n2max, kv.size() / 3);
     if (!h) return fail(-22, "null handle");
-    if (h->n_boxes > 65535) return fail(-22, "the structure sampler needs n_boxes <= 65535");
-    {
-        const long long T = (h->n_per_box + 255) / 256;
-        if (p->rdf_bins > 0 && T * (T + 1) / 2 > 0xffffffll) return fail(-22, "the pair histogram needs at most 5791 tiles of 256 atoms per box");
-    }
+    if (int r = check_boxes_tiles(h, "structure sampler", p->rdf_bins > 0 ? "pair histogram" : nullptr)) return r;
     return observer_configure(h, OBS_STRUCT, p->interval, "gamd_struct_configure", [&]() {
         StructSampler& sp = h->obs->ss;
         sp.bins = p->rdf_bins;
@@ -817,77 +890,26 @@ int32_t gamd_classical_configure(gamd_handle* h, const gamd_classical_params* p)
     if (h->cfg.kind != GAMD_KIND_LJ)
         return fail(-22, "classical potential: a GAMD_KIND_WATER handle needs electrostatics, which this Lennard-Jones potential does "
                          "not have (GAMD_KIND_LJ handles only; gamd_water_configure evaluates 3-site water)");
-    if (h->n_boxes > 65535) return fail(-22, "the classical observer needs n_boxes <= 65535");
-    {
-        const long long T = (h->n_per_box + 255) / 256;
-        if (T * (T + 1) / 2 > 0xffffffll) return fail(-22, "the classical observer needs at most 5791 tiles of 256 atoms per box");
-    }
+    if (int r = check_boxes_tiles(h, "classical observer", "classical observer")) return r;
     if (h->pending.active) return fail(-22, "an MD run is still enqueued: call gamd_sync_status before gamd_classical_configure");
     Classical& cl = h->obs->cl;
     cl.sigma = p->sigma; cl.epsilon = p->epsilon; cl.r_cut = p->r_cut; cl.r_switch = p->r_switch; cl.shift = p->shift ? 1 : 0;
     cl.params_set = true;
-    return observer_configure(h, OBS_CLASSICAL, p->interval, "gamd_classical_configure", [&]() {
-        cl.max_samples = p->max_samples > 0 ? p->max_samples : 4096;
-        return bufs_resize(classical_bufs(h)) ? fail(-12, "classical observer allocation failed") : 0;
-    });
+    return potential_configure<LjPotential>(h, OBS_CLASSICAL, p->interval, p->max_samples, "gamd_classical_configure");
 }
 
 int32_t gamd_classical_reset(gamd_handle* h) { return observer_reset(h, OBS_CLASSICAL, "gamd_classical_reset"); }
 
 int32_t gamd_classical_read(gamd_handle* h, void* stream, int64_t* steps, double* rows, int64_t max_rows, int64_t* n_rows,
                             int64_t* dropped, double* f_cl, int64_t f_cl_elems) {
-    if (!h) return fail(-22, "null handle");
-    if (max_rows < 0) return fail(-22, "max_rows is negative");
-    const Classical& cl = h->obs->cl;
-    DeviceGuard guard(h->dev);
-    hipStream_t st = (hipStream_t)stream;
-    const long long nb = h->n_boxes;
-    const long long taken = cl.clock.taken(cl.steps.p != nullptr);
-    const long long kept = std::min<long long>(taken, cl.max_samples);
-    const long long n_copy = std::min<long long>(kept, max_rows);
-    if (f_cl && f_cl_elems < 3ll * h->n) return fail(-22, "f_cl has room for %lld elements, the forces have %lld", (long long)f_cl_elems, 3ll * h->n);
-    if (n_copy > 0 && steps) HIP_TRY(hipMemcpyAsync(steps, cl.steps.p, sizeof(int64_t) * (size_t)n_copy, hipMemcpyDeviceToHost, st));
-    if (n_copy > 0 && rows) HIP_TRY(hipMemcpyAsync(rows, cl.rows.p, sizeof(double) * (size_t)(n_copy * nb * CLASSICAL_ROW), hipMemcpyDeviceToHost, st));
-    if (f_cl && cl.evaluated && cl.f_cl.p) HIP_TRY(hipMemcpyAsync(f_cl, cl.f_cl.p, sizeof(double) * 3 * (size_t)h->n, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (int t = check_traps(h)) return t;
-    if (n_rows) *n_rows = kept;
-    if (dropped) *dropped = taken - kept;
-    return 0;
+    return potential_read<LjPotential>(h, stream, steps, rows, max_rows, n_rows, dropped, f_cl, f_cl_elems);
 }
 
 int32_t gamd_classical_eval(gamd_handle* h, const float* pos_dev, const float* box, float length_per_nm, double* f_out_dev,
                             double* energy, double* virial, double* pairs, void* stream) {
-    if (!h) return fail(-22, "null handle");
-    if (!pos_dev || !box) return fail(-22, "null argument");
-    Classical& cl = h->obs->cl;
-    if (!cl.params_set) return fail(-22, "gamd_classical_eval needs the parameters of a gamd_classical_configure call (interval 0 will do)");
-    if (h->pending.active) return fail(-22, "an MD run is still enqueued: call gamd_sync_status before gamd_classical_eval");
-    for (int k = 0; k < 3 * h->n_boxes; ++k)
-        if (!(box[k] > 0.f)) return fail(-22, "box[%d][%d] = %g is not positive", k / 3, k % 3, (double)box[k]);
-    if (int r = classical_check_box(h, box)) return r;
-    DeviceGuard guard(h->dev);
-    hipStream_t st = (hipStream_t)stream;
-    InitStream init(st);
-    for (const ObsBuf& b : classical_bufs(h))               // the work buffers; the log is gamd_classical_configure's
-        if (!b.cleared && b.buf->ensure(b.want, true)) return fail(-12, "classical potential allocation failed");
-    const size_t nb = (size_t)h->n_boxes;
-    HIP_TRY(init_upload(cl.eval_box.p, box, sizeof(float) * 3 * nb));
-    // a frozen handle's kernels return at once: the row would be what the last call left
-    HIP_TRY(hipMemsetAsync(cl.eval_rows.p, 0xff, sizeof(double) * CLASSICAL_ROW * nb, st));
-    ClassicalArgs a = classical_args(h, length_per_nm > 0.f ? (double)length_per_nm : 10.0);
-    a.box_edges = cl.eval_box.as<float>();
-    a.x = pos_dev; a.f = nullptr;
-    a.rows = cl.eval_rows.as<double>(); a.steps = nullptr; a.slot = 0; a.g = 0;
-    if (int r = launch_classical(a, st)) return fail(-1, "classical potential launch failed (%d)", r);
-    cl.evaluated = true;
-    if (f_out_dev) HIP_TRY(hipMemcpyAsync(f_out_dev, cl.f_cl.p, sizeof(double) * 3 * (size_t)h->n, hipMemcpyDeviceToDevice, st));
-    std::vector<double> row(CLASSICAL_ROW * nb);
-    HIP_TRY(hipMemcpyAsync(row.data(), cl.eval_rows.p, sizeof(double) * row.size(), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (int t = check_traps(h)) return t;
-    for (size_t b = 0; b < nb; ++b) {
-        if (std::isnan(row[CLASSICAL_ROW * b + 2])) return fail(-1, "gamd_classical_eval: the handle is frozen by a neighbour-buffer overflow (call gamd_sync_status)");
+    std::vector<double> row;
+    if (int r = potential_eval<LjPotential>(h, pos_dev, nullptr, box, length_per_nm, f_out_dev, row, stream)) return r;
+    for (int b = 0; b < h->n_boxes; ++b) {
         if (energy) energy[b] = row[CLASSICAL_ROW * b];
         if (virial) virial[b] = row[CLASSICAL_ROW * b + 1];
         if (pairs) pairs[b] = row[CLASSICAL_ROW * b + 2];
@@ -912,11 +934,7 @@ int32_t gamd_water_configure(gamd_handle* h, const gamd_water_params* p) {
         return fail(-22, "water classical potential: a GAMD_KIND_LJ handle has no molecules and no charges (GAMD_KIND_WATER handles only; "
                          "gamd_classical_configure evaluates Lennard-Jones)");
     if (h->n_per_box % 3) return fail(-22, "water classical potential: n_atoms = %d per box is not a multiple of 3 (atoms ordered O,H,H)", h->n_per_box);
-    if (h->n_boxes > 65535) return fail(-22, "the water classical observer needs n_boxes <= 65535");
-    {
-        const long long T = (h->n_per_box + 255) / 256;
-        if (T * (T + 1) / 2 > 0xffffffll) return fail(-22, "the water classical observer needs at most 5791 tiles of 256 atoms per box");
-    }
+    if (int r = check_boxes_tiles(h, "water classical observer", "water classical observer")) return r;
     if (h->pending.active) return fail(-22, "an MD run is still enqueued: call gamd_sync_status before gamd_water_configure");
     WaterClassical& wc = h->obs->wc;
     // the k-vector list of the handle's current boxes, in front of anything that is taken: a refused block changes nothing
@@ -930,68 +948,20 @@ int32_t gamd_water_configure(gamd_handle* h, const gamd_water_params* p) {
     wc.params_set = true;
     if (have_box)
         if (int r = water_klist_apply(h, n2max, kv)) return r;
-    return observer_configure(h, OBS_WATER, p->interval, "gamd_water_configure", [&]() {
-        wc.max_samples = p->max_samples > 0 ? p->max_samples : 4096;
-        return bufs_resize(water_bufs(h)) ? fail(-12, "water classical observer allocation failed") : 0;
-    });
+    return potential_configure<WaterPotential>(h, OBS_WATER, p->interval, p->max_samples, "gamd_water_configure");
 }
 
 int32_t gamd_water_reset(gamd_handle* h) { return observer_reset(h, OBS_WATER, "gamd_water_reset"); }
 
 int32_t gamd_water_read(gamd_handle* h, void* stream, int64_t* steps, double* rows, int64_t max_rows, int64_t* n_rows,
                         int64_t* dropped, double* f_cl, int64_t f_cl_elems) {
-    if (!h) return fail(-22, "null handle");
-    if (max_rows < 0) return fail(-22, "max_rows is negative");
-    const WaterClassical& wc = h->obs->wc;
-    DeviceGuard guard(h->dev);
-    hipStream_t st = (hipStream_t)stream;
-    const long long nb = h->n_boxes;
-    const long long taken = wc.clock.taken(wc.steps.p != nullptr);
-    const long long kept = std::min<long long>(taken, wc.max_samples);
-    const long long n_copy = std::min<long long>(kept, max_rows);
-    if (f_cl && f_cl_elems < 3ll * h->n) return fail(-22, "f_cl has room for %lld elements, the forces have %lld", (long long)f_cl_elems, 3ll * h->n);
-    if (n_copy > 0 && steps) HIP_TRY(hipMemcpyAsync(steps, wc.steps.p, sizeof(int64_t) * (size_t)n_copy, hipMemcpyDeviceToHost, st));
-    if (n_copy > 0 && rows) HIP_TRY(hipMemcpyAsync(rows, wc.rows.p, sizeof(double) * (size_t)(n_copy * nb * WATER_ROW), hipMemcpyDeviceToHost, st));
-    if (f_cl && wc.evaluated && wc.f_cl.p) HIP_TRY(hipMemcpyAsync(f_cl, wc.f_cl.p, sizeof(double) * 3 * (size_t)h->n, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (int t = check_traps(h)) return t;
-    if (n_rows) *n_rows = kept;
-    if (dropped) *dropped = taken - kept;
-    return 0;
+    return potential_read<WaterPotential>(h, stream, steps, rows, max_rows, n_rows, dropped, f_cl, f_cl_elems);
 }
 
 int32_t gamd_water_eval(gamd_handle* h, const float* pos_dev, const uint8_t* species_dev, const float* box, float length_per_nm,
                         double* f_out_dev, double* rows, void* stream) {
-    if (!h) return fail(-22, "null handle");
-    if (!pos_dev || !box) return fail(-22, "null argument");
-    WaterClassical& wc = h->obs->wc;
-    if (!wc.params_set) return fail(-22, "gamd_water_eval needs the parameters of a gamd_water_configure call (interval 0 will do)");
-    if (h->pending.active) return fail(-22, "an MD run is still enqueued: call gamd_sync_status before gamd_water_eval");
-    for (int k = 0; k < 3 * h->n_boxes; ++k)
-        if (!(box[k] > 0.f)) return fail(-22, "box[%d][%d] = %g is not positive", k / 3, k % 3, (double)box[k]);
-    if (int r = water_check_box(h, box, species_dev)) return r;
-    DeviceGuard guard(h->dev);
-    hipStream_t st = (hipStream_t)stream;
-    InitStream init(st);
-    for (const ObsBuf& b : water_bufs(h))                   // the work buffers; the log is gamd_water_configure's
-        if (!b.cleared && b.buf->ensure(b.want, true)) return fail(-12, "water classical potential allocation failed");
-    const size_t nb = (size_t)h->n_boxes;
-    HIP_TRY(init_upload(wc.eval_box.p, box, sizeof(float) * 3 * nb));
-    // a frozen handle's kernels return at once: the row would be what the last call left
-    HIP_TRY(hipMemsetAsync(wc.eval_rows.p, 0xff, sizeof(double) * WATER_ROW * nb, st));
-    WaterArgs a = water_args(h, length_per_nm > 0.f ? (double)length_per_nm : 10.0);
-    a.box_edges = wc.eval_box.as<float>();
-    a.x = pos_dev; a.f = nullptr; a.species = species_dev;
-    a.rows = wc.eval_rows.as<double>(); a.steps = nullptr; a.slot = 0; a.g = 0;
-    if (int r = launch_water_classical(a, st)) return fail(-1, "water classical potential launch failed (%d)", r);
-    wc.evaluated = true;
-    if (f_out_dev) HIP_TRY(hipMemcpyAsync(f_out_dev, wc.f_cl.p, sizeof(double) * 3 * (size_t)h->n, hipMemcpyDeviceToDevice, st));
-    std::vector<double> row(WATER_ROW * nb);
-    HIP_TRY(hipMemcpyAsync(row.data(), wc.eval_rows.p, sizeof(double) * row.size(), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (int t = check_traps(h)) return t;
-    for (size_t b = 0; b < nb; ++b)
-        if (std::isnan(row[WATER_ROW * b + 4])) return fail(-1, "gamd_water_eval: the handle is frozen by a neighbour-buffer overflow (call gamd_sync_status)");
+    std::vector<double> row;
+    if (int r = potential_eval<WaterPotential>(h, pos_dev, species_dev, box, length_per_nm, f_out_dev, row, stream)) return r;
     if (rows) std::memcpy(rows, row.data(), sizeof(double) * row.size());
     return 0;
 }

@@ -32,29 +32,16 @@
 
 #pragma clang fp contract(off)
 
+#include "gamd_potential_dev.h"
+
 namespace {
 
 constexpr int WC_TILE = 256;
-
-// fp32 edge `c` of box `box`, widened
-__device__ __forceinline__ double water_box_edge(const WaterArgs& a, int box, int c) {
-    if (a.box_edges) return (double)a.box_edges[3 * box + c];
-    if (a.bx.n_boxes <= 1) return (double)a.box[c];
-    const float4 b = a.bx.boxes[3 * box];
-    return (double)(c == 0 ? b.x : (c == 1 ? b.y : b.z));
-}
 
 // fractional coordinate of the reciprocal-space kernels: the position wrapped into [0, L) first, s = (x - L floor(x / L)) / L.
 // Where x + k L is exact in fp32 the wrapped position is the same double for every image k, and so is every phase n.s
 // (x / L alone is not: fl((x + k L) / L) and fl(x / L) + k differ in the last bits).
 __device__ __forceinline__ double water_frac(double x, double L) { return (x - L * floor(x / L)) / L; }
-
-// the fixed tree of k_report_ke over a 256-thread workgroup: shuffle-down 32 .. 1, then (w0 + w1) + (w2 + w3) by thread 0
-__device__ __forceinline__ double water_wave_sum(double v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_down(v, d, 64);
-    return v;
-}
 
 __global__ void __launch_bounds__(256) k_water_pairs(WaterArgs a) {
     if (a.devflags[DEVFLAG_FROZEN]) return;                 // a frame that will be evaluated again
@@ -70,7 +57,7 @@ __global__ void __launch_bounds__(256) k_water_pairs(WaterArgs a) {
     const bool vi = il < npb;
     const long long jb = (long long)s * a.chunk;
     const int je = (int)(jb + a.chunk < (long long)npb ? jb + a.chunk : (long long)npb);
-    const double Lx = water_box_edge(a, box, 0), Ly = water_box_edge(a, box, 1), Lz = water_box_edge(a, box, 2);
+    const double Lx = gamd_box_edge(a, box, 0), Ly = gamd_box_edge(a, box, 1), Lz = gamd_box_edge(a, box, 2);
 
     double xi = 0.0, yi = 0.0, zi = 0.0;
     bool oi = false;
@@ -125,19 +112,13 @@ __global__ void __launch_bounds__(256) k_water_pairs(WaterArgs a) {
                 ec += qq * t;
                 fs = (qq * (t + gs)) * ir2;
                 cnt += 1.0;
-                if (oi && oj) {                             // classical.hip's pair term, op for op
-                    const double s2 = a.sig2 * ir2;
-                    const double s6 = (s2 * s2) * s2;
-                    const double s12 = s6 * s6;
-                    double u = a.eps4 * (s12 - s6) - a.u0;
-                    double ru = -((6.0 * a.eps4) * ((s12 + s12) - s6));       // 6 (4 epsilon) = 24 epsilon bit for bit
+                if (oi && oj) {                             // k_classical_pairs' term
+                    const double2 lj = gamd_lj_term(a.sig2, a.eps4, 6.0 * a.eps4, a.u0, ir2);   // 6 (4 epsilon) = 24 epsilon bit for bit
+                    double u = lj.x, ru = lj.y;
                     if (a.rs >= 0.0 && r > a.rs) {
-                        const double t1 = (r - a.rs) * a.inv_w;
-                        const double t2 = t1 * t1, tm = t1 - 1.0;
-                        const double S = 1.0 - (t2 * t1) * ((6.0 * t1 - 15.0) * t1 + 10.0);
-                        const double dS = ((-30.0 * t2) * (tm * tm)) * a.inv_w;
-                        ru = ru * S + ((u * dS) * r);
-                        u = u * S;
+                        const double2 sw = gamd_lj_switch(a.rs, a.inv_w, r);
+                        ru = ru * sw.x + ((u * sw.y) * r);
+                        u = u * sw.x;
                     }
                     elj += u;
                     fs = fs + -(ru * ir2);
@@ -159,7 +140,7 @@ __global__ void __launch_bounds__(256) k_water_rho(WaterArgs a) {
     const bool vk = k < a.n_k;
     const double nx = vk ? (double)a.kvec[3 * (size_t)k] : 0.0, ny = vk ? (double)a.kvec[3 * (size_t)k + 1] : 0.0,
                  nz = vk ? (double)a.kvec[3 * (size_t)k + 2] : 0.0;
-    const double Lx = water_box_edge(a, box, 0), Ly = water_box_edge(a, box, 1), Lz = water_box_edge(a, box, 2);
+    const double Lx = gamd_box_edge(a, box, 0), Ly = gamd_box_edge(a, box, 1), Lz = gamd_box_edge(a, box, 2);
     double re = 0.0, im = 0.0;
     for (int base = a0 + blockIdx.x * WC_TILE; base < a1; base += gridDim.x * WC_TILE) {
         __syncthreads();                                    // the previous chunk has been read
@@ -200,16 +181,16 @@ __global__ void __launch_bounds__(256) k_water_sk(WaterArgs a) {
             const double* p = a.rho_partial + (((size_t)box * a.rho_blocks + b) * (size_t)a.n_k + (size_t)k) * 2;
             re += p[0]; im += p[1];
         }
-        const double kx = a.two_pi * ((double)a.kvec[3 * (size_t)k] / water_box_edge(a, box, 0));
-        const double ky = a.two_pi * ((double)a.kvec[3 * (size_t)k + 1] / water_box_edge(a, box, 1));
-        const double kz = a.two_pi * ((double)a.kvec[3 * (size_t)k + 2] / water_box_edge(a, box, 2));
+        const double kx = a.two_pi * ((double)a.kvec[3 * (size_t)k] / gamd_box_edge(a, box, 0));
+        const double ky = a.two_pi * ((double)a.kvec[3 * (size_t)k + 1] / gamd_box_edge(a, box, 1));
+        const double kz = a.two_pi * ((double)a.kvec[3 * (size_t)k + 2] / gamd_box_edge(a, box, 2));
         const double k2 = (kx * kx + ky * ky) + kz * kz;
         const double A = k2 <= a.kc2 ? exp(-(k2 * a.inv_4a2)) / k2 : 0.0;     // beyond this box's k_cut: weight zero
         double* out = a.sk + ((size_t)box * (size_t)a.n_k + (size_t)k) * 3;
         out[0] = re; out[1] = im; out[2] = A;
         t = A * (re * re + im * im);
     }
-    t = water_wave_sum(t);
+    t = gamd_wave_sum(t);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = t;
     __syncthreads();
     if (threadIdx.x == 0) a.ublk[(size_t)box * (size_t)a.kblocks + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
@@ -231,9 +212,9 @@ __global__ void __launch_bounds__(256) k_water_recip(WaterArgs a) {
     double six = 0.0, siy = 0.0, siz = 0.0;
     if (vi) {
         const float* p = a.x + 3 * (a0 + (size_t)il);
-        six = water_frac((double)p[0], water_box_edge(a, box, 0));
-        siy = water_frac((double)p[1], water_box_edge(a, box, 1));
-        siz = water_frac((double)p[2], water_box_edge(a, box, 2));
+        six = water_frac((double)p[0], gamd_box_edge(a, box, 0));
+        siy = water_frac((double)p[1], gamd_box_edge(a, box, 1));
+        siz = water_frac((double)p[2], gamd_box_edge(a, box, 2));
     }
     double gx = 0.0, gy = 0.0, gz = 0.0;
     for (long long base = kb; base < ke; base += WC_TILE) {
@@ -268,7 +249,7 @@ __global__ void __launch_bounds__(256) k_water_atoms(WaterArgs a) {
     const int box = blockIdx.y;
     const int npb = a.bx.n_boxes > 1 ? a.bx.n_per_box : a.n;
     const size_t a0 = (size_t)box * (size_t)npb;
-    const double Lx = water_box_edge(a, box, 0), Ly = water_box_edge(a, box, 1), Lz = water_box_edge(a, box, 2);
+    const double Lx = gamd_box_edge(a, box, 0), Ly = gamd_box_edge(a, box, 1), Lz = gamd_box_edge(a, box, 2);
     const double pref = a.coul8pi / ((Lx * Ly) * Lz);
     const double kfx = a.two_pi / Lx, kfy = a.two_pi / Ly, kfz = a.two_pi / Lz;
     double acc[WATER_ACC];
@@ -298,19 +279,13 @@ __global__ void __launch_bounds__(256) k_water_atoms(WaterArgs a) {
         const double z = o ? -2.0 : 1.0;                    // the charge in units of q_h: sums of these are exact
         acc[9] += z; acc[10] += z * z;
         if (a.f) {
-            const double gx = (double)a.f[3 * i], gy = (double)a.f[3 * i + 1], gz = (double)a.f[3 * i + 2];
-            const double dx = gx - cx, dy = gy - cy, dz = gz - cz;
-            acc[3] += (fabs(dx) + fabs(dy)) + fabs(dz);
-            acc[4] += (dx * dx + dy * dy) + dz * dz;
-            const double nc = sqrt((cx * cx + cy * cy) + cz * cz), ng = sqrt((gx * gx + gy * gy) + gz * gz);
-            if (nc == 0.0 || ng == 0.0) acc[8] += 1.0;
-            else acc[5] += ((gx * cx + gy * cy) + gz * cz) / (ng * nc);
-            acc[6] += nc; acc[7] += ng;
+            gamd_force_error((double)a.f[3 * i], (double)a.f[3 * i + 1], (double)a.f[3 * i + 2], cx, cy, cz, acc[3], acc[4], acc[5],
+                             acc[6], acc[7], acc[8]);
         }
     }
 #pragma unroll
     for (int q = 0; q < WATER_ACC; ++q) {
-        const double v = water_wave_sum(acc[q]);
+        const double v = gamd_wave_sum(acc[q]);
         if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][q] = v;
     }
     __syncthreads();
@@ -333,7 +308,7 @@ __global__ void k_water_final(WaterArgs a) {
     }
     double us = 0.0;
     for (int b = 0; b < a.kblocks; ++b) us += a.ublk[(size_t)box * (size_t)a.kblocks + b];
-    const double V = (water_box_edge(a, box, 0) * water_box_edge(a, box, 1)) * water_box_edge(a, box, 2);
+    const double V = (gamd_box_edge(a, box, 0) * gamd_box_edge(a, box, 1)) * gamd_box_edge(a, box, 2);
     double* row = a.rows + ((size_t)a.slot * (size_t)nb + (size_t)box) * WATER_ROW;
     row[0] = 0.5 * s[0];                                    // every pair sits in two rows
     row[1] = 0.5 * s[1];

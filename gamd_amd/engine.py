@@ -926,20 +926,25 @@ class GamdForce:
         """Step count and rows back to zero; parameters and configuration stay."""
         check(self._lib.gamd_classical_reset(self._h), "gamd_classical_reset")
 
-    def classical_read(self, forces: bool = False) -> "RunClassical":
-        """Synchronise and fetch what the classical observer has logged since it was configured or reset; ``forces``: also
-        the classical forces of the last sample."""
+    def _potential_read(self, entry: str, width: int, cls, forces: bool):
+        """The rows, steps, drop count and (``forces``) last forces of an observer with a potential, through its read call
+        ``entry`` (row width ``width``), as a ``cls``."""
         n_rows, dropped = C.c_int64(), C.c_int64()
-        rd = self._lib.gamd_classical_read
-        check(rd(self._h, self._stream(), None, None, 0, C.byref(n_rows), C.byref(dropped), None, 0), "gamd_classical_read")
+        rd = getattr(self._lib, entry)
+        check(rd(self._h, self._stream(), None, None, 0, C.byref(n_rows), C.byref(dropped), None, 0), entry)
         rows = n_rows.value
         steps = np.zeros(rows, dtype=np.int64)
-        data = np.zeros((rows, self.n_boxes, _lib.CLASSICAL_ROW), dtype=np.float64)
+        data = np.zeros((rows, self.n_boxes, width), dtype=np.float64)
         fcl = np.full((self.n_total, 3), np.nan, dtype=np.float64) if forces else None
         vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
         check(rd(self._h, self._stream(), vp(steps), vp(data), rows, C.byref(n_rows), C.byref(dropped), vp(fcl),
-                 0 if fcl is None else fcl.size), "gamd_classical_read")
-        return RunClassical(steps, data, self.n, dropped.value, fcl)
+                 0 if fcl is None else fcl.size), entry)
+        return cls(steps, data, self.n, dropped.value, fcl)
+
+    def classical_read(self, forces: bool = False) -> "RunClassical":
+        """Synchronise and fetch what the classical observer has logged since it was configured or reset; ``forces``: also
+        the classical forces of the last sample."""
+        return self._potential_read("gamd_classical_read", _lib.CLASSICAL_ROW, RunClassical, forces)
 
     def classical_forces(self, pos: ArrayLike, box=None, length_per_nm: float = 0.0):
         """The classical potential of the last ``classical_configure`` (with the defaults and interval 0 when there was
@@ -1002,17 +1007,7 @@ class GamdForce:
     def water_classical_read(self, forces: bool = False) -> "RunWaterClassical":
         """Synchronise and fetch what the water classical observer has logged since it was configured or reset; ``forces``:
         also the classical forces of the last sample."""
-        n_rows, dropped = C.c_int64(), C.c_int64()
-        rd = self._lib.gamd_water_read
-        check(rd(self._h, self._stream(), None, None, 0, C.byref(n_rows), C.byref(dropped), None, 0), "gamd_water_read")
-        rows = n_rows.value
-        steps = np.zeros(rows, dtype=np.int64)
-        data = np.zeros((rows, self.n_boxes, _lib.WATER_ROW), dtype=np.float64)
-        fcl = np.full((self.n_total, 3), np.nan, dtype=np.float64) if forces else None
-        vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
-        check(rd(self._h, self._stream(), vp(steps), vp(data), rows, C.byref(n_rows), C.byref(dropped), vp(fcl),
-                 0 if fcl is None else fcl.size), "gamd_water_read")
-        return RunWaterClassical(steps, data, self.n, dropped.value, fcl)
+        return self._potential_read("gamd_water_read", _lib.WATER_ROW, RunWaterClassical, forces)
 
     def water_classical_forces(self, pos: ArrayLike, species, box=None, length_per_nm: float = 0.0):
         """The water classical potential of the last ``water_classical_configure`` (with the defaults and interval 0 when

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Everything the three run observers hand back, for four short runs, as one .npz — to set two builds of the library against
+"""Everything the five run observers hand back, for five short runs, as one .npz — to set two builds of the library against
 each other bit for bit.
 
     GAMD_LIB=/path/to/libgamd_hip.so python tools/observer_dump.py out.npz      (one process per library: GAMD_LIB is read
@@ -7,17 +7,24 @@ each other bit for bit.
 
 The runs use the systems of tests/test_gpu_report.py (_Case).  The reporter, the recorder and the structure sampler are armed
 together with the co-prime intervals 2, 3 and 5, so single, double and triple samples of one step all occur; the recorder
-keeps 8 frames of 20, so frames are dropped as well.
-  a  LJ, 258 atoms, BAOAB in skin mode, two md_run calls of 30 steps
+keeps 8 frames of 20, so frames are dropped as well.  The observer with a potential of the handle's kind (classical_configure
+on LJ, water_classical_configure on water; shifted and switched) samples at the interval 7 into a log of 3 rows, so it meets
+each of the others and drops rows.
+  a  LJ, 258 atoms, BAOAB in skin mode, two md_run calls of 30 steps; then classical_forces on the final positions, in bohr
   b  the same under the Nose-Hoover chain
   c  64 rigid TIP3P molecules with species, exclude_same_molecule, BAOAB
   d  two LJ boxes whose edge buffer is too small: the run freezes on the device and gamd_sync_status resumes it
-Written per case: final x, v, f and every attribute of report_read(), traj_read() and structure_read().
+  e  two boxes of 86 rigid TIP3P molecules (258 atoms: two row tiles, molecule 85 straddles the tile edge at atom 256) with
+     different positions and edges, 16 steps, the water classical observer alone at the interval 3; then
+     water_classical_forces on the final positions, in bohr
+Written per case: final x, v, f and every attribute of report_read(), traj_read(), structure_read() and
+classical_read(forces=True) / water_classical_read(forces=True); for a and e what the call outside the run returned.
 """
 import os
 import sys
 
 import numpy as np
+import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "oracle")):
@@ -31,14 +38,73 @@ def _arm(eng, case):
     eng.report_configure(2, rdf_bins=64, rdf_rmax=0.0 if water else 5.0, exclude_same_molecule=water, **case.report_kw())
     eng.traj_configure(3, max_frames=8, fields=("x", "v", "f", "image"), n_lags=4, subtract_com=True)
     eng.structure_configure(5, rdf_bins=64, sk_n2max=9, exclude_same_molecule=water)
+    if water:
+        eng.water_classical_configure(7, max_samples=3, **_water_kw(case.box))
+    else:
+        eng.classical_configure(7, max_samples=3)        # the defaults: shifted, switched over the last sigma
 
 
-def _collect(out, name, eng, x, v, f, extra=None):
+def _water_kw(box, unit=1.0):
+    r_cut = 0.48 * float(np.min(box))
+    return dict(sigma_o=3.15075 * unit, r_cut=r_cut * unit, r_switch=(r_cut - 1.0) * unit, shift=True, alpha=4.0 / r_cut / unit,
+                k_cut=8.0 * 4.0 / r_cut / unit)
+
+
+def _collect(out, name, eng, x, v, f, extra=None, observers=("report", "traj", "structure"), outside=None):
+    water = eng.cfg.kind != "lj"
     got = {"x": x.cpu().numpy(), "v": v.cpu().numpy(), "f": f.cpu().numpy(), **(extra or {})}
-    for who, obj in (("report", eng.report_read()), ("traj", eng.traj_read()), ("structure", eng.structure_read())):
+    reads = [(who, getattr(eng, who + "_read")()) for who in observers]
+    reads.append(("water_classical", eng.water_classical_read(forces=True)) if water else ("classical", eng.classical_read(forces=True)))
+    for who, obj in reads:
         got.update({f"{who}.{k}": val for k, val in vars(obj).items() if val is not None})
+    if outside:                                          # behind the reads: the call leaves its forces where forces=True reads them
+        got.update(outside(eng))
     out.update({f"{name}/{k}": np.asarray(val) for k, val in got.items()})
     eng.close()
+
+
+def _bohr():
+    from gamd_amd import workloads as wl
+    return wl.BOHR_PER_NM, float(np.float32(wl.BOHR_PER_NM)) / 10.0
+
+
+def _lj_outside(case, x):
+    def call(eng):
+        length, unit = _bohr()
+        eng.classical_configure(0, sigma=3.4 * unit, r_cut=10.2 * unit, r_switch=6.8 * unit)
+        f, e, w, c = eng.classical_forces((x.double() * unit).float(), box=case.box * unit, length_per_nm=length)
+        return {"eval.forces": f.cpu().numpy(), "eval.energy": e, "eval.virial": w, "eval.pairs": c}
+    return call
+
+
+def _water_two_boxes(out):
+    """case e"""
+    import gamd_oracle as orc
+    from gamd_amd import workloads as wl
+    from gamd_amd.engine import GamdForce
+    from test_gpu_water_classical import _Water
+    case = _Water(n_mol=86)
+    L = float(case.box)
+    boxes = np.array([[L, L, L], [L, 1.03 * L, 1.01 * L]], dtype=np.float32)
+    other = wl.water_box(86, seed=7, jitter=0.0, wrap=False)[0]
+    pairs, _ = orc.water_constraints(case.n, wl.TIP3P_R_OH, wl.TIP3P_R_HH)
+    mm = np.where(case.species == 1, wl.MASS_O, wl.MASS_H).astype(np.float64).reshape(-1, 1)
+    v1 = np.random.default_rng(16).normal(0, 1.0, (case.n, 3)) * 10.0 * np.sqrt(wl.KB * 300.0 / mm)
+    v1 = orc.rattle_velocities(other, v1, (1.0 / mm).reshape(-1), pairs)
+    species = np.tile(case.species, 2)
+    eng = GamdForce(case.sd, case.n, L, case.rc, n_boxes=2, **case.eng_kw)       # the edges differ from the first call on
+    x = torch.from_numpy(np.concatenate([case.pos, other])).float().cuda()
+    v = torch.from_numpy(np.concatenate([case.v0, v1])).float().cuda()
+    f = eng.forward(x, box=boxes, species=species, denormalize=True).clone()
+    eng.water_classical_configure(3, max_samples=3, **_water_kw(boxes))
+    eng.md_run(x, v, f, 16, gamma_per_ps=25.0, seed=11, box=boxes, **{**case.md, "species": species})
+
+    def outside(eng):
+        length, unit = _bohr()
+        eng.water_classical_configure(0, **_water_kw(boxes, unit))
+        fo, rd = eng.water_classical_forces((x.double() * unit).float(), species, box=boxes * unit, length_per_nm=length)
+        return {"eval.forces": fo.cpu().numpy(), **{f"eval.{k}": val for k, val in vars(rd).items() if val is not None}}
+    _collect(out, "e", eng, x, v, f, observers=(), outside=outside)
 
 
 def dump(path):
@@ -51,7 +117,7 @@ def dump(path):
         chain = case.run(eng, x, v, f, STEPS)
         if name != "c":
             case.run(eng, x, v, f, STEPS, first_step=STEPS, chain=chain)
-        _collect(out, name, eng, x, v, f)
+        _collect(out, name, eng, x, v, f, outside=_lj_outside(case, x) if name == "a" else None)
     case = _Case("lj", n_boxes=2)
     big, x, v, f = case.make()                  # the start forces from an ample handle, as the overflow tests do
     big.close()
@@ -60,6 +126,7 @@ def dump(path):
     case.run(eng, x, v, f, STEPS, sync=False)
     _collect(out, "d", eng, x, v, f, {"resumed": eng.sync_status()})
     assert out["d/resumed"] == 1, "case d was meant to outgrow its edge buffer"
+    _water_two_boxes(out)
     np.savez(path, **out)
     print(f"{path}: {len(out)} entries from {os.environ.get('GAMD_LIB', 'the default library')}")
 
@@ -71,6 +138,8 @@ def compare(pa, pb):
         if not (a[k].dtype == b[k].dtype and a[k].shape == b[k].shape and a[k].tobytes() == b[k].tobytes()):
             bad.append(k)
     nonzero = sum(1 for k in a.files if a[k].size and np.any(a[k]))
+    zero = [k for k in sorted(a.files) if "classical." in k and not (a[k].size and np.any(a[k]))]
+    print("all-zero or empty entries of the observers with a potential: " + (", ".join(zero) or "none"))
     print(f"{len(a.files)} / {len(b.files)} entries ({nonzero} with a non-zero value), {len(bad)} differ" + "".join("\n  " + k for k in bad))
     return 1 if bad else 0
 
