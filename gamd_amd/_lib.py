@@ -69,6 +69,7 @@ class GamdWaterParams(C.Structure):
 CLASSICAL_ROW = 9                                           # GAMD_CLASSICAL_ROW: doubles per box and row of gamd_classical_read
 WATER_ROW = 12                                              # GAMD_WATER_ROW: doubles per box and row of gamd_water_read
 TRAJ_FIELDS = {"x": 1, "v": 2, "f": 4, "image": 8}          # GAMD_TRAJ_*
+FORCE_SOURCE = {"network": 0, "classical": 1}               # GAMD_FORCE_*
 
 
 # every symbol include/gamd_hip.h declares: name -> (restype, argtypes)
@@ -110,6 +111,7 @@ SYMBOLS = {
     "gamd_classical_reset": (_i32, [_vp]),
     "gamd_classical_read": (_i32, [_vp, _vp, _vp, _vp, _i64, C.POINTER(_i64), C.POINTER(_i64), _vp, _i64]),
     "gamd_classical_eval": (_i32, [_vp, _vp, C.POINTER(C.c_float), C.c_float, _vp, _vp, _vp, _vp, _vp]),
+    "gamd_md_force_source": (_i32, [_vp, _i32]),
     "gamd_water_configure": (_i32, [_vp, C.POINTER(GamdWaterParams)]),
     "gamd_water_reset": (_i32, [_vp]),
     "gamd_water_read": (_i32, [_vp, _vp, _vp, _vp, _i64, C.POINTER(_i64), C.POINTER(_i64), _vp, _i64]),

@@ -332,7 +332,8 @@ int fill_rigid(const gamd_handle* h, int rigid_water, float mass_o, float mass_h
 
 int enqueue_forward(gamd_handle* h, const float* pos_dev, const uint8_t* species_dev, float* out_norm_dev,
                     float* out_denorm_dev, hipStream_t st, hipEvent_t* evs, int* n_ev, std::vector<std::string>* labels,
-                    const EdgeList* el = nullptr, const MdFuse* fuse = nullptr, bool copy_counters = true, bool l0_reuse = false) {
+                    const EdgeList* el = nullptr, const MdFuse* fuse = nullptr, bool copy_counters = true, bool l0_reuse = false,
+                    bool drive = false) {
     auto mark = [&](const char* label) {
         if (evs) { (void)hipEventRecord(evs[*n_ev], st); ++*n_ev; labels->push_back(label); }
     };
@@ -367,6 +368,16 @@ int enqueue_forward(gamd_handle* h, const float* pos_dev, const uint8_t* species
         h->cand_valid = true;
     } else if ((r = launch_neighbor_build(na, st))) return fail(-1, "neighbor build launch failed (%d)", r);
     mark("neighbor_build");
+
+    // classical force source (a step of an enqueued MD run, gamd_md_force_source): the neighbour stage above stays — the fused
+    // integrator halves, the observers' edge list and pos_s, and the freeze / resume machinery hang on it — and the potential's
+    // two launches stand where encoder, conv layers and decoder would
+    if (drive) {
+        if ((r = drive_enqueue(h))) return r;
+        if (copy_counters)
+            HIP_TRY(hipMemcpyAsync(h->counters_host, h->cur_counters, sizeof(int) * CNT_COUNT, hipMemcpyDeviceToHost, st));
+        return 0;
+    }
 
     EncArgs ea{};
     ea.counters = h->cur_counters;
@@ -611,6 +622,7 @@ int step_event(gamd_handle* h, hipStream_t st, bool closes = false) {
 // steps [s_begin, n_steps) of the pending MD run; skip_first: the first half of step s_begin has already been done
 int enqueue_md_steps(gamd_handle* h, long long s_begin, bool skip_first) {
     MdPending& p = h->pending;
+    const bool drive = h->force_source == GAMD_FORCE_CLASSICAL;      // cannot change while the run is pending
     int r;
     // Skin mode, BAOAB (free atoms or rigid water): the B of step s-1 and the B A O A of step s ride in the first kernel of step s's force
     // evaluation (k_step_small / k_skin_check): 2 launches less per step; the last B is launched on its own.
@@ -644,7 +656,7 @@ int enqueue_md_steps(gamd_handle* h, long long s_begin, bool skip_first) {
             }
             const MdFuse fuse{&p.m, do_second, do_first};
             if ((r = enqueue_forward(h, p.x, p.species, nullptr, p.f, p.st, nullptr, nullptr, nullptr, nullptr, &fuse,
-                                     s + 1 == p.n_steps, s > s_begin)))
+                                     s + 1 == p.n_steps, s > s_begin, drive)))
                 return r;
             if (s + 1 < p.n_steps && observers_sampled(h, s)) {        // a sampled step completes its B before the sample
                 if ((r = launch_baoab_second(p.m, p.st))) return fail(-1, "integrator launch failed (%d)", r);
@@ -666,12 +678,12 @@ int enqueue_md_steps(gamd_handle* h, long long s_begin, bool skip_first) {
             p.m.step = p.first_step + (unsigned long long)s;
             p.m.step_index = (int)s;
             if (first && (r = launch_baoab_first(p.m, p.st))) return fail(-1, "integrator launch failed (%d)", r);
-            if ((r = enqueue_forward(h, p.x, p.species, nullptr, p.f, p.st, nullptr, nullptr, nullptr, nullptr, nullptr, last, s > s_begin))) return r;
+            if ((r = enqueue_forward(h, p.x, p.species, nullptr, p.f, p.st, nullptr, nullptr, nullptr, nullptr, nullptr, last, s > s_begin, drive))) return r;
             if ((r = launch_baoab_second(p.m, p.st))) return fail(-1, "integrator launch failed (%d)", r);
         } else {
             p.a.step_index = (int)s;
             if (first && (r = launch_nhc_first(p.a, p.st))) return fail(-1, "integrator launch failed (%d)", r);
-            if ((r = enqueue_forward(h, p.x, p.species, nullptr, p.f, p.st, nullptr, nullptr, nullptr, nullptr, nullptr, last, s > s_begin))) return r;
+            if ((r = enqueue_forward(h, p.x, p.species, nullptr, p.f, p.st, nullptr, nullptr, nullptr, nullptr, nullptr, last, s > s_begin, drive))) return r;
             if ((r = launch_nhc_second(p.a, p.st))) return fail(-1, "integrator launch failed (%d)", r);
         }
         if ((r = observers_enqueue(h, s))) return r;
@@ -1571,6 +1583,7 @@ int32_t gamd_md_run(gamd_handle* h, float* x_dev, float* v_dev, float* f_dev, co
     if (n_steps < 0 || n_steps > 0x3fffffff) return fail(-22, "n_steps out of range");
     if ((r = check_model_inputs(h, species_dev))) return r;
     if ((r = observers_check_run(h, box, species_dev))) return r;
+    if (h->force_source == GAMD_FORCE_CLASSICAL && (r = drive_check_run(h, box, species_dev))) return r;
     DeviceGuard guard(h->dev);
     InitStream init((hipStream_t)stream);
     if ((r = set_box(h, box, (hipStream_t)stream))) return r;
@@ -1592,6 +1605,17 @@ int32_t gamd_md_run(gamd_handle* h, float* x_dev, float* v_dev, float* f_dev, co
     return start_run(h, x_dev, f_dev, species_dev, box, n_steps, st);
 }
 
+int32_t gamd_md_force_source(gamd_handle* h, int32_t source) {
+    if (!h) return fail(-22, "null handle");
+    if (source != GAMD_FORCE_NETWORK && source != GAMD_FORCE_CLASSICAL)
+        return fail(-22, "unknown force source %d (GAMD_FORCE_NETWORK = 0, GAMD_FORCE_CLASSICAL = 1)", (int)source);
+    if (h->pending.active) return fail(-22, "an MD run is still enqueued: call gamd_sync_status before gamd_md_force_source");
+    if (source == GAMD_FORCE_CLASSICAL)
+        if (int r = drive_check_source(h)) return r;
+    h->force_source = source;
+    return 0;
+}
+
 int32_t gamd_md_run_nhc(gamd_handle* h, float* x_dev, float* v_dev, float* f_dev, const uint8_t* species_dev,
                         const float* box, const gamd_nhc_params* p, double* chain_state_dev, int64_t n_steps, void* stream) {
     int r;
@@ -1607,6 +1631,7 @@ int32_t gamd_md_run_nhc(gamd_handle* h, float* x_dev, float* v_dev, float* f_dev
     const double* ys = p->num_yoshidasuzuki == 1 ? YS1 : p->num_yoshidasuzuki == 3 ? YS3 : p->num_yoshidasuzuki == 5 ? YS5 : nullptr;
     if (!ys) return fail(-22, "Invalid Yoshida-Suzuki value. Allowed values are: 1,3,5");
     if ((r = observers_check_run(h, box, species_dev))) return r;
+    if (h->force_source == GAMD_FORCE_CLASSICAL && (r = drive_check_run(h, box, species_dev))) return r;
     DeviceGuard guard(h->dev);
     InitStream init((hipStream_t)stream);
     if ((r = set_box(h, box, (hipStream_t)stream))) return r;

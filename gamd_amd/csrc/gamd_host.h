@@ -126,6 +126,14 @@ void observers_begin_run(gamd_handle* h, const float* box, const uint8_t* specie
 // Does step s carry a sample?  Its second half must then be complete in front of observers_enqueue(h, s); both walk one list.
 bool observers_sampled(const gamd_handle* h, long long s);
 int observers_enqueue(gamd_handle* h, long long s);
+// ---- the classical force source (gamd_md_force_source; observe.hip, drive.hip) ------------------------------------------------
+// may this handle take GAMD_FORCE_CLASSICAL (a potential of its kind with parameters set)?  0, or -22 with the message
+int drive_check_source(gamd_handle* h);
+// at the top of a classical-source run, in front of any device work: the potential's box rule and its work buffers (nothing is
+// allocated inside a run), whether or not its observer is armed
+int drive_check_run(gamd_handle* h, const float* box, const uint8_t* species_dev);
+// the force evaluation of one step of the pending run, behind the neighbour stage: the pending run's f from its x
+int drive_enqueue(gamd_handle* h);
 
 struct gamd_handle {
     gamd_config cfg{};
@@ -190,6 +198,7 @@ struct gamd_handle {
     const float* feat_dev = nullptr;   // gamd_set_node_features
     const uint8_t* rigid_checked = nullptr;   // species pointer whose O,H,H layout has been validated
     MdPending pending;
+    int force_source = GAMD_FORCE_NETWORK;   // gamd_md_force_source: where the forces of gamd_md_run / gamd_md_run_nhc come from
     Observers* obs = nullptr;       // observe.hip (observers_new / observers_free)
     bool has_bonds = false;
 

@@ -601,6 +601,13 @@ struct ClassicalArgs {
 };
 int launch_classical(const ClassicalArgs& a, hipStream_t st);
 
+// ---- classical force source (drive.hip) -------------------------------------------------------------
+// One force evaluation of a classical-source step of an enqueued MD run (gamd_md_force_source): the pair pass of classical.hip
+// (tiles, slices and arithmetic of k_classical_pairs; forces only) into a.part, then per atom the slice partials added in order
+// from 0, f_cl = F * len to a.f_cl and (float)f_cl to f_out ([n][3], the caller's atom order).  a.f, a.blk, a.rows, a.steps,
+// a.slot and a.g are not used.  Two launches, plain stores.
+int launch_classical_drive(const ClassicalArgs& a, float* f_out, hipStream_t st);
+
 // ---- water classical potential (water_classical.hip) ------------------------------------------------
 // One sample of an enqueued MD run (gamd_water_configure) or one gamd_water_eval call: 3-site water in the caller's order
 // O,H,H (molecule = index / 3, O = species != 0, q_O = -2 q_H), O-O Lennard-Jones as in classical.hip plus a plain Ewald sum

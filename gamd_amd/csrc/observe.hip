@@ -402,6 +402,8 @@ struct LjPotential {
     static void species(Args&, const uint8_t*) {}
     static int launch(const Args& a, hipStream_t st) { return launch_classical(a, st); }
     static int check_box(gamd_handle* h, const float* box, const uint8_t*) { return potential_check_box(h, state(h), who, box); }
+    // a force source as well (potential_drive): the forces alone, rounded to fp32, into the run's f
+    static int drive(const Args& a, float* f_out, hipStream_t st) { return launch_classical_drive(a, f_out, st); }
 };
 
 struct WaterPotential {
@@ -459,6 +461,19 @@ int potential_sample(gamd_handle* h, long long s) {
     a.slot = pl.clock.ordinal(s);
     if (int r = P::launch(a, p.st)) return fail(-1, "%s observer launch failed (%d)", P::who, r);
     pl.evaluated = true;
+    return 0;
+}
+
+// the force evaluation of a classical-source step of the pending run (gamd_md_force_source), behind the step's neighbour
+// stage: the potential's forces at the run's x, rounded to fp32, into the run's f.  No row, no clock: every step is driven.
+template <typename P>
+int potential_drive(gamd_handle* h, hipStream_t st) {
+    const MdPending& p = h->pending;
+    typename P::Args a = P::args(h, pending_particles(p).len);
+    for (int d = 0; d < 3; ++d) a.box[d] = h->box[d];
+    a.x = p.x; P::species(a, p.species);
+    if (int r = P::drive(a, p.f, st)) return fail(-1, "%s force source launch failed (%d)", P::who, r);
+    P::state(h).evaluated = true;
     return 0;
 }
 
@@ -687,6 +702,27 @@ int observers_enqueue(gamd_handle* h, long long s) {
             if (int r = ob.sample(h, s)) return r;
     return 0;
 }
+
+// ---- the classical force source (gamd_host.h): Lennard-Jones only; water becomes a second traits entry here ---------------------
+int drive_check_source(gamd_handle* h) {
+    if (h->cfg.kind != GAMD_KIND_LJ)
+        return fail(-22, "gamd_md_force_source: a GAMD_KIND_WATER handle has no classical force source (the Lennard-Jones potential "
+                         "has no electrostatics; GAMD_KIND_LJ handles only)");
+    if (!LjPotential::state(h).params_set)
+        return fail(-22, "gamd_md_force_source: the classical source needs the parameters of a gamd_classical_configure call (interval 0 will do)");
+    return 0;
+}
+
+int drive_check_run(gamd_handle* h, const float* box, const uint8_t* species_dev) {
+    if (int r = drive_check_source(h)) return r;
+    if (int r = LjPotential::check_box(h, box, species_dev)) return r;
+    DeviceGuard guard(h->dev);
+    InitStream init(h->init_stream);
+    if (bufs_ensure_work(LjPotential::bufs(h))) return fail(-12, "%s potential allocation failed", LjPotential::who);
+    return 0;
+}
+
+int drive_enqueue(gamd_handle* h) { return potential_drive<LjPotential>(h, h->pending.st); }
 
 static_assert(sizeof(gamd_report_params) == 40 && offsetof(gamd_report_params, ndf) == 16 && offsetof(gamd_report_params, rdf_rmax) == 28,
               "gamd_report_params layout is part of the C ABI (gamd_amd/_lib.py mirrors it)");

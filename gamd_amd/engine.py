@@ -722,7 +722,9 @@ class GamdForce:
         unit of x/v/box (10 = Angstrom, the default; 18.8972613 = bohr for the DFT model).
         ``remove_cm_motion``: subtract the centre-of-mass velocity at the top of every step like the CMMotionRemover that
         hack_integrator.py:142 runs when the OpenMM System has one; default True with ``rigid_water`` (the water drivers'
-        openmmtools WaterBox carries one), False otherwise (the LJ fluid does not)."""
+        openmmtools WaterBox carries one), False otherwise (the LJ fluid does not).
+        With the classical force source (``md_force_source("classical")``) ``f`` must hold the classical forces at ``x`` on
+        entry: ``classical_forces(x)[0].float()``."""
         self._md_state(x, v, f)
         s = self._dev_species(species)
         if remove_cm_motion is None:
@@ -749,7 +751,9 @@ class GamdForce:
         ``remove_cm_motion`` says whether it does: default True with ``rigid_water`` (the water drivers build an
         openmmtools WaterBox, whose System carries one), False otherwise (the LJ drivers' ndf is 3N).  When it does, the
         centre-of-mass velocity is also subtracted on the device where hack_integrator.py:271-272 does it: behind
-        propagateNHC() of the first half (the chain sees the velocities as they are), in front of the kick."""
+        propagateNHC() of the first half (the chain sees the velocities as they are), in front of the kick.
+        With the classical force source (``md_force_source("classical")``) ``f`` must hold the classical forces at ``x`` on
+        entry: ``classical_forces(x)[0].float()``."""
         self._md_state(x, v, f)
         reset = chain_state is None
         if reset:
@@ -773,6 +777,25 @@ class GamdForce:
         if sync:
             self.last_status = check(self._lib.gamd_sync_status(self._h, self._stream()), "gamd_sync_status")
         return chain_state
+
+    # -- force source of md_run / md_run_nhc (the classical run next to the GNN run) ---------------------------------
+    def md_force_source(self, source: str) -> None:
+        """Where the forces of ``md_run`` / ``md_run_nhc`` come from: ``"network"`` (the default) or ``"classical"``, the
+        Lennard-Jones potential of the last ``classical_configure`` (interval 0 will do), evaluated on all pairs in double
+        on the device at every step and rounded to fp32 into ``f`` — bit for bit ``classical_forces(x)[0].float()``.  Sticky
+        until set again; ``forward`` and the other force calls evaluate the network whatever the source.  Integrators,
+        observers, skin mode, several boxes and the overflow resume work as in a network-driven run.  LJ models only;
+        2 r_cut must not exceed a box edge.  Replaces the OpenMM run of the reference's data generator
+        (dataset/generate_lj_data.py:74-107).  O(N^2) per step and box."""
+        if source not in _lib.FORCE_SOURCE:
+            raise ValueError(f"source must be one of {sorted(_lib.FORCE_SOURCE)}")
+        check(self._lib.gamd_md_force_source(self._h, _lib.FORCE_SOURCE[source]), "gamd_md_force_source")
+        self._force_source = source
+
+    @property
+    def force_source(self) -> str:
+        """The force source of ``md_run`` / ``md_run_nhc`` as last set: ``"network"`` or ``"classical"``."""
+        return getattr(self, "_force_source", "network")
 
     # -- run reporter (the drivers' StateDataReporter log and a g(r) histogram, taken inside enqueued runs) ----------
     def report_configure(self, interval: int, max_samples: int = 0, ndf: Optional[float] = None, rdf_bins: int = 0,

@@ -494,6 +494,29 @@ int32_t gamd_classical_read(gamd_handle* h, void* stream, int64_t* steps, double
 int32_t gamd_classical_eval(gamd_handle* h, const float* pos_dev, const float* box, float length_per_nm, double* f_out_dev,
                             double* energy, double* virial, double* pairs, void* stream);
 
+/* Force source of an enqueued run: the classical run next to the GNN run — the reference's LJ data generator is a
+ * Nose-Hoover-chain run under the classical force (dataset/generate_lj_data.py:74-107), and lj.ipynb cells 5-6 plot the
+ * GNN-driven logs against its log.  Sticky per handle, GAMD_FORCE_NETWORK by default.  It decides where the forces of
+ * gamd_md_run and gamd_md_run_nhc come from, the resume inside gamd_sync_status included; gamd_forces*, gamd_forces_host,
+ * gamd_forces_edges and gamd_profile evaluate the network whatever the source.
+ * GAMD_FORCE_CLASSICAL: every step runs the neighbour stage as before (skin check, exact re-filter, fused integrator halves,
+ * counters, overflow detection — the observers and the freeze / resume machinery hang on it) and then, in place of encoder,
+ * conv layers and decoder, two launches: the pair pass of the classical observer on the run's x and box (same tiles, slices
+ * and arithmetic) and a per-atom pass that adds an atom's slice partials in order from 0, forms f_cl = F * length_per_nm in
+ * double and stores (float)f_cl, rounded to nearest, into the run's f in the caller's atom order.  f is bit for bit the fp32
+ * rounding of what gamd_classical_eval gives on the same positions, run after run (no floating-point atomics, no contraction,
+ * plain stores: a step enqueued again after a freeze writes the same bits).  On entry f must hold the classical forces at x
+ * (gamd_classical_eval's, rounded to fp32).  The parameters are those of the last gamd_classical_configure, which may change
+ * them between runs while the source stays; the classical observer may be armed or not (a step that is driven and sampled is
+ * evaluated twice, to the same bits).  O(N^2) per step and box.
+ * Precondition of a classical-source run: 2 * r_cut <= the shortest edge of every box; otherwise gamd_md_run /
+ * gamd_md_run_nhc return -22 (the message names r_cut) before anything is enqueued.  The potential's work buffers are ensured
+ * there as well (-12 when that fails): nothing is allocated inside a run.  The handle must be finalized like for every run.
+ * -22, with a message naming the reason: a null handle, an unknown source, while a run is pending, GAMD_FORCE_CLASSICAL on a
+ * GAMD_KIND_WATER handle, GAMD_FORCE_CLASSICAL before an accepted gamd_classical_configure (interval 0 will do). */
+enum { GAMD_FORCE_NETWORK = 0, GAMD_FORCE_CLASSICAL = 1 };
+int32_t gamd_md_force_source(gamd_handle* h, int32_t source);
+
 /* Water classical observer: the classical potential of 3-site water — the reference logs OpenMM's potential energy for its
  * TIP3P data and trains on getForces (dataset/generate_tip3p_data.py:91-103), and its rollout driver fetches classical forces
  * beside the network's (water/test_script/test_nosehoover_hb.py:107).  GAMD_KIND_WATER handles, atoms in the caller's order

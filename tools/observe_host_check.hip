@@ -3,11 +3,11 @@
 // be built with the host sanitizers.  No HIP call is made.
 //
 //   cd gamd_amd/csrc && S="-Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=all" &&
-//   for f in report traj structure classical water_classical; do
+//   for f in report traj structure classical water_classical drive; do
 //     hipcc --offload-arch=gfx950 -O1 -g -std=c++17 $S -c $f.hip -o /tmp/ohc_$f.o || break; done &&
 //   hipcc --offload-arch=gfx950 -O1 -g -std=c++17 $S -c ../../tools/observe_host_check.hip -o /tmp/ohc_main.o &&
 //   hipcc -fsanitize=address,undefined /tmp/ohc_main.o /tmp/ohc_report.o /tmp/ohc_traj.o /tmp/ohc_structure.o /tmp/ohc_classical.o \
-//     /tmp/ohc_water_classical.o -o /tmp/ohc && /tmp/ohc
+//     /tmp/ohc_water_classical.o /tmp/ohc_drive.o -o /tmp/ohc && /tmp/ohc
 #include "../gamd_amd/csrc/observe.hip"
 
 #include <cstdio>
@@ -221,7 +221,28 @@ static void check_args() {
     observers_free(&h);
 }
 
+// the classical force source: which handles may take it, and the run check's refusal in front of any device work
+static void check_drive() {
+    gamd_handle h;
+    h.n_boxes = 2; h.n_per_box = 258; h.n = 516; h.cfg.kind = GAMD_KIND_WATER;
+    h.obs = observers_new();
+    REQUIRE(h.force_source == GAMD_FORCE_NETWORK);
+    REQUIRE(drive_check_source(&h) == -22 && std::strstr(g_err, "GAMD_KIND_WATER"));
+    h.cfg.kind = GAMD_KIND_LJ;
+    REQUIRE(drive_check_source(&h) == -22 && std::strstr(g_err, "gamd_classical_configure"));
+    Classical& cl = h.obs->cl;
+    cl.sigma = 3.4; cl.epsilon = 0.995792; cl.r_cut = 10.2; cl.r_switch = 6.8; cl.shift = 1; cl.params_set = true;
+    REQUIRE(drive_check_source(&h) == 0);
+    const float box[6] = {27.27f, 27.27f, 27.27f, 27.27f, 20.39f, 27.27f};     // box 1, edge 1 is below 2 r_cut = 20.4
+    REQUIRE(drive_check_run(&h, box, nullptr) == -22 && std::strstr(g_err, "r_cut") && std::strstr(g_err, "box[1][1]"));
+    cl.params_set = false;
+    REQUIRE(drive_check_run(&h, box, nullptr) == -22 && std::strstr(g_err, "gamd_classical_configure"));
+    REQUIRE(!cl.part.p && !cl.f_cl.p);                                          // a refused run allocated nothing
+    observers_free(&h);
+}
+
 int main() {
+    check_drive();
     check_clock();
     check_kvectors();
     check_tables();
