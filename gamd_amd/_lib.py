@@ -66,6 +66,14 @@ class GamdWaterParams(C.Structure):
                 ("reserved", C.c_int32), ("alpha", C.c_double), ("k_cut", C.c_double), ("coulomb_const", C.c_double)]
 
 
+class GamdMinimizeParams(C.Structure):
+    _fields_ = [("tolerance", C.c_double), ("max_iter", C.c_int64), ("check_every", C.c_int64), ("dt_start", C.c_double),
+                ("dt_max", C.c_double), ("f_inc", C.c_double), ("f_dec", C.c_double), ("alpha_start", C.c_double),
+                ("f_alpha", C.c_double), ("max_step", C.c_double), ("n_min", C.c_int32), ("reserved", C.c_int32)]
+
+
+MINIMIZE_ROW = 8                                            # GAMD_MINIMIZE_ROW: doubles per box of gamd_minimize's rows
+MINIMIZE_STATE = ("converged", "max_iter", "failed")        # GAMD_MIN_*: a row's state and the call's return value
 CLASSICAL_ROW = 9                                           # GAMD_CLASSICAL_ROW: doubles per box and row of gamd_classical_read
 WATER_ROW = 12                                              # GAMD_WATER_ROW: doubles per box and row of gamd_water_read
 TRAJ_FIELDS = {"x": 1, "v": 2, "f": 4, "image": 8}          # GAMD_TRAJ_*
@@ -112,6 +120,7 @@ SYMBOLS = {
     "gamd_classical_read": (_i32, [_vp, _vp, _vp, _vp, _i64, C.POINTER(_i64), C.POINTER(_i64), _vp, _i64]),
     "gamd_classical_eval": (_i32, [_vp, _vp, C.POINTER(C.c_float), C.c_float, _vp, _vp, _vp, _vp, _vp]),
     "gamd_md_force_source": (_i32, [_vp, _i32]),
+    "gamd_minimize": (_i32, [_vp, _vp, C.POINTER(C.c_float), C.c_float, _vp, _vp, C.POINTER(GamdMinimizeParams), _vp, _vp]),
     "gamd_water_configure": (_i32, [_vp, C.POINTER(GamdWaterParams)]),
     "gamd_water_reset": (_i32, [_vp]),
     "gamd_water_read": (_i32, [_vp, _vp, _vp, _vp, _i64, C.POINTER(_i64), C.POINTER(_i64), _vp, _i64]),

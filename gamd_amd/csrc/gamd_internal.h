@@ -656,3 +656,33 @@ struct WaterArgs {
     long long g;               // completed MD steps at this sample
 };
 int launch_water_classical(const WaterArgs& a, hipStream_t st);
+
+// ---- energy minimiser (minimize.hip) ----------------------------------------------------------------
+// FIRE under the Lennard-Jones potential of classical.hip, per box, all state in double.  `c` carries
+// the potential's constants, the geometry of the pair pass and its work buffers (part, blk) as for ClassicalArgs, with
+// c.box_edges set; c.x, c.f, c.f_cl, c.rows, c.steps, c.slot, c.g and c.devflags are not used.  One iteration is three
+// launches (pairs, atoms, update); every kernel returns at once for a box with stopped[box] != 0.
+// (No kernel uses a value it read from memory as an address: the checked build has nothing to range-check here.)
+enum { MIN_STATE = 4,          // per box and slot: dt, alpha, n_pos, unused
+       MIN_ACC = 5,            // per box and block (the first doubles of a CLASSICAL_ROW-strided row of blk): ff, vf, vv, sum u_i, max |F_c|
+       MIN_ROW = 8 };          // per box: state, iterations, U and rms at the start, U, rms and max |F_c| at the end, the final dt
+enum { MIN_CONVERGED = 0, MIN_MAX_ITER = 1, MIN_FAILED = 2 };
+struct MinArgs {
+    ClassicalArgs c;
+    double* x64;               // [n][3] positions, length unit, unwrapped
+    double* v64;               // [n][3] FIRE velocities
+    double* f64;               // [n][3] kJ/mol/nm at x64
+    double* state;             // [n_boxes][2][MIN_STATE]: iteration `it` reads slot it & 1 and writes the other
+    int* stopped;              // [n_boxes] 0: running, else 1 + MIN_*
+    double* rows;              // [n_boxes][MIN_ROW]
+    double tol;                // kJ/mol/nm
+    double dt_start, dt_max, f_inc, f_dec, alpha_start, f_alpha, max_step;
+    int n_min;
+    int last;                  // the pass behind the last iteration: a box still running stops as MIN_MAX_ITER, nothing moves
+    long long it;              // position updates enqueued in front of this pass
+};
+int launch_minimize_init(const MinArgs& m, const float* x, hipStream_t st);
+int launch_minimize_iter(const MinArgs& m, hipStream_t st);
+// x_out = fp32(x64) wrapped (skipped for a box that failed at iteration 0); f_out = f_in for every box that did not fail
+int launch_minimize_store_x(const MinArgs& m, float* x_out, hipStream_t st);
+int launch_minimize_store_f(const MinArgs& m, const float* f_in, float* f_out, hipStream_t st);

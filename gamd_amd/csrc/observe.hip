@@ -7,6 +7,7 @@
 // The last two are observers with a potential: a PotentialLog and a traits struct (LjPotential, WaterPotential) behind one
 // sample, one read call and one eval call (potential_*).
 #include "gamd_host.h"
+#include "gamd_minimize_host.h"
 
 #include <algorithm>
 #include <array>
@@ -102,9 +103,17 @@ struct WaterClassical : PotentialLog {
     DevBuf kvec, rho_partial, sk, ublk;// ... per k-vector
 };
 
+// energy minimiser (gamd_minimize, minimize.hip): no observer — no clock, no entry in observer_list() — but a user of the
+// classical potential's parameters and work buffers with state of its own
+struct Minimizer {
+    DevBuf x64, v64, f64;              // [n][3] doubles
+    DevBuf f32;                        // [n][3] floats: the force source's output in front of the per-box store
+    DevBuf state, stopped, rows;
+};
+
 }  // namespace
 
-struct Observers { Reporter rep; Recorder rec; StructSampler ss; Classical cl; WaterClassical wc; };
+struct Observers { Reporter rep; Recorder rec; StructSampler ss; Classical cl; WaterClassical wc; Minimizer mn; };
 
 namespace {
 
@@ -165,6 +174,15 @@ ObsBufs potential_bufs(gamd_handle* h, PotentialLog& pl, size_t row, size_t part
 }
 
 ObsBufs classical_bufs(gamd_handle* h) { return potential_bufs(h, h->obs->cl, CLASSICAL_ROW, CLASSICAL_PART, CLASSICAL_ROW); }
+
+// energy minimiser: all of it work buffers (k_min_init writes every one in front of its first reader)
+ObsBufs minimize_bufs(gamd_handle* h) {
+    Minimizer& mn = h->obs->mn;
+    const size_t nb = (size_t)h->n_boxes, n3 = 3 * (size_t)h->n;
+    return {{&mn.x64, sizeof(double) * n3, false}, {&mn.v64, sizeof(double) * n3, false}, {&mn.f64, sizeof(double) * n3, false},
+            {&mn.f32, sizeof(float) * n3, false}, {&mn.state, sizeof(double) * 2 * MIN_STATE * nb, false},
+            {&mn.stopped, sizeof(int) * nb, false}, {&mn.rows, sizeof(double) * MIN_ROW * nb, false}};
+}
 
 // water classical observer: the pair pass has the classical observer's tiles, slices and blocks; the k slices of the reciprocal
 // force pass are as many as the pair slices, the blocks of the rho(k) pass the structure sampler's
@@ -673,6 +691,7 @@ Observers* observers_new() { return new Observers(); }
 void observers_free(gamd_handle* h) {
     for (const Observer& ob : observer_list(h))
         for (const ObsBuf& b : ob.bufs(h)) b.buf->release();
+    for (const ObsBuf& b : minimize_bufs(h)) b.buf->release();
     delete h->obs; h->obs = nullptr;
 }
 
@@ -740,6 +759,11 @@ static_assert(sizeof(gamd_water_params) == 88 && offsetof(gamd_water_params, q_h
               offsetof(gamd_water_params, shift) == 56 && offsetof(gamd_water_params, alpha) == 64 && offsetof(gamd_water_params, coulomb_const) == 80,
               "gamd_water_params layout is part of the C ABI (gamd_amd/_lib.py mirrors it)");
 static_assert(GAMD_WATER_ROW == WATER_ROW, "the row of gamd_water_read is the kernels' row");
+static_assert(sizeof(gamd_minimize_params) == 88 && offsetof(gamd_minimize_params, max_iter) == 8 && offsetof(gamd_minimize_params, dt_start) == 24 &&
+              offsetof(gamd_minimize_params, max_step) == 72 && offsetof(gamd_minimize_params, n_min) == 80,
+              "gamd_minimize_params layout is part of the C ABI (gamd_amd/_lib.py mirrors it)");
+static_assert(GAMD_MINIMIZE_ROW == MIN_ROW && GAMD_MIN_CONVERGED == MIN_CONVERGED && GAMD_MIN_MAX_ITER == MIN_MAX_ITER && GAMD_MIN_FAILED == MIN_FAILED,
+              "the row and the states of gamd_minimize are the kernels'");
 
 extern "C" {
 
@@ -951,6 +975,76 @@ int32_t gamd_classical_eval(gamd_handle* h, const float* pos_dev, const float* b
         if (pairs) pairs[b] = row[CLASSICAL_ROW * b + 2];
     }
     return 0;
+}
+
+int32_t gamd_minimize(gamd_handle* h, float* x_dev, const float* box, float length_per_nm, float* f_dev, double* x64_dev,
+                      const gamd_minimize_params* params, double* rows_host, void* stream) {
+    // the parameter block is checked first: these answers need no device
+    gamd_minimize_params q;
+    if (int r = minimize_fill_params(params, &q, g_err, sizeof(g_err))) return r;
+    if (!h) return fail(-22, "null handle");
+    if (h->cfg.kind != GAMD_KIND_LJ)
+        return fail(-22, "gamd_minimize: a GAMD_KIND_WATER handle has no classical potential to minimise (the Lennard-Jones "
+                         "potential has no electrostatics; GAMD_KIND_LJ handles only)");
+    Classical& cl = LjPotential::state(h);
+    if (!cl.params_set) return fail(-22, "gamd_minimize needs the parameters of a gamd_classical_configure call (interval 0 will do)");
+    if (h->pending.active) return fail(-22, "an MD run is still enqueued: call gamd_sync_status before gamd_minimize");
+    if (!x_dev || !f_dev || !box) return fail(-22, "null argument");
+    for (int k = 0; k < 3 * h->n_boxes; ++k)
+        if (!(box[k] > 0.f)) return fail(-22, "box[%d][%d] = %g is not positive", k / 3, k % 3, (double)box[k]);
+    if (int r = LjPotential::check_box(h, box, nullptr)) return r;
+    DeviceGuard guard(h->dev);
+    hipStream_t st = (hipStream_t)stream;
+    InitStream init(st);
+    // every allocation in front of the first enqueue
+    if (bufs_ensure_work(LjPotential::bufs(h)) || bufs_ensure_work(minimize_bufs(h))) return fail(-12, "gamd_minimize: allocation failed");
+    const size_t nb = (size_t)h->n_boxes, n3 = 3 * (size_t)h->n;
+    std::vector<int> stopped(nb, 0);
+    std::vector<double> rows(MIN_ROW * nb, 0.0);
+    HIP_TRY(init_upload(cl.eval_box.p, box, sizeof(float) * 3 * nb));
+    // the force source's kernels return at once on a frozen handle: f would be what the last call left
+    int frozen = 0;
+    HIP_TRY(hipMemcpyAsync(&frozen, h->devflags.as<int>() + DEVFLAG_FROZEN, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (frozen) return fail(-1, "gamd_minimize: the handle is frozen by a neighbour-buffer overflow (call gamd_sync_status)");
+    Minimizer& mn = h->obs->mn;
+    MinArgs m{};
+    m.c = LjPotential::args(h, length_per_nm > 0.f ? (double)length_per_nm : 10.0);
+    m.c.box_edges = cl.eval_box.as<float>();
+    m.x64 = mn.x64.as<double>(); m.v64 = mn.v64.as<double>(); m.f64 = mn.f64.as<double>();
+    m.state = mn.state.as<double>(); m.stopped = mn.stopped.as<int>(); m.rows = mn.rows.as<double>();
+    m.tol = q.tolerance; m.dt_start = q.dt_start; m.dt_max = q.dt_max; m.f_inc = q.f_inc; m.f_dec = q.f_dec;
+    m.alpha_start = q.alpha_start; m.f_alpha = q.f_alpha; m.max_step = q.max_step; m.n_min = q.n_min;
+    int r;
+    if ((r = launch_minimize_init(m, x_dev, st))) return fail(-1, "gamd_minimize launch failed (%d)", r);
+    bool all_stopped = false;
+    while (m.it < q.max_iter && !all_stopped) {
+        const long long chunk = std::min<long long>(q.check_every, q.max_iter - m.it);
+        for (long long k = 0; k < chunk; ++k, ++m.it)
+            if ((r = launch_minimize_iter(m, st))) return fail(-1, "gamd_minimize launch failed (%d)", r);
+        HIP_TRY(hipMemcpyAsync(stopped.data(), mn.stopped.p, sizeof(int) * nb, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        all_stopped = std::all_of(stopped.begin(), stopped.end(), [](int s) { return s != 0; });
+    }
+    if (!all_stopped) {                                     // U and rms where max_iter left the boxes that still run
+        m.last = 1;
+        if ((r = launch_minimize_iter(m, st))) return fail(-1, "gamd_minimize launch failed (%d)", r);
+    }
+    // x, then the force source's own kernels on exactly that x
+    if ((r = launch_minimize_store_x(m, x_dev, st))) return fail(-1, "gamd_minimize launch failed (%d)", r);
+    ClassicalArgs a = m.c;
+    a.x = x_dev;
+    if ((r = launch_classical_drive(a, mn.f32.as<float>(), st))) return fail(-1, "gamd_minimize launch failed (%d)", r);
+    cl.evaluated = true;
+    if ((r = launch_minimize_store_f(m, mn.f32.as<float>(), f_dev, st))) return fail(-1, "gamd_minimize launch failed (%d)", r);
+    if (x64_dev) HIP_TRY(hipMemcpyAsync(x64_dev, mn.x64.p, sizeof(double) * n3, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemcpyAsync(rows.data(), mn.rows.p, sizeof(double) * rows.size(), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (int t = check_traps(h)) return t;
+    if (rows_host) std::memcpy(rows_host, rows.data(), sizeof(double) * rows.size());
+    int worst = 0;
+    for (size_t b = 0; b < nb; ++b) worst = std::max(worst, (int)rows[MIN_ROW * b]);
+    return worst;
 }
 
 int32_t gamd_water_configure(gamd_handle* h, const gamd_water_params* p) {

@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import GamdClassicalParams, GamdWaterParams, GamdReportParams, GamdStructParams, GamdTrajParams, GamdConfig, GamdMdParams, GamdNhcParams, TRAJ_FIELDS, check
+from ._lib import GamdClassicalParams, GamdMinimizeParams, GamdWaterParams, GamdReportParams, GamdStructParams, GamdTrajParams, GamdConfig, GamdMdParams, GamdNhcParams, TRAJ_FIELDS, check
 from .weights import ModelConfig, infer_config, validate_state_dict
 
 ArrayLike = Union[np.ndarray, torch.Tensor]
@@ -367,6 +367,31 @@ class RunWaterClassical(RunClassical):
 
     def pressure(self, ke, volumes):
         raise NotImplementedError("the water classical observer logs no virial: with rigid molecules the atomic virial is not the pressure")
+
+
+class MinimizeResult:
+    """What ``GamdForce.minimize`` did.  ``status``: the call's return value (0 every box converged, 1 a box stopped at
+    max_iter, 2 a box failed: not finite).  Per box, float64 [B] unless noted: ``state`` (list of "converged" | "max_iter" |
+    "failed"), ``iterations`` (int64: position updates), ``energy_start`` / ``rms_start`` and ``energy`` / ``rms`` (kJ/mol,
+    kJ/mol/nm: root mean square of the 3N force components, OpenMM's tolerance), ``fmax`` (largest |force component| at the
+    end), ``dt`` (the final pseudo-time step).  ``x`` / ``f``: the tensors the call wrote; ``x64``: the unrounded, unwrapped
+    double positions or None.  ``rows`` is the library's table [B, 8]."""
+
+    def __init__(self, status: int, rows, x=None, f=None, x64=None):
+        self.status = int(status)
+        self.rows = np.asarray(rows, dtype=np.float64)
+        self.state = [_lib.MINIMIZE_STATE[int(s)] for s in self.rows[:, 0]]
+        self.iterations = self.rows[:, 1].astype(np.int64)
+        self.energy_start, self.rms_start = self.rows[:, 2], self.rows[:, 3]
+        self.energy, self.rms, self.fmax, self.dt = self.rows[:, 4], self.rows[:, 5], self.rows[:, 6], self.rows[:, 7]
+        self.x, self.f, self.x64 = x, f, x64
+
+    @property
+    def converged(self) -> bool:
+        return self.status == 0
+
+    def __repr__(self):
+        return f"MinimizeResult(state={self.state}, iterations={self.iterations.tolist()}, energy={self.energy.tolist()}, rms={self.rms.tolist()})"
 
 
 class GamdForce:
@@ -983,6 +1008,39 @@ class GamdForce:
         check(self._lib.gamd_classical_eval(self._h, C.c_void_p(p.data_ptr()), self._box_arg(box), float(length_per_nm),
                                             C.c_void_p(out.data_ptr()), vp(e), vp(w), vp(c), self._stream()), "gamd_classical_eval")
         return out, e, w, c
+
+    # -- energy minimiser (the drivers' minimizeEnergy in front of the first step) -------------------------------------
+    def minimize(self, x: torch.Tensor, f: Optional[torch.Tensor] = None, tolerance: float = 10.0, max_iter: int = 0, box=None,
+                 length_per_nm: float = 0.0, return_x64: bool = False, check_every: int = 0, **fire) -> "MinimizeResult":
+        """Relax the positions ``x`` (float32 CUDA tensor, changed in place) of every box under the classical potential of the
+        last ``classical_configure`` (with the defaults and interval 0 when there was none) on the device, until the root
+        mean square of the 3N force components of a box is at most ``tolerance`` (kJ/mol/nm; the meaning of OpenMM's
+        ``minimizeEnergy(tolerance)``) or ``max_iter`` position updates are done (0 = 10 000).  The algorithm is FIRE in
+        double, not OpenMM's L-BFGS: no parity with it is claimed.  ``fire``: any of dt_start, dt_max, n_min, f_inc, f_dec,
+        alpha_start, f_alpha, max_step (0 or absent: the default, include/gamd_hip.h; the defaults are for Angstrom).
+
+        On return ``x`` holds the result rounded to fp32 and wrapped into the box and ``f`` (allocated when None) the
+        classical forces at exactly that ``x`` — ``classical_forces(x)[0].float()`` bit for bit, what a classical-source
+        ``md_run`` / ``md_run_nhc`` needs on entry.  A box that was not finite at the start (two atoms at one point) keeps its
+        ``x``; nothing is written to ``f`` for a box that failed.  ``return_x64``: also the unrounded, unwrapped double
+        positions (``result.x64``).  LJ models only; 2 r_cut must not exceed a box edge.  Synchronises."""
+        unknown = set(fire) - {"dt_start", "dt_max", "n_min", "f_inc", "f_dec", "alpha_start", "f_alpha", "max_step"}
+        if unknown:
+            raise TypeError(f"minimize() got unexpected FIRE constants {sorted(unknown)}")
+        if not getattr(self, "_classical_set", False):
+            self.classical_configure(0)
+        if f is None:
+            f = torch.zeros_like(x)
+        self._md_state(x, f)
+        x64 = torch.empty((self.n_total, 3), dtype=torch.float64, device=self.device) if return_x64 else None
+        g = lambda k: float(fire.get(k, 0.0))
+        p = GamdMinimizeParams(float(tolerance), int(max_iter), int(check_every), g("dt_start"), g("dt_max"), g("f_inc"), g("f_dec"),
+                               g("alpha_start"), g("f_alpha"), g("max_step"), int(fire.get("n_min", 0)), 0)
+        rows = np.zeros((self.n_boxes, _lib.MINIMIZE_ROW), dtype=np.float64)
+        st = check(self._lib.gamd_minimize(self._h, C.c_void_p(x.data_ptr()), self._box_arg(box), float(length_per_nm),
+                                           C.c_void_p(f.data_ptr()), C.c_void_p(x64.data_ptr()) if return_x64 else None,
+                                           C.byref(p), rows.ctypes.data_as(C.c_void_p), self._stream()), "gamd_minimize")
+        return MinimizeResult(st, rows, x, f, x64)
 
     # -- water classical observer (3-site water: O-O Lennard-Jones plus an Ewald sum, on sampled frames; force labels) ------
     def water_classical_configure(self, interval: int, max_samples: int = 0, q_h: float = 0.417, sigma_o: Optional[float] = None,

@@ -580,6 +580,64 @@ int32_t gamd_water_read(gamd_handle* h, void* stream, int64_t* steps, double* ro
 int32_t gamd_water_eval(gamd_handle* h, const float* pos_dev, const uint8_t* species_dev, const float* box, float length_per_nm,
                         double* f_out_dev, double* rows, void* stream);
 
+/* Energy minimiser: every reference driver relaxes its start in front of the first step (minimizeEnergy(tolerance = 1 kJ/mol),
+ * dataset/generate_lj_data.py:83; minimizeEnergy(1e-6), LJ/test_script/test_langevin.py:84, test_nosehoover.py:88).
+ * gamd_minimize relaxes the positions of every box of a GAMD_KIND_LJ handle under the classical potential of the last
+ * gamd_classical_configure (interval 0 will do) ON THE DEVICE and leaves x and f as a classical-source gamd_md_run /
+ * gamd_md_run_nhc expects them on entry.  It is NOT OpenMM's L-BFGS and claims no parity with it: the algorithm is FIRE
+ * (Bitzek et al., Phys. Rev. Lett. 97, 170201 (2006)) in the semi-implicit Euler form.  What is matched is the meaning of the
+ * tolerance: the root mean square of all 3N force components of a box, in kJ/mol/nm.
+ * Per box and iteration, on double positions x (the fp32 input widened) and double velocities v (0 at the start), with the
+ * scalars dt = dt_start, alpha = alpha_start, n_pos = 0:
+ *   1. F (kJ/mol/nm, through length_per_nm) and U (kJ/mol) at x: the pair term of gamd_classical_configure, operation for
+ *      operation, box edges the fp32 edges widened.
+ *   2. ff = sum F.F, vf = sum v.F, vv = sum v.v and U in a fixed order; rms = sqrt(ff / 3N).  U or ff not finite: the box stops
+ *      as GAMD_MIN_FAILED with the positions of this iteration.  Else rms <= tolerance: it stops as GAMD_MIN_CONVERGED.
+ *   3. vf > 0: v = (1 - alpha) v + (alpha sqrt(vv / ff)) F; then, if n_pos > n_min, dt = min(dt f_inc, dt_max) and
+ *      alpha = alpha f_alpha; then n_pos += 1.  Otherwise v = 0, alpha = alpha_start, dt = dt f_dec, n_pos = 0.
+ *   4. v = v + dt F, dr = dt v, per atom dr *= max_step / |dr| where |dr| > max_step, x = x + dr.
+ * F is in kJ/mol/nm while x and max_step are in the handle's length unit: dt is a pseudo-time that absorbs the units (and the
+ * mass), so dt_start and dt_max go with the length unit — the defaults are for Angstrom.  After max_iter position updates a
+ * box that still runs is evaluated once more (steps 1 and 2) and, unless that converges, stops as GAMD_MIN_MAX_ITER.
+ * Everything is in double with fixed summation orders, no floating-point atomics and no contraction: the same bits run after
+ * run, whatever check_every is, and every box of a handle gets the bits it gets alone.  The host enqueues check_every
+ * iterations at a time and looks at the boxes' states only between such chunks; a box that stopped is skipped on the device.
+ * Nothing is allocated between the first and the last enqueue.  O(N^2) per iteration and box.
+ * On return (the stream is synchronised):
+ *   x_dev        float [n_boxes * n_atoms][3] DEVICE, in and out: the double positions rounded to nearest and wrapped into the
+ *                box by the integrators' expression.  A box that was not finite at the start keeps x as given.
+ *   f_dev        float [n_boxes * n_atoms][3] DEVICE, out: the classical force at exactly those fp32 positions, by the kernels
+ *                of the classical force source — bit for bit the fp32 rounding of gamd_classical_eval's forces on x_dev, the
+ *                precondition of a GAMD_FORCE_CLASSICAL run.  Nothing is written for a box that failed.
+ *   x64_dev      double [n_boxes * n_atoms][3] DEVICE or NULL: the unrounded, unwrapped positions.
+ *   rows_host    double [n_boxes][GAMD_MINIMIZE_ROW] HOST or NULL: state (GAMD_MIN_*), iterations (position updates), U and rms
+ *                at the start, U, rms and the largest |force component| at the end, the final dt.
+ * Returns 0: every box converged; 1: at least one box stopped at max_iter; 2: at least one box failed (not finite).
+ * -22, with a message naming the reason: a null params / x_dev / f_dev / box, a non-positive or non-finite tolerance, negative
+ * counts, a constant outside its range (f_dec, f_alpha, alpha_start in (0, 1); f_inc > 1; dt_max >= dt_start > 0;
+ * max_step > 0), a null handle, a GAMD_KIND_WATER handle, no accepted gamd_classical_configure, a pending run, a box edge
+ * that is not positive or below 2 * r_cut (the message names r_cut).  -12 when an allocation fails; -1 on a handle that a
+ * neighbour-buffer overflow of gamd_forces_async left frozen (call gamd_sync_status first).
+ * Device memory besides the classical observer's work buffers: 84 B per atom. */
+typedef struct gamd_minimize_params {
+    double tolerance;        /* kJ/mol/nm, > 0 and finite (the reference's data generator: 1; its rollout drivers: 1e-6) */
+    int64_t max_iter;        /* position updates at most; 0 = 10000 */
+    int64_t check_every;     /* iterations enqueued between two looks at the boxes' states; 0 = 64 */
+    double dt_start;         /* 0 = 0.002 */
+    double dt_max;           /* 0 = 0.02 */
+    double f_inc;            /* 0 = 1.1 */
+    double f_dec;            /* 0 = 0.5 */
+    double alpha_start;      /* 0 = 0.1 */
+    double f_alpha;          /* 0 = 0.99 */
+    double max_step;         /* length unit of the handle; 0 = 0.1 */
+    int32_t n_min;           /* 0 = 5 */
+    int32_t reserved;        /* 0 */
+} gamd_minimize_params;
+enum { GAMD_MINIMIZE_ROW = 8 };
+enum { GAMD_MIN_CONVERGED = 0, GAMD_MIN_MAX_ITER = 1, GAMD_MIN_FAILED = 2 };
+int32_t gamd_minimize(gamd_handle* h, float* x_dev, const float* box, float length_per_nm, float* f_dev, double* x64_dev,
+                      const gamd_minimize_params* params, double* rows_host, void* stream);
+
 /* Event-timed replay of one force evaluation: per-kernel milliseconds of the last gamd_profile call.
  * names: newline-separated kernel labels; ms: one float per label.  For bench.py's roofline block. */
 int32_t gamd_profile(gamd_handle* h, const float* pos_dev, const uint8_t* species_dev, const float* box,

@@ -3,10 +3,12 @@
 logs PE / KE / total energy and writes data_{seed}_{t}.npz) as ONE enqueued run, and what such a run costs.
 
     python tools/lj_ground_truth.py [--workloads c1 c2] [--steps 200] [--interval 50] [--frames 4] [--energy-ps 2.0]
-                                    [--seed 0] [--out DIR]
+                                    [--seed 0] [--out DIR] [--start lattice|random] [--minimize TOL]
 
-For a seeded LJ box (C1: 258 atoms, C2: 10 000 atoms; the workload's own lattice box, no energy minimiser) on one handle in skin
-mode, as bench.py runs it:
+For a seeded LJ box (C1: 258 atoms, C2: 10 000 atoms; the workload's own lattice box, or with --start random uniform random
+points in it) on one handle in skin mode, as bench.py runs it:
+  0. with --minimize TOL, the generator's minimizeEnergy (dataset/generate_lj_data.py:83, tolerance 1 there): the start relaxed
+     on the device by GamdForce.minimize to an RMS force of TOL kJ/mol/nm (FIRE, not OpenMM's L-BFGS); --start random needs it;
   1. the generator: classical force source, traj_configure(interval, fields x v f), report_configure(interval),
      classical_configure(interval), one md_run_nhc of frames * interval steps, then RunTrajectory.write_dataset and
      RunClassical.write_state_data into --out (a temporary directory by default);
@@ -29,7 +31,8 @@ sys.path.insert(0, ROOT)
 LAYERS = 4
 
 
-def _engine(workload, seed):
+def _engine(workload, seed, start="lattice"):
+    import numpy as np
     import torch
     from gamd_amd.engine import GamdForce
     from gamd_amd.weights import ModelConfig, make_state_dict, SHIPPED_SCALERS
@@ -37,6 +40,8 @@ def _engine(workload, seed):
     sd = make_state_dict(ModelConfig(kind="lj", conv_layer=LAYERS), 0, 7.0, 2.2)
     n, rc = (10000, 3.0 * wk.LJ_SIGMA) if workload == "c2" else (258, 7.5)
     pos, box = wk.lj_box(n, seed=1234 + seed)
+    if start == "random":                                          # uniform points in the same box: overlaps, needs --minimize
+        pos = np.random.default_rng(1234 + seed).random((n, 3)) * box
     eng = GamdForce(sd, n, box, rc, scaler=SHIPPED_SCALERS["lj"], neighbor_skin=rc / 6.0)
     x0 = torch.from_numpy(pos).float().cuda()
     v0 = torch.from_numpy(wk.maxwell_boltzmann(n, 100.0, seed=99 + seed)).float().cuda()
@@ -96,14 +101,29 @@ def main():
     ap.add_argument("--energy-ps", type=float, default=2.0)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--start", choices=["lattice", "random"], default="lattice",
+                    help="the workload's lattice box, or uniform random points in it (which overlap: give --minimize)")
+    ap.add_argument("--minimize", type=float, default=None, metavar="TOL",
+                    help="relax the start on the device to an RMS force of TOL kJ/mol/nm first (the generator's minimizeEnergy: 1)")
     args = ap.parse_args()
+    if args.start == "random" and args.minimize is None:
+        ap.error("--start random gives overlapping atoms: a classical run cannot start there without --minimize TOL")
     out_dir = args.out or tempfile.mkdtemp(prefix="lj_ground_truth_")
     out = {}
     for w in args.workloads:
-        eng, x0, v0 = _engine(w, args.seed)
+        eng, x0, v0 = _engine(w, args.seed, args.start)
         n = x0.shape[0]
         eng.classical_configure(0)
         res = dict(n=n)
+        # 0. the generator's minimizeEnergy (dataset/generate_lj_data.py:83), on the device
+        if args.minimize is not None:
+            m = eng.minimize(x0, tolerance=args.minimize)
+            if m.status != 0:
+                raise SystemExit(f"{w}: the minimiser stopped as {m.state[0]} after {int(m.iterations[0])} iterations (rms {m.rms[0]:.3e} kJ/mol/nm)")
+            res["minimize"] = dict(tolerance=args.minimize, start=args.start, iterations=int(m.iterations[0]), u0=float(m.energy_start[0]),
+                                   rms0=float(m.rms_start[0]), u=float(m.energy[0]), rms=float(m.rms[0]))
+            print(f"{w}: {args.start} start minimised to rms {m.rms[0]:.3e} kJ/mol/nm in {int(m.iterations[0])} iterations: "
+                  f"U {m.energy_start[0]:.6e} -> {m.energy[0]:.6f} kJ/mol")
         # 1. the generator loop as one enqueued run
         x, v, f = _start(eng, x0, v0, "classical")
         eng.traj_configure(args.interval, max_frames=args.frames, fields=("x", "v", "f"))
