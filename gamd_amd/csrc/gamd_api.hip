@@ -63,6 +63,32 @@ int alloc_edges(gamd_handle* h, long long e_cap) {
     return 0;
 }
 
+// ---- the candidate radius of the Verlet-skin reuse, in fp32 ---------------------------------------------------------------
+// Reuse rests on the triangle inequality: a pair that is an edge now (D1 <= rc) and whose atoms have each moved at most skin / 2
+// since the build was at most rc + skin apart then (D0 <= D1 + 2 skin / 2), so it is in the candidate rows.  Every one of these
+// four statements is decided by an fp32 predicate over wrapped coordinates, and each predicate sees the true minimum-image
+// distance D only up to an ABSOLUTE error that scales with the box edge L, not with D.  With eps = 2^-24 (half an ulp, relative):
+//   per component (gamd_min_image_wrapped on d = pc - pb, both in [0, L]):  d: eps L;  d + L/2: 1.5 eps L (|.| <= 1.5 L);
+//     +/- L: eps L;  - L/2: 0.5 eps L   -> |r~ - r| <= 4 eps L   (a different image near +/- L/2 has the same |r| to that error)
+//   vector:  | |r~| - D | <= sqrt(3) 4 eps L  < 7 eps L
+//   squares and sums: three roundings per term, (1 + 3 eps) on d2, 1.5 eps D <= 1.3 eps L on the root (D <= sqrt(3) L / 2)
+//   the threshold itself (rc2, skin_half2 rounded; the torch flavour's rounded sqrt):  <= eps D < 1 eps L
+//   => each predicate decides "D~ < T" for some D~ with |D~ - D| <= E,  E = 10 eps L.
+// Chain:  edge now => D1 <= rc + E;  not moved (twice) => each displacement <= skin / 2 + E;  so D0 <= rc + skin + 3 E, and the
+// build's predicate sees D0~ <= rc + skin + 4 E.  The candidate radius must exceed that: rc + skin + 40 eps L, and 48 eps L once
+// its own two roundings (rc_build, rc2_build) and a strict '<' are paid for.  L is the longest edge of any box of the handle
+// (NbrArgs carries one radius for the whole batch).  At L = 30 / 150 / 1000 the margin is 8.6e-5 / 4.3e-4 / 2.9e-3: with
+// rc + skin = 8.75 that is 1e-5 ... 3e-4 of the radius, 3e-5 ... 1e-3 of the candidates.  The exact filter and the move test are
+// unchanged, so the edge set and the CSR order are what they were.  Without the margin a reuse step can miss an edge
+// (tests/test_gpu_nbr_cutoff.py, profiles/nbr_cutoff_parity.md: 76-80 of 80 constructed pairs).
+constexpr double GAMD_SKIN_MARGIN_EPS = 48.0 / 16777216.0;             // 48 x 2^-24, times the longest box edge
+// The cell grid must hold the enlarged radius: a candidate pair is at most rc_build + E apart along every axis, and cell_coord
+// (p * (nc / L), two roundings, |p nc / L| <= nc) places an atom up to 3 eps L from where it is, so two candidates land in the same
+// or in adjacent cells when the cells are rc + skin + (48 + 10 + 6) eps L wide.  The 1.0001 factor gives more than that while
+// 64 eps L <= 1e-4 (rc + skin), i.e. up to L = 26 (rc + skin); beyond that the second term takes over.  Without a skin the
+// margin is zero and the grid is the 1.0001 rule alone.
+constexpr double GAMD_CELL_MARGIN_EPS = 64.0 / 16777216.0;
+
 // box: host [n_boxes][3].  Every box gets the cell grid a single-box handle would give it (cells at least cutoff + skin
 // wide), cells numbered box after box; h->box / h->nc keep box 0 (what the single-box kernels' argument blocks carry).
 int set_box(gamd_handle* h, const float* box, hipStream_t st = nullptr) {
@@ -78,10 +104,15 @@ int set_box(gamd_handle* h, const float* box, hipStream_t st = nullptr) {
     h->cand_valid = false;                                        // candidates were built for another box
     std::vector<int> grid((size_t)nb * 4);
     long long ncell = 0;
+    float box_max = 0.f;
+    for (int k = 0; k < 3 * nb; ++k) box_max = std::max(box_max, box[k]);
+    // narrowest cell that holds the (candidate) radius: see GAMD_CELL_MARGIN_EPS; the first term decides up to 26 radii per edge
+    const double radius = (double)h->cfg.cutoff + (double)h->skin;
+    const double cell_min = std::max(radius * 1.0001, h->skin > 0.f ? radius + GAMD_CELL_MARGIN_EPS * (double)box_max : 0.0);
     for (int b = 0; b < nb; ++b) {
         long long nc_b = 1;
         for (int d = 0; d < 3; ++d) {
-            const int nc = std::max(1, (int)std::floor((double)box[3 * b + d] / (((double)h->cfg.cutoff + (double)h->skin) * 1.0001)));
+            const int nc = std::max(1, (int)std::floor((double)box[3 * b + d] / cell_min));
             grid[(size_t)4 * b + d] = nc;
             nc_b *= nc;
         }
@@ -90,6 +121,7 @@ int set_box(gamd_handle* h, const float* box, hipStream_t st = nullptr) {
         ncell += nc_b;
     }
     for (int d = 0; d < 3; ++d) { h->box[d] = box[d]; h->nc[d] = grid[d]; }
+    h->box_max = box_max;
     h->ncell = (int)ncell;
     if ((int)ncell > h->ncell_cap) {
         int r = 0;
@@ -154,7 +186,8 @@ NbrArgs nbr_args(gamd_handle* h, const float* pos_dev, const uint8_t* species_de
     a.sticky = h->sticky_dev;
     if (h->skin > 0.f) {
         a.skin_half2 = 0.25f * h->skin * h->skin;
-        a.rc_build = h->cfg.cutoff + h->skin;
+        // rc + skin plus the rounding margin (GAMD_SKIN_MARGIN_EPS above): summed in double, rounded once
+        a.rc_build = (float)((double)h->cfg.cutoff + (double)h->skin + GAMD_SKIN_MARGIN_EPS * (double)h->box_max);
         a.rc2_build = (float)((double)a.rc_build * (double)a.rc_build);
         a.cand_deg = h->cand_deg.as<int>();
         a.cand_ptr = h->cand_ptr.as<int>();

@@ -209,6 +209,7 @@ struct gamd_handle {
     bool cand_valid = false;
 
     float box[3] = {0, 0, 0};
+    float box_max = 0.f;            // longest edge of any box as last set: scale of the candidate radius' rounding margin
     int nc[3] = {1, 1, 1};
     int ncell = 1;                  // cells of all boxes together
 

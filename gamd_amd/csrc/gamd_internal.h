@@ -192,7 +192,7 @@ struct NbrArgs {
                            // surface as an overflow on the grid-wide path, never send n > 1024 atoms into the one-workgroup kernel)
     int cells_one_wg;      // candidate rebuild: the four cell-list phases in one single-workgroup launch (rebuilds are rare: one
                            // gated launch per reuse step instead of four) or as four grid-wide kernels (rebuilds are frequent)
-    float rc_build, rc2_build;   // rc + skin
+    float rc_build, rc2_build;   // rc + skin + the fp32 rounding margin (gamd_api.hip GAMD_SKIN_MARGIN_EPS)
 };
 struct MdArgs;
 // Integrator work that the small-system skin path (n <= 1024, NbrArgs::counters_next set) folds into its first kernel:

@@ -565,7 +565,7 @@ __global__ void k_chunk_meta(NbrArgs a) {
 }
 
 // ---- Verlet-skin reuse ----------------------------------------------------------------------------
-// argument block of the candidate pass (rc + skin, candidate arrays, no self loops: the exact filter appends them)
+// argument block of the candidate pass (rc + skin + rounding margin, candidate arrays, no self loops: the exact filter appends them)
 __device__ __forceinline__ NbrArgs cand_args(const NbrArgs& a) {
     NbrArgs c = a;
     c.rc = a.rc_build; c.rc2 = a.rc2_build;

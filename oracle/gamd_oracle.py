@@ -78,7 +78,11 @@ def neighbor_edges(pos: Tensor, box, cutoff: float, flavour: str = "jaxmd",
         else:
             # md_module.py:65: dist_mat[a, b] = pos[b] - pos[a]
             d = _min_image(pos[None, :, :] - pos[s:e, None, :], boxt)
-            m = torch.norm(d, dim=-1) <= rc
+            # md_module.py:104 torch.norm(distance, dim=1), written out: every product rounded, then (xx + yy) + zz, then the
+            # root.  torch.norm's CPU kernel accumulates acc + x * x, which the AVX2 / AVX-512 builds contract into fused
+            # multiply-adds: membership of a pair ON the cutoff then depends on the host's instruction set
+            # (tests/test_nbr_reference.py, profiles/nbr_cutoff_parity.md).
+            m = (d * d).sum(-1).sqrt() <= rc
             idx = torch.arange(s, e)
             m[idx - s, idx] = False
         a, b = torch.nonzero(m, as_tuple=True)
