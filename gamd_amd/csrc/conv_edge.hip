@@ -51,7 +51,8 @@
 namespace {
 
 // two 64 KiB weight slots and b1, b3, b4 (L0: b1, b3, S0 + D0)
-constexpr int conv_lds_floats(bool l0) { return 2 * GAMD_WFRAG_FLOATS + 3 * 128; }
+// (folded edge LayerNorm: + the weight fragment of phase 1's extra K step, 4 output blocks x 64 lanes)
+constexpr int conv_lds_floats(bool l0, bool fold = false) { return 2 * GAMD_WFRAG_FLOATS + 3 * 128 + (fold ? 256 : 0); }
 
 // 128x128 GEMM of the chain with a software-pipelined element-wise post-op: while output tile tp is being accumulated (64
 // MFMAs in 16 groups of 4), post(tp-1, g) finishes element g of the previous, already complete, output tile.  Only tile 3's
@@ -60,8 +61,9 @@ constexpr int conv_lds_floats(bool l0) { return 2 * GAMD_WFRAG_FLOATS + 3 * 128;
 // during this phase" (the weight copy for the next phase, piece stores, C-in gathers) are issued there instead of in front
 // of the first MFMA, where they would queue behind the other waves' gathers on the CU's address path and keep the matrix
 // pipe idle after every barrier.
-template <bool F2, typename Post, typename Mid>
-__device__ __forceinline__ void gemm128_post(const f32x4* W, int lane, const f32x16 (&X)[4], f32x16 (&acc)[4], Post post, Mid mid) {
+// tail(tp) runs behind the 64 MFMAs of output tile tp, before anything reads it: further K steps of that tile.
+template <bool F2, typename Post, typename Mid, typename Tail>
+__device__ __forceinline__ void gemm128_post(const f32x4* W, int lane, const f32x16 (&X)[4], f32x16 (&acc)[4], Post post, Mid mid, Tail tail) {
 #pragma unroll
     for (int tp = 0; tp < 4; ++tp) {
         if (tp == 1) mid();
@@ -78,9 +80,14 @@ __device__ __forceinline__ void gemm128_post(const f32x4* W, int lane, const f32
                 if (tp > 0) post(tp - 1, t * 4 + q);
             }
         }
+        tail(tp);
     }
 #pragma unroll
     for (int g = 0; g < 16; ++g) post(3, g);
+}
+template <bool F2, typename Post, typename Mid>
+__device__ __forceinline__ void gemm128_post(const f32x4* W, int lane, const f32x16 (&X)[4], f32x16 (&acc)[4], Post post, Mid mid) {
+    gemm128_post<F2>(W, lane, X, acc, post, mid, [](int) {});
 }
 
 // End of a phase: every wave has its own weight DMA (issued during the phase, before the N most
@@ -117,18 +124,23 @@ __device__ __forceinline__ void load_e_tile(const float* __restrict__ e_frag, in
 // (Other schedules that were measured and dropped are recorded in profiles/r02_ / r03_conv_edge_experiments.md.)
 // TIME (profiling build only, GAMD_CONV_TIME): per-segment s_memtime counters -> a.tdbg.
 // L0: the layer-0 form of LJ models (see the top of the file; a.b3 and a.w3p are then packed in the F2 output order).
-template <bool TIME, bool L0>
+// FOLD: the folded edge LayerNorm (gamd_ln_fold_host.h).  The tile is x2' = rstd x2, a.w1p is A = W1 diag(gamma) B
+// followed by the fragment (a, 0) of one extra K step, a.b1 = b1 + W1 beta; the step's other operand is the tile's rstd
+// fragment (a.e_rstd: lanes 0-31 rstd, lanes 32-63 zero), loaded with the tile and held in one register through phase 1.
+// Everything behind phase 1's accumulators is the general form's.
+template <bool TIME, bool L0, bool FOLD = false>
 __global__ void __launch_bounds__(512, 2) k_conv_edge(ConvEdgeArgs a) {
     if (a.devflags[DEVFLAG_FROZEN]) return;          // frozen run: nothing to compute until the host has regrown and resumed
     extern __shared__ __attribute__((aligned(16))) float lds[];
     // L0: the three vectors (b1, b3, S0 + D0) in front of the weight slots, where every lane's address of them is one register
     // + an immediate offset (behind 128 KiB each needs registers of its own)
-    float* buf0 = lds + (L0 ? 3 * 128 : 0);
+    float* buf0 = lds + (L0 ? 3 * 128 + (FOLD ? 256 : 0) : 0);
     float* buf1 = buf0 + GAMD_WFRAG_FLOATS;
     float* vb1 = L0 ? lds : buf1 + GAMD_WFRAG_FLOATS;
     float* vb3 = vb1 + 128;
     float* vb4 = vb3 + 128;
     float* vSD0 = vb4;                // L0: no W4, its slot holds S0 + D0
+    float* vax = vb4 + 128;           // FOLD: (a, 0) per output block, lane order
 
     const int tid = threadIdx.x, lane = tid & 63, slot = lane & 31, half = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -159,15 +171,32 @@ __global__ void __launch_bounds__(512, 2) k_conv_edge(ConvEdgeArgs a) {
     long long tprev = 0;
 #define TMARK(i) do { if (TIME) { const long long tn__ = (long long)__builtin_readcyclecounter(); tacc[i] += tn__ - tprev; tprev = tn__; } } while (0)
 
+    // (FOLD: the extra K step's fragment, loaded in front of the bias vectors and stored behind them: one round trip for all)
+    float vax_t = 0.f;
+    if (FOLD && tid < 256) vax_t = a.w1p[GAMD_WFRAG_FLOATS + tid];
     if (tid < 128) {
         vb1[tid] = a.b1[tid]; vb3[tid] = a.b3[tid];
         if (L0) vSD0[tid] = a.S[tid] + a.D[tid];
         else vb4[tid] = a.b4[tid];
     }
+    if (FOLD && tid < 256) vax[tid] = vax_t;
     stage(a.w1p, buf0);
 
     // three 64-register sets rotate through the roles {GEMM input, GEMM output, prefetched gather}
     f32x16 RA[4], RB[4], RC[4];
+    float rs = 0.f;                   // FOLD: the rstd fragment of the tile in RA
+    // FOLD: phase 1's extra K step on output tile tp
+    // (its weight fragment is read with the accumulator start, in front of the GEMM: read where it is used, each of the four
+    // MFMAs waits out an LDS round trip -- measured +7 us per launch at C2 instead of +3)
+    float wxr[4] = {0.f, 0.f, 0.f, 0.f};
+    auto fold_head = [&]() {
+        if constexpr (FOLD) {
+#pragma unroll
+            for (int tp = 0; tp < 4; ++tp) wxr[tp] = vax[tp * 64 + lane];
+            asm volatile("" : "+v"(wxr[0]), "+v"(wxr[1]), "+v"(wxr[2]), "+v"(wxr[3]));      // (hipcc sinks the reads back otherwise)
+        }
+    };
+    auto fold_tail = [&](int tp) { if constexpr (FOLD) RB[tp] = mfma32(wxr[tp], rs, RB[tp]); };
     auto init_b4 = [&]() {
 #pragma unroll
         for (int tp = 0; tp < 4; ++tp) {
@@ -188,6 +217,7 @@ __global__ void __launch_bounds__(512, 2) k_conv_edge(ConvEdgeArgs a) {
             src = GAMD_CHK_RANGE(a.sticky, a.col[x], 0, a.zero_row, GAMD_CHK_CONV_SRC);
             if (!L0) dst = GAMD_CHK_RANGE(a.sticky, a.erow[x], 0, a.zero_row, GAMD_CHK_CONV_DST);
         } else { src = a.zero_row; dst = a.zero_row; }
+        if (FOLD && active) rs = a.e_rstd[(size_t)tile * 64 + lane];
         if (active) load_e_tile(a.e_frag, tile, lane, RA);
     }
     asm volatile("" ::"v"(src), "v"(dst));      // compiler-visible wait for the index loads (see phase 4)
@@ -231,6 +261,8 @@ __global__ void __launch_bounds__(512, 2) k_conv_edge(ConvEdgeArgs a) {
     // phase_barrier<0> BEFORE their gathers: the branch is around the barrier, not around the loads, so both groups run the
     // same gather code into the same registers.
     auto early_barrier = [&](bool gathered) { if (gathered) phase_barrier<16>(); else phase_barrier<0>(); };
+    // the same behind the next tile's loads: FOLD adds the rstd fragment to the 16 loads of the tile
+    auto early_barrier_e = [&](bool gathered) { if (gathered) phase_barrier<FOLD ? 17 : 16>(); else phase_barrier<0>(); };
     // one store per finished piece of the previous tile: closing edges (mask bits) and, if the chunk's last valid edge does
     // not close a segment, that edge too (the run continues in the next chunk as its own piece)
     auto piece_stores = [&]() {
@@ -272,10 +304,11 @@ __global__ void __launch_bounds__(512, 2) k_conv_edge(ConvEdgeArgs a) {
         // ===== phase 1: RB = SiLU(W1 e + b1)        in RA = e, RC = pieces of the previous tile =====
         if (active) {
             load_bias_chain(vb1, half, RB);
+            fold_head();
             TMARK(0);
             gemm128_post<false>((const f32x4*)bx, lane, RA, RB,
                                 [&](int tp, int g) { RB[tp][g] = gamd_silu_hw(RB[tp][g]); },
-                                [&]() { FENCE(); piece_stores(); stage(a.w2p, by); FENCE(); });
+                                [&]() { FENCE(); piece_stores(); stage(a.w2p, by); FENCE(); }, fold_tail);
             TMARK(1);
         } else {
             piece_stores();
@@ -340,9 +373,10 @@ __global__ void __launch_bounds__(512, 2) k_conv_edge(ConvEdgeArgs a) {
         // boundary 3: the next tile's e -> RA.  Younger than the copy of W1: e (early waves)
         if (!early) phase_barrier<0>();
         TMARK(11);
+        if (FOLD && active_n) rs = a.e_rstd[(size_t)tile_n * 64 + lane];      // (first: its wait is the tile's first)
         if (active_n) load_e_tile(a.e_frag, tile_n, lane, RA);
         TMARK(12);
-        if (early) early_barrier(active_n);
+        if (early) early_barrier_e(active_n);
         TMARK(13);
         tile = tile_n; active = active_n; src = src_n;
     }
@@ -359,6 +393,7 @@ __global__ void __launch_bounds__(512, 2) k_conv_edge(ConvEdgeArgs a) {
         // ===== phase 1: RB = SiLU(W1 e + b1)        in RA = e (prefetched), RC = pieces of the previous tile =====
         if (active) {
             load_bias_chain(vb1, half, RB);
+            fold_head();
             TMARK(0);
             gemm128_post<false>((const f32x4*)buf0, lane, RA, RB,
                                 [&](int tp, int g) { RB[tp][g] = gamd_silu_hw(RB[tp][g]); },
@@ -368,7 +403,7 @@ __global__ void __launch_bounds__(512, 2) k_conv_edge(ConvEdgeArgs a) {
                                     load_row_chain(a.D + (size_t)dst * GAMD_H, half, RC);
                                     stage(a.w2p, buf1);
                                     FENCE();
-                                });
+                                }, fold_tail);
             TMARK(1);
         } else {
             piece_stores();
@@ -447,9 +482,10 @@ __global__ void __launch_bounds__(512, 2) k_conv_edge(ConvEdgeArgs a) {
         // boundary 4: the next tile's e -> RA.  Younger than the copy of W1: e (early waves)
         if (!early) phase_barrier<0>();
         TMARK(11);
+        if (FOLD && active_n) rs = a.e_rstd[(size_t)tile_n * 64 + lane];      // (first: its wait is the tile's first)
         if (active_n) load_e_tile(a.e_frag, tile_n, lane, RA);
         TMARK(12);
-        if (early) early_barrier(active_n);
+        if (early) early_barrier_e(active_n);
         TMARK(13);
         tile = tile_n; active = active_n; src = src_n; dst = dst_n;
     }
@@ -463,12 +499,12 @@ __global__ void __launch_bounds__(512, 2) k_conv_edge(ConvEdgeArgs a) {
 #undef TMARK
 }
 
-template <bool TIME, bool L0>
+template <bool TIME, bool L0, bool FOLD = false>
 int launch(const ConvEdgeArgs& a, int n_blocks, hipStream_t st) {
-    const size_t lds = sizeof(float) * conv_lds_floats(L0);
+    const size_t lds = sizeof(float) * conv_lds_floats(L0, FOLD);
     static PerDeviceOnce once;
-    if (int e = gamd_allow_dynamic_lds(once, (int)lds, k_conv_edge<TIME, L0>)) return e;
-    hipLaunchKernelGGL((k_conv_edge<TIME, L0>), dim3(n_blocks), dim3(512), lds, st, a);
+    if (int e = gamd_allow_dynamic_lds(once, (int)lds, k_conv_edge<TIME, L0, FOLD>)) return e;
+    hipLaunchKernelGGL((k_conv_edge<TIME, L0, FOLD>), dim3(n_blocks), dim3(512), lds, st, a);
     GAMD_CHECK_LAUNCH();
     return 0;
 }
@@ -478,15 +514,15 @@ int launch(const ConvEdgeArgs& a, int n_blocks, hipStream_t st) {
 int launch_conv_edge(const ConvEdgeArgs& a, int n_blocks, hipStream_t st) {
 #ifdef GAMD_PROFILING
     static const bool timed = getenv("GAMD_CONV_TIME") != nullptr;
-    if (timed) return launch<true, false>(a, n_blocks, st);
+    if (timed) return a.e_rstd ? launch<true, false, true>(a, n_blocks, st) : launch<true, false>(a, n_blocks, st);
 #endif
-    return launch<false, false>(a, n_blocks, st);
+    return a.e_rstd ? launch<false, false, true>(a, n_blocks, st) : launch<false, false>(a, n_blocks, st);
 }
 
 int launch_conv_edge_l0(const ConvEdgeArgs& a, int n_blocks, hipStream_t st) {
 #ifdef GAMD_PROFILING
     static const bool timed = getenv("GAMD_CONV_TIME") != nullptr;
-    if (timed) return launch<true, true>(a, n_blocks, st);
+    if (timed) return a.e_rstd ? launch<true, true, true>(a, n_blocks, st) : launch<true, true>(a, n_blocks, st);
 #endif
-    return launch<false, true>(a, n_blocks, st);
+    return a.e_rstd ? launch<false, true, true>(a, n_blocks, st) : launch<false, true>(a, n_blocks, st);
 }

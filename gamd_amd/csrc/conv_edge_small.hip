@@ -21,8 +21,11 @@ constexpr int XLD = GAMD_XLD;
 // order of wide.hip's phase 2 ((S + D) first, then the GEMM) instead of conv_edge.hip's (D, GEMM, + S).
 // L0: conv_edge.hip's layer-0 form (LJ models): S0 / D0 = row 0 of a.S / a.D (phase 2 in the WIDE order), phase 3 in the F2
 // orientation on a.w3p (packed in that order) with the segment sum of SiLU over the real edges, no phase 4.
-template <int EHT, int HT, bool WIDE, bool L0>
-__global__ void __launch_bounds__(256) k_conv_edge_small(ConvEdgeArgs a) {
+// FOLD: conv_edge.hip's folded edge LayerNorm (EHT = HT = 1, not WIDE): the tile is rstd x2, a.w1p = A and the fragment of the
+// extra K step, whose other operand is the tile's rstd fragment; W2, W3, W4 come from their own pointers.  The folded
+// instantiations are held to 256 registers (two waves per SIMD; 0 leaves the others' budget as it was).
+template <int EHT, int HT, bool WIDE, bool L0, bool FOLD = false>
+__global__ void __launch_bounds__(256, FOLD ? 2 : 0) k_conv_edge_small(ConvEdgeArgs a) {
     if (a.devflags[DEVFLAG_FROZEN]) return;          // frozen run: nothing to compute until the host has regrown and resumed
     constexpr int H = 128 * HT;
     __shared__ __attribute__((aligned(16))) float xbuf[32 * XLD];
@@ -43,7 +46,15 @@ __global__ void __launch_bounds__(256) k_conv_edge_small(ConvEdgeArgs a) {
         f32x16 X[4], XE[EHT][4], acc;
         WQuarter wa, wb;
         const float* wblk = a.w1p;                       // block k at wblk + k * GAMD_WFRAG_FLOATS
-        load_wquarter(wblk, quarter, lane, wa);
+        // FOLD: A is not part of the run; blocks 1, 2, 3 = W2, W3, W4
+        auto blk = [&](int k) { return FOLD ? (k == 1 ? a.w2p : k == 2 ? a.w3p : a.w4p) : wblk + (size_t)k * GAMD_WFRAG_FLOATS; };
+        // (FOLD: the lane's offset into the weight images is rebuilt per tile -- four separate images are four loop-invariant
+        // 64-bit addresses, which hipcc hoists out of the tile loop and spills)
+        int wl = lane;
+        if constexpr (FOLD) asm volatile("" : "+v"(wl));
+        float wx = 0.f, rs = 0.f;
+        if (FOLD) { wx = a.w1p[GAMD_WFRAG_FLOATS + quarter * 64 + lane]; rs = a.e_rstd[(size_t)tile * 64 + lane]; }
+        load_wquarter(wblk, quarter, wl, wa);
 #pragma unroll
         for (int kb = 0; kb < EHT; ++kb) {               // e tile in fragment order = chain layout registers
             const f32x4* ef = (const f32x4*)a.e_frag + ((size_t)tile * EHT + kb) * 16 * 64;
@@ -57,10 +68,12 @@ __global__ void __launch_bounds__(256) k_conv_edge_small(ConvEdgeArgs a) {
                 }
         }
         // rows this wave needs later: its quarter of S[src], D[dst]; hn[src] of its 16 edges x its 32 features
-        const f32x16 s_q = load_slice(a.S + (L0 ? 0 : (size_t)src * 128), quarter, half);
+        // (FOLD: S[src] and hn[src] are fetched behind phase 1 instead, see there)
+        f32x16 s_q;
+        if (!FOLD || L0) s_q = load_slice(a.S + (L0 ? 0 : (size_t)src * 128), quarter, half);
         const f32x16 d_q = load_slice(a.D + (L0 ? 0 : (size_t)dst * 128), quarter, half);
         f32x16 hn_q[HT];
-        if (!L0) {
+        if (!L0 && !FOLD) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int rho = (r & 3) + 8 * (r >> 2) + 4 * half;
@@ -81,19 +94,31 @@ __global__ void __launch_bounds__(256) k_conv_edge_small(ConvEdgeArgs a) {
         for (int kb = 0; kb < EHT; ++kb) {
             WQuarter& cur = (kb & 1) ? wb : wa;
             WQuarter& nxt = (kb & 1) ? wa : wb;
-            load_wquarter(wblk + (size_t)(kb + 1) * GAMD_WFRAG_FLOATS, quarter, lane, nxt);     // next K block, or W2
+            load_wquarter(blk(kb + 1), quarter, wl, nxt);     // next K block, or W2
             gemm_quarter<false>(cur, XE[kb], acc);
         }
+        if (FOLD) acc = mfma32(wx, rs, acc);               // the extra K step (a, 0) x (rstd, 0)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[r] = gamd_silu_hw(acc[r]);
         exchange(xbuf, quarter, slot, half, acc, X);
+        if constexpr (FOLD && !L0) {
+            // the rows phases 2 and 4 need, fetched here, behind the exchange's barriers: in front of phase 1 their 32 registers
+            // come on top of W1, W2 and the tile, more than the 256 this form keeps to
+            s_q = load_slice(a.S + (size_t)src * 128, quarter, half);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int rho = (r & 3) + 8 * (r >> 2) + 4 * half;
+                const int s = __shfl(src, rho, 64);
+                hn_q[0][r] = a.hn[(size_t)s * H + feat4(0)];
+            }
+        }
         // block index parity decides which buffer holds what from here on
         constexpr int B2 = EHT;                          // W2, then W3 = B2 + 1, W4[ob] = B2 + 2 + ob
         WQuarter& w2 = (B2 & 1) ? wb : wa;
         WQuarter& w3 = (B2 & 1) ? wa : wb;
         // phase 2: conv_edge.hip: T3 = SiLU((D[dst] + W2 T1) + S[src]);  wide.hip: T3 = SiLU((S + D) + W2 T1)
         if (WIDE || L0) acc = s_q + d_q; else acc = d_q;                 // (L0: conv_edge.hip's layer-0 form, (S0 + D0) first)
-        load_wquarter(L0 ? a.w3p : wblk + (size_t)(B2 + 1) * GAMD_WFRAG_FLOATS, quarter, lane, w3);
+        load_wquarter(L0 ? a.w3p : blk(B2 + 1), quarter, wl, w3);
         gemm_quarter<false>(w2, X, acc);
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[r] = gamd_silu_hw((WIDE || L0) ? acc[r] : acc[r] + s_q[r]);
@@ -127,7 +152,7 @@ __global__ void __launch_bounds__(256) k_conv_edge_small(ConvEdgeArgs a) {
         }
         // phase 3: T4 = SiLU(W3 T3 + b3)
         acc = load_slice(a.b3, quarter, half);
-        load_wquarter(wblk + (size_t)(B2 + 2) * GAMD_WFRAG_FLOATS, quarter, lane, w2);
+        load_wquarter(blk(B2 + 2), quarter, wl, w2);
         gemm_quarter<false>(w3, X, acc);
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[r] = gamd_silu_hw(acc[r]);
@@ -140,7 +165,7 @@ __global__ void __launch_bounds__(256) k_conv_edge_small(ConvEdgeArgs a) {
         for (int ob = 0; ob < HT; ++ob) {
             WQuarter& cur = (ob & 1) ? w3 : w2;
             WQuarter& nxt = (ob & 1) ? w2 : w3;
-            if (ob + 1 < HT) load_wquarter(wblk + (size_t)(B2 + 3 + ob) * GAMD_WFRAG_FLOATS, quarter, lane, nxt);
+            if (ob + 1 < HT) load_wquarter(blk(B2 + 3 + ob), quarter, wl, nxt);
             const float b = a.b4[128 * ob + 32 * quarter + slot];
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[r] = b;
@@ -173,13 +198,15 @@ __global__ void __launch_bounds__(256) k_conv_edge_small(ConvEdgeArgs a) {
 }  // namespace
 
 int launch_conv_edge_small(const ConvEdgeArgs& a, int n_blocks, hipStream_t st) {
-    hipLaunchKernelGGL((k_conv_edge_small<1, 1, false, false>), dim3(n_blocks), dim3(256), 0, st, a);
+    if (a.e_rstd) hipLaunchKernelGGL((k_conv_edge_small<1, 1, false, false, true>), dim3(n_blocks), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((k_conv_edge_small<1, 1, false, false>), dim3(n_blocks), dim3(256), 0, st, a);
     GAMD_CHECK_LAUNCH();
     return 0;
 }
 
 int launch_conv_edge_small_l0(const ConvEdgeArgs& a, int n_blocks, hipStream_t st) {
-    hipLaunchKernelGGL((k_conv_edge_small<1, 1, false, true>), dim3(n_blocks), dim3(256), 0, st, a);
+    if (a.e_rstd) hipLaunchKernelGGL((k_conv_edge_small<1, 1, false, true, true>), dim3(n_blocks), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((k_conv_edge_small<1, 1, false, true>), dim3(n_blocks), dim3(256), 0, st, a);
     GAMD_CHECK_LAUNCH();
     return 0;
 }

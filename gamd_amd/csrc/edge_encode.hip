@@ -16,6 +16,38 @@ namespace {
 
 constexpr int ENC_W1_FLOATS = 4 * 6 * 64 * 4;              // K padded to 48 (24 MFMA steps)
 constexpr int ENC_LDS_FLOATS = ENC_W1_FLOATS + 2 * GAMD_WFRAG_FLOATS + 5 * 128 + 64;
+constexpr int ENC_R_FLOATS = 10 * 1024;                    // folded form: the ten 32 x 32 blocks (tp, t >= tp) of R
+
+// block (tp, t >= tp) of the packed upper-triangular R (lnf_pack_r), in 1 KiB float4 groups
+__device__ __forceinline__ constexpr int enc_r_block(int tp, int t) { return (tp == 0 ? 0 : tp == 1 ? 4 : tp == 2 ? 7 : 9) + (t - tp); }
+
+// vt[tp] = this lane's sum of squares over output block tp of b + R X^T, for the block upper-triangular R: output block tp takes
+// K blocks t >= tp.  Only the sums leave, in layernorm_chain_centered's order (a chain of fused multiply-adds per block), so a
+// block's 16 accumulators are free again as soon as it is complete.
+template <typename WPtr, typename BPtr>
+__device__ __forceinline__ void gemm128_upper_sq(WPtr W, BPtr b, int lane, int half, const f32x16 (&X)[4], float (&vt)[4]) {
+#pragma unroll
+    for (int tp = 0; tp < 4; ++tp) {
+        f32x16 acc;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const f32x4 v = *reinterpret_cast<const f32x4*>(&b[32 * tp + 8 * q + 4 * half]);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[q * 4 + j] = v[j];
+        }
+#pragma unroll
+        for (int t = tp; t < 4; ++t)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const f32x4 w = W[(enc_r_block(tp, t) * 4 + q) * 64 + lane];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc = mfma32(w[j], X[t][q * 4 + j], acc);
+            }
+        vt[tp] = 0.f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) vt[tp] = fmaf(acc[r], acc[r], vt[tp]);
+    }
+}
 
 // Edge features of nn_module.py:603-634 (+ the bond flag of :510-511) for this lane's edge, already in the operand order of
 // the first GEMM: MFMA K step s covers features (2 s, 2 s + 1), lanes 0-31 supply the even one, lanes 32-63 the odd one.
@@ -78,7 +110,11 @@ __device__ __forceinline__ void gelu_block(const f32x16 (&acc)[4], f32x16 (&X)[4
     __builtin_amdgcn_s_setprio(0);
 }
 
-template <int NFEAT>
+// FOLD: the folded edge LayerNorm (gamd_ln_fold_host.h).  The third GEMM runs over the upper-triangular R of B = Q R (a.w3p: the
+// ten blocks with t >= tp, output block tp needs k >= 32 tp only: 160 MFMAs instead of 256) from Q^T c (a.b3), and only its row
+// norms are used: the tile stored is x2' = rstd x2, the GEMM's INPUT, with rstd beside it (a.rstd_out).  gamma and beta have
+// moved into the conv layers' first matrices.
+template <int NFEAT, bool FOLD = false>
 __global__ void __launch_bounds__(512, 2) k_edge_encode(EncArgs a) {
     if (a.devflags[DEVFLAG_FROZEN]) return;          // frozen run: nothing to compute until the host has regrown and resumed
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -97,11 +133,11 @@ __global__ void __launch_bounds__(512, 2) k_edge_encode(EncArgs a) {
     for (int i = tid; i < ENC_W1_FLOATS / 4; i += 512) ((f32x4*)w1)[i] = ((const f32x4*)a.w1p)[i];
     for (int i = tid; i < GAMD_WFRAG_FLOATS / 4; i += 512) {
         ((f32x4*)w2)[i] = ((const f32x4*)a.w2p)[i];
-        ((f32x4*)w3)[i] = ((const f32x4*)a.w3p)[i];
+        if (!FOLD || i < ENC_R_FLOATS / 4) ((f32x4*)w3)[i] = ((const f32x4*)a.w3p)[i];
     }
     if (tid < 128) {
         vb1[tid] = a.b1[tid]; vb2[tid] = a.b2[tid]; vb3[tid] = a.b3[tid];
-        vg[tid] = a.ln_g[tid]; vbeta[tid] = a.ln_b[tid];
+        if (!FOLD) { vg[tid] = a.ln_g[tid]; vbeta[tid] = a.ln_b[tid]; }
     }
     if (tid < 40) cen[tid] = a.centers[tid];
     __syncthreads();
@@ -153,7 +189,10 @@ __global__ void __launch_bounds__(512, 2) k_edge_encode(EncArgs a) {
         const int src = src_c, dst = dst_c;
         float F[24];
         __builtin_amdgcn_s_setprio(1);
-        edge_features<NFEAT>(a, cen, src, dst, ps, pd, half, F);
+        // (FOLD, non-uniform centres: the table straight from memory, as k_edge_encode_small reads it -- behind 152 KiB of LDS
+        // each of its twenty addresses is a loop-invariant register of its own)
+        if constexpr (FOLD) edge_features<NFEAT>(a, a.centers, src, dst, ps, pd, half, F);
+        else edge_features<NFEAT>(a, cen, src, dst, ps, pd, half, F);
         asm volatile("" : "+v"(F[0]), "+v"(F[23]));      // the features are complete before the priority drops
         __builtin_amdgcn_s_setprio(0);
         if (a.feat_dbg && valid) {
@@ -176,6 +215,10 @@ __global__ void __launch_bounds__(512, 2) k_edge_encode(EncArgs a) {
             }
         }
         gelu_block(acc, X, gk);
+        if constexpr (FOLD) {      // (as in front of GEMM 3 below)
+#pragma unroll
+            for (int t = 0; t < 4; ++t) asm volatile("" : "+v"(X[t]));
+        }
         // ---- GEMM 2 ----
         load_bias_chain(vb2, half, acc);
         gemm128<false>((const f32x4*)w2, lane, X, acc);
@@ -187,10 +230,28 @@ __global__ void __launch_bounds__(512, 2) k_edge_encode(EncArgs a) {
         src_c = ok_n ? src_n : 0; dst_c = ok_n ? dst_n : 0;
         ps = a.pos_s[src_c]; pd = a.pos_s[dst_c];
         // ---- GEMM 3 + LayerNorm ----
+        if constexpr (FOLD) {
+            // x2 is complete here: it outlives the GEMM, and hipcc would otherwise sink the last step of each GELU towards its
+            // MFMA and keep three registers per element alive instead of one (spills)
+#pragma unroll
+            for (int t = 0; t < 4; ++t) asm volatile("" : "+v"(X[t]));
+            // the LayerNorm's sums as layernorm_chain_centered forms them; what leaves is the GEMM's input times rstd
+            float vt[4];
+            gemm128_upper_sq((const f32x4*)w3, vb3, lane, half, X, vt);
+            const float var = gamd_xhalf_sum((vt[0] + vt[1]) + (vt[2] + vt[3])) * a.ln_inv_width;
+            const float rstd = 1.0f / sqrtf(var + 1e-5f);
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[t][r] = X[t][r] * rstd;
+            asm volatile("" ::"v"(ps.x), "v"(ps.y), "v"(ps.z), "v"(ps.w), "v"(pd.x), "v"(pd.y), "v"(pd.z), "v"(pd.w));
+            a.rstd_out[(size_t)tile * 64 + lane] = half ? 0.f : rstd;
+        } else {
         load_bias_chain(vb3, half, acc);
         gemm128<false>((const f32x4*)w3, lane, X, acc);
         layernorm_chain_centered(acc, vg, vbeta, half, 1e-5f, a.ln_inv_width);     // W3, b3 arrive centred
-        if (a.self_loop) {
+        }
+        if (!FOLD && a.self_loop) {
             // self_loop_mode 1: the last edge of every row is the loop an in-place add_self_loop would have appended AFTER
             // edata['e'] was set (nn_module.py:649-652): its embedding is DGL's zero fill, not an encoded feature row
             if (valid && gamd_is_appended_loop(a, x, src, dst)) {
@@ -222,8 +283,32 @@ __global__ void __launch_bounds__(512, 2) k_edge_encode(EncArgs a) {
 // from its weight quarter read straight from L2, applies GELU to its 16 values per lane (a quarter of the VALU work per
 // wave), and the 128-wide rows are re-assembled through LDS between the GEMMs.  Same operations in the same order per
 // output element as k_edge_encode (including the LayerNorm sums: per 32-feature block, then a fixed tree): bit-identical.
-template <int NFEAT>
-__global__ void __launch_bounds__(256) k_edge_encode_small(EncArgs a) {
+// output block TP of R X^T from the wave's groups of R (wq.w[(t - TP) * 4 + q], t >= TP)
+template <int TP>
+__device__ __forceinline__ void gemm_quarter_upper(const WQuarter& wq, const f32x16 (&X)[4], f32x16& acc) {
+#pragma unroll
+    for (int t = TP; t < 4; ++t)
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc = mfma32(wq.w[(t - TP) * 4 + q][j], X[t][q * 4 + j], acc);
+}
+
+// one 32-feature block of x2' = rstd x2: four 1 KiB groups of the tile's fragment
+__device__ __forceinline__ void store_scaled_quarter(f32x4* out, const f32x16& x, float rstd) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        f32x4 o;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] = x[q * 4 + j] * rstd;
+        out[q * 64] = o;
+    }
+}
+
+// FOLD: as in k_edge_encode; wave `quarter` runs output block tp = quarter of R over its 4 - quarter K blocks.  The folded
+// instantiation is held to 256 registers (two waves per SIMD; 0 leaves the general one's budget as it was).
+template <int NFEAT, bool FOLD = false>
+__global__ void __launch_bounds__(256, FOLD ? 2 : 0) k_edge_encode_small(EncArgs a) {
     if (a.devflags[DEVFLAG_FROZEN]) return;          // frozen run: nothing to compute until the host has regrown and resumed
     __shared__ __attribute__((aligned(16))) float xbuf[32 * GAMD_XLD];
     __shared__ float red[4][64];
@@ -264,14 +349,36 @@ __global__ void __launch_bounds__(256) k_edge_encode_small(EncArgs a) {
         exchange(xbuf, quarter, slot, half, acc, X);
         // GEMM 2 + GELU
         acc = load_slice(a.b2, quarter, half);
+        // FOLD: this wave's 4 (4 - quarter) groups of R; the index is clamped to the image for the slots it does not use
+        auto r_group = [&](int i) { const int gi = enc_r_block(quarter, quarter) * 4 + i; return gi < ENC_R_FLOATS / 256 ? gi : ENC_R_FLOATS / 256 - 1; };
+        if constexpr (FOLD) {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) wb.w[i] = ((const f32x4*)a.w3p)[r_group(i) * 64 + lane];
+        } else {
         load_wquarter(a.w3p, quarter, lane, wb);
+        }
         gemm_quarter<false>(wa, X, acc);
+        if constexpr (FOLD) {
+            // the second half behind GEMM 2, where W2's registers are free (all sixteen in front of it do not fit into 256)
+#pragma unroll
+            for (int i = 8; i < 16; ++i) wb.w[i] = ((const f32x4*)a.w3p)[r_group(i) * 64 + lane];
+        }
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[r] = gamd_gelu_hw(acc[r]);
         exchange(xbuf, quarter, slot, half, acc, X);
         // GEMM 3 (rows arrive centred) + LayerNorm
         acc = load_slice(a.b3, quarter, half);
+        if constexpr (FOLD) {
+            // K blocks t = quarter .. 3 in the order of gemm128_upper_sq (quarter is wave-uniform: a scalar branch)
+            switch (quarter) {
+                case 0: gemm_quarter_upper<0>(wb, X, acc); break;
+                case 1: gemm_quarter_upper<1>(wb, X, acc); break;
+                case 2: gemm_quarter_upper<2>(wb, X, acc); break;
+                default: gemm_quarter_upper<3>(wb, X, acc); break;
+            }
+        } else {
         gemm_quarter<false>(wb, X, acc);
+        }
         float v = 0.f;
 #pragma unroll
         for (int r = 0; r < 16; ++r) v = fmaf(acc[r], acc[r], v);
@@ -280,6 +387,18 @@ __global__ void __launch_bounds__(256) k_edge_encode_small(EncArgs a) {
         __syncthreads();
         const float var = gamd_xhalf_sum((red[0][lane] + red[1][lane]) + (red[2][lane] + red[3][lane])) * a.ln_inv_width;
         const float rstd = 1.0f / sqrtf(var + 1e-5f);
+        if constexpr (FOLD) {
+            // this wave's quarter of x2' = rstd x2, and rstd itself once per tile
+            f32x4* outf = (f32x4*)a.e_frag + ((size_t)tile * 16 + quarter * 4) * 64 + lane;
+            switch (quarter) {
+                case 0: store_scaled_quarter(outf, X[0], rstd); break;
+                case 1: store_scaled_quarter(outf, X[1], rstd); break;
+                case 2: store_scaled_quarter(outf, X[2], rstd); break;
+                default: store_scaled_quarter(outf, X[3], rstd); break;
+            }
+            if (quarter == 0) a.rstd_out[(size_t)tile * 64 + lane] = half ? 0.f : rstd;
+            continue;
+        }
         const f32x16 g = load_slice(a.ln_g, quarter, half), b = load_slice(a.ln_b, quarter, half);
         const bool zero_row = valid && gamd_is_appended_loop(a, x, src, dst);      // appended loop: e = 0
         f32x4* out = (f32x4*)a.e_frag + (size_t)tile * 16 * 64;
@@ -296,7 +415,9 @@ __global__ void __launch_bounds__(256) k_edge_encode_small(EncArgs a) {
 }  // namespace
 
 int launch_edge_encode_small(const EncArgs& a, int n_blocks, hipStream_t st) {
-    if (a.n_feat == 44) hipLaunchKernelGGL((k_edge_encode_small<44>), dim3(n_blocks), dim3(256), 0, st, a);
+    if (a.rstd_out && a.n_feat == 44) hipLaunchKernelGGL((k_edge_encode_small<44, true>), dim3(n_blocks), dim3(256), 0, st, a);
+    else if (a.rstd_out && a.n_feat == 45) hipLaunchKernelGGL((k_edge_encode_small<45, true>), dim3(n_blocks), dim3(256), 0, st, a);
+    else if (a.n_feat == 44) hipLaunchKernelGGL((k_edge_encode_small<44>), dim3(n_blocks), dim3(256), 0, st, a);
     else if (a.n_feat == 45) hipLaunchKernelGGL((k_edge_encode_small<45>), dim3(n_blocks), dim3(256), 0, st, a);
     else return -22;
     GAMD_CHECK_LAUNCH();
@@ -306,8 +427,10 @@ int launch_edge_encode_small(const EncArgs& a, int n_blocks, hipStream_t st) {
 int launch_edge_encode(const EncArgs& a, int n_blocks, hipStream_t st) {
     const size_t lds = sizeof(float) * ENC_LDS_FLOATS;
     static PerDeviceOnce once;
-    if (int e = gamd_allow_dynamic_lds(once, (int)lds, k_edge_encode<44>, k_edge_encode<45>)) return e;
-    if (a.n_feat == 44) hipLaunchKernelGGL((k_edge_encode<44>), dim3(n_blocks), dim3(512), lds, st, a);
+    if (int e = gamd_allow_dynamic_lds(once, (int)lds, k_edge_encode<44>, k_edge_encode<45>, k_edge_encode<44, true>, k_edge_encode<45, true>)) return e;
+    if (a.rstd_out && a.n_feat == 44) hipLaunchKernelGGL((k_edge_encode<44, true>), dim3(n_blocks), dim3(512), lds, st, a);
+    else if (a.rstd_out && a.n_feat == 45) hipLaunchKernelGGL((k_edge_encode<45, true>), dim3(n_blocks), dim3(512), lds, st, a);
+    else if (a.n_feat == 44) hipLaunchKernelGGL((k_edge_encode<44>), dim3(n_blocks), dim3(512), lds, st, a);
     else if (a.n_feat == 45) hipLaunchKernelGGL((k_edge_encode<45>), dim3(n_blocks), dim3(512), lds, st, a);
     else return -22;
     GAMD_CHECK_LAUNCH();

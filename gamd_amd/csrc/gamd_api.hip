@@ -1,6 +1,7 @@
 // gamd_api.hip — weight packing, the force evaluation, the MD driver and their extern "C" entry points of include/gamd_hip.h
 // (the handle itself is in gamd_host.h; the run observers' entry points are in observe.hip).
 #include "gamd_host.h"
+#include "gamd_ln_fold_host.h"
 
 #include <algorithm>
 #include <cmath>
@@ -44,6 +45,7 @@ int alloc_edges(gamd_handle* h, long long e_cap) {
     r |= h->chunk_piece.ensure(sizeof(int) * (ec / GAMD_CHUNK + 2), true);
     r |= h->chunk_mask.ensure(sizeof(unsigned) * (ec / GAMD_CHUNK + 2), true);
     r |= h->e_frag.ensure(sizeof(float) * 4096 * (size_t)h->EHT * (ec / GAMD_TILE + 1), false);
+    if (h->ln_fold) r |= h->e_rstd.ensure(sizeof(float) * 64 * (ec / GAMD_TILE + 1), false);
     r |= h->partial.ensure(sizeof(float) * (size_t)h->H * (ec / GAMD_CHUNK + (size_t)h->n + 2), false);
     h->piece_cap = (long long)(ec / GAMD_CHUNK + (size_t)h->n + 2);
     if (h->update_edge) {                        // e_emb rows of one layer and the updated embedding tiles (H == Eh)
@@ -442,6 +444,7 @@ int enqueue_forward(gamd_handle* h, const float* pos_dev, const uint8_t* species
     ea.e_cap = h->e_cap;
     ea.sticky = h->sticky_dev;
     ea.feat_dbg = h->cfg.keep_stages ? h->feat_dbg.as<float>() : nullptr;
+    ea.rstd_out = h->ln_fold ? h->e_rstd.as<float>() : nullptr;
     // fp32 path, few tiles (measured crossover ~500 tiles, half a tile per SIMD): the latency-oriented kernels, one tile
     // per 4-wave workgroup (conv_edge_small.hip, k_edge_encode_small).  They are bit-identical to the throughput kernels, so
     // the choice (from the last known edge count, or the density estimate before the first call) never shows in the results.
@@ -552,6 +555,7 @@ int enqueue_forward(gamd_handle* h, const float* pos_dev, const uint8_t* species
         // layer-0 form: three GEMMs per edge, phi_edge's part applied per atom by post(0) (timed as conv layer 0 all the same)
         const bool hoist = l == 0 && h->l0_hoist;
         if (hoist) { ca.w3p = ld.w3p_l0; ca.b3 = ld.b3_l0; }
+        ca.e_rstd = h->ln_fold ? h->e_rstd.as<float>() : nullptr;
         ca.partial = h->partial.as<float>();
         ca.piece_cap = h->piece_cap;
         ca.sticky = h->sticky_dev;
@@ -778,7 +782,7 @@ int32_t gamd_create(const gamd_config* cfg, gamd_handle** out) {
         return fail(-22, "unknown self_loop_mode %d", cfg->self_loop_mode);
     if (cfg->self_loop_mode != GAMD_SELF_LOOP_DGL07_NOOP && cfg->edge_dtype != GAMD_EDGE_F32)
         return fail(-22, "self_loop_mode 1 is built for the fp32 edge dtype only");
-    if (cfg->kernel_select & ~(GAMD_KSEL_FORCE_GENERIC_WIDTH | GAMD_KSEL_FORCE_HALF_QUANTUM | GAMD_KSEL_NO_LAYER0_HOIST))
+    if (cfg->kernel_select & ~(GAMD_KSEL_FORCE_GENERIC_WIDTH | GAMD_KSEL_FORCE_HALF_QUANTUM | GAMD_KSEL_NO_LAYER0_HOIST | GAMD_KSEL_NO_LN_FOLD))
         return fail(-22, "unknown kernel_select bits 0x%x", cfg->kernel_select);
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
@@ -830,6 +834,11 @@ int32_t gamd_create(const gamd_config* cfg, gamd_handle** out) {
     const bool lp_generic = cfg->edge_dtype != GAMD_EDGE_F32 && (generic || !exact128);
     h->wide_enc = generic || forced || lp_generic || Dp > 128;
     h->wide_conv = H != 128 || Eh != 128 || forced || lp_generic || Dp > 128;
+    // Folded edge LayerNorm (gamd_ln_fold_host.h): the fp32 128-wide kernels without appended self loops; not with keep_stages
+    // (e is then a stage the getters hand out), not under GAMD_KSEL_NO_LN_FOLD, not for update_edge_emb models (which
+    // gamd_finalize_weights moves to the generic-width kernels)
+    h->ln_fold = cfg->edge_dtype == GAMD_EDGE_F32 && !h->wide_enc && !h->wide_conv && cfg->self_loop_mode == GAMD_SELF_LOOP_DGL07_NOOP &&
+                 !cfg->keep_stages && !(cfg->kernel_select & GAMD_KSEL_NO_LN_FOLD);
     h->n_feat = (cfg->no_expand_edge ? 4 : 44) + (cfg->use_bond ? 1 : 0);
     h->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     const size_t n = (size_t)h->n;
@@ -932,7 +941,7 @@ int32_t gamd_destroy(gamd_handle* h) {
     DevBuf* bufs[] = {&h->boxes_dev, &h->box_shift, &h->wblob, &h->pos_w, &h->pos_s, &h->cell_of, &h->perm, &h->inv_perm, &h->deg, &h->row_ptr,
                       &h->na_excl, &h->bond_nbr, &h->hbuf, &h->hn, &h->S, &h->D, &h->P, &h->l0_h, &h->l0_hn, &h->l0_S, &h->l0_D, &h->l0_P, &h->f_norm, &h->f_den,
                       &h->cell_cnt, &h->cell_fill, &h->cell_start, &h->col, &h->erow, &h->chunk_piece,
-                      &h->chunk_mask, &h->e_frag, &h->e_emb, &h->e_frag2, &h->partial, &h->feat_dbg, &h->counters, &h->tdbg, &h->tmp_eid, &h->ke_partial, &h->com_partial,
+                      &h->chunk_mask, &h->e_frag, &h->e_rstd, &h->e_emb, &h->e_frag2, &h->partial, &h->feat_dbg, &h->counters, &h->tdbg, &h->tmp_eid, &h->ke_partial, &h->com_partial,
                       &h->ref_pos, &h->cand_deg, &h->cand_ptr, &h->cand_col};
     for (DevBuf* b : bufs) b->release();
     observers_free(h);
@@ -1046,6 +1055,7 @@ int32_t gamd_finalize_weights(gamd_handle* h) {
         if (h->cfg.edge_dtype != GAMD_EDGE_F32 || h->cfg.self_loop_mode)
             return fail(-22, "update_edge_emb is built for the fp32 edge MLP without appended self loops");
         h->wide_enc = h->wide_conv = true;
+        h->ln_fold = false;
     }
     if (update_edge != h->update_edge) {
         h->update_edge = update_edge;
@@ -1073,6 +1083,16 @@ int32_t gamd_finalize_weights(gamd_handle* h) {
                 bo.data[32 * q + s] = b.data[4 * s + q];
             }
     };
+    // Folded edge LayerNorm: B = C W_e3, c = C b_e3 (the centred last encoder Linear, in double) for the layers' first matrices
+    std::vector<double> fold_B, fold_c;
+    const HostTensor *fold_g = nullptr, *fold_b = nullptr;
+    if (h->ln_fold) {
+        const HostTensor *w = get("edge_encoder.mlp_layer.4.weight", {Et, Dt}, {Eh, Dp}), *b = get("edge_encoder.mlp_layer.4.bias", {Et}, {Eh});
+        fold_g = get("edge_layer_norm.weight", {Et}, {Eh});
+        fold_b = get("edge_layer_norm.bias", {Et}, {Eh});
+        if (!w || !b || !fold_g || !fold_b) return -2;
+        lnf_center(w->data.data(), b->data.data(), (int)Et, fold_B, fold_c);
+    }
     for (int l = 0; l < L; ++l) {
         const std::string p = "graph_conv.conv." + std::to_string(l);
         // edge_affine = MLP(Eh, hidden_dim, hidden_layer=2): its inner width is MLP's default 128 (nn_module.py:25,95)
@@ -1203,7 +1223,21 @@ int32_t gamd_finalize_weights(gamd_handle* h) {
         } else {
             // one contiguous run of blocks: W1[:, kb] (EHT) | W2 | W3 | W4[ob, :] (HT) -- the order the kernels stream them
             // (hidden_dim above 128, wide_d.hip: W1[:, kb] (EHT) | W2[db, :] (DT) | W3[ob][db] (DT x DT) | W4[ob][db] (HT x DT))
+            if (h->ln_fold) {
+                // A_l = W1 diag(gamma) B and the extra K step's fragment (a_l, 0) take W1's place, b1'_l = b1 + W1 beta takes b1's
+                std::vector<double> A, av, b1f;
+                lnf_layer(ea0w->data.data(), ea0b->data.data(), fold_g->data.data(), fold_b->data.data(), fold_B, fold_c, A, av, b1f);
+                const std::vector<float> Af = lnf_round(A), af = lnf_round(av);
+                o.w1p = bb.add((size_t)LNF_A_FLOATS);
+                lnf_pack_a(Af.data(), af.data(), bb.host.data() + o.w1p);
+                HostTensor b1t;
+                b1t.shape = {128};
+                b1t.data = lnf_round(b1f);
+                padded.push_back(std::move(b1t));
+                ea0b = &padded.back();
+            } else {
             o.w1p = put_blocks(ea0w, 1, (int)EHT);
+            }
             o.w2p = put_blocks(ea2w, (int)DT, 1);
             o.w3p = put_blocks(t1w, (int)DT, (int)DT);
             if (DT > 1) {
@@ -1276,8 +1310,16 @@ int32_t gamd_finalize_weights(gamd_handle* h) {
         mb /= (double)Et;
         for (int64_t o = 0; o < Et; ++o) e4b_c.data[(size_t)o] = (float)((double)e4b->data[(size_t)o] - mb);
     }
-    const size_t o_e3 = bf16_edges ? put_edge_bf16(e4w) : f16x3_edges ? put_edge_f16x3(e4w) : enc_wide_f16 ? put_blocks_f16x3(&e4w_c, (int)EHT, 1)
+    if (h->ln_fold) {
+        // the encoder needs |B x2 + c| only: R of B = Q R (its six all-zero blocks left out) and Q^T c take W3's and b3's places
+        std::vector<double> Rm, cq;
+        lnf_qr(fold_B, fold_c, Rm, cq);
+        e4b_c.data = lnf_round(cq);
+        e4w_c.data = lnf_round(Rm);
+    }
+    const size_t o_e3 = h->ln_fold ? bb.add((size_t)LNF_R_FLOATS) : bf16_edges ? put_edge_bf16(e4w) : f16x3_edges ? put_edge_f16x3(e4w) : enc_wide_f16 ? put_blocks_f16x3(&e4w_c, (int)EHT, 1)
                                                                                                               : put_blocks(&e4w_c, (int)EHT, (int)DT);
+    if (h->ln_fold) lnf_pack_r(e4w_c.data.data(), bb.host.data() + o_e3);
     const size_t o_eb1 = put_vec(e0b), o_eb2 = put_vec(e2b), o_eb3 = put_vec(&e4b_c), o_elg = put_vec(elg), o_elb = put_vec(elb);
     const size_t o_cen = expand ? put_vec(cen) : bb.add(64);
     const size_t o_d1 = put_node(d0w, (int)DT, (int)HT), o_db1 = put_vec(d0b), o_d2 = put_vec(d2w), o_db2 = put_vec(d2b);
@@ -1592,8 +1634,10 @@ int32_t gamd_debug_get(gamd_handle* h, int32_t what, void* host_out, size_t byte
     if (what == GAMD_DBG_PERM) { src = h->perm.p; avail = sizeof(int) * n; }
     else if (what == GAMD_DBG_ROWPTR) { src = h->row_ptr.p; avail = sizeof(int) * (n + 1); }
     else if (what == GAMD_DBG_COL) { src = h->col.p; avail = sizeof(int) * E; }
-    else if (what == GAMD_DBG_EFRAG) { src = h->e_frag.p; avail = sizeof(float) * 4096 * (size_t)h->EHT * ((E + 31) / 32); }
-    else if (what == GAMD_DBG_FEAT) {
+    else if (what == GAMD_DBG_EFRAG) {
+        if (h->ln_fold) return fail(-22, "EFRAG needs keep_stages=1 on this handle: the edge LayerNorm is folded into the conv layers and e is never formed");
+        src = h->e_frag.p; avail = sizeof(float) * 4096 * (size_t)h->EHT * ((E + 31) / 32);
+    } else if (what == GAMD_DBG_FEAT) {
         if (!h->cfg.keep_stages) return fail(-22, "FEAT needs keep_stages=1");
         src = h->feat_dbg.p; avail = sizeof(float) * 48 * E;
     } else if (what >= GAMD_DBG_H0 && what <= GAMD_DBG_H0 + h->L) {

@@ -84,6 +84,7 @@ struct LayerDev {
     const float *w16p = nullptr;                        // generic-width fp32: the blocks again, packed for wide16.hip
     const float *e_ln_g = nullptr, *e_ln_b = nullptr;   // update_edge_emb: this layer's edge_layer_norm
     const float *w3p_l0 = nullptr, *b3_l0 = nullptr;    // layer-0 form (gamd_handle::l0_hoist): W3, b3 in the F2 output order
+                                                        // (gamd_handle::ln_fold: w1p = A_l + the extra K step's fragment, b1 = b1'_l)
     NodeLayerW node;
 };
 
@@ -151,6 +152,8 @@ struct gamd_handle {
     bool node_f16 = false;                       // node.hip's GEMMs in split-fp16 (reduced-precision edge modes, 128-wide kernels)
     bool wide_enc = false, wide_conv = false;    // generic-width kernels of wide.hip
     bool l0_hoist = false;                       // LJ, fp32, 128-wide: layer 0 in its three-GEMM form (conv_edge.hip, node.hip post(0))
+    bool ln_fold = false;                        // fp32, 128-wide, no update_edge / appended loops / keep_stages: edge LayerNorm folded
+                                                 // into the encoder's norm and every layer's first matrix (gamd_ln_fold_host.h)
     long long small_tile_limit = 512;            // fp32 path: at most this many 32-edge tiles -> conv_edge_small.hip
     std::map<std::string, HostTensor> host_w;
     bool finalized = false;
@@ -181,6 +184,7 @@ struct gamd_handle {
     long long e_cap = 0;
     long long piece_cap = 0;        // rows of `partial`
     DevBuf col, erow, chunk_piece, chunk_mask, e_frag, partial, feat_dbg, e_emb, e_frag2;
+    DevBuf e_rstd;                               // ln_fold: [tiles][64] rstd fragments beside e_frag (EncArgs::rstd_out)
     DevBuf counters, tdbg, tmp_eid, ke_partial, com_partial;
     DevBuf cnt2;                    // small systems in skin mode: two counter blocks used alternately (no per-call memset)
     int cnt_parity = 0;

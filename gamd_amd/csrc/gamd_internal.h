@@ -239,6 +239,9 @@ struct EncArgs {
     int* sticky;               // host-mapped flags (checked build: GAMD_CHK_RANGE reports here)
     int e_format;              // generic-width encoder (wide.hip): 0 = fp32 fragments, 1 = bf16 fragments (wide_lp.hip), 2 = (hi, lo)
                                // fp16 operand images for the split-fp16 conv kernels (the layout edge_encode_f16x3.hip writes)
+    float* rstd_out;           // folded edge LayerNorm (launch_edge_encode / _small, gamd_ln_fold_host.h): [tiles][64] in lane order,
+                               // lanes 0-31 the edge's rstd, lanes 32-63 zero; e_frag then holds rstd x2, w3p the ten non-zero
+                               // blocks of R, b3 = Q^T c, ln_g / ln_b are not read.  Null: e = LayerNorm(W3 x2 + b3)
 };
 // self_loop_mode 1: is CSR slot x (source src, destination dst) the loop that was appended behind the row's real edges?  It is the
 // last slot of its row that is not a padding slot (padding follows only in the row of a box's last atom, n_boxes > 1).
@@ -290,6 +293,9 @@ struct ConvEdgeArgs {
     long long piece_cap;       // rows of `partial` (checked build: every piece index is tested against it)
     float* emb_out;            // update_edge_emb (generic-width kernels only): e_emb = theta_edge(...) of every edge, [E][H] rows
                                // in CSR order, for launch_edge_update; null otherwise
+    const float* e_rstd;       // folded edge LayerNorm (launch_conv_edge, _l0, _small, _small_l0): EncArgs::rstd_out; e_frag then
+                               // holds rstd x2, w1p is A_l followed by the extra K step's fragment (a_l, 0) (lnf_pack_a), b1 = b1'_l.
+                               // Null: the general form
 };
 int launch_conv_edge(const ConvEdgeArgs& a, int n_blocks, hipStream_t st);
 // layer-0 form (LJ models, conv_edge.hip): three GEMMs per edge, pieces hold sums of SiLU(W3 T2 + b3) over the real edges;

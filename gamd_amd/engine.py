@@ -27,6 +27,7 @@ FLAVOUR = {"jaxmd": 0, "torch": 1}
 SELF_LOOP = {"dgl07_noop": 0, "append_zero_feature_loops": 1}
 KSEL_FORCE_GENERIC_WIDTH = 1
 KSEL_NO_LAYER0_HOIST = 4        # LJ, fp32: layer 0 in its general four-GEMM form (include/gamd_hip.h)
+KSEL_NO_LN_FOLD = 8             # fp32, 128-wide: e = LayerNorm(...) formed by the encoder, not folded into the conv layers
 
 
 def _box3(box) -> np.ndarray:
@@ -680,7 +681,8 @@ class GamdForce:
         return self.debug_csr()[1] < self.n_total
 
     def debug_e(self) -> np.ndarray:
-        """e [E, edge_embedding_dim] de-fragmented to CSR edge order."""
+        """e [E, edge_embedding_dim] de-fragmented to CSR edge order.  Needs keep_stages=True (or KSEL_NO_LN_FOLD) where the
+        fp32 128-wide kernels fold the edge LayerNorm into the conv layers: e is then never formed and the library refuses."""
         e = self.counts()[0]
         nt = (e + 31) // 32
         nb = (self.cfg.edge_embedding_dim + 127) // 128               # widths below a 128-block are zero-padded on the device

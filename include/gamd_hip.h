@@ -95,7 +95,10 @@ typedef struct gamd_config {
                                 work units (wide16.hip, v_mfma_f32_16x16x4_f32; bit-identical results, measured slower at every
                                 size tried: never chosen automatically); GAMD_KSEL_NO_LAYER0_HOIST (4): LJ models in fp32 on the
                                 128-wide kernels run layer 0 in its general form (four GEMMs per edge) instead of the layer-0
-                                form (three GEMMs per edge, the last Linear applied per atom; equal up to fp32 rounding) */
+                                form (three GEMMs per edge, the last Linear applied per atom; equal up to fp32 rounding);
+                                GAMD_KSEL_NO_LN_FOLD (8): the fp32 128-wide kernels form the edge embedding e = LayerNorm(...)
+                                in the encoder, as they do under keep_stages, instead of folding the LayerNorm's affine part
+                                into every conv layer's first matrix (equal up to fp32 rounding) */
     int32_t small_tile_limit;/* fp32 path: edge counts of at most this many 32-edge tiles run the latency-oriented conv kernel
                                 (one tile per 4-wave workgroup, bit-identical results).  0 = default (512), -1 = never */
     int32_t n_boxes;         /* 0 or 1: one box (default).  B > 1: B INDEPENDENT boxes of n_atoms atoms each, evaluated and
@@ -112,7 +115,7 @@ typedef struct gamd_config {
                                 index B*n).  A neighbour-buffer overflow in any box regrows the shared buffers. */
 } gamd_config;
 enum { GAMD_SELF_LOOP_DGL07_NOOP = 0, GAMD_SELF_LOOP_APPEND_ZERO_FEATURE = 1 };
-enum { GAMD_KSEL_FORCE_GENERIC_WIDTH = 1, GAMD_KSEL_FORCE_HALF_QUANTUM = 2, GAMD_KSEL_NO_LAYER0_HOIST = 4 };
+enum { GAMD_KSEL_FORCE_GENERIC_WIDTH = 1, GAMD_KSEL_FORCE_HALF_QUANTUM = 2, GAMD_KSEL_NO_LAYER0_HOIST = 4, GAMD_KSEL_NO_LN_FOLD = 8 };
 
 const char* gamd_version(void);
 const char* gamd_last_error(void);
