@@ -78,6 +78,7 @@ CLASSICAL_ROW = 9                                           # GAMD_CLASSICAL_ROW
 WATER_ROW = 12                                              # GAMD_WATER_ROW: doubles per box and row of gamd_water_read
 TRAJ_FIELDS = {"x": 1, "v": 2, "f": 4, "image": 8}          # GAMD_TRAJ_*
 FORCE_SOURCE = {"network": 0, "classical": 1}               # GAMD_FORCE_*
+WATER_FORCE_SOURCE = {"water_classical": 2}                 # GAMD_FORCE_WATER_CLASSICAL (GAMD_KIND_WATER handles)
 
 
 # every symbol include/gamd_hip.h declares: name -> (restype, argtypes)

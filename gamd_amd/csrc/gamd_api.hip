@@ -406,7 +406,7 @@ int enqueue_forward(gamd_handle* h, const float* pos_dev, const uint8_t* species
 
     // classical force source (a step of an enqueued MD run, gamd_md_force_source): the neighbour stage above stays — the fused
     // integrator halves, the observers' edge list and pos_s, and the freeze / resume machinery hang on it — and the potential's
-    // two launches stand where encoder, conv layers and decoder would
+    // launches (two for Lennard-Jones, five for water) stand where encoder, conv layers and decoder would
     if (drive) {
         if ((r = drive_enqueue(h))) return r;
         if (copy_counters)
@@ -659,7 +659,7 @@ int step_event(gamd_handle* h, hipStream_t st, bool closes = false) {
 // steps [s_begin, n_steps) of the pending MD run; skip_first: the first half of step s_begin has already been done
 int enqueue_md_steps(gamd_handle* h, long long s_begin, bool skip_first) {
     MdPending& p = h->pending;
-    const bool drive = h->force_source == GAMD_FORCE_CLASSICAL;      // cannot change while the run is pending
+    const bool drive = h->force_source != GAMD_FORCE_NETWORK;        // cannot change while the run is pending
     int r;
     // Skin mode, BAOAB (free atoms or rigid water): the B of step s-1 and the B A O A of step s ride in the first kernel of step s's force
     // evaluation (k_step_small / k_skin_check): 2 launches less per step; the last B is launched on its own.
@@ -1660,7 +1660,10 @@ int32_t gamd_md_run(gamd_handle* h, float* x_dev, float* v_dev, float* f_dev, co
     if (n_steps < 0 || n_steps > 0x3fffffff) return fail(-22, "n_steps out of range");
     if ((r = check_model_inputs(h, species_dev))) return r;
     if ((r = observers_check_run(h, box, species_dev))) return r;
-    if (h->force_source == GAMD_FORCE_CLASSICAL && (r = drive_check_run(h, box, species_dev))) return r;
+    if (h->force_source == GAMD_FORCE_WATER_CLASSICAL && !p->rigid_water)
+        return fail(-22, "the water classical force source needs rigid_water: the potential has no bond or angle term (same-molecule "
+                         "pairs are excluded), so only the constraints hold a molecule together");
+    if (h->force_source != GAMD_FORCE_NETWORK && (r = drive_check_run(h, box, species_dev))) return r;
     DeviceGuard guard(h->dev);
     InitStream init((hipStream_t)stream);
     if ((r = set_box(h, box, (hipStream_t)stream))) return r;
@@ -1684,11 +1687,11 @@ int32_t gamd_md_run(gamd_handle* h, float* x_dev, float* v_dev, float* f_dev, co
 
 int32_t gamd_md_force_source(gamd_handle* h, int32_t source) {
     if (!h) return fail(-22, "null handle");
-    if (source != GAMD_FORCE_NETWORK && source != GAMD_FORCE_CLASSICAL)
-        return fail(-22, "unknown force source %d (GAMD_FORCE_NETWORK = 0, GAMD_FORCE_CLASSICAL = 1)", (int)source);
+    if (source != GAMD_FORCE_NETWORK && source != GAMD_FORCE_CLASSICAL && source != GAMD_FORCE_WATER_CLASSICAL)
+        return fail(-22, "unknown force source %d (GAMD_FORCE_NETWORK = 0, GAMD_FORCE_CLASSICAL = 1, GAMD_FORCE_WATER_CLASSICAL = 2)", (int)source);
     if (h->pending.active) return fail(-22, "an MD run is still enqueued: call gamd_sync_status before gamd_md_force_source");
-    if (source == GAMD_FORCE_CLASSICAL)
-        if (int r = drive_check_source(h)) return r;
+    if (source != GAMD_FORCE_NETWORK)
+        if (int r = drive_check_source(h, source)) return r;
     h->force_source = source;
     return 0;
 }
@@ -1708,7 +1711,10 @@ int32_t gamd_md_run_nhc(gamd_handle* h, float* x_dev, float* v_dev, float* f_dev
     const double* ys = p->num_yoshidasuzuki == 1 ? YS1 : p->num_yoshidasuzuki == 3 ? YS3 : p->num_yoshidasuzuki == 5 ? YS5 : nullptr;
     if (!ys) return fail(-22, "Invalid Yoshida-Suzuki value. Allowed values are: 1,3,5");
     if ((r = observers_check_run(h, box, species_dev))) return r;
-    if (h->force_source == GAMD_FORCE_CLASSICAL && (r = drive_check_run(h, box, species_dev))) return r;
+    if (h->force_source == GAMD_FORCE_WATER_CLASSICAL && !p->rigid_water)
+        return fail(-22, "the water classical force source needs rigid_water: the potential has no bond or angle term (same-molecule "
+                         "pairs are excluded), so only the constraints hold a molecule together");
+    if (h->force_source != GAMD_FORCE_NETWORK && (r = drive_check_run(h, box, species_dev))) return r;
     DeviceGuard guard(h->dev);
     InitStream init((hipStream_t)stream);
     if ((r = set_box(h, box, (hipStream_t)stream))) return r;

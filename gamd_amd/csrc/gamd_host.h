@@ -128,10 +128,12 @@ void observers_begin_run(gamd_handle* h, const float* box, const uint8_t* specie
 bool observers_sampled(const gamd_handle* h, long long s);
 int observers_enqueue(gamd_handle* h, long long s);
 // ---- the classical force source (gamd_md_force_source; observe.hip, drive.hip) ------------------------------------------------
-// may this handle take GAMD_FORCE_CLASSICAL (a potential of its kind with parameters set)?  0, or -22 with the message
-int drive_check_source(gamd_handle* h);
-// at the top of a classical-source run, in front of any device work: the potential's box rule and its work buffers (nothing is
-// allocated inside a run), whether or not its observer is armed
+// may this handle take `source`, GAMD_FORCE_CLASSICAL or GAMD_FORCE_WATER_CLASSICAL (the potential of its kind with parameters
+// set)?  0, or -22 with the message
+int drive_check_source(gamd_handle* h, int source);
+// at the top of a run whose h->force_source is one of the two, in front of any device work: the potential's box rule and its
+// work buffers (nothing is allocated inside a run), whether or not its observer is armed.  Water: species, and the k-vector
+// list of these boxes built or swapped, which no pending run may still read (-22 while one is).
 int drive_check_run(gamd_handle* h, const float* box, const uint8_t* species_dev);
 // the force evaluation of one step of the pending run, behind the neighbour stage: the pending run's f from its x
 int drive_enqueue(gamd_handle* h);

@@ -662,6 +662,15 @@ struct WaterArgs {
     long long g;               // completed MD steps at this sample
 };
 int launch_water_classical(const WaterArgs& a, hipStream_t st);
+// k_water_rho, k_water_sk, k_water_recip alone, with launch_water_classical's checks for them: a.rpart (and a.sk, a.ublk) from a.x
+int launch_water_recip(const WaterArgs& a, hipStream_t st);
+
+// ---- water classical force source (water_drive.hip) -------------------------------------------------
+// One force evaluation of a water-source step of an enqueued MD run (gamd_md_force_source, GAMD_FORCE_WATER_CLASSICAL): the pair
+// pass of water_classical.hip (tiles, slices and arithmetic of k_water_pairs; forces only) into a.part, launch_water_recip, then
+// per atom the pair slices and the k slices added in order from 0, f_cl to a.f_cl and (float)f_cl to f_out ([n][3], the
+// caller's atom order).  a.f, a.blk, a.rows, a.steps, a.slot and a.g are not used.  Five launches, plain stores.
+int launch_water_drive(const WaterArgs& a, float* f_out, hipStream_t st);
 
 // ---- energy minimiser (minimize.hip) ----------------------------------------------------------------
 // FIRE under the Lennard-Jones potential of classical.hip, per box, all state in double.  `c` carries

@@ -142,6 +142,20 @@ __device__ __forceinline__ void settle_positions(const Vec3 (&x0)[3], Vec3 (&x1)
     x1[2] = base + ((c3x * n1) + (c3y * n2)) + (c2z * n0);
 }
 
+// One constrained position update of a molecule: x -> SETTLE(x + d), d the unconstrained displacements (dt v), and the velocity
+// correction of the constraint, corr = (xc - x1) / dt as hack_integrator.py:152 / :163 / :280 form it.  Everything is formed
+// relative to the OLD oxygen: the correction is the difference of two coordinates of the size of a bond (ulp 1e-7 A), not of
+// two absolute positions (ulp 1e-6 - 2e-6 A at 10 - 20 A), whose rounding over dt = 0.5 fs would be 4e-3 A/ps in v.
+__device__ __forceinline__ void settle_step(Vec3 (&x)[3], const Vec3 (&d)[3], float inv_dt, Vec3 (&corr)[3], const RigidWater& g) {
+    const Vec3 o = x[0];
+    Vec3 r0[3], r1[3], rc[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { r0[k] = x[k] - o; r1[k] = r0[k] + d[k]; rc[k] = r1[k]; }
+    settle_positions(r0, rc, g);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { corr[k] = inv_dt * (rc[k] - r1[k]); x[k] = o + rc[k]; }
+}
+
 // remove the relative velocity along the three bonds: v_i += w_i sum_k (+-) g_k r_k with A g = -r_k.u_k
 __device__ __forceinline__ void settle_velocities(const Vec3 (&x)[3], Vec3 (&v)[3], const RigidWater& g) {
     const float wo = 1.0f / g.m_o, wh = 1.0f / g.m_h;
@@ -197,12 +211,12 @@ __device__ __forceinline__ void d_baoab_first_mol(const MdArgs& a, int m) {
     settle_velocities(x, v, a.rigid);                                                     //    :146
 #pragma unroll
     for (int stage = 0; stage < 2; ++stage) {
-        Vec3 x1[3], xc[3];
+        Vec3 d[3], corr[3];
 #pragma unroll
-        for (int k = 0; k < 3; ++k) { x1[k] = x[k] + (hdt * v[k]); xc[k] = x1[k]; }      // A  :149 / :160
-        settle_positions(x, xc, a.rigid);                                                 //    :151 / :162
+        for (int k = 0; k < 3; ++k) d[k] = hdt * v[k];                                    // A  :149 / :160
+        settle_step(x, d, 1.0f / hdt, corr, a.rigid);                                     //    :151 / :162
 #pragma unroll
-        for (int k = 0; k < 3; ++k) { v[k] = v[k] + ((1.0f / hdt) * (xc[k] - x1[k])); x[k] = xc[k]; }   // :152 / :163
+        for (int k = 0; k < 3; ++k) v[k] = v[k] + corr[k];                                //    :152 / :163
         settle_velocities(x, v, a.rigid);                                                 //    :153 / :164
         if (stage == 0) {
 #pragma unroll

@@ -253,7 +253,7 @@ __global__ void k_nhc_apply_first_rigid(NhcArgs a) {
     GAMD_MD_GATE(0);
     const int m = blockIdx.x * blockDim.x + threadIdx.x;
     if (3 * m >= a.n) return;
-    Vec3 x[3], v[3], f[3], x1[3], xc[3];
+    Vec3 x[3], v[3], f[3], d[3], corr[3];
     load_mol(a.x, m, x); load_mol(a.v, m, v); load_mol(a.f, m, f);
     const BoxAtom ba = md_box_atom(a.bx, 3 * m);
     float box[3];
@@ -266,14 +266,13 @@ __global__ void k_nhc_apply_first_rigid(NhcArgs a) {
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         v[k] = ((scale * v[k]) - vcom) + ((0.5f * a.dt * a.len * w[k]) * f[k]);
-        x1[k] = x[k] + (a.dt * v[k]);
-        xc[k] = x1[k];
+        d[k] = a.dt * v[k];
     }
-    settle_positions(x, xc, a.rigid);
+    settle_step(x, d, 1.0f / a.dt, corr, a.rigid);
 #pragma unroll
-    for (int k = 0; k < 3; ++k) v[k] = v[k] + ((1.0f / a.dt) * (xc[k] - x1[k]));
-    wrap_mol(xc, box);
-    store_mol(a.x, m, xc); store_mol(a.v, m, v);
+    for (int k = 0; k < 3; ++k) v[k] = v[k] + corr[k];
+    wrap_mol(x, box);
+    store_mol(a.x, m, x); store_mol(a.v, m, v);
 }
 
 __global__ void k_nhc_apply_second(NhcArgs a) {

@@ -463,6 +463,8 @@ struct WaterPotential {
         if (int r = water_klist(wc.k_cut, box, h->n_boxes, &n2max, &kv)) return r;
         return water_klist_apply(h, n2max, kv);
     }
+    // a force source as well (potential_drive): the forces alone, rounded to fp32, into the run's f
+    static int drive(const Args& a, float* f_out, hipStream_t st) { return launch_water_drive(a, f_out, st); }
 };
 
 // the sample of step s of the pending run, behind its second half: f holds the network forces at x
@@ -722,26 +724,51 @@ int observers_enqueue(gamd_handle* h, long long s) {
     return 0;
 }
 
-// ---- the classical force source (gamd_host.h): Lennard-Jones only; water becomes a second traits entry here ---------------------
-int drive_check_source(gamd_handle* h) {
-    if (h->cfg.kind != GAMD_KIND_LJ)
-        return fail(-22, "gamd_md_force_source: a GAMD_KIND_WATER handle has no classical force source (the Lennard-Jones potential "
-                         "has no electrostatics; GAMD_KIND_LJ handles only)");
-    if (!LjPotential::state(h).params_set)
-        return fail(-22, "gamd_md_force_source: the classical source needs the parameters of a gamd_classical_configure call (interval 0 will do)");
-    return 0;
+// ---- the classical force sources (gamd_host.h): one traits entry per source, GAMD_FORCE_CLASSICAL (Lennard-Jones, GAMD_KIND_LJ
+// handles) and GAMD_FORCE_WATER_CLASSICAL (3-site water, GAMD_KIND_WATER handles) -----------------------------------------------
+int drive_check_source(gamd_handle* h, int source) {
+    if (source == GAMD_FORCE_CLASSICAL) {
+        if (h->cfg.kind != GAMD_KIND_LJ)
+            return fail(-22, "gamd_md_force_source: a GAMD_KIND_WATER handle has no Lennard-Jones force source (that potential has no "
+                             "electrostatics; GAMD_KIND_LJ handles only — GAMD_FORCE_WATER_CLASSICAL = 2 drives 3-site water)");
+        if (!LjPotential::state(h).params_set)
+            return fail(-22, "gamd_md_force_source: the classical source needs the parameters of a gamd_classical_configure call (interval 0 will do)");
+        return 0;
+    }
+    if (source == GAMD_FORCE_WATER_CLASSICAL) {
+        if (h->cfg.kind != GAMD_KIND_WATER)
+            return fail(-22, "gamd_md_force_source: a GAMD_KIND_LJ handle has no molecules and no charges for the water classical "
+                             "source (GAMD_KIND_WATER handles only — GAMD_FORCE_CLASSICAL = 1 drives Lennard-Jones)");
+        if (!WaterPotential::state(h).params_set)
+            return fail(-22, "gamd_md_force_source: the water classical source needs the parameters of a gamd_water_configure call (interval 0 will do)");
+        return 0;
+    }
+    return fail(-22, "internal: force source %d has no potential", source);
 }
 
-int drive_check_run(gamd_handle* h, const float* box, const uint8_t* species_dev) {
-    if (int r = drive_check_source(h)) return r;
-    if (int r = LjPotential::check_box(h, box, species_dev)) return r;
+namespace {
+template <typename P>
+int potential_drive_check_run(gamd_handle* h, const float* box, const uint8_t* species_dev) {
+    if (int r = P::check_box(h, box, species_dev)) return r;
     DeviceGuard guard(h->dev);
     InitStream init(h->init_stream);
-    if (bufs_ensure_work(LjPotential::bufs(h))) return fail(-12, "%s potential allocation failed", LjPotential::who);
+    if (bufs_ensure_work(P::bufs(h))) return fail(-12, "%s potential allocation failed", P::who);
     return 0;
 }
+}  // namespace
 
-int drive_enqueue(gamd_handle* h) { return potential_drive<LjPotential>(h, h->pending.st); }
+int drive_check_run(gamd_handle* h, const float* box, const uint8_t* species_dev) {
+    if (int r = drive_check_source(h, h->force_source)) return r;
+    if (h->force_source == GAMD_FORCE_CLASSICAL) return potential_drive_check_run<LjPotential>(h, box, species_dev);
+    // the k-vector list may be swapped for these boxes: nothing of an earlier run may still read it
+    if (h->pending.active) return fail(-22, "an MD run is still enqueued: call gamd_sync_status before the next run of a handle whose force source is the water classical potential");
+    return potential_drive_check_run<WaterPotential>(h, box, species_dev);
+}
+
+int drive_enqueue(gamd_handle* h) {
+    return h->force_source == GAMD_FORCE_WATER_CLASSICAL ? potential_drive<WaterPotential>(h, h->pending.st)
+                                                         : potential_drive<LjPotential>(h, h->pending.st);
+}
 
 static_assert(sizeof(gamd_report_params) == 40 && offsetof(gamd_report_params, ndf) == 16 && offsetof(gamd_report_params, rdf_rmax) == 28,
               "gamd_report_params layout is part of the C ABI (gamd_amd/_lib.py mirrors it)");

@@ -323,6 +323,21 @@ __global__ void k_water_final(WaterArgs a) {
 
 }  // namespace
 
+// the reciprocal-space kernels alone, for the force source (water_drive.hip): rho, S(k) and the per-atom k sums of a.x into
+// a.rpart (and the block sums of A |S|^2 into a.ublk, which the source does not read)
+int launch_water_recip(const WaterArgs& a, hipStream_t st) {
+    const int nb = a.bx.n_boxes > 1 ? a.bx.n_boxes : 1, npb = a.bx.n_boxes > 1 ? a.bx.n_per_box : a.n;
+    const long long T = (npb + WC_TILE - 1) / WC_TILE;
+    if (npb < 3 || npb % 3 || nb > 65535 || a.tiles != (int)T) return -1;
+    if (a.n_k < 1 || a.n_k > (1 << 17) || a.kslices < 1 || a.kchunk < 1 || (long long)a.kslices * a.kchunk < a.n_k || T * a.kslices > 0x7fffffll) return -1;
+    if (a.kblocks != (a.n_k + 255) / 256 || a.rho_blocks < 1 || a.rho_blocks > 65535) return -1;
+    if (!a.x || !a.species || !a.kvec || !a.rho_partial || !a.sk || !a.ublk || !a.rpart || !a.devflags) return -1;
+    hipLaunchKernelGGL(k_water_rho, dim3(a.rho_blocks, (a.n_k + 63) / 64, nb), dim3(256), 0, st, a); GAMD_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_water_sk, dim3(a.kblocks, nb), dim3(256), 0, st, a); GAMD_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_water_recip, dim3((unsigned)(T * a.kslices), nb), dim3(256), 0, st, a); GAMD_CHECK_LAUNCH();
+    return 0;
+}
+
 int launch_water_classical(const WaterArgs& a, hipStream_t st) {
     const int nb = a.bx.n_boxes > 1 ? a.bx.n_boxes : 1, npb = a.bx.n_boxes > 1 ? a.bx.n_per_box : a.n;
     const long long T = (npb + WC_TILE - 1) / WC_TILE;
@@ -332,9 +347,7 @@ int launch_water_classical(const WaterArgs& a, hipStream_t st) {
     if (a.kblocks != (a.n_k + 255) / 256 || a.rho_blocks < 1 || a.rho_blocks > 65535) return -1;
     if (!a.x || !a.species || !a.kvec || !a.part || !a.rho_partial || !a.sk || !a.ublk || !a.rpart || !a.f_cl || !a.blk || !a.rows || !a.devflags) return -1;
     hipLaunchKernelGGL(k_water_pairs, dim3((unsigned)(T * a.slices), nb), dim3(256), 0, st, a); GAMD_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_water_rho, dim3(a.rho_blocks, (a.n_k + 63) / 64, nb), dim3(256), 0, st, a); GAMD_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_water_sk, dim3(a.kblocks, nb), dim3(256), 0, st, a); GAMD_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_water_recip, dim3((unsigned)(T * a.kslices), nb), dim3(256), 0, st, a); GAMD_CHECK_LAUNCH();
+    if (int r = launch_water_recip(a, st)) return r;        // (its checks are among those above)
     hipLaunchKernelGGL(k_water_atoms, dim3(a.blocks, nb), dim3(256), 0, st, a); GAMD_CHECK_LAUNCH();
     hipLaunchKernelGGL(k_water_final, dim3((nb + 63) / 64), dim3(64), 0, st, a); GAMD_CHECK_LAUNCH();
     return 0;

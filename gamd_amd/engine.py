@@ -751,7 +751,8 @@ class GamdForce:
         hack_integrator.py:142 runs when the OpenMM System has one; default True with ``rigid_water`` (the water drivers'
         openmmtools WaterBox carries one), False otherwise (the LJ fluid does not).
         With the classical force source (``md_force_source("classical")``) ``f`` must hold the classical forces at ``x`` on
-        entry: ``classical_forces(x)[0].float()``."""
+        entry: ``classical_forces(x)[0].float()``; with the water source (``md_force_source("water_classical")``, which
+        needs ``rigid_water``) ``water_classical_forces(x, species)[0].float()``."""
         self._md_state(x, v, f)
         s = self._dev_species(species)
         if remove_cm_motion is None:
@@ -780,7 +781,8 @@ class GamdForce:
         centre-of-mass velocity is also subtracted on the device where hack_integrator.py:271-272 does it: behind
         propagateNHC() of the first half (the chain sees the velocities as they are), in front of the kick.
         With the classical force source (``md_force_source("classical")``) ``f`` must hold the classical forces at ``x`` on
-        entry: ``classical_forces(x)[0].float()``."""
+        entry: ``classical_forces(x)[0].float()``; with the water source (``md_force_source("water_classical")``, which
+        needs ``rigid_water``) ``water_classical_forces(x, species)[0].float()``."""
         self._md_state(x, v, f)
         reset = chain_state is None
         if reset:
@@ -813,15 +815,23 @@ class GamdForce:
         until set again; ``forward`` and the other force calls evaluate the network whatever the source.  Integrators,
         observers, skin mode, several boxes and the overflow resume work as in a network-driven run.  LJ models only;
         2 r_cut must not exceed a box edge.  Replaces the OpenMM run of the reference's data generator
-        (dataset/generate_lj_data.py:74-107).  O(N^2) per step and box."""
-        if source not in _lib.FORCE_SOURCE:
-            raise ValueError(f"source must be one of {sorted(_lib.FORCE_SOURCE)}")
-        check(self._lib.gamd_md_force_source(self._h, _lib.FORCE_SOURCE[source]), "gamd_md_force_source")
+        (dataset/generate_lj_data.py:74-107).  O(N^2) per step and box.
+
+        ``"water_classical"`` (water models only) is the same under the 3-site water potential of the last
+        ``water_classical_configure`` (interval 0 will do): O-O Lennard-Jones plus a plain Ewald sum, bit for bit
+        ``water_classical_forces(x, species)[0].float()``.  A run then needs ``rigid_water`` (the potential has no bond
+        or angle term), ``species``, and 2 r_cut below every box edge.  Replaces the OpenMM run of
+        dataset/generate_tip3p_data.py:76-103.  O(N^2 + N K) per step and box, K the k-vectors of the Ewald sum."""
+        table = {**_lib.FORCE_SOURCE, **_lib.WATER_FORCE_SOURCE}
+        if source not in table:
+            raise ValueError(f"source must be one of {sorted(table)}")
+        check(self._lib.gamd_md_force_source(self._h, table[source]), "gamd_md_force_source")
         self._force_source = source
 
     @property
     def force_source(self) -> str:
-        """The force source of ``md_run`` / ``md_run_nhc`` as last set: ``"network"`` or ``"classical"``."""
+        """The force source of ``md_run`` / ``md_run_nhc`` as last set: ``"network"``, ``"classical"`` or
+        ``"water_classical"``."""
         return getattr(self, "_force_source", "network")
 
     # -- run reporter (the drivers' StateDataReporter log and a g(r) histogram, taken inside enqueued runs) ----------

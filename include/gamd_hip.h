@@ -516,8 +516,23 @@ int32_t gamd_classical_eval(gamd_handle* h, const float* pos_dev, const float* b
  * gamd_md_run_nhc return -22 (the message names r_cut) before anything is enqueued.  The potential's work buffers are ensured
  * there as well (-12 when that fails): nothing is allocated inside a run.  The handle must be finalized like for every run.
  * -22, with a message naming the reason: a null handle, an unknown source, while a run is pending, GAMD_FORCE_CLASSICAL on a
- * GAMD_KIND_WATER handle, GAMD_FORCE_CLASSICAL before an accepted gamd_classical_configure (interval 0 will do). */
-enum { GAMD_FORCE_NETWORK = 0, GAMD_FORCE_CLASSICAL = 1 };
+ * GAMD_KIND_WATER handle, GAMD_FORCE_CLASSICAL before an accepted gamd_classical_configure (interval 0 will do).
+ * GAMD_FORCE_WATER_CLASSICAL: the same for a GAMD_KIND_WATER handle under the 3-site water potential of gamd_water_configure
+ * (O-O Lennard-Jones plus a plain Ewald sum, in double) — the reference's water data generator is a rigid-water
+ * Nose-Hoover-chain run under that potential (dataset/generate_tip3p_data.py:76-103).  Behind the neighbour stage five
+ * launches: the pair pass of the water observer with the force accumulators only, the observer's own three reciprocal-space
+ * kernels (charge density, S(k), per-atom k sums), and a per-atom pass that adds the pair slices and the k slices in order
+ * from 0 and stores f_cl and (float)f_cl.  f is bit for bit the fp32 rounding of what gamd_water_eval gives on the same
+ * positions and species, and must hold that on entry.  O(N^2 + N K) per step and box, K the k-vectors of the list.
+ * A water-source run needs, or gamd_md_run / gamd_md_run_nhc return -22 before anything is enqueued (x, v, f untouched):
+ * rigid_water in its parameters (the potential has no bond or angle term and excludes same-molecule pairs, so only the
+ * constraints hold a molecule together), species, 2 * r_cut <= every box edge, and no run pending on the handle (the k-vector
+ * list is built or swapped for the run's boxes at that point).
+ * -22 from gamd_md_force_source besides the above: GAMD_FORCE_WATER_CLASSICAL on a GAMD_KIND_LJ handle, or before an accepted
+ * gamd_water_configure (interval 0 will do).
+ * Not built: a minimiser for water, the TIP4P M-site, PME, long-range dispersion.  The default parameters of
+ * gamd_water_configure remain UNVERIFIED against OpenMM. */
+enum { GAMD_FORCE_NETWORK = 0, GAMD_FORCE_CLASSICAL = 1, GAMD_FORCE_WATER_CLASSICAL = 2 };
 int32_t gamd_md_force_source(gamd_handle* h, int32_t source);
 
 /* Water classical observer: the classical potential of 3-site water — the reference logs OpenMM's potential energy for its

@@ -3,11 +3,11 @@
 // be built with the host sanitizers.  No HIP call is made.
 //
 //   cd gamd_amd/csrc && S="-Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=all" &&
-//   for f in report traj structure classical water_classical drive minimize; do
+//   for f in report traj structure classical water_classical drive water_drive minimize; do
 //     hipcc --offload-arch=gfx950 -O1 -g -std=c++17 $S -c $f.hip -o /tmp/ohc_$f.o || break; done &&
 //   hipcc --offload-arch=gfx950 -O1 -g -std=c++17 $S -c ../../tools/observe_host_check.hip -o /tmp/ohc_main.o &&
 //   hipcc -fsanitize=address,undefined /tmp/ohc_main.o /tmp/ohc_report.o /tmp/ohc_traj.o /tmp/ohc_structure.o /tmp/ohc_classical.o \
-//     /tmp/ohc_water_classical.o /tmp/ohc_drive.o /tmp/ohc_minimize.o -o /tmp/ohc && /tmp/ohc
+//     /tmp/ohc_water_classical.o /tmp/ohc_drive.o /tmp/ohc_water_drive.o /tmp/ohc_minimize.o -o /tmp/ohc && /tmp/ohc
 // (the parameter block of gamd_minimize has a program of its own: tools/minimize_host_check.cpp)
 #include "../gamd_amd/csrc/observe.hip"
 
@@ -222,23 +222,42 @@ static void check_args() {
     observers_free(&h);
 }
 
-// the classical force source: which handles may take it, and the run check's refusal in front of any device work
+// the classical force sources: which handles may take which, and the run check's refusals in front of any device work
 static void check_drive() {
     gamd_handle h;
     h.n_boxes = 2; h.n_per_box = 258; h.n = 516; h.cfg.kind = GAMD_KIND_WATER;
     h.obs = observers_new();
     REQUIRE(h.force_source == GAMD_FORCE_NETWORK);
-    REQUIRE(drive_check_source(&h) == -22 && std::strstr(g_err, "GAMD_KIND_WATER"));
+    REQUIRE(GAMD_FORCE_NETWORK == 0 && GAMD_FORCE_CLASSICAL == 1 && GAMD_FORCE_WATER_CLASSICAL == 2);
+    REQUIRE(drive_check_source(&h, GAMD_FORCE_CLASSICAL) == -22 && std::strstr(g_err, "GAMD_KIND_WATER") && std::strstr(g_err, "GAMD_FORCE_WATER_CLASSICAL"));
+    REQUIRE(drive_check_source(&h, GAMD_FORCE_WATER_CLASSICAL) == -22 && std::strstr(g_err, "gamd_water_configure"));
     h.cfg.kind = GAMD_KIND_LJ;
-    REQUIRE(drive_check_source(&h) == -22 && std::strstr(g_err, "gamd_classical_configure"));
+    REQUIRE(drive_check_source(&h, GAMD_FORCE_WATER_CLASSICAL) == -22 && std::strstr(g_err, "GAMD_KIND_LJ"));
+    REQUIRE(drive_check_source(&h, GAMD_FORCE_CLASSICAL) == -22 && std::strstr(g_err, "gamd_classical_configure"));
     Classical& cl = h.obs->cl;
     cl.sigma = 3.4; cl.epsilon = 0.995792; cl.r_cut = 10.2; cl.r_switch = 6.8; cl.shift = 1; cl.params_set = true;
-    REQUIRE(drive_check_source(&h) == 0);
+    REQUIRE(drive_check_source(&h, GAMD_FORCE_CLASSICAL) == 0);
+    h.force_source = GAMD_FORCE_CLASSICAL;
     const float box[6] = {27.27f, 27.27f, 27.27f, 27.27f, 20.39f, 27.27f};     // box 1, edge 1 is below 2 r_cut = 20.4
     REQUIRE(drive_check_run(&h, box, nullptr) == -22 && std::strstr(g_err, "r_cut") && std::strstr(g_err, "box[1][1]"));
     cl.params_set = false;
     REQUIRE(drive_check_run(&h, box, nullptr) == -22 && std::strstr(g_err, "gamd_classical_configure"));
     REQUIRE(!cl.part.p && !cl.f_cl.p);                                          // a refused run allocated nothing
+    // water: parameters, a pending run, species, the box rule — each in front of the k-vector list and of any allocation
+    h.cfg.kind = GAMD_KIND_WATER;
+    h.force_source = GAMD_FORCE_WATER_CLASSICAL;
+    WaterClassical& wc = h.obs->wc;
+    REQUIRE(drive_check_run(&h, box, nullptr) == -22 && std::strstr(g_err, "gamd_water_configure"));
+    wc.q_h = 0.417; wc.sigma = 3.15075; wc.epsilon = 0.635968; wc.r_cut = 10.2; wc.r_switch = 0.0; wc.shift = 0;
+    wc.alpha = 0.35; wc.k_cut = 3.0; wc.coulomb = 138.935456; wc.params_set = true;
+    REQUIRE(drive_check_source(&h, GAMD_FORCE_WATER_CLASSICAL) == 0);
+    h.pending.active = true;
+    REQUIRE(drive_check_run(&h, box, nullptr) == -22 && std::strstr(g_err, "still enqueued"));
+    h.pending.active = false;
+    REQUIRE(drive_check_run(&h, box, nullptr) == -22 && std::strstr(g_err, "species"));
+    const uint8_t* some_species = reinterpret_cast<const uint8_t*>(&h);        // only tested against null
+    REQUIRE(drive_check_run(&h, box, some_species) == -22 && std::strstr(g_err, "r_cut") && std::strstr(g_err, "box[1][1]"));
+    REQUIRE(wc.n2max == -1 && !wc.kvec.p && !wc.part.p && !wc.rpart.p && !wc.f_cl.p);   // a refused run built and allocated nothing
     observers_free(&h);
 }
 
