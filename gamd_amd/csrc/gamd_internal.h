@@ -664,6 +664,8 @@ struct WaterArgs {
 int launch_water_classical(const WaterArgs& a, hipStream_t st);
 // k_water_rho, k_water_sk, k_water_recip alone, with launch_water_classical's checks for them: a.rpart (and a.sk, a.ublk) from a.x
 int launch_water_recip(const WaterArgs& a, hipStream_t st);
+// k_water_sk alone (it reads no positions): a.sk and a.ublk from a.rho_partial, for the water minimiser's own rho and force passes
+int launch_water_sk(const WaterArgs& a, hipStream_t st);
 
 // ---- water classical force source (water_drive.hip) -------------------------------------------------
 // One force evaluation of a water-source step of an enqueued MD run (gamd_md_force_source, GAMD_FORCE_WATER_CLASSICAL): the pair
@@ -701,3 +703,34 @@ int launch_minimize_iter(const MinArgs& m, hipStream_t st);
 // x_out = fp32(x64) wrapped (skipped for a box that failed at iteration 0); f_out = f_in for every box that did not fail
 int launch_minimize_store_x(const MinArgs& m, float* x_out, hipStream_t st);
 int launch_minimize_store_f(const MinArgs& m, const float* f_in, float* f_out, hipStream_t st);
+
+// ---- water energy minimiser (water_minimize.hip) ------------------------------------------------------
+// Rigid-molecule FIRE under the 3-site water potential of water_classical.hip, per box, all state in double (DESIGN.md section
+// 4.13).  `w` carries the potential's constants, the geometry of the pair and reciprocal passes and the observer's work buffers
+// (part, rho_partial, sk, ublk, rpart, blk) as for WaterArgs, with w.box_edges and w.species set; w.x, w.f, w.f_cl, w.rows,
+// w.steps, w.slot and w.g are not used, and w.kchunk is not either: slice s of the reciprocal force pass walks the 256-vector
+// blocks s, s + kslices, ... of the list, so a longer list (another box of the handle has a longer edge) only appends terms of
+// weight zero.  One iteration is six launches (pairs; rho, sk, recip; molecules; update); every k_wmin_* kernel returns at once
+// for a box with stopped[box] != 0.  States, rows and the scalar slots are the minimiser's (MIN_*).
+// (No kernel uses a value it read from memory as an address: the checked build has nothing to range-check here.)
+enum { WMIN_ACC = 7 };         // per box and block (the first doubles of a WATER_ACC-strided row of blk): ff, vf, vv, sum u_LJ, sum u_coul, sum z^2, max |F_c|
+struct WMinArgs {
+    WaterArgs w;
+    double* x64;               // [n][3] positions, length unit, unwrapped, every molecule on the rigid geometry
+    double* v64;               // [n][3] FIRE velocities (projected by the molecule pass)
+    double* f64;               // [n][3] kJ/mol/nm at x64, projected onto the constraint manifold
+    double* state;             // [n_boxes][2][MIN_STATE]
+    int* stopped;              // [n_boxes] 0: running, else 1 + MIN_*
+    double* rows;              // [n_boxes][MIN_ROW]
+    double tol;                // kJ/mol/nm
+    double dt_start, dt_max, f_inc, f_dec, alpha_start, f_alpha, max_step;
+    double ra, rb, rc;         // the unit-weight canonical triangle: rc = r_hh / 2, t = sqrt(r_oh^2 - rc^2), ra = 2 t / 3, rb = t / 3
+    int n_min;
+    int last;                  // the pass behind the last iteration: a box still running stops as MIN_MAX_ITER, nothing moves
+    long long it;              // position updates enqueued in front of this pass
+};
+int launch_wmin_init(const WMinArgs& m, const float* x, hipStream_t st);
+int launch_wmin_iter(const WMinArgs& m, hipStream_t st);
+// x_io = fp32(x64) with molecules whole and the oxygen in [0, L) (skipped for a box that failed at iteration 0); x64_out (may be
+// null) = x64, or the input widened for such a box
+int launch_wmin_store_x(const WMinArgs& m, float* x_io, double* x64_out, hipStream_t st);

@@ -43,6 +43,11 @@ __device__ __forceinline__ double2 gamd_lj_switch(double rs, double inv_w, doubl
     return make_double2(S, dS);
 }
 
+// fractional coordinate of the reciprocal-space kernels (water_classical.hip, water_minimize.hip): the position wrapped into
+// [0, L) first, s = (x - L floor(x / L)) / L.  Where x + k L is exact in fp32 the wrapped position is the same double for every
+// image k, and so is every phase n.s (x / L alone is not: fl((x + k L) / L) and fl(x / L) + k differ in the last bits).
+__device__ __forceinline__ double water_frac(double x, double L) { return (x - L * floor(x / L)) / L; }
+
 // one atom's terms of the force-error sums of the run's force g against the classical force c (both kJ/mol/nm):
 // sum |D_c|, sum |D|^2, sum cos, sum |c|, sum |g|, and the atoms left out of the cosine because one of the two is zero
 __device__ __forceinline__ void gamd_force_error(double gx, double gy, double gz, double cx, double cy, double cz, double& sum_abs,

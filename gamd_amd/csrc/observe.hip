@@ -1123,4 +1123,91 @@ int32_t gamd_water_eval(gamd_handle* h, const float* pos_dev, const uint8_t* spe
     return 0;
 }
 
+int32_t gamd_water_minimize(gamd_handle* h, float* x_dev, const uint8_t* species_dev, const float* box, float length_per_nm,
+                            double r_oh, double r_hh, float* f_dev, double* x64_dev, const gamd_minimize_params* params,
+                            double* rows_host, void* stream) {
+    // the parameter block is checked first: these answers need no device
+    gamd_minimize_params q;
+    if (int r = minimize_fill_params(params, &q, g_err, sizeof(g_err))) return r;
+    const double len = length_per_nm > 0.f ? (double)length_per_nm : 10.0;
+    if (!(r_oh >= 0.0) || !(r_hh >= 0.0) || !std::isfinite(r_oh) || !std::isfinite(r_hh))
+        return fail(-22, "gamd_water_minimize: r_oh = %g, r_hh = %g: a length is not positive", r_oh, r_hh);
+    if (r_oh == 0.0) r_oh = 0.9572 * (len / 10.0);          // TIP3P, as the md parameter blocks document it
+    if (r_hh == 0.0) r_hh = (2.0 * 0.9572 * std::sin(0.5 * 104.52 * (3.141592653589793 / 180.0))) * (len / 10.0);    // 1.5139 A
+    if (!(r_hh < 2.0 * r_oh)) return fail(-22, "gamd_water_minimize: r_hh = %g is not below 2 r_oh = %g: no such triangle", r_hh, 2.0 * r_oh);
+    if (!h) return fail(-22, "null handle");
+    if (h->cfg.kind != GAMD_KIND_WATER)
+        return fail(-22, "gamd_water_minimize: a GAMD_KIND_LJ handle has no molecules and no charges (GAMD_KIND_WATER handles only; "
+                         "gamd_minimize relaxes Lennard-Jones boxes)");
+    if (h->n_per_box % 3) return fail(-22, "gamd_water_minimize: n_atoms = %d per box is not a multiple of 3 (atoms ordered O,H,H)", h->n_per_box);
+    WaterClassical& wc = WaterPotential::state(h);
+    if (!wc.params_set) return fail(-22, "gamd_water_minimize needs the parameters of a gamd_water_configure call (interval 0 will do)");
+    if (h->pending.active) return fail(-22, "an MD run is still enqueued: call gamd_sync_status before gamd_water_minimize");
+    if (!x_dev || !f_dev || !box) return fail(-22, "null argument");
+    for (int k = 0; k < 3 * h->n_boxes; ++k)
+        if (!(box[k] > 0.f)) return fail(-22, "box[%d][%d] = %g is not positive", k / 3, k % 3, (double)box[k]);
+    if (int r = WaterPotential::check_box(h, box, species_dev)) return r;      // species, 2 r_cut, the k-vector list of these boxes
+    DeviceGuard guard(h->dev);
+    hipStream_t st = (hipStream_t)stream;
+    InitStream init(st);
+    // every allocation in front of the first enqueue
+    if (bufs_ensure_work(WaterPotential::bufs(h)) || bufs_ensure_work(minimize_bufs(h))) return fail(-12, "gamd_water_minimize: allocation failed");
+    const size_t nb = (size_t)h->n_boxes;
+    std::vector<int> stopped(nb, 0);
+    std::vector<double> rows(MIN_ROW * nb, 0.0);
+    HIP_TRY(init_upload(wc.eval_box.p, box, sizeof(float) * 3 * nb));
+    // the force source's kernels return at once on a frozen handle: f would be what the last call left
+    int frozen = 0;
+    HIP_TRY(hipMemcpyAsync(&frozen, h->devflags.as<int>() + DEVFLAG_FROZEN, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (frozen) return fail(-22, "gamd_water_minimize: the handle is frozen by a neighbour-buffer overflow (call gamd_sync_status)");
+    Minimizer& mn = h->obs->mn;
+    WMinArgs m{};
+    m.w = WaterPotential::args(h, len);
+    m.w.box_edges = wc.eval_box.as<float>();
+    m.w.species = species_dev;
+    m.x64 = mn.x64.as<double>(); m.v64 = mn.v64.as<double>(); m.f64 = mn.f64.as<double>();
+    m.state = mn.state.as<double>(); m.stopped = mn.stopped.as<int>(); m.rows = mn.rows.as<double>();
+    m.tol = q.tolerance; m.dt_start = q.dt_start; m.dt_max = q.dt_max; m.f_inc = q.f_inc; m.f_dec = q.f_dec;
+    m.alpha_start = q.alpha_start; m.f_alpha = q.f_alpha; m.max_step = q.max_step; m.n_min = q.n_min;
+    m.rc = 0.5 * r_hh;
+    const double t = std::sqrt(r_oh * r_oh - m.rc * m.rc);
+    m.ra = (2.0 * t) / 3.0; m.rb = t / 3.0;
+    // the store of f goes through the LJ minimiser's kernel: its gate, rows and geometry are the same
+    MinArgs ms{};
+    ms.c.n = m.w.n; ms.c.bx = m.w.bx; ms.c.box_edges = m.w.box_edges;
+    ms.c.tiles = m.w.tiles; ms.c.slices = m.w.slices; ms.c.chunk = m.w.chunk; ms.c.blocks = m.w.blocks;
+    ms.c.part = m.w.part; ms.c.blk = m.w.blk;
+    ms.x64 = m.x64; ms.v64 = m.v64; ms.f64 = m.f64; ms.state = m.state; ms.stopped = m.stopped; ms.rows = m.rows;
+    int r;
+    if ((r = launch_wmin_init(m, x_dev, st))) return fail(-1, "gamd_water_minimize launch failed (%d)", r);
+    bool all_stopped = false;
+    while (m.it < q.max_iter && !all_stopped) {
+        const long long chunk = std::min<long long>(q.check_every, q.max_iter - m.it);
+        for (long long k = 0; k < chunk; ++k, ++m.it)
+            if ((r = launch_wmin_iter(m, st))) return fail(-1, "gamd_water_minimize launch failed (%d)", r);
+        HIP_TRY(hipMemcpyAsync(stopped.data(), mn.stopped.p, sizeof(int) * nb, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        all_stopped = std::all_of(stopped.begin(), stopped.end(), [](int s) { return s != 0; });
+    }
+    if (!all_stopped) {                                     // U and rms where max_iter left the boxes that still run
+        m.last = 1;
+        if ((r = launch_wmin_iter(m, st))) return fail(-1, "gamd_water_minimize launch failed (%d)", r);
+    }
+    // x (and x64), then the water force source's own kernels on exactly that x
+    if ((r = launch_wmin_store_x(m, x_dev, x64_dev, st))) return fail(-1, "gamd_water_minimize launch failed (%d)", r);
+    WaterArgs a = m.w;
+    a.x = x_dev;
+    if ((r = launch_water_drive(a, mn.f32.as<float>(), st))) return fail(-1, "gamd_water_minimize launch failed (%d)", r);
+    wc.evaluated = true;
+    if ((r = launch_minimize_store_f(ms, mn.f32.as<float>(), f_dev, st))) return fail(-1, "gamd_water_minimize launch failed (%d)", r);
+    HIP_TRY(hipMemcpyAsync(rows.data(), mn.rows.p, sizeof(double) * rows.size(), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (int t2 = check_traps(h)) return t2;
+    if (rows_host) std::memcpy(rows_host, rows.data(), sizeof(double) * rows.size());
+    int worst = 0;
+    for (size_t b = 0; b < nb; ++b) worst = std::max(worst, (int)rows[MIN_ROW * b]);
+    return worst;
+}
+
 }  // extern "C"

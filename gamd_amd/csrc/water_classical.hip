@@ -38,11 +38,6 @@ namespace {
 
 constexpr int WC_TILE = 256;
 
-// fractional coordinate of the reciprocal-space kernels: the position wrapped into [0, L) first, s = (x - L floor(x / L)) / L.
-// Where x + k L is exact in fp32 the wrapped position is the same double for every image k, and so is every phase n.s
-// (x / L alone is not: fl((x + k L) / L) and fl(x / L) + k differ in the last bits).
-__device__ __forceinline__ double water_frac(double x, double L) { return (x - L * floor(x / L)) / L; }
-
 __global__ void __launch_bounds__(256) k_water_pairs(WaterArgs a) {
     if (a.devflags[DEVFLAG_FROZEN]) return;                 // a frame that will be evaluated again
     __shared__ double sx[WC_TILE], sy[WC_TILE], sz[WC_TILE];
@@ -335,6 +330,14 @@ int launch_water_recip(const WaterArgs& a, hipStream_t st) {
     hipLaunchKernelGGL(k_water_rho, dim3(a.rho_blocks, (a.n_k + 63) / 64, nb), dim3(256), 0, st, a); GAMD_CHECK_LAUNCH();
     hipLaunchKernelGGL(k_water_sk, dim3(a.kblocks, nb), dim3(256), 0, st, a); GAMD_CHECK_LAUNCH();
     hipLaunchKernelGGL(k_water_recip, dim3((unsigned)(T * a.kslices), nb), dim3(256), 0, st, a); GAMD_CHECK_LAUNCH();
+    return 0;
+}
+
+int launch_water_sk(const WaterArgs& a, hipStream_t st) {
+    const int nb = a.bx.n_boxes > 1 ? a.bx.n_boxes : 1;
+    if (nb > 65535 || a.n_k < 1 || a.n_k > (1 << 17) || a.kblocks != (a.n_k + 255) / 256 || a.rho_blocks < 1) return -1;
+    if (!a.kvec || !a.rho_partial || !a.sk || !a.ublk || !a.devflags) return -1;
+    hipLaunchKernelGGL(k_water_sk, dim3(a.kblocks, nb), dim3(256), 0, st, a); GAMD_CHECK_LAUNCH();
     return 0;
 }
 

@@ -1126,6 +1126,55 @@ class GamdForce:
                                         row.ctypes.data_as(C.c_void_p), self._stream()), "gamd_water_eval")
         return out, RunWaterClassical([0], row, self.n)
 
+    # -- water energy minimiser (the water drivers' minimizeEnergy in front of the first step) ---------------------------
+    def water_minimize(self, x: torch.Tensor, species, f: Optional[torch.Tensor] = None, tolerance: float = 10.0, max_iter: int = 0,
+                       box=None, length_per_nm: float = 0.0, r_oh: float = 0.0, r_hh: float = 0.0, return_x64: bool = False,
+                       check_every: int = 0, **fire) -> "MinimizeResult":
+        """Relax the rigid 3-site molecules ``x`` (float32 CUDA tensor, atoms ordered O,H,H, changed in place) of every box
+        under the water classical potential of the last ``water_classical_configure`` (with the defaults and interval 0 when
+        there was none) on the device, until the root mean square over 3N of the components of the force projected onto the
+        constraint manifold is at most ``tolerance`` (kJ/mol/nm) or ``max_iter`` position updates are done (0 = 10 000).
+        Rigid-molecule FIRE in double with SETTLE, unit weights in the constraint arithmetic; not OpenMM's L-BFGS: no
+        parity with it is claimed.  ``r_oh``, ``r_hh``: the rigid geometry in the engine's length unit (0: TIP3P scaled by
+        ``length_per_nm`` / 10); the input is put on it first.  ``fire`` as in ``minimize`` (the defaults are for Angstrom).
+
+        On return ``x`` holds the result rounded to fp32 with molecules whole and every oxygen in [0, L), and ``f``
+        (allocated when None) the classical forces at exactly that ``x`` — ``water_classical_forces(x, species)[0].float()``
+        bit for bit, what a water-source ``md_run`` / ``md_run_nhc`` with ``rigid_water`` needs on entry.  A box that was
+        not finite at the start keeps its ``x``; nothing is written to ``f`` for a box that failed.  ``return_x64``: also the
+        unrounded, unwrapped, exactly rigid double positions (``result.x64``).  Water models only; 2 r_cut must not exceed a
+        box edge.  Synchronises."""
+        unknown = set(fire) - {"dt_start", "dt_max", "n_min", "f_inc", "f_dec", "alpha_start", "f_alpha", "max_step"}
+        if unknown:
+            raise TypeError(f"water_minimize() got unexpected FIRE constants {sorted(unknown)}")
+        if not getattr(self, "_water_set", False):
+            self.water_classical_configure(0, length_per_nm=length_per_nm)
+        if f is None:
+            f = torch.zeros_like(x)
+        self._md_state(x, f)
+        flags = None
+        if species is not None:
+            s = torch.as_tensor(species).reshape(-1).to(device=self.device)
+            if s.numel() == self.n and self.n_boxes > 1:
+                s = s.repeat(self.n_boxes)
+            if s.numel() != self.n_total:
+                raise ValueError("species must have one entry per atom")
+            flags = (s != 0).to(torch.uint8).contiguous()
+        unit = float(np.float32(length_per_nm)) / 10.0 if length_per_nm else 1.0     # the fp32 value the library holds
+        from . import workloads as wl
+        r_oh = float(r_oh) if r_oh else wl.TIP3P_R_OH * unit
+        r_hh = float(r_hh) if r_hh else wl.TIP3P_R_HH * unit
+        x64 = torch.empty((self.n_total, 3), dtype=torch.float64, device=self.device) if return_x64 else None
+        g = lambda k: float(fire.get(k, 0.0))
+        p = GamdMinimizeParams(float(tolerance), int(max_iter), int(check_every), g("dt_start"), g("dt_max"), g("f_inc"), g("f_dec"),
+                               g("alpha_start"), g("f_alpha"), g("max_step"), int(fire.get("n_min", 0)), 0)
+        rows = np.zeros((self.n_boxes, _lib.MINIMIZE_ROW), dtype=np.float64)
+        st = check(self._lib.gamd_water_minimize(self._h, C.c_void_p(x.data_ptr()), C.c_void_p(flags.data_ptr()) if flags is not None else None,
+                                                 self._box_arg(box), float(length_per_nm), r_oh, r_hh, C.c_void_p(f.data_ptr()),
+                                                 C.c_void_p(x64.data_ptr()) if return_x64 else None, C.byref(p),
+                                                 rows.ctypes.data_as(C.c_void_p), self._stream()), "gamd_water_minimize")
+        return MinimizeResult(st, rows, x, f, x64)
+
     def sync_status(self) -> int:
         """0, or 1 when an enqueued MD run overflowed a neighbour buffer, froze on the device and was resumed."""
         return check(self._lib.gamd_sync_status(self._h, self._stream()), "gamd_sync_status")

@@ -530,8 +530,8 @@ int32_t gamd_classical_eval(gamd_handle* h, const float* pos_dev, const float* b
  * list is built or swapped for the run's boxes at that point).
  * -22 from gamd_md_force_source besides the above: GAMD_FORCE_WATER_CLASSICAL on a GAMD_KIND_LJ handle, or before an accepted
  * gamd_water_configure (interval 0 will do).
- * Not built: a minimiser for water, the TIP4P M-site, PME, long-range dispersion.  The default parameters of
- * gamd_water_configure remain UNVERIFIED against OpenMM. */
+ * gamd_water_minimize (below) relaxes a start and leaves x and f as this source expects them.  Not built: the TIP4P M-site,
+ * PME, long-range dispersion.  The default parameters of gamd_water_configure remain UNVERIFIED against OpenMM. */
 enum { GAMD_FORCE_NETWORK = 0, GAMD_FORCE_CLASSICAL = 1, GAMD_FORCE_WATER_CLASSICAL = 2 };
 int32_t gamd_md_force_source(gamd_handle* h, int32_t source);
 
@@ -655,6 +655,54 @@ enum { GAMD_MINIMIZE_ROW = 8 };
 enum { GAMD_MIN_CONVERGED = 0, GAMD_MIN_MAX_ITER = 1, GAMD_MIN_FAILED = 2 };
 int32_t gamd_minimize(gamd_handle* h, float* x_dev, const float* box, float length_per_nm, float* f_dev, double* x64_dev,
                       const gamd_minimize_params* params, double* rows_host, void* stream);
+
+/* Energy minimiser for rigid 3-site water: every water driver of the reference relaxes its start in front of the first step
+ * (minimizeEnergy, dataset/generate_tip3p_data.py:85).  gamd_water_minimize is gamd_minimize for a GAMD_KIND_WATER handle under
+ * the potential of the last gamd_water_configure (interval 0 will do), ON THE DEVICE, and leaves x and f as a
+ * GAMD_FORCE_WATER_CLASSICAL gamd_md_run / gamd_md_run_nhc with rigid_water expects them on entry.  It is NOT OpenMM's L-BFGS
+ * (which treats the constraints by restraints) and claims no parity with it: the algorithm is FIRE on rigid molecules.  What is
+ * shared is the meaning of the tolerance — here the root mean square over 3N of the components of the PROJECTED force.
+ * Atoms in the caller's order O,H,H, molecule = index / 3, O = species != 0.  r_oh, r_hh: the rigid geometry in the length
+ * unit; 0 = TIP3P (0.9572 A, 104.52 degrees: r_hh = 1.5139 A) scaled by length_per_nm / 10.  All constraint arithmetic takes
+ * UNIT weights for the three atoms, not their masses: the projection is then the orthogonal one and the projected force F_c is
+ * the gradient on the constraint manifold.  The canonical triangle of SETTLE is rc = r_hh / 2, t = sqrt(r_oh^2 - rc^2),
+ * ra = 2 t / 3, rb = t / 3.
+ * Start: x = the fp32 input widened, then every molecule put on the exact geometry by SETTLE in double with reference = new =
+ * the input; v = 0; dt = dt_start, alpha = alpha_start, n_pos = 0.  Per box and iteration:
+ *   1. F (kJ/mol/nm) and U (kJ/mol) at x, the terms of gamd_water_configure operation for operation on the double positions:
+ *      a same-molecule pair takes the erf branch, another pair with r^2 < r_cut^2 the erfc branch and, O-O, the Lennard-Jones
+ *      term; the reciprocal sum over the handle's k-vector list; U = ((U_real + U_excl + U_recip) + U_self) + U_LJ.
+ *   2. Per molecule F and v are projected onto the tangent space of the three bond constraints at x (a 3x3 solve): F_c, v.
+ *      ff = sum F_c.F_c, vf = sum v.F_c, vv = sum v.v in a fixed order; rms = sqrt(ff / 3N), N atoms.
+ *   3. U or ff not finite: the box stops as GAMD_MIN_FAILED.  Else rms <= tolerance: GAMD_MIN_CONVERGED.  Else, in the pass
+ *      behind max_iter position updates: GAMD_MIN_MAX_ITER.  A box that stops applies no update.
+ *   4. FIRE's mixing and step exactly as gamd_minimize spells them, on F_c: v = v + dt F_c, dr = dt v; per MOLECULE one factor
+ *      max_step / max_k |dr_k| where the largest |dr_k| of its three atoms exceeds max_step; x = SETTLE(reference x, new x + dr).
+ * gamd_minimize_params and its defaults mean what they mean for gamd_minimize.  Everything is in double with fixed summation
+ * orders, no floating-point atomics and no contraction: the same bits run after run, whatever check_every is, and every box of
+ * a handle gets the bits it gets alone.  O(N^2 + N K) per iteration and box, six launches.
+ * On return (the stream is synchronised):
+ *   x_dev        float [n_boxes * n_atoms][3] DEVICE, in and out: molecules whole, the oxygen in [0, L) per component.  Per
+ *                molecule and component, with L the fp32 edge widened and xO, xH the double positions:
+ *                  s = L floor(xO / L);  if xO - s < 0: s = s - L;  if (float)(xO - s) >= L: s = s + L;
+ *                  O = max((float)(xO - s), 0),  H = (float)(xH - s)   (round to nearest)
+ *                — an oxygen that rounds up to L goes to 0 and takes its hydrogens along.  A box that was not finite at the
+ *                start (two atoms at one point, a molecule SETTLE cannot place) keeps x as given.
+ *   f_dev        float [n_boxes * n_atoms][3] DEVICE, out: the water force source's force at exactly those fp32 positions —
+ *                bit for bit the fp32 rounding of gamd_water_eval's forces on x_dev.  Nothing is written for a box that failed.
+ *   x64_dev      double [n_boxes * n_atoms][3] DEVICE or NULL: the unrounded, unwrapped positions, every molecule exactly
+ *                rigid (the input widened for a box that failed at iteration 0).
+ *   rows_host    double [n_boxes][GAMD_MINIMIZE_ROW] HOST or NULL: state, iterations, U and rms at the start, U, rms and the
+ *                largest |F_c component| at the end, the final dt.
+ * Returns 0 / 1 / 2 as gamd_minimize.  -22, with a message naming the reason, before anything is enqueued: what gamd_minimize
+ * refuses in the parameter block, a negative or non-finite r_oh / r_hh, r_hh >= 2 r_oh, a null handle, a GAMD_KIND_LJ handle,
+ * an atom count per box that is no multiple of 3, no accepted gamd_water_configure, a pending run, a null x_dev / f_dev / box,
+ * no species, a box edge that is not positive or below 2 * r_cut (the message names r_cut), a handle that a neighbour-buffer
+ * overflow left frozen (call gamd_sync_status first).  -12 when an allocation fails.
+ * Device memory besides the water classical observer's work buffers: 84 B per atom (x, v, F_c in double and the fp32 force). */
+int32_t gamd_water_minimize(gamd_handle* h, float* x_dev, const uint8_t* species_dev, const float* box, float length_per_nm,
+                            double r_oh, double r_hh, float* f_dev, double* x64_dev, const gamd_minimize_params* params,
+                            double* rows_host, void* stream);
 
 /* Event-timed replay of one force evaluation: per-kernel milliseconds of the last gamd_profile call.
  * names: newline-separated kernel labels; ms: one float per label.  For bench.py's roofline block. */

@@ -3,11 +3,11 @@
 // be built with the host sanitizers.  No HIP call is made.
 //
 //   cd gamd_amd/csrc && S="-Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=all" &&
-//   for f in report traj structure classical water_classical drive water_drive minimize; do
+//   for f in report traj structure classical water_classical drive water_drive minimize water_minimize; do
 //     hipcc --offload-arch=gfx950 -O1 -g -std=c++17 $S -c $f.hip -o /tmp/ohc_$f.o || break; done &&
 //   hipcc --offload-arch=gfx950 -O1 -g -std=c++17 $S -c ../../tools/observe_host_check.hip -o /tmp/ohc_main.o &&
 //   hipcc -fsanitize=address,undefined /tmp/ohc_main.o /tmp/ohc_report.o /tmp/ohc_traj.o /tmp/ohc_structure.o /tmp/ohc_classical.o \
-//     /tmp/ohc_water_classical.o /tmp/ohc_drive.o /tmp/ohc_water_drive.o /tmp/ohc_minimize.o -o /tmp/ohc && /tmp/ohc
+//     /tmp/ohc_water_classical.o /tmp/ohc_drive.o /tmp/ohc_water_drive.o /tmp/ohc_minimize.o /tmp/ohc_water_minimize.o -o /tmp/ohc && /tmp/ohc
 // (the parameter block of gamd_minimize has a program of its own: tools/minimize_host_check.cpp)
 #include "../gamd_amd/csrc/observe.hip"
 

@@ -4,7 +4,8 @@ classical force that logs PE / KE / total energy every 50 steps and writes data_
 such a run costs.
 
     python tools/water_ground_truth.py [--workloads w774 c3] [--steps 200] [--interval 50] [--frames 4] [--dt-fs 2.0]
-                                       [--energy-ps 1.0] [--ewald-tol 1e-8] [--relax-steps 2000] [--seed 0] [--out DIR]
+                                       [--energy-ps 1.0] [--ewald-tol 1e-8] [--minimize-tolerance 10] [--relax-steps 0] [--seed 0]
+                                       [--out DIR]
 
 For a seeded box of rigid 3-site water (w774: 258 molecules = 774 atoms, the generator's 2 nm box; c3: 1 390 molecules = 4 170
 atoms) on one handle in skin mode, as bench.py runs the water workloads, each workload in a fresh process:
@@ -18,11 +19,13 @@ atoms) on one handle in skin mode, as bench.py runs the water workloads, each wo
   4. the series E_tot = KE + PE of a gamma = 0 rigid BAOAB run (no friction, no noise) over --energy-ps at --dt-fs and at half of
      it, sampled every 10 fs, from the end of the generator run: the maximum deviation from the first sample and a fitted
      slope, for each.
-The start is the workload's lattice box (wl.water_box: whole rigid molecules on a cubic lattice, random orientations), NOT a
-minimised one: the generator's minimizeEnergy (:85) has no counterpart for water yet — GamdForce.minimize relaxes Lennard-Jones
-boxes only.  Left alone, the lattice releases about 20 kJ/mol per molecule and heats a 300 K start past 1 000 K within 0.4 ps;
-so, in its place, step 0 relaxes the lattice by --relax-steps steps of a strongly damped water-classical Langevin run at 300 K
-(--relax-dt-fs, --relax-gamma; 0 steps: none), and everything below starts from its end.  The potential is the plain Ewald sum of
+The start is the workload's lattice box (wl.water_box: whole rigid molecules on a cubic lattice, random orientations).  Left
+alone, the lattice releases about 20 kJ/mol per molecule and heats a 300 K start past 1 000 K within 0.4 ps; so, as the
+generator's minimizeEnergy (:85) does, step 0 minimises it on the device first: GamdForce.water_minimize to
+--minimize-tolerance kJ/mol/nm (rigid-molecule FIRE, not OpenMM's L-BFGS; 0: not minimised).  The earlier stand-in stays
+available: --relax-steps steps of a strongly damped water-classical Langevin run at 300 K (--relax-dt-fs, --relax-gamma;
+0 steps, the default: none), behind the minimiser when both are on.  Everything below starts from the end of step 0.  The
+potential is the plain Ewald sum of
 water_classical_configure, not OpenMM's PME, without long-range dispersion, and its default parameters are UNVERIFIED against
 OpenMM: the files have the generator's layout, not its numbers.  Records, not pass/fail bars."""
 import argparse
@@ -106,7 +109,18 @@ def _one(args, w, out_dir):
     n = x0.shape[0]
     eng.water_classical_configure(0, ewald_tol=args.ewald_tol)
     res = dict(n=n)
-    # 0. in place of the generator's minimizeEnergy: the lattice relaxed by a strongly damped driven run
+    # 0. the generator's minimizeEnergy: the lattice minimised on the device ...
+    if args.minimize_tolerance > 0:
+        x = x0.clone()
+        m = eng.water_minimize(x, species, tolerance=args.minimize_tolerance, r_oh=md["r_oh"], r_hh=md["r_hh"])
+        res["minimize"] = dict(tolerance=args.minimize_tolerance, state=m.state[0], iterations=int(m.iterations[0]), u0=float(m.energy_start[0]),
+                               u=float(m.energy[0]), rms0=float(m.rms_start[0]), rms=float(m.rms[0]))
+        print(f"{w}: lattice minimised to tolerance {args.minimize_tolerance:g} kJ/mol/nm: {m.state[0]} after {int(m.iterations[0])} iterations, "
+              f"PE {res['minimize']['u0']:.3f} -> {res['minimize']['u']:.3f} kJ/mol, projected rms {res['minimize']['rms0']:.3f} -> {res['minimize']['rms']:.3f}")
+        if m.status == 2:
+            raise SystemExit(f"{w}: the minimiser failed (the start is not finite)")
+        x0 = x
+    # ... and / or relaxed by a strongly damped driven run
     if args.relax_steps > 0:
         x, v, f = _start(eng, x0, v0, species, "water_classical")
         eng.report_configure(args.relax_steps, max_samples=1, rigid_water=True)
@@ -170,8 +184,10 @@ def main():
     ap.add_argument("--dt-fs", type=float, default=2.0, help="the generator's time step (dataset/generate_tip3p_data.py:51)")
     ap.add_argument("--energy-ps", type=float, default=1.0)
     ap.add_argument("--ewald-tol", type=float, default=1e-8)
-    ap.add_argument("--relax-steps", type=int, default=2000,
-                    help="water-classical Langevin steps at 300 K in front of everything else, in place of the missing minimiser (0: none)")
+    ap.add_argument("--minimize-tolerance", type=float, default=10.0,
+                    help="step 0: GamdForce.water_minimize to this tolerance in kJ/mol/nm (0: the start is not minimised)")
+    ap.add_argument("--relax-steps", type=int, default=0,
+                    help="water-classical Langevin steps at 300 K in front of everything else, behind the minimiser (0: none)")
     ap.add_argument("--relax-dt-fs", type=float, default=1.0)
     ap.add_argument("--relax-gamma", type=float, default=25.0, help="friction of the relaxation run, 1 / ps")
     ap.add_argument("--seed", type=int, default=0)
@@ -185,7 +201,7 @@ def main():
     out = {}
     for w in args.workloads:                                                # a fresh process per workload; this one opens no GPU
         cmd = [sys.executable, os.path.abspath(__file__), "--only", w, "--out", out_dir] + \
-              [a for k in ("steps", "interval", "frames", "dt_fs", "energy_ps", "ewald_tol", "relax_steps", "relax_dt_fs", "relax_gamma", "seed")
+              [a for k in ("steps", "interval", "frames", "dt_fs", "energy_ps", "ewald_tol", "minimize_tolerance", "relax_steps", "relax_dt_fs", "relax_gamma", "seed")
                for a in ("--" + k.replace("_", "-"), str(getattr(args, k)))]
         p = subprocess.run(cmd, capture_output=True, text=True)
         sys.stdout.write(p.stdout.split("RESULT ", 1)[0])
