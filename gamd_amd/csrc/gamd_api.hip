@@ -1,17 +1,16 @@
-// gamd_api.hip — weight packing, the force evaluation, the MD driver and their extern "C" entry points of include/gamd_hip.h
-// (the handle itself is in gamd_host.h; the run observers' entry points are in observe.hip).
+// gamd_api.hip — the weight upload, the force evaluation, the MD driver and their extern "C" entry points of include/gamd_hip.h
+// (the handle itself is in gamd_host.h, weight packing in gamd_weights_host.h; the run observers' entry points are in observe.hip).
 #include "gamd_host.h"
-#include "gamd_ln_fold_host.h"
 
 #include <algorithm>
 #include <cmath>
 #include <cstddef>
 #include <cstdlib>
 #include <cstring>
-#include <deque>
 
 static_assert(sizeof(gamd_config) == 96 && offsetof(gamd_config, n_boxes) == 88 && offsetof(gamd_config, edge_capacity) == 40,
               "gamd_config layout is part of the C ABI (gamd_amd/_lib.py mirrors it)");
+static_assert(WH_FRAG_FLOATS == GAMD_WFRAG_FLOATS, "gamd_weights_host.h restates the size of a packed 128x128 weight");
 
 namespace {
 
@@ -202,149 +201,6 @@ NbrArgs nbr_args(gamd_handle* h, const float* pos_dev, const uint8_t* species_de
         a.cand_stride = (int)std::max<long long>(1, std::min<long long>(h->cand_cap / h->n, 1 << 20));
     }
     return a;
-}
-
-// ---- weight packing ---------------------------------------------------------------------------
-// W [128 out][128 in] block of a row-major matrix with row stride ld -> fragment order of gamd_common.h
-void pack128(const float* W, float* out, int ld = 128) {
-    for (int tp = 0; tp < 4; ++tp)
-        for (int t = 0; t < 4; ++t)
-            for (int q = 0; q < 4; ++q)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int j = 0; j < 4; ++j) {
-                        const int n = 32 * tp + (lane & 31), k = 32 * t + 8 * q + 4 * (lane >> 5) + j;
-                        out[((((tp * 4 + t) * 4 + q) * 64 + lane) * 4) + j] = W[(size_t)n * ld + k];
-                    }
-}
-// W [128 out][128 in] -> operand order of node.hip's 16x16x4 chain: block (ob, blk) = 16 output features x 16 inputs,
-// lane (i = lane & 15, g = lane >> 4) holds W[16 ob + i][16 blk + 4 g + 0..3]; a wave's quarter (ob = 2 w, 2 w + 1) is contiguous
-void pack16(const float* W, float* out, int ld = 128) {
-    for (int ob = 0; ob < 8; ++ob)
-        for (int blk = 0; blk < 8; ++blk)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int r = 0; r < 4; ++r)
-                    out[(((ob * 8 + blk) * 64 + lane) * 4) + r] = W[(size_t)(16 * ob + (lane & 15)) * ld + 16 * blk + 4 * (lane >> 4) + r];
-}
-// the same matrix as (hi | lo) fp16 fragments for node.hip's split-fp16 GEMMs on 16x16x32: fragment ((ob * 4 + m) * 2 + part),
-// lane (o = lane & 15, g = lane >> 4), value j = W[16 ob + o][32 m + 16 (j >> 2) + 4 g + (j & 3)]  -- 64 KiB like the fp32 image
-void split_f16(float w, uint16_t* hi, uint16_t* lo);
-void pack16_f16x3(const float* W, uint16_t* out) {
-    for (int ob = 0; ob < 8; ++ob)
-        for (int m = 0; m < 4; ++m)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int j = 0; j < 8; ++j) {
-                    const int k = 32 * m + 16 * (j >> 2) + 4 * (lane >> 4) + (j & 3);
-                    const size_t hi = ((((size_t)(ob * 4 + m) * 2 + 0) * 64 + lane) * 8) + j, lo = ((((size_t)(ob * 4 + m) * 2 + 1) * 64 + lane) * 8) + j;
-                    split_f16(W[(size_t)(16 * ob + (lane & 15)) * 128 + k], out + hi, out + lo);
-                }
-}
-// encoder first layer W [128][n_feat]: MFMA step s covers features (2s, 2s+1); K padded to 48
-void pack_enc1(const float* W, int n_feat, float* out) {
-    for (int tp = 0; tp < 4; ++tp)
-        for (int g = 0; g < 6; ++g)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int j = 0; j < 4; ++j) {
-                    const int n = 32 * tp + (lane & 31), k = 2 * (4 * g + j) + (lane >> 5);
-                    out[(((tp * 6 + g) * 64 + lane) * 4) + j] = k < n_feat ? W[n * n_feat + k] : 0.f;
-                }
-}
-
-// ---- packing for the 16-edge generic-width conv kernel (wide16.hip) --------------------------------------------------------
-// K position p = 4 m + g of the 32-edge kernels' accumulation order <-> input feature kfeat(m, g); image [ob 8][m4 8][lane 64][c 4]
-// = W[row(ob, lane & 15)][kfeat(4 m4 + c, lane >> 4)].  chained = true (W1, W2, W3): packed output row 16 ob + 4 g' + r' is feature
-// kfeat(4 ob + r', g'), so the C/D registers of one GEMM are the B operands of the next; chained = false (W4): packed column n of
-// block ob is feature 64 (ob >> 2) + 4 n + (ob & 3) (a lane of the F2 output owns four consecutive features).
-int kfeat16x(int m, int g) { return 32 * (m >> 3) + 8 * ((m >> 1) & 3) + 4 * (g & 1) + (g >> 1) + 2 * (m & 1); }
-void pack16x(const float* W, float* out, int ld, bool chained) {
-    for (int ob = 0; ob < 8; ++ob)
-        for (int m4 = 0; m4 < 8; ++m4)
-            for (int lane = 0; lane < 64; ++lane) {
-                const int i = lane & 15, g = lane >> 4;
-                const int row = chained ? kfeat16x(4 * ob + (i & 3), i >> 2) : 64 * (ob >> 2) + 4 * i + (ob & 3);
-                for (int c = 0; c < 4; ++c)
-                    out[(((size_t)ob * 8 + m4) * 64 + lane) * 4 + c] = W[(size_t)row * ld + kfeat16x(4 * m4 + c, g)];
-            }
-}
-
-// ---- bf16 packing (config 5), layout of gamd_bf16.h --------------------------------------------
-uint16_t f2bf(float x) {                       // round to nearest even
-    uint32_t u; memcpy(&u, &x, 4);
-    if ((u & 0x7f800000u) == 0x7f800000u) return (uint16_t)(u >> 16);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-}
-void pack128_bf16(const float* W, uint16_t* out, int ld = 128) {
-    for (int tp = 0; tp < 4; ++tp)
-        for (int t = 0; t < 4; ++t)
-            for (int u = 0; u < 2; ++u)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int j = 0; j < 8; ++j) {
-                        const int r = 8 * u + j, half = lane >> 5;
-                        const int n = 32 * tp + (lane & 31), k = 32 * t + (r & 3) + 8 * (r >> 2) + 4 * half;
-                        out[((((tp * 4 + t) * 2 + u) * 64 + lane) * 8) + j] = f2bf(W[(size_t)n * ld + k]);
-                    }
-}
-void pack_enc1_bf16(const float* W, int n_feat, uint16_t* out) {     // [tp][s][lane][8], K padded to 48
-    for (int tp = 0; tp < 4; ++tp)
-        for (int s = 0; s < 3; ++s)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int j = 0; j < 8; ++j) {
-                    const int n = 32 * tp + (lane & 31), k = 16 * s + 8 * (lane >> 5) + j;
-                    out[(((tp * 3 + s) * 64 + lane) * 8) + j] = k < n_feat ? f2bf(W[n * n_feat + k]) : (uint16_t)0;
-                }
-}
-
-// ---- split-fp16 packing (GAMD_EDGE_F16X3), layout of gamd_f16x3.h: [hi part | lo part] ------------------
-void split_f16(float w, uint16_t* hi, uint16_t* lo) {
-    const _Float16 h = (_Float16)w;                              // round to nearest even, subnormals kept
-    const _Float16 l = (_Float16)(w - (float)h);
-    memcpy(hi, &h, 2); memcpy(lo, &l, 2);
-}
-void pack128_f16x3(const float* W, uint16_t* out, int ld = 128) {  // 2 x 16384 halves = 64 KiB; W: a 128 x 128 block, row stride ld
-    for (int tp = 0; tp < 4; ++tp)
-        for (int t = 0; t < 4; ++t)
-            for (int u = 0; u < 2; ++u)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int j = 0; j < 8; ++j) {
-                        const int r = 8 * u + j, half = lane >> 5;
-                        const int n = 32 * tp + (lane & 31), k = 32 * t + (r & 3) + 8 * (r >> 2) + 4 * half;
-                        const size_t at = ((((tp * 4 + t) * 2 + u) * 64 + lane) * 8) + j;
-                        split_f16(W[(size_t)n * ld + k], out + at, out + 16384 + at);
-                    }
-}
-void pack_enc1_f16x3(const float* W, int n_feat, uint16_t* out) {   // 2 x [tp][s][lane][8], K padded to 48
-    for (int tp = 0; tp < 4; ++tp)
-        for (int s = 0; s < 3; ++s)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int j = 0; j < 8; ++j) {
-                    const int n = 32 * tp + (lane & 31), k = 16 * s + 8 * (lane >> 5) + j;
-                    const size_t at = (((tp * 3 + s) * 64 + lane) * 8) + j;
-                    split_f16(k < n_feat ? W[n * n_feat + k] : 0.f, out + at, out + 6144 + at);
-                }
-}
-
-struct BlobBuilder {
-    std::vector<float> host;
-    size_t add(size_t n_floats) {
-        const size_t off = host.size();
-        host.resize(off + ((n_floats + 63) & ~(size_t)63), 0.f);
-        return off;
-    }
-};
-
-const HostTensor* find_w(gamd_handle* h, const std::string& name, std::initializer_list<int64_t> shape) {
-    auto it = h->host_w.find(name);
-    if (it == h->host_w.end()) { fail(-2, "missing weight '%s'", name.c_str()); return nullptr; }
-    if (it->second.shape != std::vector<int64_t>(shape)) {
-        std::string got;
-        for (auto d : it->second.shape) got += std::to_string(d) + ",";
-        std::string want;
-        for (auto d : shape) want += std::to_string(d) + ",";
-        fail(-22, "weight '%s' has shape (%s), expected (%s) for this configuration", name.c_str(), got.c_str(),
-             want.c_str());
-        return nullptr;
-    }
-    return &it->second;
 }
 
 struct EdgeList { const int* centre; const int* neigh; long long n; };
@@ -968,416 +824,52 @@ int32_t gamd_load_weight(gamd_handle* h, const char* name, const float* data, co
     return 0;
 }
 
+// Transformation and packing are pack_weights (gamd_weights_host.h, host only); here: its flags onto the handle, the upload,
+// and its offset tables turned into the device pointers of the same names.
 int32_t gamd_finalize_weights(gamd_handle* h) {
     if (!h) return fail(-22, "null handle");
     DeviceGuard guard(h->dev);
     InitStream init(h->init_stream);
-    const int F = h->n_feat, L = h->L;
-    const int64_t H = h->H, Eh = h->Eh, HT = h->HT, EHT = h->EHT;         // padded widths the kernels work in
-    const int64_t Ht = h->H_true, Et = h->Eh_true, Dt = h->D_true;        // the state_dict's widths
-    const int64_t Dp = h->Dp, DT = h->DT;                                 // hidden_dim padded to 128-blocks (DT = 2: wide_d.hip)
-    const bool expand = !h->cfg.no_expand_edge;
-    BlobBuilder bb;
-    struct Off { size_t w1p, w2p, w3p, w4p, w16p = 0, b1, b3, b4, elng = 0, elnb = 0, lng, lnb, wsp, wdp, wpdp, bS, bP, wpep, wphip, bphi;
-                 size_t w3p_l0 = 0, b3_l0 = 0, m0 = 0, c0 = 0; };
-    std::vector<Off> lo(L);
-    // get(name, true shape, padded shape): the tensor as the reference stores it, zero-padded to the kernels' block widths.
-    // Padded output rows / input columns are zeros, so padded features are exact zeros through every layer.
-    std::deque<HostTensor> padded;
-    auto get = [&](const std::string& nm, std::initializer_list<int64_t> shp, std::initializer_list<int64_t> pad) -> const HostTensor* {
-        const HostTensor* t = find_w(h, nm, shp);
-        if (!t) return nullptr;
-        const std::vector<int64_t> ps(pad);
-        if (t->shape == ps) return t;
-        HostTensor o;
-        o.shape = ps;
-        const int64_t r = ps.size() == 2 ? t->shape[0] : 1, c = ps.size() == 2 ? t->shape[1] : t->shape[0];
-        const int64_t cp = ps.size() == 2 ? ps[1] : ps[0], rp = ps.size() == 2 ? ps[0] : 1;
-        o.data.assign((size_t)(rp * cp), 0.f);
-        for (int64_t i = 0; i < r; ++i) std::copy(t->data.begin() + i * c, t->data.begin() + (i + 1) * c, o.data.begin() + i * cp);
-        padded.push_back(std::move(o));
-        return &padded.back();
-    };
-    auto put_vec = [&](const HostTensor* t) { size_t o = bb.add(t->data.size()); std::copy(t->data.begin(), t->data.end(), bb.host.begin() + o); return o; };
-    // [128 OB][128 KB] matrix -> OB*KB packed 128x128 blocks, block (ob, kb) at index ob*KB + kb
-    auto put_blocks = [&](const HostTensor* t, int OB, int KB) {
-        size_t o = bb.add((size_t)OB * KB * GAMD_WFRAG_FLOATS);
-        for (int ob = 0; ob < OB; ++ob)
-            for (int kb = 0; kb < KB; ++kb)
-                pack128(t->data.data() + (size_t)128 * ob * 128 * KB + 128 * kb,
-                        bb.host.data() + o + (size_t)(ob * KB + kb) * GAMD_WFRAG_FLOATS, 128 * KB);
-        return o;
-    };
-    // [128 OB][128 KB] matrix -> OB*KB [hi | lo] fp16 images, block (ob, kb) at index ob*KB + kb (the order put_blocks uses)
-    auto put_blocks_f16x3_fn = [&](const HostTensor* t, int OB, int KB) {
-        size_t o = bb.add((size_t)OB * KB * GAMD_WFRAG_FLOATS);
-        for (int ob = 0; ob < OB; ++ob)
-            for (int kb = 0; kb < KB; ++kb)
-                pack128_f16x3(t->data.data() + (size_t)128 * ob * 128 * KB + 128 * kb,
-                              reinterpret_cast<uint16_t*>(bb.host.data() + o + (size_t)(ob * KB + kb) * GAMD_WFRAG_FLOATS), 128 * KB);
-        return o;
-    };
-    // node-side matrices: the 128-wide node kernel (node.hip) runs on 16x16x4 MFMAs with its own operand order; the
-    // generic-width node kernel of wide.hip keeps the 32x32x2 fragment blocks
-    // Reduced-precision edge modes (bf16, split-fp16) on the 128-wide kernels: the node kernel's five GEMMs run in split-fp16 too
-    // (fp32-grade results at 3/16 of the fp32 matrix time, node.hip and wide.hip's k_node_wide)
-    h->node_f16 = h->cfg.edge_dtype != GAMD_EDGE_F32;
-    auto put_node = [&](const HostTensor* t, int OB, int KB) {
-        if (h->wide_conv) return h->node_f16 ? put_blocks_f16x3_fn(t, OB, KB) : put_blocks(t, OB, KB);
-        size_t o = bb.add(GAMD_WFRAG_FLOATS);
-        if (h->node_f16) pack16_f16x3(t->data.data(), reinterpret_cast<uint16_t*>(bb.host.data() + o));
-        else pack16(t->data.data(), bb.host.data() + o);
-        return o;
-    };
-    const bool bf16_edges = h->cfg.edge_dtype == GAMD_EDGE_BF16 && !h->wide_conv;     // 128 / 128 / 128 expanded: the specialised kernels
-    const bool bf16_wide = h->cfg.edge_dtype == GAMD_EDGE_BF16 && h->wide_conv;       // any other width / feature set: wide_lp.hip
-    const bool f16x3_edges = h->cfg.edge_dtype == GAMD_EDGE_F16X3 && !h->wide_conv;   // 128 / 128 / 128 expanded: the specialised kernels
-    const bool f16x3_wide = h->cfg.edge_dtype == GAMD_EDGE_F16X3 && h->wide_conv;     // any other width / feature set: wide_lp.hip
-    auto put_edge_f16x3 = [&](const HostTensor* t) {
-        size_t o = bb.add(GAMD_WFRAG_FLOATS);
-        pack128_f16x3(t->data.data(), reinterpret_cast<uint16_t*>(bb.host.data() + o));
-        return o;
-    };
-    auto put_blocks_f16x3 = put_blocks_f16x3_fn;
-    auto put_edge_bf16 = [&](const HostTensor* t) {
-        size_t o = bb.add(GAMD_WFRAG_FLOATS / 2);
-        pack128_bf16(t->data.data(), reinterpret_cast<uint16_t*>(bb.host.data() + o));
-        return o;
-    };
-
-    // update_edge_emb=True checkpoints (WaterMDDynamicBoxNet(update_edge=True), nn_module.py:91-92): every conv layer owns an
-    // edge_layer_norm; LayerNorm(in_edge_feats) is applied to e_emb of width in_node_feats (:141), so the two must agree.
-    // Served by the generic-width kernels (wide.hip) for any width.
-    const bool update_edge = h->host_w.count("graph_conv.conv.0.edge_layer_norm.weight") != 0;
-    if (update_edge) {
-        if (Ht != Et)
-            return fail(-22, "update_edge_emb needs encoding_size == edge_embedding_dim (got %d, %d)", (int)Ht, (int)Et);
-        if (h->cfg.edge_dtype != GAMD_EDGE_F32 || h->cfg.self_loop_mode)
-            return fail(-22, "update_edge_emb is built for the fp32 edge MLP without appended self loops");
-        h->wide_enc = h->wide_conv = true;
-        h->ln_fold = false;
-    }
-    if (update_edge != h->update_edge) {
-        h->update_edge = update_edge;
+    WeightSpec spec;
+    spec.kind = h->cfg.kind; spec.edge_dtype = h->cfg.edge_dtype; spec.no_expand_edge = h->cfg.no_expand_edge;
+    spec.self_loop_mode = h->cfg.self_loop_mode; spec.kernel_select = h->cfg.kernel_select;
+    spec.n_layers = h->L; spec.n_feat = h->n_feat;
+    spec.H_true = h->H_true; spec.Eh_true = h->Eh_true; spec.D_true = h->D_true;
+    spec.H = h->H; spec.Eh = h->Eh; spec.Dp = h->Dp;
+    spec.wide_enc = h->wide_enc; spec.wide_conv = h->wide_conv; spec.ln_fold = h->ln_fold;
+    const PackedWeights pw = pack_weights(spec, h->host_w);
+    if (pw.err) return fail(pw.err, "%s", pw.msg);
+    h->node_f16 = pw.node_f16;
+    h->wide_enc = pw.wide_enc; h->wide_conv = pw.wide_conv; h->ln_fold = pw.ln_fold;
+    if (pw.update_edge != h->update_edge) {                      // e_emb / e_frag2 come and go with it
+        h->update_edge = pw.update_edge;
         if (alloc_edges(h, h->e_cap)) return -12;
     }
-    // BatchNorm checkpoints carry running statistics next to norm_layers' weight and bias
-    const bool norm_bn = h->host_w.count("graph_conv.norm_layers.0.running_mean") != 0;
-    h->norm_bn = norm_bn ? 1 : 0;
-    // Layer-0 form (conv_edge.hip): every atom of an LJ model enters layer 0 with the same row node_emb (nn_module.py:681), so
-    // hn0 = norm_layers[0](node_emb) is one row and phi_edge of the aggregated messages is M0 sum_j T3_j + d_i c0.  The fp32
-    // 128-wide kernels only; not for update_edge_emb models (their layers read e_emb) nor under GAMD_KSEL_NO_LAYER0_HOIST.
-    h->l0_hoist = h->cfg.kind == GAMD_KIND_LJ && h->cfg.edge_dtype == GAMD_EDGE_F32 && !h->wide_conv && DT == 1 && !update_edge &&
-                  !(h->cfg.kernel_select & GAMD_KSEL_NO_LAYER0_HOIST);
-    const HostTensor* emb0 = h->l0_hoist ? get("node_emb", {1, Ht}, {1, H}) : nullptr;
-    if (h->l0_hoist && !emb0) return -2;
-    // rows 32 q + s <- rows 4 s + q of a [128][128] matrix and its bias: the F2 output order of the last GEMM of the 128-wide
-    // fp32 / bf16 conv kernels (a lane holds four consecutive features of each edge)
-    auto permute_f2 = [](const HostTensor& w, const HostTensor& b, HostTensor& wo, HostTensor& bo) {
-        wo = w;
-        bo = b;
-        for (int q = 0; q < 4; ++q)
-            for (int s = 0; s < 32; ++s) {
-                std::copy(w.data.begin() + (size_t)(4 * s + q) * 128, w.data.begin() + (size_t)(4 * s + q + 1) * 128,
-                          wo.data.begin() + (size_t)(32 * q + s) * 128);
-                bo.data[32 * q + s] = b.data[4 * s + q];
-            }
-    };
-    // Folded edge LayerNorm: B = C W_e3, c = C b_e3 (the centred last encoder Linear, in double) for the layers' first matrices
-    std::vector<double> fold_B, fold_c;
-    const HostTensor *fold_g = nullptr, *fold_b = nullptr;
-    if (h->ln_fold) {
-        const HostTensor *w = get("edge_encoder.mlp_layer.4.weight", {Et, Dt}, {Eh, Dp}), *b = get("edge_encoder.mlp_layer.4.bias", {Et}, {Eh});
-        fold_g = get("edge_layer_norm.weight", {Et}, {Eh});
-        fold_b = get("edge_layer_norm.bias", {Et}, {Eh});
-        if (!w || !b || !fold_g || !fold_b) return -2;
-        lnf_center(w->data.data(), b->data.data(), (int)Et, fold_B, fold_c);
-    }
-    for (int l = 0; l < L; ++l) {
-        const std::string p = "graph_conv.conv." + std::to_string(l);
-        // edge_affine = MLP(Eh, hidden_dim, hidden_layer=2): its inner width is MLP's default 128 (nn_module.py:25,95)
-        const HostTensor *ea0w = get(p + ".edge_affine.mlp_layer.0.weight", {128, Et}, {128, Eh}), *ea0b = get(p + ".edge_affine.mlp_layer.0.bias", {128}, {128});
-        const HostTensor *ea2w = get(p + ".edge_affine.mlp_layer.2.weight", {Dt, 128}, {Dp, 128}), *ea2b = get(p + ".edge_affine.mlp_layer.2.bias", {Dt}, {Dp});
-        const HostTensor *sw = get(p + ".src_affine.weight", {Dt, Ht}, {Dp, H}), *sb = get(p + ".src_affine.bias", {Dt}, {Dp});
-        const HostTensor *dw = get(p + ".dst_affine.weight", {Dt, Ht}, {Dp, H}), *db = get(p + ".dst_affine.bias", {Dt}, {Dp});
-        const HostTensor *t1w = get(p + ".theta_edge.mlp_layer.1.weight", {Dt, Dt}, {Dp, Dp}), *t1b = get(p + ".theta_edge.mlp_layer.1.bias", {Dt}, {Dp});
-        const HostTensor *t3w = get(p + ".theta_edge.mlp_layer.3.weight", {Ht, Dt}, {H, Dp}), *t3b = get(p + ".theta_edge.mlp_layer.3.bias", {Ht}, {H});
-        const HostTensor *pdw = get(p + ".phi_dst.weight", {Dt, Ht}, {Dp, H}), *pdb = get(p + ".phi_dst.bias", {Dt}, {Dp});
-        const HostTensor *pew = get(p + ".phi_edge.weight", {Dt, Ht}, {Dp, H}), *peb = get(p + ".phi_edge.bias", {Dt}, {Dp});
-        const HostTensor *phw = get(p + ".phi.mlp_layer.1.weight", {Ht, Dt}, {H, Dp}), *phb = get(p + ".phi.mlp_layer.1.bias", {Ht}, {H});
-        const HostTensor *ng = get("graph_conv.norm_layers." + std::to_string(l) + ".weight", {Ht}, {H});
-        const HostTensor *nb = get("graph_conv.norm_layers." + std::to_string(l) + ".bias", {Ht}, {H});
-        if (!ea0w || !ea0b || !ea2w || !ea2b || !sw || !sb || !dw || !db || !t1w || !t1b || !t3w || !t3b || !pdw ||
-            !pdb || !pew || !peb || !phw || !phb || !ng || !nb)
-            return -2;
-        if (norm_bn) {
-            // use_layer_norm=False (the constructors' default, nn_module.py:171-196,579): norm_layers are nn.BatchNorm1d; the
-            // rollout runs the model in eval mode, where it is the per-feature affine map torch's CPU kernel evaluates as
-            // x * alpha + beta with alpha = weight / sqrt(running_var + eps), beta = bias - running_mean * alpha (float).
-            // Folded here into the ln_g / ln_b slots; padded features keep alpha = beta = 0.
-            const std::string np_ = "graph_conv.norm_layers." + std::to_string(l);
-            const HostTensor *rm = get(np_ + ".running_mean", {Ht}, {H}), *rv = get(np_ + ".running_var", {Ht}, {H});
-            if (!rm || !rv) return -2;
-            HostTensor al, be;
-            al.shape = be.shape = {H};
-            al.data.assign((size_t)H, 0.f);
-            be.data.assign((size_t)H, 0.f);
-            for (int64_t i = 0; i < Ht; ++i) {
-                const float invstd = 1.0f / std::sqrt(rv->data[i] + 1e-5f);
-                al.data[i] = ng->data[i] * invstd;
-                be.data[i] = nb->data[i] - rm->data[i] * al.data[i];
-            }
-            padded.push_back(std::move(al)); ng = &padded.back();
-            padded.push_back(std::move(be)); nb = &padded.back();
-        }
-        // bf16 edge MLP (conv_edge_bf16.hip): the pre-activations of the layer's three SiLUs are computed times log2 e, so that
-        // SiLU(x) log2 e = x' / (1 + 2^-x') needs no multiply in front of its exponential: W1, b1 (first SiLU), the S / D tables
-        // (second: W2 sees the first SiLU's output times log2 e and needs no factor itself), b3 (third) carry log2 e, W4 ln 2
-        if (bf16_edges) {
-            auto scaled = [&](const HostTensor* t, double f) -> const HostTensor* {
-                HostTensor o = *t;
-                for (float& v : o.data) v = (float)((double)v * f);
-                padded.push_back(std::move(o));
-                return &padded.back();
-            };
-            const double LOG2E = 1.4426950408889634, LN2 = 0.6931471805599453;
-            ea0w = scaled(ea0w, LOG2E); ea0b = scaled(ea0b, LOG2E); t1b = scaled(t1b, LOG2E); t3w = scaled(t3w, LN2);
-            sw = scaled(sw, LOG2E); dw = scaled(dw, LOG2E);
-            sb = scaled(sb, LOG2E); db = scaled(db, LOG2E); ea2b = scaled(ea2b, LOG2E);      // bS = (b_src + b_dst) + b_edge_affine.2
-        }
-        Off& o = lo[l];
-        if (l == 0 && h->l0_hoist) {
-            // hn0 as k_node mode 0 forms it (LayerNorm over the true width, or the folded eval BatchNorm), then
-            // M0 = W_pe diag(hn0) W4 and c0 = W_pe (hn0 * b4), in double and rounded once; M0 takes phi_edge's place in post(0)
-            std::vector<double> hn0((size_t)H, 0.0);
-            if (norm_bn) {
-                for (int64_t i = 0; i < H; ++i) hn0[i] = (double)emb0->data[i] * ng->data[i] + nb->data[i];
-            } else {
-                double mean = 0.0, var = 0.0;
-                for (int64_t i = 0; i < Ht; ++i) mean += emb0->data[i];
-                mean /= (double)Ht;
-                for (int64_t i = 0; i < Ht; ++i) var += ((double)emb0->data[i] - mean) * ((double)emb0->data[i] - mean);
-                var /= (double)Ht;
-                const double rstd = 1.0 / std::sqrt(var + 1e-5);
-                for (int64_t i = 0; i < Ht; ++i) hn0[i] = ((double)emb0->data[i] - mean) * rstd * ng->data[i] + nb->data[i];
-            }
-            HostTensor m0, c0;
-            m0.shape = {Dp, Dp};
-            m0.data.assign((size_t)(Dp * Dp), 0.f);
-            c0.shape = {Dp};
-            c0.data.assign((size_t)Dp, 0.f);
-            std::vector<double> row((size_t)Dp);
-            for (int64_t r = 0; r < Dp; ++r) {
-                std::fill(row.begin(), row.end(), 0.0);
-                double cr = 0.0;
-                for (int64_t i = 0; i < H; ++i) {
-                    const double a = (double)pew->data[(size_t)(r * H + i)] * hn0[i];
-                    if (a == 0.0) continue;
-                    for (int64_t k = 0; k < Dp; ++k) row[k] += a * t3w->data[(size_t)(i * Dp + k)];
-                    cr += a * t3b->data[i];
-                }
-                for (int64_t k = 0; k < Dp; ++k) m0.data[(size_t)(r * Dp + k)] = (float)row[k];
-                c0.data[r] = (float)cr;
-            }
-            HostTensor w3f, b3f;
-            permute_f2(*t1w, *t1b, w3f, b3f);
-            o.w3p_l0 = put_blocks(&w3f, 1, 1);
-            o.b3_l0 = put_vec(&b3f);
-            o.m0 = put_node(&m0, 1, 1);
-            o.c0 = put_vec(&c0);
-        }
-        HostTensor b4_perm;
-        // 128-wide fp32 and bf16 kernels (conv_edge.hip, conv_edge_small.hip, conv_edge_bf16.hip): output row 32 q + s of the
-        // packed W4 is feature 4 s + q, so a lane of the last GEMM's F2 output holds four CONSECUTIVE features of each edge —
-        // hn[src] is gathered and the pieces are stored 16 bytes at a time.  b4 is stored in the same order.
-        HostTensor w4_perm;
-        auto permute_w4 = [&]() {
-            permute_f2(*t3w, *t3b, w4_perm, b4_perm);
-            t3b = &b4_perm;
-        };
-        if (bf16_edges) {
-            permute_w4();
-            o.w1p = put_edge_bf16(ea0w); o.w2p = put_edge_bf16(ea2w); o.w3p = put_edge_bf16(t1w); o.w4p = put_edge_bf16(&w4_perm);
-        } else if (f16x3_edges) {
-            o.w1p = put_edge_f16x3(ea0w); o.w2p = put_edge_f16x3(ea2w); o.w3p = put_edge_f16x3(t1w); o.w4p = put_edge_f16x3(t3w);
-        } else if (bf16_wide) {
-            // one contiguous run of 32 KiB bf16 images: W1[:, kb] (EHT) | W2 | W3 | W4[ob, :] (HT)
-            auto put_blocks_bf16 = [&](const HostTensor* t, int OB, int KB) {
-                size_t o = bb.add((size_t)OB * KB * (GAMD_WFRAG_FLOATS / 2));
-                for (int ob = 0; ob < OB; ++ob)
-                    for (int kb = 0; kb < KB; ++kb)
-                        pack128_bf16(t->data.data() + (size_t)128 * ob * 128 * KB + 128 * kb,
-                                     reinterpret_cast<uint16_t*>(bb.host.data() + o + (size_t)(ob * KB + kb) * (GAMD_WFRAG_FLOATS / 2)), 128 * KB);
-                return o;
-            };
-            o.w1p = put_blocks_bf16(ea0w, 1, (int)EHT);
-            o.w2p = put_blocks_bf16(ea2w, 1, 1);
-            o.w3p = put_blocks_bf16(t1w, 1, 1);
-            o.w4p = put_blocks_bf16(t3w, (int)HT, 1);
-        } else if (f16x3_wide) {
-            // one contiguous run of [hi | lo] images: W1[:, kb] (EHT) | W2 | W3 | W4[ob, :] (HT)
-            o.w1p = put_blocks_f16x3(ea0w, 1, (int)EHT);
-            o.w2p = put_blocks_f16x3(ea2w, 1, 1);
-            o.w3p = put_blocks_f16x3(t1w, 1, 1);
-            o.w4p = put_blocks_f16x3(t3w, (int)HT, 1);
-        } else {
-            // one contiguous run of blocks: W1[:, kb] (EHT) | W2 | W3 | W4[ob, :] (HT) -- the order the kernels stream them
-            // (hidden_dim above 128, wide_d.hip: W1[:, kb] (EHT) | W2[db, :] (DT) | W3[ob][db] (DT x DT) | W4[ob][db] (HT x DT))
-            if (h->ln_fold) {
-                // A_l = W1 diag(gamma) B and the extra K step's fragment (a_l, 0) take W1's place, b1'_l = b1 + W1 beta takes b1's
-                std::vector<double> A, av, b1f;
-                lnf_layer(ea0w->data.data(), ea0b->data.data(), fold_g->data.data(), fold_b->data.data(), fold_B, fold_c, A, av, b1f);
-                const std::vector<float> Af = lnf_round(A), af = lnf_round(av);
-                o.w1p = bb.add((size_t)LNF_A_FLOATS);
-                lnf_pack_a(Af.data(), af.data(), bb.host.data() + o.w1p);
-                HostTensor b1t;
-                b1t.shape = {128};
-                b1t.data = lnf_round(b1f);
-                padded.push_back(std::move(b1t));
-                ea0b = &padded.back();
-            } else {
-            o.w1p = put_blocks(ea0w, 1, (int)EHT);
-            }
-            o.w2p = put_blocks(ea2w, (int)DT, 1);
-            o.w3p = put_blocks(t1w, (int)DT, (int)DT);
-            if (DT > 1) {
-                o.w4p = put_blocks(t3w, (int)HT, (int)DT);
-            } else if (h->wide_conv) {
-                o.w4p = put_blocks(t3w, (int)HT, 1);
-                // the same run of blocks for the opt-in 16-edge kernel (wide16.hip): W1[:, kb] | W2 | W3 chained, W4[ob, :] not
-                o.w16p = bb.add((size_t)(EHT + 2 + HT) * GAMD_WFRAG_FLOATS);
-                size_t at = o.w16p;
-                for (int kb = 0; kb < (int)EHT; ++kb, at += GAMD_WFRAG_FLOATS) pack16x(ea0w->data.data() + 128 * kb, bb.host.data() + at, 128 * (int)EHT, true);
-                pack16x(ea2w->data.data(), bb.host.data() + at, 128, true); at += GAMD_WFRAG_FLOATS;
-                pack16x(t1w->data.data(), bb.host.data() + at, 128, true); at += GAMD_WFRAG_FLOATS;
-                for (int ob = 0; ob < (int)HT; ++ob, at += GAMD_WFRAG_FLOATS) pack16x(t3w->data.data() + (size_t)128 * ob * 128, bb.host.data() + at, 128, false);
-            } else {
-                permute_w4();
-                o.w4p = put_blocks(&w4_perm, 1, 1);
-            }
-        }
-        o.b1 = put_vec(ea0b); o.b3 = put_vec(t1b); o.b4 = put_vec(t3b);
-        o.lng = put_vec(ng); o.lnb = put_vec(nb);
-        if (update_edge) {
-            const HostTensor *eg = get(p + ".edge_layer_norm.weight", {Et}, {Eh}), *eb = get(p + ".edge_layer_norm.bias", {Et}, {Eh});
-            if (!eg || !eb) return -2;
-            o.elng = put_vec(eg); o.elnb = put_vec(eb);
-        }
-        o.wsp = put_node(sw, (int)DT, (int)HT); o.wdp = put_node(dw, (int)DT, (int)HT); o.wpdp = put_node(pdw, (int)DT, (int)HT);
-        o.bS = bb.add((size_t)Dp);
-        for (int i = 0; i < (int)Dp; ++i) bb.host[o.bS + i] = (sb->data[i] + db->data[i]) + ea2b->data[i];
-        o.bP = bb.add((size_t)Dp);
-        for (int i = 0; i < (int)Dp; ++i) bb.host[o.bP + i] = pdb->data[i] + peb->data[i];
-        o.wpep = put_node(pew, (int)DT, (int)HT); o.wphip = put_node(phw, (int)HT, (int)DT); o.bphi = put_vec(phb);
-    }
-    const HostTensor *e0w = get("edge_encoder.mlp_layer.0.weight", {Dt, (int64_t)F}, {Dp, (int64_t)F}), *e0b = get("edge_encoder.mlp_layer.0.bias", {Dt}, {Dp});
-    const HostTensor *e2w = get("edge_encoder.mlp_layer.2.weight", {Dt, Dt}, {Dp, Dp}), *e2b = get("edge_encoder.mlp_layer.2.bias", {Dt}, {Dp});
-    const HostTensor *e4w = get("edge_encoder.mlp_layer.4.weight", {Et, Dt}, {Eh, Dp}), *e4b = get("edge_encoder.mlp_layer.4.bias", {Et}, {Eh});
-    const HostTensor *elg = get("edge_layer_norm.weight", {Et}, {Eh}), *elb = get("edge_layer_norm.bias", {Et}, {Eh});
-    const HostTensor *cen = expand ? get("edge_expand.centers", {40}, {40}) : nullptr;
-    const HostTensor *lm = get("length_mean", {1}, {1}), *ls = get("length_std", {1}, {1});
-    const HostTensor *d0w = get("graph_decoder.mlp_layer.0.weight", {Dt, Ht}, {Dp, H}), *d0b = get("graph_decoder.mlp_layer.0.bias", {Dt}, {Dp});
-    const HostTensor *d2w = get("graph_decoder.mlp_layer.2.weight", {3, Dt}, {3, Dp}), *d2b = get("graph_decoder.mlp_layer.2.bias", {3}, {3});
-    if (!e0w || !e0b || !e2w || !e2b || !e4w || !e4b || !elg || !elb || (expand && !cen) || !lm || !ls || !d0w || !d0b ||
-        !d2w || !d2b)
-        return -2;
-    // (hidden_dim above 128: the DT 128-row images of the first Linear side by side in one 64 KiB slot, the streamed blocks of
-    //  W2 and W3 right behind it — k_edge_encode_wide_d walks them as one run)
-    const size_t o_e1 = bb.add(DT > 1 ? (size_t)GAMD_WFRAG_FLOATS : (size_t)(4 * 6 * 64 * 4));
-    if (DT > 1) for (int64_t b = 0; b < DT; ++b) pack_enc1(e0w->data.data() + (size_t)(128 * b * F), F, bb.host.data() + o_e1 + (size_t)b * (4 * 6 * 64 * 4));
-    else if (bf16_edges) pack_enc1_bf16(e0w->data.data(), F, reinterpret_cast<uint16_t*>(bb.host.data() + o_e1));
-    else if (f16x3_edges) pack_enc1_f16x3(e0w->data.data(), F, reinterpret_cast<uint16_t*>(bb.host.data() + o_e1));
-    else pack_enc1(e0w->data.data(), F, bb.host.data() + o_e1);
-    // generic-width encoder in the reduced-precision modes: its two 128-wide GEMMs run in split-fp16 (wide.hip, e_format != 0)
-    const bool enc_wide_f16 = h->wide_enc && h->cfg.edge_dtype != GAMD_EDGE_F32;
-    const size_t o_e2 = bf16_edges ? put_edge_bf16(e2w) : f16x3_edges ? put_edge_f16x3(e2w) : enc_wide_f16 ? put_blocks_f16x3(e2w, 1, 1)
-                                                                                                              : put_blocks(e2w, (int)DT, (int)DT);
-    // fp32 path: the last encoder Linear is stored with its OUTPUT rows centred, W' = W - mean over rows, b' = b - mean(b)
-    // (in double): y' = W' x + b' = y - mean(y) exactly in real arithmetic, so edge_layer_norm's mean subtraction
-    // (nn_module.py:646) is done here once instead of per edge; the kernels only normalise the variance
-    // (layernorm_chain_centered; wide.hip's generic LayerNorm sees a mean of ~0 and is unaffected).
-    HostTensor e4w_c = *e4w, e4b_c = *e4b;
-    if (!bf16_edges && !f16x3_edges) {
-        // (the mean is over the Et true output rows; zero-padded rows stay zero)
-        for (int64_t k = 0; k < Dp; ++k) {
-            double m = 0.0;
-            for (int64_t o = 0; o < Et; ++o) m += (double)e4w->data[(size_t)(o * Dp + k)];
-            m /= (double)Et;
-            for (int64_t o = 0; o < Et; ++o) e4w_c.data[(size_t)(o * Dp + k)] = (float)((double)e4w->data[(size_t)(o * Dp + k)] - m);
-        }
-        double mb = 0.0;
-        for (int64_t o = 0; o < Et; ++o) mb += (double)e4b->data[(size_t)o];
-        mb /= (double)Et;
-        for (int64_t o = 0; o < Et; ++o) e4b_c.data[(size_t)o] = (float)((double)e4b->data[(size_t)o] - mb);
-    }
-    if (h->ln_fold) {
-        // the encoder needs |B x2 + c| only: R of B = Q R (its six all-zero blocks left out) and Q^T c take W3's and b3's places
-        std::vector<double> Rm, cq;
-        lnf_qr(fold_B, fold_c, Rm, cq);
-        e4b_c.data = lnf_round(cq);
-        e4w_c.data = lnf_round(Rm);
-    }
-    const size_t o_e3 = h->ln_fold ? bb.add((size_t)LNF_R_FLOATS) : bf16_edges ? put_edge_bf16(e4w) : f16x3_edges ? put_edge_f16x3(e4w) : enc_wide_f16 ? put_blocks_f16x3(&e4w_c, (int)EHT, 1)
-                                                                                                              : put_blocks(&e4w_c, (int)EHT, (int)DT);
-    if (h->ln_fold) lnf_pack_r(e4w_c.data.data(), bb.host.data() + o_e3);
-    const size_t o_eb1 = put_vec(e0b), o_eb2 = put_vec(e2b), o_eb3 = put_vec(&e4b_c), o_elg = put_vec(elg), o_elb = put_vec(elb);
-    const size_t o_cen = expand ? put_vec(cen) : bb.add(64);
-    const size_t o_d1 = put_node(d0w, (int)DT, (int)HT), o_db1 = put_vec(d0b), o_d2 = put_vec(d2w), o_db2 = put_vec(d2b);
-    size_t o_emb = 0, o_nw = 0, o_nb = 0;
-    if (h->cfg.kind == GAMD_KIND_LJ) {
-        const HostTensor* emb = get("node_emb", {1, Ht}, {1, H});
-        if (!emb) return -2;
-        o_emb = put_vec(emb);
-    } else {
-        const HostTensor *nw = get("node_encoder.weight", {Ht, 1}, {H, 1}), *nb = get("node_encoder.bias", {Ht}, {H});
-        if (!nw || !nb) return -2;
-        o_nw = put_vec(nw); o_nb = put_vec(nb);
-    }
-    h->length_mean = lm->data[0];
-    h->length_std = ls->data[0];
-    h->rbf = RbfGrid{};
-    if (expand) {
-        // RBFExpansion builds linspace(low, high, n) (nn_module.py:237-239): uniform up to fp32 rounding.  Anything else
-        // (hand-edited centres) keeps the exact per-centre form.
-        const double c0 = cen->data[0], delta = ((double)cen->data[39] - c0) / 39.0;
-        bool uniform = delta > 0.0;
-        for (int k = 0; k < 40 && uniform; ++k)
-            uniform = std::fabs((double)cen->data[k] - (c0 + k * delta)) <= 2.5e-7 * std::max(1.0, std::fabs(c0 + k * delta));
-        if (uniform) {
-            const double gexp = -(1.0 / 0.025) * 1.4426950408889634, s = 2.0 * delta;     // -gamma log2(e), chain step
-            h->rbf = RbfGrid{1, (float)c0, (float)delta, (float)(-2.0 * gexp * s), (float)(gexp * s * s),
-                             (float)std::exp2(2.0 * gexp * s * s)};
-        }
-    }
+    h->norm_bn = pw.norm_bn ? 1 : 0;
+    h->l0_hoist = pw.l0_hoist;
+    h->length_mean = pw.length_mean;
+    h->length_std = pw.length_std;
+    h->rbf = RbfGrid{pw.rbf.uniform, pw.rbf.c0, pw.rbf.delta, pw.rbf.A, pw.rbf.B, pw.rbf.C};
 
-    if (h->wblob.ensure(sizeof(float) * bb.host.size(), false)) return fail(-12, "weight blob allocation failed");
-    HIP_TRY(init_upload(h->wblob.p, bb.host.data(), sizeof(float) * bb.host.size()));
+    if (h->wblob.ensure(sizeof(float) * pw.blob.size(), false)) return fail(-12, "weight blob allocation failed");
+    HIP_TRY(init_upload(h->wblob.p, pw.blob.data(), sizeof(float) * pw.blob.size()));
     const float* B = h->wblob.as<float>();
-    h->layers.assign(L, LayerDev{});
-    for (int l = 0; l < L; ++l) {
-        const Off& o = lo[l];
+    auto at = [B](size_t off) { return off == WOFF_NONE ? nullptr : B + off; };
+    h->layers.assign(pw.layers.size(), LayerDev{});
+    for (size_t l = 0; l < pw.layers.size(); ++l) {
+        const LayerOff& o = pw.layers[l];
         LayerDev& d = h->layers[l];
-        d.w1p = B + o.w1p; d.w2p = B + o.w2p; d.w3p = B + o.w3p; d.w4p = B + o.w4p;
-        d.w16p = (h->wide_conv && h->cfg.edge_dtype == GAMD_EDGE_F32 && DT == 1) ? B + o.w16p : nullptr;
-        d.b1 = B + o.b1; d.b3 = B + o.b3; d.b4 = B + o.b4;
-        d.node.ln_g = B + o.lng; d.node.ln_b = B + o.lnb;
-        if (update_edge) { d.e_ln_g = B + o.elng; d.e_ln_b = B + o.elnb; }
-        d.node.wsp = B + o.wsp; d.node.wdp = B + o.wdp; d.node.wpdp = B + o.wpdp;
-        d.node.bS = B + o.bS; d.node.bP = B + o.bP;
-        d.node.wpep = B + o.wpep; d.node.wphip = B + o.wphip; d.node.bphi = B + o.bphi;
-        d.node.c0 = nullptr;
-        if (l == 0 && h->l0_hoist) {
-            d.w3p_l0 = B + o.w3p_l0; d.b3_l0 = B + o.b3_l0;
-            d.node.wpep = B + o.m0; d.node.c0 = B + o.c0;
-        }
+#define GAMD_W_SET(f) d.f = at(o.f);
+        GAMD_W_LAYER_FIELDS(GAMD_W_SET)        // w16p stays null unless the blob carries the wide16.hip image
+#undef GAMD_W_SET
+#define GAMD_W_SET(f) d.node.f = at(o.node.f);
+        GAMD_W_NODE_FIELDS(GAMD_W_SET)         // c0: null but in the layer-0 form ...
+#undef GAMD_W_SET
+        if (o.m0 != WOFF_NONE) d.node.wpep = at(o.m0);            // ... where post(0) multiplies by M0 in phi_edge's place
     }
-    h->enc_w1p = B + o_e1; h->enc_w2p = B + o_e2; h->enc_w3p = B + o_e3;
-    h->enc_b1 = B + o_eb1; h->enc_b2 = B + o_eb2; h->enc_b3 = B + o_eb3;
-    h->enc_lng = B + o_elg; h->enc_lnb = B + o_elb; h->centers = B + o_cen;
-    h->dec_w1p = B + o_d1; h->dec_b1 = B + o_db1; h->dec_w2 = B + o_d2; h->dec_b2 = B + o_db2;
-    h->node_emb = h->cfg.kind == GAMD_KIND_LJ ? B + o_emb : nullptr;
-    h->nenc_w = h->cfg.kind == GAMD_KIND_LJ ? nullptr : B + o_nw;
-    h->nenc_b = h->cfg.kind == GAMD_KIND_LJ ? nullptr : B + o_nb;
+#define GAMD_W_SET(f) h->f = at(pw.g.f);
+    GAMD_W_GLOBAL_FIELDS(GAMD_W_SET)           // node_emb (LJ) or nenc_w / nenc_b (water): the other kind's stay null
+#undef GAMD_W_SET
     h->finalized = true;
     return 0;
 }

@@ -4,6 +4,7 @@
 #include "../../include/gamd_hip.h"
 #include "gamd_common.h"
 #include "gamd_internal.h"
+#include "gamd_weights_host.h"
 
 #include <cstdarg>
 #include <cstdio>
@@ -28,11 +29,6 @@ inline int fail(int code, const char* fmt, ...) {
         hipError_t e__ = (expr);                                                                   \
         if (e__ != hipSuccess) return fail(-1000 - (int)e__, "%s: %s", #expr, hipGetErrorString(e__)); \
     } while (0)
-
-struct HostTensor {
-    std::vector<int64_t> shape;
-    std::vector<float> data;
-};
 
 // Initialising work — zeroing a fresh buffer, uploading a small table — goes to ONE stream and is waited for on THAT stream
 // before the call returns: the caller's stream inside the entry points that take one, the handle's private non-blocking

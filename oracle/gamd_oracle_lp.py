@@ -23,7 +23,7 @@ variant "f16x3_128"  edge_encode_f16x3.hip, conv_edge_f16x3.hip, k_node<true> (1
 variant "f16x3_wide" wide.hip's k_edge_encode_wide (e_format 2), wide_lp.hip's k_conv_edge_f16x3_wide, k_node_wide<HT, true>
 
 Operand split (gamd_f16x3.h): an MFMA operand x is hi = fp16(x), lo = fp16(x - hi), round to nearest even, subnormals kept, the
-residual formed in fp32 (gamd_split8, silu_split_pair, node.hip split16; host: split_f16 in gamd_api.hip); a product is
+residual formed in fp32 (gamd_split8, silu_split_pair, node.hip split16; host: split_f16 in gamd_weights_host.h); a product is
 W_hi x_hi + (W_hi x_lo + W_lo x_hi), the lo x lo term is dropped.  Weights are split as the host packs them (no factors in these
 families), activations where the kernel splits them.  The model has no overflow path: tests/test_lp_reference.py holds every
 operand of every split case below 65504 (`operand_log`).
@@ -49,7 +49,7 @@ import gamd_oracle as orc
 
 Tensor = torch.Tensor
 
-LOG2E = 1.4426950408889634      # gamd_api.hip, gamd_finalize_weights: `const double LOG2E = ..., LN2 = ...`
+LOG2E = 1.4426950408889634      # gamd_weights_host.h, scale_for_exp2: `const double LOG2E = ..., LN2 = ...`
 LN2 = 0.6931471805599453
 
 
@@ -88,7 +88,7 @@ def spec_of(variant: Variant) -> Optional[Spec]:
 # rounding
 # --------------------------------------------------------------------------
 def round_bf16(x: Tensor, mode: str = "rne") -> Tensor:
-    """The value as the nearest bf16 (ties to even: v_cvt_pk_bf16_f32, gamd_bf16.h gamd_pk_bf16; host: f2bf in gamd_api.hip),
+    """The value as the nearest bf16 (ties to even: v_cvt_pk_bf16_f32, gamd_bf16.h gamd_pk_bf16; host: f2bf in gamd_weights_host.h),
     in x's dtype.  The kernels round fp32 values, so a float64 input is taken to fp32 first."""
     x32 = x.to(torch.float32)
     if mode == "rne":
