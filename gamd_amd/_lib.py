@@ -123,6 +123,7 @@ SYMBOLS = {
     "gamd_md_force_source": (_i32, [_vp, _i32]),
     "gamd_minimize": (_i32, [_vp, _vp, C.POINTER(C.c_float), C.c_float, _vp, _vp, C.POINTER(GamdMinimizeParams), _vp, _vp]),
     "gamd_water_configure": (_i32, [_vp, C.POINTER(GamdWaterParams)]),
+    "gamd_water_msite": (_i32, [_vp, C.c_double]),
     "gamd_water_reset": (_i32, [_vp]),
     "gamd_water_read": (_i32, [_vp, _vp, _vp, _vp, _i64, C.POINTER(_i64), C.POINTER(_i64), _vp, _i64]),
     "gamd_water_eval": (_i32, [_vp, _vp, _vp, C.POINTER(C.c_float), C.c_float, _vp, _vp, _vp]),

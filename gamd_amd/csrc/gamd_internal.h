@@ -666,6 +666,8 @@ int launch_water_classical(const WaterArgs& a, hipStream_t st);
 int launch_water_recip(const WaterArgs& a, hipStream_t st);
 // k_water_sk alone (it reads no positions): a.sk and a.ublk from a.rho_partial, for the water minimiser's own rho and force passes
 int launch_water_sk(const WaterArgs& a, hipStream_t st);
+// k_water_final alone (it reads no positions): the row of a.slot from a.blk and a.ublk, for the 4-site passes of water_msite.hip
+int launch_water_final(const WaterArgs& a, hipStream_t st);
 
 // ---- water classical force source (water_drive.hip) -------------------------------------------------
 // One force evaluation of a water-source step of an enqueued MD run (gamd_md_force_source, GAMD_FORCE_WATER_CLASSICAL): the pair
@@ -673,6 +675,25 @@ int launch_water_sk(const WaterArgs& a, hipStream_t st);
 // per atom the pair slices and the k slices added in order from 0, f_cl to a.f_cl and (float)f_cl to f_out ([n][3], the
 // caller's atom order).  a.f, a.blk, a.rows, a.steps, a.slot and a.g are not used.  Five launches, plain stores.
 int launch_water_drive(const WaterArgs& a, float* f_out, hipStream_t st);
+
+// ---- the TIP4P M-site in the water classical potential (water_msite.hip) ------------------------------
+// The potential of WaterArgs with the negative charge on a virtual site M = O' + w_h (d_1 + d_2) of every molecule
+// (gamd_water_msite): the charge sites are M, H1, H2, the Lennard-Jones site is O, and M's force goes
+// back to the atoms with the weights 1 - 2 w_h, w_h, w_h.  `w` is the 3-site argument block unchanged (w.x the fp32 atoms);
+// molecule = index / 3 with the oxygen first.  w_h != 0: the 3-site launchers serve w_h = 0.
+// (No kernel uses a value it read from memory as an address: the checked build has nothing to range-check here.)
+enum { W4_LJ = 4 };            // per molecule and pair slice: the oxygen's Lennard-Jones Fx, Fy, Fz (per length unit) and u_LJ of its row
+struct W4Args {
+    WaterArgs w;
+    double w_h, w_o;           // the hydrogens' weight and 1 - 2 w_h
+    int mchunk;                // molecules per slice of the Lennard-Jones pass: slices * mchunk >= n_per_box / 3
+    double* sites;             // [n][3] charge-site positions, length unit: M in the oxygen's row, the hydrogen wrapped into [0, L) in its own
+    double* ljpart;            // [n_boxes][slices][n_per_box / 3][W4_LJ]
+};
+// k_w4_sites, k_w4_pairs, k_w4_lj, k_w4_rho, k_water_sk, k_w4_recip, k_w4_atoms, k_water_final: launch_water_classical's row and f_cl
+int launch_w4_classical(const W4Args& a, hipStream_t st);
+// ... the first six and k_w4_drive: launch_water_drive's f_cl and f_out (the energies of the pair pass are computed and not read)
+int launch_w4_drive(const W4Args& a, float* f_out, hipStream_t st);
 
 // ---- energy minimiser (minimize.hip) ----------------------------------------------------------------
 // FIRE under the Lennard-Jones potential of classical.hip, per box, all state in double.  `c` carries

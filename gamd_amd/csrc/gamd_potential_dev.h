@@ -48,6 +48,22 @@ __device__ __forceinline__ double2 gamd_lj_switch(double rs, double inv_w, doubl
 // image k, and so is every phase n.s (x / L alone is not: fl((x + k L) / L) and fl(x / L) + k differ in the last bits).
 __device__ __forceinline__ double water_frac(double x, double L) { return (x - L * floor(x / L)) / L; }
 
+// the TIP4P virtual site of one molecule (water_msite.hip; OpenMM's ThreeParticleAverageSite with weights 1 - 2 w, w, w):
+// M = O' + w (d_1 + d_2), d_k = H_k - O per component as d - L rint(d / L), from the fp32 positions widened, and O' = O wrapped
+// into [0, L) by water_wrap.  The hydrogens may be in any image; where x + k L is exact in fp32, d_k and O' — and so M — are the
+// same doubles for every image of every atom.  The one place M is computed: every 4-site kernel reads its result.
+__device__ __forceinline__ double water_wrap(double x, double L) { return x - L * floor(x / L); }
+
+__device__ __forceinline__ void water_msite(const float* o, const float* h1, const float* h2, double Lx, double Ly, double Lz, double w,
+                                            double& mx, double& my, double& mz) {
+    const double ox = (double)o[0], oy = (double)o[1], oz = (double)o[2];
+    double ax = (double)h1[0] - ox, ay = (double)h1[1] - oy, az = (double)h1[2] - oz;
+    double bx = (double)h2[0] - ox, by = (double)h2[1] - oy, bz = (double)h2[2] - oz;
+    ax = ax - Lx * rint(ax / Lx); ay = ay - Ly * rint(ay / Ly); az = az - Lz * rint(az / Lz);
+    bx = bx - Lx * rint(bx / Lx); by = by - Ly * rint(by / Ly); bz = bz - Lz * rint(bz / Lz);
+    mx = water_wrap(ox, Lx) + w * (ax + bx); my = water_wrap(oy, Ly) + w * (ay + by); mz = water_wrap(oz, Lz) + w * (az + bz);
+}
+
 // one atom's terms of the force-error sums of the run's force g against the classical force c (both kJ/mol/nm):
 // sum |D_c|, sum |D|^2, sum cos, sum |c|, sum |g|, and the atoms left out of the cosine because one of the two is zero
 __device__ __forceinline__ void gamd_force_error(double gx, double gy, double gz, double cx, double cy, double cz, double& sum_abs,

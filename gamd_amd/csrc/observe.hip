@@ -101,6 +101,8 @@ struct WaterClassical : PotentialLog {
     int n2max = -1, n_k = 0;           // the list in force: every n with 0 < |n|^2 <= n2max (-1: none yet)
     DevBuf rpart;                      // one evaluation: per atom and k slice
     DevBuf kvec, rho_partial, sk, ublk;// ... per k-vector
+    double w_h = 0.0;                  // gamd_water_msite: the hydrogens' weight of the TIP4P M-site, 0 = 3-site
+    DevBuf sites, ljpart;              // w_h != 0: per atom, and per atom and pair slice (water_msite.hip)
 };
 
 // energy minimiser (gamd_minimize, minimize.hip): no observer — no clock, no entry in observer_list() — but a user of the
@@ -197,6 +199,10 @@ ObsBufs water_bufs(gamd_handle* h) {
                              {&wc.rho_partial, sizeof(double) * 2 * nb * (size_t)struct_rho_blocks(h) * K, false},
                              {&wc.sk, sizeof(double) * 3 * nb * K, false},
                              {&wc.ublk, sizeof(double) * nb * ((K + 255) / 256), false}});
+    // the M-site's own: nothing while the potential is 3-site
+    const size_t m = wc.w_h != 0.0 ? 1 : 0;
+    t.push_back({&wc.sites, m * sizeof(double) * 3 * n, false});
+    t.push_back({&wc.ljpart, m * sizeof(double) * W4_LJ * (n / 3) * (size_t)classical_slices(h), false});
     return t;
 }
 
@@ -418,10 +424,10 @@ struct LjPotential {
         return a;
     }
     static void species(Args&, const uint8_t*) {}
-    static int launch(const Args& a, hipStream_t st) { return launch_classical(a, st); }
+    static int launch(const gamd_handle*, const Args& a, hipStream_t st) { return launch_classical(a, st); }
     static int check_box(gamd_handle* h, const float* box, const uint8_t*) { return potential_check_box(h, state(h), who, box); }
     // a force source as well (potential_drive): the forces alone, rounded to fp32, into the run's f
-    static int drive(const Args& a, float* f_out, hipStream_t st) { return launch_classical_drive(a, f_out, st); }
+    static int drive(const gamd_handle*, const Args& a, float* f_out, hipStream_t st) { return launch_classical_drive(a, f_out, st); }
 };
 
 struct WaterPotential {
@@ -451,7 +457,14 @@ struct WaterPotential {
         return a;
     }
     static void species(Args& a, const uint8_t* species_dev) { a.species = species_dev; }
-    static int launch(const Args& a, hipStream_t st) { return launch_water_classical(a, st); }
+    // the site model in force (gamd_water_msite): w_h = 0 is the 3-site launcher as it was
+    static W4Args msite(const gamd_handle* h, const Args& a) {
+        const WaterClassical& wc = state(h);
+        return W4Args{a, wc.w_h, 1.0 - 2.0 * wc.w_h, (classical_chunk(h) + 2) / 3, wc.sites.as<double>(), wc.ljpart.as<double>()};
+    }
+    static int launch(const gamd_handle* h, const Args& a, hipStream_t st) {
+        return state(h).w_h != 0.0 ? launch_w4_classical(msite(h, a), st) : launch_water_classical(a, st);
+    }
     // species, 2 r_cut <= every edge, a k-vector list of at most 131 072 triples for these boxes (built and uploaded here when
     // the boxes need another one than the list in force)
     static int check_box(gamd_handle* h, const float* box, const uint8_t* species_dev) {
@@ -464,7 +477,9 @@ struct WaterPotential {
         return water_klist_apply(h, n2max, kv);
     }
     // a force source as well (potential_drive): the forces alone, rounded to fp32, into the run's f
-    static int drive(const Args& a, float* f_out, hipStream_t st) { return launch_water_drive(a, f_out, st); }
+    static int drive(const gamd_handle* h, const Args& a, float* f_out, hipStream_t st) {
+        return state(h).w_h != 0.0 ? launch_w4_drive(msite(h, a), f_out, st) : launch_water_drive(a, f_out, st);
+    }
 };
 
 // the sample of step s of the pending run, behind its second half: f holds the network forces at x
@@ -479,7 +494,7 @@ int potential_sample(gamd_handle* h, long long s) {
     a.rows = pl.rows.as<double>(); a.steps = pl.steps.as<long long>();
     a.g = pl.clock.completed(s);
     a.slot = pl.clock.ordinal(s);
-    if (int r = P::launch(a, p.st)) return fail(-1, "%s observer launch failed (%d)", P::who, r);
+    if (int r = P::launch(h, a, p.st)) return fail(-1, "%s observer launch failed (%d)", P::who, r);
     pl.evaluated = true;
     return 0;
 }
@@ -492,7 +507,7 @@ int potential_drive(gamd_handle* h, hipStream_t st) {
     typename P::Args a = P::args(h, pending_particles(p).len);
     for (int d = 0; d < 3; ++d) a.box[d] = h->box[d];
     a.x = p.x; P::species(a, p.species);
-    if (int r = P::drive(a, p.f, st)) return fail(-1, "%s force source launch failed (%d)", P::who, r);
+    if (int r = P::drive(h, a, p.f, st)) return fail(-1, "%s force source launch failed (%d)", P::who, r);
     P::state(h).evaluated = true;
     return 0;
 }
@@ -653,7 +668,7 @@ int potential_eval(gamd_handle* h, const float* pos_dev, const uint8_t* species_
     a.box_edges = pl.eval_box.as<float>();
     a.x = pos_dev; a.f = nullptr; P::species(a, species_dev);
     a.rows = pl.eval_rows.as<double>(); a.steps = nullptr; a.slot = 0; a.g = 0;
-    if (int r = P::launch(a, st)) return fail(-1, "%s potential launch failed (%d)", P::who, r);
+    if (int r = P::launch(h, a, st)) return fail(-1, "%s potential launch failed (%d)", P::who, r);
     pl.evaluated = true;
     if (f_out_dev) HIP_TRY(hipMemcpyAsync(f_out_dev, pl.f_cl.p, sizeof(double) * 3 * (size_t)h->n, hipMemcpyDeviceToDevice, st));
     row = std::vector<double>(P::ROW * nb);
@@ -1108,6 +1123,26 @@ int32_t gamd_water_configure(gamd_handle* h, const gamd_water_params* p) {
     return potential_configure<WaterPotential>(h, OBS_WATER, p->interval, p->max_samples, "gamd_water_configure");
 }
 
+int32_t gamd_water_msite(gamd_handle* h, double w_h) {
+    if (!h) return fail(-22, "null handle");
+    if (h->cfg.kind != GAMD_KIND_WATER)
+        return fail(-22, "gamd_water_msite: a GAMD_KIND_LJ handle has no molecules and no charges (GAMD_KIND_WATER handles only)");
+    WaterClassical& wc = h->obs->wc;
+    if (!wc.params_set) return fail(-22, "gamd_water_msite needs the parameters of a gamd_water_configure call (interval 0 will do)");
+    if (h->pending.active) return fail(-22, "an MD run is still enqueued: call gamd_sync_status before gamd_water_msite");
+    if (!std::isfinite(w_h) || !(w_h >= 0.0) || !(w_h < 0.5))
+        return fail(-22, "gamd_water_msite: w_h = %g is not in [0, 0.5) (the oxygen's weight 1 - 2 w_h must stay positive)", w_h);
+    const double before = wc.w_h;
+    wc.w_h = w_h;
+    DeviceGuard guard(h->dev);
+    InitStream init(h->init_stream);
+    if (bufs_ensure_work(water_bufs(h))) {
+        wc.w_h = before;
+        return fail(-12, "gamd_water_msite: allocation failed");
+    }
+    return 0;
+}
+
 int32_t gamd_water_reset(gamd_handle* h) { return observer_reset(h, OBS_WATER, "gamd_water_reset"); }
 
 int32_t gamd_water_read(gamd_handle* h, void* stream, int64_t* steps, double* rows, int64_t max_rows, int64_t* n_rows,
@@ -1143,6 +1178,9 @@ int32_t gamd_water_minimize(gamd_handle* h, float* x_dev, const uint8_t* species
     WaterClassical& wc = WaterPotential::state(h);
     if (!wc.params_set) return fail(-22, "gamd_water_minimize needs the parameters of a gamd_water_configure call (interval 0 will do)");
     if (h->pending.active) return fail(-22, "an MD run is still enqueued: call gamd_sync_status before gamd_water_minimize");
+    if (wc.w_h != 0.0)
+        return fail(-22, "gamd_water_minimize: the TIP4P M-site is set (gamd_water_msite, w_h = %.9g) and there is no 4-site rigid minimiser: "
+                         "minimise with w_h = 0, set the weight, then take f from gamd_water_eval", wc.w_h);
     if (!x_dev || !f_dev || !box) return fail(-22, "null argument");
     for (int k = 0; k < 3 * h->n_boxes; ++k)
         if (!(box[k] > 0.f)) return fail(-22, "box[%d][%d] = %g is not positive", k / 3, k % 3, (double)box[k]);

@@ -341,6 +341,14 @@ int launch_water_sk(const WaterArgs& a, hipStream_t st) {
     return 0;
 }
 
+int launch_water_final(const WaterArgs& a, hipStream_t st) {
+    const int nb = a.bx.n_boxes > 1 ? a.bx.n_boxes : 1;
+    if (nb > 65535 || a.blocks < 1 || a.blocks > 65535 || a.slot < 0 || a.kblocks < 1) return -1;
+    if (!a.blk || !a.ublk || !a.rows || !a.devflags) return -1;
+    hipLaunchKernelGGL(k_water_final, dim3((nb + 63) / 64), dim3(64), 0, st, a); GAMD_CHECK_LAUNCH();
+    return 0;
+}
+
 int launch_water_classical(const WaterArgs& a, hipStream_t st) {
     const int nb = a.bx.n_boxes > 1 ? a.bx.n_boxes : 1, npb = a.bx.n_boxes > 1 ? a.bx.n_per_box : a.n;
     const long long T = (npb + WC_TILE - 1) / WC_TILE;

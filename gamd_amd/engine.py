@@ -346,6 +346,12 @@ class RunClassical:
 
 
 COULOMB_KJ_NM = 138.935456                   # 1 / (4 pi eps0) in kJ nm / (mol e^2), as OpenMM's ONE_4PI_EPS0 is remembered (UNVERIFIED)
+# the 3-site defaults of water_classical_configure, and TIP4P-Ew as keyword arguments of it (lengths in Angstrom; the rigid
+# geometry is TIP3P's, 0.9572 Angstrom and 104.52 degrees, so |OM| = 0.125 Angstrom).  Both sets are meant to be those of OpenMM's
+# tip3p.xml / tip4pew.xml, but they were written down from memory and are UNVERIFIED: neither OpenMM nor openmmtools was
+# available to compare against.
+TIP3P = dict(q_h=0.417, sigma_o=3.15075, epsilon_o=0.635968, m_site=0.0)
+TIP4PEW = dict(q_h=0.52422, sigma_o=3.16435, epsilon_o=0.680946, m_site=0.106676721)
 
 
 class RunWaterClassical(RunClassical):
@@ -817,8 +823,8 @@ class GamdForce:
         2 r_cut must not exceed a box edge.  Replaces the OpenMM run of the reference's data generator
         (dataset/generate_lj_data.py:74-107).  O(N^2) per step and box.
 
-        ``"water_classical"`` (water models only) is the same under the 3-site water potential of the last
-        ``water_classical_configure`` (interval 0 will do): O-O Lennard-Jones plus a plain Ewald sum, bit for bit
+        ``"water_classical"`` (water models only) is the same under the water potential of the last
+        ``water_classical_configure`` (interval 0 will do; 3-site, or 4-site with its ``m_site``): O-O Lennard-Jones plus a plain Ewald sum, bit for bit
         ``water_classical_forces(x, species)[0].float()``.  A run then needs ``rigid_water`` (the potential has no bond
         or angle term), ``species``, and 2 r_cut below every box edge.  Replaces the OpenMM run of
         dataset/generate_tip3p_data.py:76-103.  O(N^2 + N K) per step and box, K the k-vectors of the Ewald sum."""
@@ -1059,7 +1065,7 @@ class GamdForce:
                                   epsilon_o: float = 0.635968, r_cut: Optional[float] = None, r_switch: float = 0.0,
                                   shift: bool = False, ewald_tol: float = 1e-10, alpha: Optional[float] = None,
                                   k_cut: Optional[float] = None, coulomb_const: float = COULOMB_KJ_NM,
-                                  length_per_nm: float = 0.0) -> None:
+                                  length_per_nm: float = 0.0, m_site: float = 0.0) -> None:
         """While configured, every ``interval``-th completed step of md_run / md_run_nhc (counted across calls, by a counter
         of its own) evaluates the classical potential of 3-site water in double on the device — O-O Lennard-Jones plus
         point charges q_H and q_O = -2 q_H by a plain Ewald sum (real space inside ``r_cut``, same-molecule exclusion,
@@ -1076,9 +1082,21 @@ class GamdForce:
         neither).  The defaults (q_H = 0.417 e, sigma_O = 3.15075 Angstrom, epsilon_O = 0.635968 kJ/mol, 138.935456 kJ nm /
         (mol e^2), cutoff 9.5 Angstrom) are meant to be those of OpenMM's ``tip3p.xml`` and of the drivers'
         ``WaterBox(cutoff=9.5 Angstrom)``, but they were written down from memory and are UNVERIFIED: neither OpenMM nor
-        openmmtools was available to compare against.  The sum is the limit OpenMM's PME approximates, not PME; no
-        long-range dispersion correction, no TIP4P M-site (a TIP4P handle evaluates the 3-site parameters it is given), no
-        virial.  Check the parameters against your OpenMM system before comparing energies."""
+        openmmtools was available to compare against.
+
+        ``m_site`` = w > 0 puts the negative charge on the TIP4P virtual site M = O + w (d_1 + d_2) of every molecule (d_k
+        the minimum-image vectors O -> H_k; OpenMM's ThreeParticleAverageSite with weights 1 - 2 w, w, w): the Coulomb terms
+        are then taken on M, H, H, the Lennard-Jones term stays on O with a cutoff test of its own, and M's force goes back
+        to the atoms with the same weights, the exact gradient with respect to O, H, H.  Handles, integrators and SETTLE
+        still see three atoms.  The observer, ``water_classical_forces`` and the ``"water_classical"`` force source all
+        follow it; ``water_minimize`` refuses it.  Every call states the whole potential: the default 0 is 3-site water,
+        bit for bit what it was.  ``water_classical_configure(0, **TIP4PEW)`` (module constant: q_H = 0.52422 e, sigma_O =
+        3.16435 Angstrom, epsilon_O = 0.680946 kJ/mol, w = 0.106676721) is meant to be OpenMM's ``tip4pew.xml``; these values
+        too were written down from memory and are UNVERIFIED.  ``sigma_o`` given explicitly is in the engine's length unit.
+
+        The sum is the limit OpenMM's PME approximates, not PME.  Not built: PME, the long-range dispersion correction, a
+        virial, a 4-site minimiser; no parity with OpenMM is claimed.  Check the parameters against your OpenMM system
+        before comparing energies."""
         unit = float(np.float32(length_per_nm)) / 10.0 if length_per_nm else 1.0     # the fp32 value the library holds
         sigma_o = 3.15075 * unit if sigma_o is None else float(sigma_o)
         r_cut = 9.5 * unit if r_cut is None else float(r_cut)
@@ -1091,6 +1109,7 @@ class GamdForce:
         p = GamdWaterParams(int(interval), int(max_samples), float(q_h), sigma_o, float(epsilon_o), r_cut, float(r_switch),
                             int(bool(shift)), 0, float(alpha), float(k_cut), float(coulomb_const))
         check(self._lib.gamd_water_configure(self._h, C.byref(p)), "gamd_water_configure")
+        check(self._lib.gamd_water_msite(self._h, float(m_site)), "gamd_water_msite")
         self._water_set = True
 
     def water_classical_reset(self) -> None:
@@ -1143,7 +1162,11 @@ class GamdForce:
         bit for bit, what a water-source ``md_run`` / ``md_run_nhc`` with ``rigid_water`` needs on entry.  A box that was
         not finite at the start keeps its ``x``; nothing is written to ``f`` for a box that failed.  ``return_x64``: also the
         unrounded, unwrapped, exactly rigid double positions (``result.x64``).  Water models only; 2 r_cut must not exceed a
-        box edge.  Synchronises."""
+        box edge.  Synchronises.
+
+        The minimiser is 3-site: with ``m_site`` != 0 in force it raises (the library answers -22 and names the M-site)
+        before anything is enqueued.  A 4-site start: minimise with ``m_site=0``, configure again with the weight, and pass
+        ``water_classical_forces(x, species)[0].float()`` as ``f`` on entry of the run."""
         unknown = set(fire) - {"dt_start", "dt_max", "n_min", "f_inc", "f_dec", "alpha_start", "f_alpha", "max_step"}
         if unknown:
             raise TypeError(f"water_minimize() got unexpected FIRE constants {sorted(unknown)}")

@@ -530,8 +530,10 @@ int32_t gamd_classical_eval(gamd_handle* h, const float* pos_dev, const float* b
  * list is built or swapped for the run's boxes at that point).
  * -22 from gamd_md_force_source besides the above: GAMD_FORCE_WATER_CLASSICAL on a GAMD_KIND_LJ handle, or before an accepted
  * gamd_water_configure (interval 0 will do).
- * gamd_water_minimize (below) relaxes a start and leaves x and f as this source expects them.  Not built: the TIP4P M-site,
- * PME, long-range dispersion.  The default parameters of gamd_water_configure remain UNVERIFIED against OpenMM. */
+ * gamd_water_minimize (below) relaxes a start and leaves x and f as this source expects them.  With gamd_water_msite the
+ * source drives the 4-site (TIP4P) form of the potential by seven launches; a start is then minimised with w_h = 0 (see there).
+ * Not built: PME, long-range dispersion, the 4-site minimiser.  The default parameters of gamd_water_configure remain UNVERIFIED
+ * against OpenMM. */
 enum { GAMD_FORCE_NETWORK = 0, GAMD_FORCE_CLASSICAL = 1, GAMD_FORCE_WATER_CLASSICAL = 2 };
 int32_t gamd_md_force_source(gamd_handle* h, int32_t source);
 
@@ -552,8 +554,9 @@ int32_t gamd_md_force_source(gamd_handle* h, int32_t source);
  * and the forces are the exact negative gradients of these terms times length_per_nm (kJ/mol/nm).  The integer triples are one
  * list per handle, built for the longest edge of the boxes of the run or call and sorted by (|n|^2, n_x, n_y, n_z); a box gives
  * the vectors beyond its own k_cut the weight A = 0.  At most 131 072 triples: a longer list is refused with -22 (the message
- * names k_cut).  Not included: TIP4P M-sites (a TIP4P handle evaluates the 3-site parameters it is given), the long-range
- * dispersion correction, and any virial or pressure (with rigid molecules the atomic virial is not the pressure).
+ * names k_cut).  The TIP4P M-site is set by gamd_water_msite (below): until then a handle evaluates the 3-site form of the
+ * parameters it is given.  Not included: the long-range dispersion correction, and any virial or pressure (with rigid molecules
+ * the atomic virial is not the pressure).
  * Sample point, step counter, rows, resume rule and the off state are those of the classical observer above.  A row holds, per
  * box: U_LJ, U_real + U_excl, U_recip, U_self, the different-molecule pairs inside r_cut, the five force-error sums of f against
  * the classical force in the order of gamd_classical_params, the atoms left out of the cosine, and sum_i q_i, which is exactly
@@ -597,6 +600,40 @@ int32_t gamd_water_read(gamd_handle* h, void* stream, int64_t* steps, double* ro
  * boxes need more than 131 072 k-vectors. */
 int32_t gamd_water_eval(gamd_handle* h, const float* pos_dev, const uint8_t* species_dev, const float* box, float length_per_nm,
                         double* f_out_dev, double* rows, void* stream);
+/* The TIP4P M-site: the reference's third ground-truth generator is WaterBox(model='tip4pew')
+ * (dataset/generate_tip4p_data.py), and it drops the M-site before the network (train_utils.py:58-59) — so do handles,
+ * integrators and SETTLE here, which see O,H,H.  The site lives inside the potential: w_h > 0 moves the negative charge of every
+ * molecule from the oxygen onto a virtual site M (OpenMM's ThreeParticleAverageSite with weights 1 - 2 w_h, w_h, w_h;
+ * TIP4P-Ew: w_h = 0.106676721).  Per molecule, atoms in the caller's order O,H,H (molecule = index / 3, the oxygen first):
+ *     d_k  = H_k - O per component as d - L rint(d / L)      (the atoms may be in any periodic image)
+ *     M    = O' + w_h (d_1 + d_2), in double from the fp32 positions widened, O' = O - L floor(O / L)
+ * The CHARGE SITES of a molecule are M (q = -2 q_H), H1 and H2 (q_H, wrapped into [0, L) like O'); the LENNARD-JONES SITE is O.
+ * Every Coulomb term of the formulas above is taken on charge-site positions: U_real over different-molecule site pairs with
+ * site distance r^2 < r_cut^2, U_excl over the three same-molecule site pairs M-H1, M-H2, H1-H2, S(k) and U_recip over the
+ * sites; U_self is unchanged (sum q^2 is).  U_LJ is taken on O-O distances with a cutoff test of its own on the O-O distance:
+ * a pair of molecules can be inside for one term and outside for the other.  With F_s the complete force on a charge site
+ * (pair slices added in order from 0, plus the k term) and F_LJ the Lennard-Jones force, per component and in this order
+ *     F_O  = F_LJ(O) + (1 - 2 w_h) F_M
+ *     F_Hk = F_s(Hk) + w_h F_M
+ * and then times length_per_nm: the exact negative gradient with respect to the three real atoms.  The GAMD_WATER_ROW layout is
+ * unchanged; its pair entry counts the different-molecule CHARGE-SITE pairs inside r_cut, and sum q is still exactly 0.0.
+ * The M-site is a property of the potential, not a force source: gamd_water_eval, the observer inside gamd_md_run /
+ * gamd_md_run_nhc and a GAMD_FORCE_WATER_CLASSICAL run all follow the weight in force.  w_h = 0 restores the 3-site potential,
+ * served by the 3-site kernels bit for bit; the weight holds across later gamd_water_configure calls until it is changed.
+ * With w_h != 0 the observer is eight launches (a site prepass, the Coulomb pair pass, the O-O Lennard-Jones pass, charge
+ * density, S(k), per-atom k sums, the per-atom pass, the final row) and the force source seven behind the neighbour stage (its
+ * pair passes are the observer's: energies are computed and not read); f is bit for bit the fp32 rounding of gamd_water_eval's forces, and must hold that on entry.
+ * gamd_water_minimize with w_h != 0 returns -22 (the message names the M-site) before anything is enqueued: there is no 4-site
+ * rigid minimiser.  Start recipe: gamd_water_minimize with w_h = 0, gamd_water_msite(h, w_h), gamd_water_eval on the minimised
+ * x, its forces rounded to fp32 as f on entry of the run.
+ * -22, with a message naming the reason: a null handle, a GAMD_KIND_LJ handle, no accepted gamd_water_configure, a pending
+ * run, w_h not finite, negative or >= 0.5.  -12 when the extra work buffers cannot be allocated: they are ensured here or at
+ * run entry, never inside a run.  Device memory added while w_h != 0: 24 B per atom (the sites) and 32 B per molecule and pair
+ * slice (the oxygen's Lennard-Jones force and energy, apart from the site force).
+ * Not built: PME, the long-range dispersion correction, a virial, the 4-site minimiser.  The TIP4P-Ew parameters the Python
+ * package offers (q_H = 0.52422 e, sigma_O = 3.16435 Angstrom, epsilon_O = 0.680946 kJ/mol, w_h = 0.106676721) were written
+ * down from memory and are UNVERIFIED against OpenMM's tip4pew.xml; no parity with OpenMM is claimed. */
+int32_t gamd_water_msite(gamd_handle* h, double w_h);
 
 /* Energy minimiser: every reference driver relaxes its start in front of the first step (minimizeEnergy(tolerance = 1 kJ/mol),
  * dataset/generate_lj_data.py:83; minimizeEnergy(1e-6), LJ/test_script/test_langevin.py:84, test_nosehoover.py:88).

@@ -2,6 +2,7 @@
 """What a sample of the water classical observer costs: the per-step device times of sampled and unsampled steps of ONE run on ONE handle.
 
     python tools/water_classical_cost.py [--steps 200] [--interval 10] [--rounds 3] [--ewald-tol 1e-10] [--workloads c3 w774] [--plain]
+                                           [--m-site W]
 
 On the C3 workload (1 390 rigid TIP3P molecules = 4 170 atoms) and the 774-atom box (258 molecules), in skin mode as bench.py
 runs the water workloads, per-step device times come from gamd_timing_read_steps over a warmed run of --steps steps with the
@@ -10,6 +11,7 @@ from the event in front of its first kernel to the event in front of the next st
 second half (and, in skin mode, that second half launched on its own) falls into the sampled step's time.  Printed per workload
 and round: p50 of the unsampled steps, p50 of the sampled steps, their difference (the cost of one sample), and the same run's
 p50 with the observer off on the same handle; then the medians over the rounds.  A record, not a pass/fail bar.
+--m-site W (TIP4P-Ew: 0.106676721) samples the 4-site form of the potential with the package's TIP4PEW parameters instead.
 --plain times the same runs without touching the observer's entry points at all: the tool then also runs in a checkout of a
 commit that does not have them (copy it into that checkout's tools/), which is how the unsampled steps of an armed run are set
 against the parent commit's library on one machine.
@@ -48,11 +50,16 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--ewald-tol", type=float, default=1e-10)
     ap.add_argument("--workloads", nargs="+", default=["c3", "w774"], choices=["c3", "w774"])
+    ap.add_argument("--m-site", type=float, default=0.0, help="the hydrogens' weight of the TIP4P M-site with the TIP4PEW parameters; 0: 3-site water")
     ap.add_argument("--plain", action="store_true", help="observer-off runs only, without calling the observer's entry points")
     args = ap.parse_args()
     if args.interval < 2 or args.steps % args.interval:
         ap.error("--steps must be a multiple of --interval, and --interval at least 2")
     out = {}
+    pot = {}
+    if args.m_site:
+        from gamd_amd.engine import TIP4PEW
+        pot = dict(TIP4PEW, m_site=args.m_site)
     for workload in args.workloads:
         eng, x, v, f, md = _engine(workload)
         eng.md_run(x, v, f, 50, **md)                             # warm-up: allocations, first candidate build, clocks
@@ -61,7 +68,7 @@ def main():
             res = {}
             for name, interval in ((("off", 0),) if args.plain else (("off", 0), ("on", args.interval))):
                 if not args.plain:
-                    eng.water_classical_configure(interval, ewald_tol=args.ewald_tol)
+                    eng.water_classical_configure(interval, ewald_tol=args.ewald_tol, **pot)
                 eng.timing_enable(True)
                 eng.md_run(x, v, f, args.steps, first_step=done, **md)
                 ms = eng.timing_read_steps()

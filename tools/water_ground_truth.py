@@ -5,7 +5,7 @@ such a run costs.
 
     python tools/water_ground_truth.py [--workloads w774 c3] [--steps 200] [--interval 50] [--frames 4] [--dt-fs 2.0]
                                        [--energy-ps 1.0] [--ewald-tol 1e-8] [--minimize-tolerance 10] [--relax-steps 0] [--seed 0]
-                                       [--out DIR]
+                                       [--m-site W] [--out DIR]
 
 For a seeded box of rigid 3-site water (w774: 258 molecules = 774 atoms, the generator's 2 nm box; c3: 1 390 molecules = 4 170
 atoms) on one handle in skin mode, as bench.py runs the water workloads, each workload in a fresh process:
@@ -27,7 +27,12 @@ available: --relax-steps steps of a strongly damped water-classical Langevin run
 0 steps, the default: none), behind the minimiser when both are on.  Everything below starts from the end of step 0.  The
 potential is the plain Ewald sum of
 water_classical_configure, not OpenMM's PME, without long-range dispersion, and its default parameters are UNVERIFIED against
-OpenMM: the files have the generator's layout, not its numbers.  Records, not pass/fail bars."""
+OpenMM: the files have the generator's layout, not its numbers.  Records, not pass/fail bars.
+
+--m-site W (TIP4P-Ew: 0.106676721) runs all of it under the 4-site form of the potential — the reference's third generator,
+dataset/generate_tip4p_data.py — with the package's TIP4PEW charges and Lennard-Jones parameters (UNVERIFIED as well) and the
+weight W: step 0 minimises with the same parameters and the weight 0 (the minimiser is 3-site), then the weight is set and
+every start takes its f from water_classical_forces.  The timings then stand next to those of a run without the option."""
 import argparse
 import json
 import os
@@ -85,17 +90,25 @@ def _step_ms(eng, x0, v0, species, md, source, steps, dt_ps):
     return float(np.percentile(ms, 50)), float(ms.mean())
 
 
-def _energy_series(eng, x0, v0, species, md, dt_ps, total_ps, ewald_tol):
+def _potential(args, minimiser=False):
+    """keyword arguments of water_classical_configure: the 3-site defaults, or TIP4P-Ew with the weight of --m-site"""
+    from gamd_amd.engine import TIP4PEW
+    if not args.m_site:
+        return dict(ewald_tol=args.ewald_tol)
+    return dict(TIP4PEW, m_site=0.0 if minimiser else args.m_site, ewald_tol=args.ewald_tol)
+
+
+def _energy_series(eng, x0, v0, species, md, dt_ps, total_ps, pot):
     import numpy as np
     every = max(1, int(round(0.010 / dt_ps)))
     steps = int(round(total_ps / dt_ps)) // every * every
     x, v, f = _start(eng, x0, v0, species, "water_classical")
     eng.report_configure(every, max_samples=steps // every, rigid_water=True)
-    eng.water_classical_configure(every, max_samples=steps // every, ewald_tol=ewald_tol)
+    eng.water_classical_configure(every, max_samples=steps // every, **pot)
     eng.md_run(x, v, f, steps, dt_ps=dt_ps, gamma_per_ps=0.0, **{**md, "temperature_k": 0.0})
     rep, rd = eng.report_read(), eng.water_classical_read()
     eng.report_configure(0)
-    eng.water_classical_configure(0, ewald_tol=ewald_tol)
+    eng.water_classical_configure(0, **pot)
     assert np.array_equal(rep.steps, rd.steps) and rd.dropped == 0
     e = rd.energy[:, 0] + rep.ke[:, 0]
     slope = float(np.polyfit(dt_ps * rep.steps, e, 1)[0])             # kJ/mol per ps
@@ -107,8 +120,9 @@ def _one(args, w, out_dir):
     dt_ps = 1e-3 * args.dt_fs
     eng, x0, v0, species, md = _engine(w, args.seed)
     n = x0.shape[0]
-    eng.water_classical_configure(0, ewald_tol=args.ewald_tol)
-    res = dict(n=n)
+    pot = _potential(args)
+    eng.water_classical_configure(0, **_potential(args, minimiser=True))
+    res = dict(n=n, m_site=args.m_site)
     # 0. the generator's minimizeEnergy: the lattice minimised on the device ...
     if args.minimize_tolerance > 0:
         x = x0.clone()
@@ -120,16 +134,17 @@ def _one(args, w, out_dir):
         if m.status == 2:
             raise SystemExit(f"{w}: the minimiser failed (the start is not finite)")
         x0 = x
+    eng.water_classical_configure(0, **pot)                                 # the weight, behind the minimiser
     # ... and / or relaxed by a strongly damped driven run
     if args.relax_steps > 0:
         x, v, f = _start(eng, x0, v0, species, "water_classical")
         eng.report_configure(args.relax_steps, max_samples=1, rigid_water=True)
-        eng.water_classical_configure(args.relax_steps, max_samples=1, ewald_tol=args.ewald_tol)
+        eng.water_classical_configure(args.relax_steps, max_samples=1, **pot)
         u0 = float(eng.water_classical_forces(x, species)[1].energy[0, 0])
         eng.md_run(x, v, f, args.relax_steps, dt_ps=1e-3 * args.relax_dt_fs, gamma_per_ps=args.relax_gamma, seed=args.seed, **md)
         rep, rd = eng.report_read(), eng.water_classical_read()
         eng.report_configure(0)
-        eng.water_classical_configure(0, ewald_tol=args.ewald_tol)
+        eng.water_classical_configure(0, **pot)
         res["relax"] = dict(steps=args.relax_steps, dt_fs=args.relax_dt_fs, gamma_per_ps=args.relax_gamma, u0=u0, u=float(rd.energy[-1, 0]),
                             temperature=float(rep.temperature[-1, 0]))
         print(f"{w}: lattice relaxed by {args.relax_steps} Langevin steps of {args.relax_dt_fs:g} fs at gamma {args.relax_gamma:g} / ps: "
@@ -139,7 +154,7 @@ def _one(args, w, out_dir):
     x, v, f = _start(eng, x0, v0, species, "water_classical")
     eng.traj_configure(args.interval, max_frames=args.frames, fields=("x", "v", "f"))
     eng.report_configure(args.interval, max_samples=args.frames, rigid_water=True)
-    eng.water_classical_configure(args.interval, max_samples=args.frames, ewald_tol=args.ewald_tol)
+    eng.water_classical_configure(args.interval, max_samples=args.frames, **pot)
     eng.md_run_nhc(x, v, f, args.frames * args.interval, dt_ps=dt_ps, frequency_per_ps=1.0, **md)
     tr, rep, rd = eng.traj_read(), eng.report_read(), eng.water_classical_read()
     wdir = os.path.join(out_dir, w)
@@ -148,18 +163,18 @@ def _one(args, w, out_dir):
     rd.write_state_data(rep, log, dt_ps)
     eng.traj_configure(0)
     eng.report_configure(0)
-    eng.water_classical_configure(0, ewald_tol=args.ewald_tol)
+    eng.water_classical_configure(0, **pot)
     res["generator"] = dict(frames=len(paths), log=log, pe=[float(e) for e in rd.energy[:, 0]], temperature=[float(t) for t in rep.temperature[:, 0]],
                             pairs=float(rd.pairs[-1, 0]))
     x_end, v_end = x.clone(), v.clone()
     # 2., 3. cost
     for source in ("water_classical", "network"):
         p50, mean = _step_ms(eng, x0, v0, species, md, source, args.steps, dt_ps)
-        res[source] = dict(p50_ms=p50, mean_ms=mean, force_launches=5 if source == "water_classical" else 2 + 2 * LAYERS)
+        res[source] = dict(p50_ms=p50, mean_ms=mean, force_launches=(7 if args.m_site else 5) if source == "water_classical" else 2 + 2 * LAYERS)
     # 4. energy conservation of the driven run, from the generator run's end
-    res["energy"] = [_energy_series(eng, x_end, v_end, species, md, dt, args.energy_ps, args.ewald_tol) for dt in (dt_ps, 0.5 * dt_ps)]
+    res["energy"] = [_energy_series(eng, x_end, v_end, species, md, dt, args.energy_ps, pot) for dt in (dt_ps, 0.5 * dt_ps)]
     eng.close()
-    print(f"\n### {w.upper()} ({n} atoms, {res['generator']['pairs']:.0f} pairs inside r_cut), skin mode, rigid Nose-Hoover chain, "
+    print(f"\n### {w.upper()}{' M-site ' + format(args.m_site, 'g') if args.m_site else ''} ({n} atoms, {res['generator']['pairs']:.0f} pairs inside r_cut), skin mode, rigid Nose-Hoover chain, "
           f"dt {args.dt_fs:g} fs, ewald_tol {args.ewald_tol:g}, {args.steps} timed steps\n")
     print(f"generator: {len(paths)} frames and {log} written; PE {res['generator']['pe']}; T {res['generator']['temperature']}")
     print("\n| force source | p50 ms/step | mean ms/step | launches of the force path per step |")
@@ -190,6 +205,8 @@ def main():
                     help="water-classical Langevin steps at 300 K in front of everything else, behind the minimiser (0: none)")
     ap.add_argument("--relax-dt-fs", type=float, default=1.0)
     ap.add_argument("--relax-gamma", type=float, default=25.0, help="friction of the relaxation run, 1 / ps")
+    ap.add_argument("--m-site", type=float, default=0.0,
+                    help="the hydrogens' weight of the TIP4P M-site (TIP4P-Ew: 0.106676721) with the TIP4PEW parameters; 0: 3-site water")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--out", default=None)
     ap.add_argument("--only", default=None, help=argparse.SUPPRESS)          # one workload, in this process
@@ -201,7 +218,7 @@ def main():
     out = {}
     for w in args.workloads:                                                # a fresh process per workload; this one opens no GPU
         cmd = [sys.executable, os.path.abspath(__file__), "--only", w, "--out", out_dir] + \
-              [a for k in ("steps", "interval", "frames", "dt_fs", "energy_ps", "ewald_tol", "minimize_tolerance", "relax_steps", "relax_dt_fs", "relax_gamma", "seed")
+              [a for k in ("steps", "interval", "frames", "dt_fs", "energy_ps", "ewald_tol", "minimize_tolerance", "relax_steps", "relax_dt_fs", "relax_gamma", "m_site", "seed")
                for a in ("--" + k.replace("_", "-"), str(getattr(args, k)))]
         p = subprocess.run(cmd, capture_output=True, text=True)
         sys.stdout.write(p.stdout.split("RESULT ", 1)[0])
