@@ -6,11 +6,9 @@
 // evaluated, N (N - 1) pair terms per box and sample, in double, from the caller's fp32 positions in the CALLER's atom order (the
 // sorted order depends on the arrival order of the cell-fill atomics).
 //
-//   k_classical_pairs   grid (T * slices, boxes), T = 256-atom row tiles per box: workgroup (I, s) keeps atom t of tile I in
-//                       the registers of thread t and walks the atoms [s * chunk, (s + 1) * chunk) of the box, staged 256 at a
-//                       time in LDS as doubles (every lane of a wave reads the same LDS address).  FULL rows (j != i, both
-//                       i < j and i > j): an atom's force is the sum of its own row, no atomics.  Per atom and slice one
-//                       partial row {Fx, Fy, Fz, e_i, w_i, pairs_i}, summed over j in ascending order from 0.
+//   k_classical_pairs   the Lennard-Jones tile walk (gamd_lj_walk, gamd_passes_dev.h) on the fp32 positions widened, with every
+//                       accumulator: per atom and slice one partial row {Fx, Fy, Fz, e_i, w_i, pairs_i}.  FULL rows: an atom's
+//                       force is the sum of its own row, no atomics.
 //   k_classical_atoms   grid (blocks per box, boxes): per atom, the slices' partial rows added in order from 0, f_cl = F * len;
 //                       with f given, the atom's terms of the five force-error sums; per-thread sums over the thread's atoms
 //                       (fixed assignment), then the fixed tree of k_report_ke (shuffle 32 .. 1, (w0 + w1) + (w2 + w3)).
@@ -25,72 +23,13 @@
 
 #pragma clang fp contract(off)
 
-#include "gamd_potential_dev.h"
+#include "gamd_passes_dev.h"
 
 namespace {
 
-constexpr int CL_TILE = 256;
-
 __global__ void __launch_bounds__(256) k_classical_pairs(ClassicalArgs a) {
     if (a.devflags[DEVFLAG_FROZEN]) return;                 // a frame that will be evaluated again
-    __shared__ double sx[CL_TILE], sy[CL_TILE], sz[CL_TILE];
-    const int tid = threadIdx.x;
-    const int I = (int)(blockIdx.x / (unsigned)a.slices), s = (int)(blockIdx.x % (unsigned)a.slices);
-    const int box = blockIdx.y;
-    const int npb = a.bx.n_boxes > 1 ? a.bx.n_per_box : a.n;
-    const size_t a0 = (size_t)box * (size_t)npb;            // the caller's order is box-major
-    if (I >= a.tiles) return;                               // (uniform; cannot happen with the launcher's grid)
-    const int il = I * CL_TILE + tid;                       // atom of this thread inside its box
-    const bool vi = il < npb;
-    const long long jb = (long long)s * a.chunk;
-    const int je = (int)(jb + a.chunk < (long long)npb ? jb + a.chunk : (long long)npb);
-    const double Lx = gamd_box_edge(a, box, 0), Ly = gamd_box_edge(a, box, 1), Lz = gamd_box_edge(a, box, 2);
-
-    double xi = 0.0, yi = 0.0, zi = 0.0;
-    if (vi) {
-        const float* p = a.x + 3 * (a0 + (size_t)il);
-        xi = (double)p[0]; yi = (double)p[1]; zi = (double)p[2];
-    }
-    double fx = 0.0, fy = 0.0, fz = 0.0, e = 0.0, w = 0.0, cnt = 0.0;
-    for (long long base = jb; base < je; base += CL_TILE) {
-        __syncthreads();                                    // the previous chunk has been read
-        const int nj = (int)(je - base < CL_TILE ? je - base : CL_TILE);
-        if (tid < nj) {
-            const float* p = a.x + 3 * (a0 + (size_t)base + (size_t)tid);
-            sx[tid] = (double)p[0]; sy[tid] = (double)p[1]; sz[tid] = (double)p[2];
-        }
-        __syncthreads();
-        if (!vi) continue;
-        const int self = (int)((long long)il - base);       // this atom's own slot in the chunk, if it is there
-        for (int jj = 0; jj < nj; ++jj) {
-            double dx = xi - sx[jj], dy = yi - sy[jj], dz = zi - sz[jj];
-            dx = dx - Lx * rint(dx / Lx);
-            dy = dy - Ly * rint(dy / Ly);
-            dz = dz - Lz * rint(dz / Lz);
-            const double r2 = (dx * dx + dy * dy) + dz * dz;
-            if (jj == self || !(r2 < a.rc2)) continue;
-            const double ir2 = 1.0 / r2;
-            const double2 lj = gamd_lj_term(a.sig2, a.eps4, a.eps24, a.u0, ir2);
-            double u = lj.x, ru = lj.y;                     // u_LJ - u0 and r u_LJ'(r)
-            if (a.rs >= 0.0) {                              // (the square root only where there is a switch)
-                const double r = sqrt(r2);
-                if (r > a.rs) {
-                    const double2 sw = gamd_lj_switch(a.rs, a.inv_w, r);
-                    ru = ru * sw.x + ((u * sw.y) * r);      // r u'(r), u = (u_LJ - u0) S
-                    u = u * sw.x;
-                }
-            }
-            const double fs = -(ru * ir2);                  // F_ij = -u'(r) d / r = fs d
-            fx += fs * dx; fy += fs * dy; fz += fs * dz;
-            e += u;
-            w += -ru;                                       // d . F_ij = -r u'(r)
-            cnt += 1.0;
-        }
-    }
-    if (vi) {
-        double* out = a.part + (((size_t)box * (size_t)a.slices + (size_t)s) * (size_t)npb + (size_t)il) * CLASSICAL_PART;
-        out[0] = fx; out[1] = fy; out[2] = fz; out[3] = e; out[4] = w; out[5] = cnt;
-    }
+    gamd_lj_walk<CLASSICAL_PART>(a, GamdPosF32{a.x});
 }
 
 __global__ void __launch_bounds__(256) k_classical_atoms(ClassicalArgs a) {
@@ -151,13 +90,11 @@ __global__ void k_classical_final(ClassicalArgs a) {
 }  // namespace
 
 int launch_classical(const ClassicalArgs& a, hipStream_t st) {
-    const int nb = a.bx.n_boxes > 1 ? a.bx.n_boxes : 1, npb = a.bx.n_boxes > 1 ? a.bx.n_per_box : a.n;
-    const long long T = (npb + CL_TILE - 1) / CL_TILE;
-    if (npb < 1 || nb > 65535 || a.tiles != (int)T || a.slices < 1 || a.chunk < 1 || a.blocks < 1 || a.blocks > 65535 || a.slot < 0) return -1;
-    if ((long long)a.slices * a.chunk < npb || T * a.slices > 0x7fffffll) return -1;   // the slices cover a row; grid.x * 256 threads stay below 2^31
+    PassGeom g;
+    if (pass_geometry(a, 1, &g) || a.blocks < 1 || a.blocks > 65535 || a.slot < 0) return -1;
     if (!a.x || !a.part || !a.f_cl || !a.blk || !a.rows || !a.devflags) return -1;
-    hipLaunchKernelGGL(k_classical_pairs, dim3((unsigned)(T * a.slices), nb), dim3(256), 0, st, a); GAMD_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_classical_atoms, dim3(a.blocks, nb), dim3(256), 0, st, a); GAMD_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_classical_final, dim3((nb + 63) / 64), dim3(64), 0, st, a); GAMD_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_classical_pairs, dim3((unsigned)(g.T * a.slices), g.nb), dim3(256), 0, st, a); GAMD_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_classical_atoms, dim3(a.blocks, g.nb), dim3(256), 0, st, a); GAMD_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_classical_final, dim3((g.nb + 63) / 64), dim3(64), 0, st, a); GAMD_CHECK_LAUNCH();
     return 0;
 }

@@ -669,6 +669,31 @@ int launch_water_sk(const WaterArgs& a, hipStream_t st);
 // k_water_final alone (it reads no positions): the row of a.slot from a.blk and a.ublk, for the 4-site passes of water_msite.hip
 int launch_water_final(const WaterArgs& a, hipStream_t st);
 
+// ---- what every launcher of the tiled passes checks (gamd_passes_dev.h) --------------------------------------------------
+// The rows: `unit` atoms at least and a multiple of it per box (1, or 3 for molecules), the box count inside grid.y, T = the
+// 256-atom row tiles as the handle counted them (pass_rows: all a launcher without a pair pass needs); for the pair pass the
+// slices cover a row, and grid.x * 256 threads stay below 2^31.
+struct PassGeom { int nb, npb; long long T; };
+template <typename Args>
+inline int pass_rows(const Args& a, int unit, PassGeom* g) {
+    g->nb = a.bx.n_boxes > 1 ? a.bx.n_boxes : 1; g->npb = a.bx.n_boxes > 1 ? a.bx.n_per_box : a.n;
+    g->T = (g->npb + 255) / 256;
+    return g->npb < unit || g->npb % unit || g->nb > 65535 || a.tiles != (int)g->T ? -1 : 0;
+}
+template <typename Args>
+inline int pass_geometry(const Args& a, int unit, PassGeom* g) {
+    if (pass_rows(a, unit, g) || a.slices < 1 || a.chunk < 1) return -1;
+    if ((long long)a.slices * a.chunk < g->npb || g->T * a.slices > 0x7fffffll) return -1;
+    return 0;
+}
+// ... and the k side of the water passes; `chunked`: the k slices are contiguous kchunk-vector pieces that cover the list
+inline int pass_k_geometry(const WaterArgs& a, long long T, bool chunked) {
+    if (a.n_k < 1 || a.n_k > (1 << 17) || a.kslices < 1 || T * a.kslices > 0x7fffffll) return -1;
+    if (chunked && (a.kchunk < 1 || (long long)a.kslices * a.kchunk < a.n_k)) return -1;
+    if (a.kblocks != (a.n_k + 255) / 256 || a.rho_blocks < 1 || a.rho_blocks > 65535) return -1;
+    return 0;
+}
+
 // ---- water classical force source (water_drive.hip) -------------------------------------------------
 // One force evaluation of a water-source step of an enqueued MD run (gamd_md_force_source, GAMD_FORCE_WATER_CLASSICAL): the pair
 // pass of water_classical.hip (tiles, slices and arithmetic of k_water_pairs; forces only) into a.part, launch_water_recip, then
@@ -705,11 +730,11 @@ enum { MIN_STATE = 4,          // per box and slot: dt, alpha, n_pos, unused
        MIN_ACC = 5,            // per box and block (the first doubles of a CLASSICAL_ROW-strided row of blk): ff, vf, vv, sum u_i, max |F_c|
        MIN_ROW = 8 };          // per box: state, iterations, U and rms at the start, U, rms and max |F_c| at the end, the final dt
 enum { MIN_CONVERGED = 0, MIN_MAX_ITER = 1, MIN_FAILED = 2 };
-struct MinArgs {
-    ClassicalArgs c;
-    double* x64;               // [n][3] positions, length unit, unwrapped
-    double* v64;               // [n][3] FIRE velocities
-    double* f64;               // [n][3] kJ/mol/nm at x64
+// what the two minimisers share: FIRE's buffers, parameters and the position of this pass (gamd_passes_dev.h)
+struct FireArgs {
+    double* x64;               // [n][3] positions, length unit, unwrapped (water: every molecule on the rigid geometry)
+    double* v64;               // [n][3] FIRE velocities (water: projected by the molecule pass)
+    double* f64;               // [n][3] kJ/mol/nm at x64 (water: projected onto the constraint manifold)
     double* state;             // [n_boxes][2][MIN_STATE]: iteration `it` reads slot it & 1 and writes the other
     int* stopped;              // [n_boxes] 0: running, else 1 + MIN_*
     double* rows;              // [n_boxes][MIN_ROW]
@@ -719,11 +744,16 @@ struct MinArgs {
     int last;                  // the pass behind the last iteration: a box still running stops as MIN_MAX_ITER, nothing moves
     long long it;              // position updates enqueued in front of this pass
 };
+struct MinArgs {
+    ClassicalArgs c;
+    FireArgs fire;
+};
 int launch_minimize_init(const MinArgs& m, const float* x, hipStream_t st);
 int launch_minimize_iter(const MinArgs& m, hipStream_t st);
 // x_out = fp32(x64) wrapped (skipped for a box that failed at iteration 0); f_out = f_in for every box that did not fail
 int launch_minimize_store_x(const MinArgs& m, float* x_out, hipStream_t st);
-int launch_minimize_store_f(const MinArgs& m, const float* f_in, float* f_out, hipStream_t st);
+// (either minimiser's: n and bx are the handle's atoms and boxes)
+int launch_minimize_store_f(const FireArgs& m, int n, const BoxRef& bx, const float* f_in, float* f_out, hipStream_t st);
 
 // ---- water energy minimiser (water_minimize.hip) ------------------------------------------------------
 // Rigid-molecule FIRE under the 3-site water potential of water_classical.hip, per box, all state in double (DESIGN.md section
@@ -737,18 +767,8 @@ int launch_minimize_store_f(const MinArgs& m, const float* f_in, float* f_out, h
 enum { WMIN_ACC = 7 };         // per box and block (the first doubles of a WATER_ACC-strided row of blk): ff, vf, vv, sum u_LJ, sum u_coul, sum z^2, max |F_c|
 struct WMinArgs {
     WaterArgs w;
-    double* x64;               // [n][3] positions, length unit, unwrapped, every molecule on the rigid geometry
-    double* v64;               // [n][3] FIRE velocities (projected by the molecule pass)
-    double* f64;               // [n][3] kJ/mol/nm at x64, projected onto the constraint manifold
-    double* state;             // [n_boxes][2][MIN_STATE]
-    int* stopped;              // [n_boxes] 0: running, else 1 + MIN_*
-    double* rows;              // [n_boxes][MIN_ROW]
-    double tol;                // kJ/mol/nm
-    double dt_start, dt_max, f_inc, f_dec, alpha_start, f_alpha, max_step;
+    FireArgs fire;
     double ra, rb, rc;         // the unit-weight canonical triangle: rc = r_hh / 2, t = sqrt(r_oh^2 - rc^2), ra = 2 t / 3, rb = t / 3
-    int n_min;
-    int last;                  // the pass behind the last iteration: a box still running stops as MIN_MAX_ITER, nothing moves
-    long long it;              // position updates enqueued in front of this pass
 };
 int launch_wmin_init(const WMinArgs& m, const float* x, hipStream_t st);
 int launch_wmin_iter(const WMinArgs& m, hipStream_t st);

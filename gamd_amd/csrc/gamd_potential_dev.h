@@ -1,5 +1,5 @@
-// gamd_potential_dev.h — the device terms the kernels of the observers with a potential share (classical.hip,
-// water_classical.hip; DESIGN.md sections 4.9 and 4.10).  Every helper spells out one order of operations: the host computes
+// gamd_potential_dev.h — the device terms the kernels of the two classical potentials share (DESIGN.md sections 4.9 - 4.13; the
+// passes built from them are in gamd_passes_dev.h).  Every helper spells out one order of operations: the host computes
 // u_LJ(r_cut) by gamd_lj_term's (potential_args, observe.hip), and tests/classical_ref.py mirrors them.  Contraction is off from
 // here on, as in the files that include it.
 #pragma once
@@ -41,6 +41,34 @@ __device__ __forceinline__ double2 gamd_lj_switch(double rs, double inv_w, doubl
     const double S = 1.0 - (t2 * t) * ((6.0 * t - 15.0) * t + 10.0);
     const double dS = ((-30.0 * t2) * (tm * tm)) * inv_w;
     return make_double2(S, dS);
+}
+
+// The Lennard-Jones term of one pair in force: (u, r u') = ((u_LJ - u0) S, r d/dr of it) from the potential's constants in `a`
+// (ClassicalArgs or WaterArgs; eps24 is the caller's: a.eps24, or 6.0 * a.eps4 where only 4 epsilon is carried — the same
+// double).  Every pair kernel of either potential calls one of the two spellings, which differ in what the caller has at hand:
+// _r2 takes r^2 and draws the square root only where a switch is configured (the Lennard-Jones walks, k_w4_lj); _r takes r (the
+// water walk has it for the Coulomb term).  By value, like the helpers above.
+__device__ __forceinline__ double2 gamd_lj_switched(double2 lj, double rs, double inv_w, double r) {
+    const double2 sw = gamd_lj_switch(rs, inv_w, r);
+    double u = lj.x, ru = lj.y;
+    ru = ru * sw.x + ((u * sw.y) * r);                      // r u'(r), u = (u_LJ - u0) S.  (r u' first, then u: the values do
+    u = u * sw.x;                                           // not depend on it, k_classical_pairs' inner loop schedule does)
+    return make_double2(u, ru);
+}
+template <typename Args>
+__device__ __forceinline__ double2 gamd_lj_pair_r2(const Args& a, double eps24, double ir2, double r2) {
+    double2 lj = gamd_lj_term(a.sig2, a.eps4, eps24, a.u0, ir2);
+    if (a.rs >= 0.0) {                                      // (the square root only where there is a switch)
+        const double r = sqrt(r2);
+        if (r > a.rs) lj = gamd_lj_switched(lj, a.rs, a.inv_w, r);
+    }
+    return lj;
+}
+template <typename Args>
+__device__ __forceinline__ double2 gamd_lj_pair_r(const Args& a, double eps24, double ir2, double r) {
+    double2 lj = gamd_lj_term(a.sig2, a.eps4, eps24, a.u0, ir2);
+    if (a.rs >= 0.0 && r > a.rs) lj = gamd_lj_switched(lj, a.rs, a.inv_w, r);
+    return lj;
 }
 
 // fractional coordinate of the reciprocal-space kernels (water_classical.hip, water_minimize.hip): the position wrapped into

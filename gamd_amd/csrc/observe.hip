@@ -397,6 +397,13 @@ int water_klist_apply(gamd_handle* h, int n2max, const std::vector<int>& kv) {
     return 0;
 }
 
+// every edge of every box the caller hands in
+int check_box_positive(const gamd_handle* h, const float* box) {
+    for (int k = 0; k < 3 * h->n_boxes; ++k)
+        if (!(box[k] > 0.f)) return fail(-22, "box[%d][%d] = %g is not positive", k / 3, k % 3, (double)box[k]);
+    return 0;
+}
+
 // the minimum image is the nearest image only inside the sphere of half the shortest edge
 int potential_check_box(const gamd_handle* h, const PotentialLog& pl, const char* who, const float* box) {
     for (int k = 0; k < 3 * h->n_boxes; ++k)
@@ -653,8 +660,7 @@ int potential_eval(gamd_handle* h, const float* pos_dev, const uint8_t* species_
     PotentialLog& pl = P::state(h);
     if (!pl.params_set) return fail(-22, "%s_eval needs the parameters of a %s_configure call (interval 0 will do)", P::api, P::api);
     if (h->pending.active) return fail(-22, "an MD run is still enqueued: call gamd_sync_status before %s_eval", P::api);
-    for (int k = 0; k < 3 * h->n_boxes; ++k)
-        if (!(box[k] > 0.f)) return fail(-22, "box[%d][%d] = %g is not positive", k / 3, k % 3, (double)box[k]);
+    if (int r = check_box_positive(h, box)) return r;
     if (int r = P::check_box(h, box, species_dev)) return r;
     DeviceGuard guard(h->dev);
     hipStream_t st = (hipStream_t)stream;
@@ -679,6 +685,98 @@ int potential_eval(gamd_handle* h, const float* pos_dev, const uint8_t* species_
         if (std::isnan(row[P::ROW * b + P::FROZEN_COL]))
             return fail(-1, "%s_eval: the handle is frozen by a neighbour-buffer overflow (call gamd_sync_status)", P::api);
     return 0;
+}
+
+// What a minimiser supplies besides the potential it builds on: its name in the error texts, its argument block (the
+// potential's, FIRE's and what is its own, which its entry point fills), its launchers, the code a frozen handle is refused with,
+// and whether the caller's x64 is a copy behind the run (LJ) or written by its store-x kernel (water).
+struct LjMinimizer {
+    using P = LjPotential;
+    using Args = MinArgs;
+    static constexpr const char* api = "gamd_minimize";
+    enum { FROZEN_CODE = -1, COPY_X64 = 1 };
+    static P::Args& potential(Args& m) { return m.c; }
+    static int init(const Args& m, const float* x, hipStream_t st) { return launch_minimize_init(m, x, st); }
+    static int iter(const Args& m, hipStream_t st) { return launch_minimize_iter(m, st); }
+    static int store_x(const Args& m, float* x, double*, hipStream_t st) { return launch_minimize_store_x(m, x, st); }
+};
+
+struct WaterMinimizer {
+    using P = WaterPotential;
+    using Args = WMinArgs;
+    static constexpr const char* api = "gamd_water_minimize";
+    enum { FROZEN_CODE = -22, COPY_X64 = 0 };
+    static P::Args& potential(Args& m) { return m.w; }
+    static int init(const Args& m, const float* x, hipStream_t st) { return launch_wmin_init(m, x, st); }
+    static int iter(const Args& m, hipStream_t st) { return launch_wmin_iter(m, st); }
+    static int store_x(const Args& m, float* x, double* x64_out, hipStream_t st) { return launch_wmin_store_x(m, x, x64_out, st); }
+};
+
+// The minimiser's run behind the checks that are its entry point's own: the boxes, every allocation, the look at the frozen
+// flag, init, the iterations in chunks of check_every with a look at the gates behind each, the pass behind the last iteration,
+// x, the force source's own kernels on exactly that x, f, the rows.  `m` arrives with what is the minimiser's own filled in.
+template <typename M>
+int minimize_run(gamd_handle* h, typename M::Args m, float* x_dev, const uint8_t* species_dev, const float* box, double len,
+                 float* f_dev, double* x64_dev, const gamd_minimize_params& q, double* rows_host, void* stream) {
+    using P = typename M::P;
+    if (!x_dev || !f_dev || !box) return fail(-22, "null argument");
+    if (int r = check_box_positive(h, box)) return r;
+    if (int r = P::check_box(h, box, species_dev)) return r;
+    PotentialLog& pl = P::state(h);
+    DeviceGuard guard(h->dev);
+    hipStream_t st = (hipStream_t)stream;
+    InitStream init(st);
+    // every allocation in front of the first enqueue
+    if (bufs_ensure_work(P::bufs(h)) || bufs_ensure_work(minimize_bufs(h))) return fail(-12, "%s: allocation failed", M::api);
+    const size_t nb = (size_t)h->n_boxes, n3 = 3 * (size_t)h->n;
+    std::vector<int> stopped(nb, 0);
+    std::vector<double> rows(MIN_ROW * nb, 0.0);
+    HIP_TRY(init_upload(pl.eval_box.p, box, sizeof(float) * 3 * nb));
+    // the force source's kernels return at once on a frozen handle: f would be what the last call left
+    int frozen = 0;
+    HIP_TRY(hipMemcpyAsync(&frozen, h->devflags.as<int>() + DEVFLAG_FROZEN, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (frozen) return fail(M::FROZEN_CODE, "%s: the handle is frozen by a neighbour-buffer overflow (call gamd_sync_status)", M::api);
+    Minimizer& mn = h->obs->mn;
+    typename P::Args& a = M::potential(m);
+    a = P::args(h, len);
+    a.box_edges = pl.eval_box.template as<float>();
+    P::species(a, species_dev);
+    FireArgs& fi = m.fire;
+    fi.x64 = mn.x64.as<double>(); fi.v64 = mn.v64.as<double>(); fi.f64 = mn.f64.as<double>();
+    fi.state = mn.state.as<double>(); fi.stopped = mn.stopped.as<int>(); fi.rows = mn.rows.as<double>();
+    fi.tol = q.tolerance; fi.dt_start = q.dt_start; fi.dt_max = q.dt_max; fi.f_inc = q.f_inc; fi.f_dec = q.f_dec;
+    fi.alpha_start = q.alpha_start; fi.f_alpha = q.f_alpha; fi.max_step = q.max_step; fi.n_min = q.n_min;
+    int r;
+    if ((r = M::init(m, x_dev, st))) return fail(-1, "%s launch failed (%d)", M::api, r);
+    bool all_stopped = false;
+    while (fi.it < q.max_iter && !all_stopped) {
+        const long long chunk = std::min<long long>(q.check_every, q.max_iter - fi.it);
+        for (long long k = 0; k < chunk; ++k, ++fi.it)
+            if ((r = M::iter(m, st))) return fail(-1, "%s launch failed (%d)", M::api, r);
+        HIP_TRY(hipMemcpyAsync(stopped.data(), mn.stopped.p, sizeof(int) * nb, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        all_stopped = std::all_of(stopped.begin(), stopped.end(), [](int s) { return s != 0; });
+    }
+    if (!all_stopped) {                                     // U and rms where max_iter left the boxes that still run
+        fi.last = 1;
+        if ((r = M::iter(m, st))) return fail(-1, "%s launch failed (%d)", M::api, r);
+    }
+    // x (and the water minimiser's x64), then the force source's own kernels on exactly that x
+    if ((r = M::store_x(m, x_dev, x64_dev, st))) return fail(-1, "%s launch failed (%d)", M::api, r);
+    typename P::Args drive = a;
+    drive.x = x_dev;
+    if ((r = P::drive(h, drive, mn.f32.as<float>(), st))) return fail(-1, "%s launch failed (%d)", M::api, r);
+    pl.evaluated = true;
+    if ((r = launch_minimize_store_f(fi, a.n, a.bx, mn.f32.as<float>(), f_dev, st))) return fail(-1, "%s launch failed (%d)", M::api, r);
+    if (M::COPY_X64 && x64_dev) HIP_TRY(hipMemcpyAsync(x64_dev, mn.x64.p, sizeof(double) * n3, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemcpyAsync(rows.data(), mn.rows.p, sizeof(double) * rows.size(), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (int t = check_traps(h)) return t;
+    if (rows_host) std::memcpy(rows_host, rows.data(), sizeof(double) * rows.size());
+    int worst = 0;
+    for (size_t b = 0; b < nb; ++b) worst = std::max(worst, (int)rows[MIN_ROW * b]);
+    return worst;
 }
 
 // one of each +-n with 0 < |n|^2 <= n2max (the one whose first non-zero component is positive), sorted by (|n|^2, nx, ny, nz)
@@ -1031,62 +1129,8 @@ int32_t gamd_minimize(gamd_handle* h, float* x_dev, const float* box, float leng
     Classical& cl = LjPotential::state(h);
     if (!cl.params_set) return fail(-22, "gamd_minimize needs the parameters of a gamd_classical_configure call (interval 0 will do)");
     if (h->pending.active) return fail(-22, "an MD run is still enqueued: call gamd_sync_status before gamd_minimize");
-    if (!x_dev || !f_dev || !box) return fail(-22, "null argument");
-    for (int k = 0; k < 3 * h->n_boxes; ++k)
-        if (!(box[k] > 0.f)) return fail(-22, "box[%d][%d] = %g is not positive", k / 3, k % 3, (double)box[k]);
-    if (int r = LjPotential::check_box(h, box, nullptr)) return r;
-    DeviceGuard guard(h->dev);
-    hipStream_t st = (hipStream_t)stream;
-    InitStream init(st);
-    // every allocation in front of the first enqueue
-    if (bufs_ensure_work(LjPotential::bufs(h)) || bufs_ensure_work(minimize_bufs(h))) return fail(-12, "gamd_minimize: allocation failed");
-    const size_t nb = (size_t)h->n_boxes, n3 = 3 * (size_t)h->n;
-    std::vector<int> stopped(nb, 0);
-    std::vector<double> rows(MIN_ROW * nb, 0.0);
-    HIP_TRY(init_upload(cl.eval_box.p, box, sizeof(float) * 3 * nb));
-    // the force source's kernels return at once on a frozen handle: f would be what the last call left
-    int frozen = 0;
-    HIP_TRY(hipMemcpyAsync(&frozen, h->devflags.as<int>() + DEVFLAG_FROZEN, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (frozen) return fail(-1, "gamd_minimize: the handle is frozen by a neighbour-buffer overflow (call gamd_sync_status)");
-    Minimizer& mn = h->obs->mn;
-    MinArgs m{};
-    m.c = LjPotential::args(h, length_per_nm > 0.f ? (double)length_per_nm : 10.0);
-    m.c.box_edges = cl.eval_box.as<float>();
-    m.x64 = mn.x64.as<double>(); m.v64 = mn.v64.as<double>(); m.f64 = mn.f64.as<double>();
-    m.state = mn.state.as<double>(); m.stopped = mn.stopped.as<int>(); m.rows = mn.rows.as<double>();
-    m.tol = q.tolerance; m.dt_start = q.dt_start; m.dt_max = q.dt_max; m.f_inc = q.f_inc; m.f_dec = q.f_dec;
-    m.alpha_start = q.alpha_start; m.f_alpha = q.f_alpha; m.max_step = q.max_step; m.n_min = q.n_min;
-    int r;
-    if ((r = launch_minimize_init(m, x_dev, st))) return fail(-1, "gamd_minimize launch failed (%d)", r);
-    bool all_stopped = false;
-    while (m.it < q.max_iter && !all_stopped) {
-        const long long chunk = std::min<long long>(q.check_every, q.max_iter - m.it);
-        for (long long k = 0; k < chunk; ++k, ++m.it)
-            if ((r = launch_minimize_iter(m, st))) return fail(-1, "gamd_minimize launch failed (%d)", r);
-        HIP_TRY(hipMemcpyAsync(stopped.data(), mn.stopped.p, sizeof(int) * nb, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        all_stopped = std::all_of(stopped.begin(), stopped.end(), [](int s) { return s != 0; });
-    }
-    if (!all_stopped) {                                     // U and rms where max_iter left the boxes that still run
-        m.last = 1;
-        if ((r = launch_minimize_iter(m, st))) return fail(-1, "gamd_minimize launch failed (%d)", r);
-    }
-    // x, then the force source's own kernels on exactly that x
-    if ((r = launch_minimize_store_x(m, x_dev, st))) return fail(-1, "gamd_minimize launch failed (%d)", r);
-    ClassicalArgs a = m.c;
-    a.x = x_dev;
-    if ((r = launch_classical_drive(a, mn.f32.as<float>(), st))) return fail(-1, "gamd_minimize launch failed (%d)", r);
-    cl.evaluated = true;
-    if ((r = launch_minimize_store_f(m, mn.f32.as<float>(), f_dev, st))) return fail(-1, "gamd_minimize launch failed (%d)", r);
-    if (x64_dev) HIP_TRY(hipMemcpyAsync(x64_dev, mn.x64.p, sizeof(double) * n3, hipMemcpyDeviceToDevice, st));
-    HIP_TRY(hipMemcpyAsync(rows.data(), mn.rows.p, sizeof(double) * rows.size(), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (int t = check_traps(h)) return t;
-    if (rows_host) std::memcpy(rows_host, rows.data(), sizeof(double) * rows.size());
-    int worst = 0;
-    for (size_t b = 0; b < nb; ++b) worst = std::max(worst, (int)rows[MIN_ROW * b]);
-    return worst;
+    return minimize_run<LjMinimizer>(h, MinArgs{}, x_dev, nullptr, box, length_per_nm > 0.f ? (double)length_per_nm : 10.0, f_dev, x64_dev, q,
+                                     rows_host, stream);
 }
 
 int32_t gamd_water_configure(gamd_handle* h, const gamd_water_params* p) {
@@ -1181,71 +1225,11 @@ int32_t gamd_water_minimize(gamd_handle* h, float* x_dev, const uint8_t* species
     if (wc.w_h != 0.0)
         return fail(-22, "gamd_water_minimize: the TIP4P M-site is set (gamd_water_msite, w_h = %.9g) and there is no 4-site rigid minimiser: "
                          "minimise with w_h = 0, set the weight, then take f from gamd_water_eval", wc.w_h);
-    if (!x_dev || !f_dev || !box) return fail(-22, "null argument");
-    for (int k = 0; k < 3 * h->n_boxes; ++k)
-        if (!(box[k] > 0.f)) return fail(-22, "box[%d][%d] = %g is not positive", k / 3, k % 3, (double)box[k]);
-    if (int r = WaterPotential::check_box(h, box, species_dev)) return r;      // species, 2 r_cut, the k-vector list of these boxes
-    DeviceGuard guard(h->dev);
-    hipStream_t st = (hipStream_t)stream;
-    InitStream init(st);
-    // every allocation in front of the first enqueue
-    if (bufs_ensure_work(WaterPotential::bufs(h)) || bufs_ensure_work(minimize_bufs(h))) return fail(-12, "gamd_water_minimize: allocation failed");
-    const size_t nb = (size_t)h->n_boxes;
-    std::vector<int> stopped(nb, 0);
-    std::vector<double> rows(MIN_ROW * nb, 0.0);
-    HIP_TRY(init_upload(wc.eval_box.p, box, sizeof(float) * 3 * nb));
-    // the force source's kernels return at once on a frozen handle: f would be what the last call left
-    int frozen = 0;
-    HIP_TRY(hipMemcpyAsync(&frozen, h->devflags.as<int>() + DEVFLAG_FROZEN, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (frozen) return fail(-22, "gamd_water_minimize: the handle is frozen by a neighbour-buffer overflow (call gamd_sync_status)");
-    Minimizer& mn = h->obs->mn;
     WMinArgs m{};
-    m.w = WaterPotential::args(h, len);
-    m.w.box_edges = wc.eval_box.as<float>();
-    m.w.species = species_dev;
-    m.x64 = mn.x64.as<double>(); m.v64 = mn.v64.as<double>(); m.f64 = mn.f64.as<double>();
-    m.state = mn.state.as<double>(); m.stopped = mn.stopped.as<int>(); m.rows = mn.rows.as<double>();
-    m.tol = q.tolerance; m.dt_start = q.dt_start; m.dt_max = q.dt_max; m.f_inc = q.f_inc; m.f_dec = q.f_dec;
-    m.alpha_start = q.alpha_start; m.f_alpha = q.f_alpha; m.max_step = q.max_step; m.n_min = q.n_min;
     m.rc = 0.5 * r_hh;
     const double t = std::sqrt(r_oh * r_oh - m.rc * m.rc);
     m.ra = (2.0 * t) / 3.0; m.rb = t / 3.0;
-    // the store of f goes through the LJ minimiser's kernel: its gate, rows and geometry are the same
-    MinArgs ms{};
-    ms.c.n = m.w.n; ms.c.bx = m.w.bx; ms.c.box_edges = m.w.box_edges;
-    ms.c.tiles = m.w.tiles; ms.c.slices = m.w.slices; ms.c.chunk = m.w.chunk; ms.c.blocks = m.w.blocks;
-    ms.c.part = m.w.part; ms.c.blk = m.w.blk;
-    ms.x64 = m.x64; ms.v64 = m.v64; ms.f64 = m.f64; ms.state = m.state; ms.stopped = m.stopped; ms.rows = m.rows;
-    int r;
-    if ((r = launch_wmin_init(m, x_dev, st))) return fail(-1, "gamd_water_minimize launch failed (%d)", r);
-    bool all_stopped = false;
-    while (m.it < q.max_iter && !all_stopped) {
-        const long long chunk = std::min<long long>(q.check_every, q.max_iter - m.it);
-        for (long long k = 0; k < chunk; ++k, ++m.it)
-            if ((r = launch_wmin_iter(m, st))) return fail(-1, "gamd_water_minimize launch failed (%d)", r);
-        HIP_TRY(hipMemcpyAsync(stopped.data(), mn.stopped.p, sizeof(int) * nb, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        all_stopped = std::all_of(stopped.begin(), stopped.end(), [](int s) { return s != 0; });
-    }
-    if (!all_stopped) {                                     // U and rms where max_iter left the boxes that still run
-        m.last = 1;
-        if ((r = launch_wmin_iter(m, st))) return fail(-1, "gamd_water_minimize launch failed (%d)", r);
-    }
-    // x (and x64), then the water force source's own kernels on exactly that x
-    if ((r = launch_wmin_store_x(m, x_dev, x64_dev, st))) return fail(-1, "gamd_water_minimize launch failed (%d)", r);
-    WaterArgs a = m.w;
-    a.x = x_dev;
-    if ((r = launch_water_drive(a, mn.f32.as<float>(), st))) return fail(-1, "gamd_water_minimize launch failed (%d)", r);
-    wc.evaluated = true;
-    if ((r = launch_minimize_store_f(ms, mn.f32.as<float>(), f_dev, st))) return fail(-1, "gamd_water_minimize launch failed (%d)", r);
-    HIP_TRY(hipMemcpyAsync(rows.data(), mn.rows.p, sizeof(double) * rows.size(), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (int t2 = check_traps(h)) return t2;
-    if (rows_host) std::memcpy(rows_host, rows.data(), sizeof(double) * rows.size());
-    int worst = 0;
-    for (size_t b = 0; b < nb; ++b) worst = std::max(worst, (int)rows[MIN_ROW * b]);
-    return worst;
+    return minimize_run<WaterMinimizer>(h, m, x_dev, species_dev, box, len, f_dev, x64_dev, q, rows_host, stream);
 }
 
 }  // extern "C"

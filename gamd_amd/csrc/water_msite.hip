@@ -6,17 +6,17 @@
 //   k_w4_sites      the prepass: one thread per atom writes its charge-site position as doubles into `sites` — the oxygen's row
 //                   holds M = O' + w (d_1 + d_2) (water_msite, gamd_potential_dev.h: the one place M is computed), a hydrogen's
 //                   its own position wrapped into [0, L).  Every site is the same double whatever image its atoms are given in.
-//   k_w4_pairs      k_water_pairs' tiling, grid (T * slices, boxes), on the site positions: Coulomb with k_water_pairs'
-//                   operations — a same-molecule pair (M-H1, M-H2, H1-H2) takes the erf branch, a different-molecule pair with
-//                   site r^2 < r_cut^2 the erfc branch and counts.  Per atom and slice the row of k_water_pairs
-//                   {F_site, 0, u_coul, pairs} into `part`.
+//   k_w4_pairs      k_water_pairs' walk (gamd_water_walk, gamd_passes_dev.h: the one body of both) on the site positions
+//                   with the Lennard-Jones term off: a same-molecule pair (M-H1, M-H2, H1-H2) takes the erf branch, a
+//                   different-molecule pair with site r^2 < r_cut^2 the erfc branch and counts.  Per atom and slice the row of
+//                   k_water_pairs {F_site, 0, u_coul, pairs} into `part`.
 //   k_w4_lj         the Lennard-Jones term in a pass of its own over oxygens (with it in the pair kernel that kernel needed 180
 //                   vector registers, over the bar of 168): grid (Tm * slices, boxes), thread t keeps the oxygen of molecule t of
 //                   its tile (atom 3 m, fp32 widened) and walks the oxygens of its slice of molecules, staged 256 at a time;
 //                   k_classical_pairs' term on O-O distances with a cutoff test of its OWN on the O-O distance.  Per molecule
 //                   and slice {F_LJ, u_LJ} into `ljpart`: kept apart from the site force, the two are spread differently.
-//   k_w4_rho        k_water_rho's scheme on the site positions.
-//   k_w4_recip      k_water_recip's scheme on the site positions.
+//   k_w4_rho        k_water_rho's pass (gamd_water_rho) on the site positions.
+//   k_w4_recip      k_water_recip's pass (gamd_water_recip, the same kchunk walk) on the site positions.
 //   k_w4_atoms      k_water_atoms with the redistribution: a site's force F_s = pair slices in order from 0 + (pq kf) k slices in
 //                   order from 0, as k_water_atoms forms it; F_O = F_LJ(O) + w_O F_M, F_Hk = F_s(Hk) + w F_M, then times len.  A
 //                   hydrogen sums its molecule's oxygen row again in the same order (molecules straddle workgroups; the row is
@@ -32,11 +32,9 @@
 
 #pragma clang fp contract(off)
 
-#include "gamd_potential_dev.h"
+#include "gamd_passes_dev.h"
 
 namespace {
-
-constexpr int W4_TILE = 256;
 
 __global__ void __launch_bounds__(256) k_w4_sites(W4Args b) {
     const WaterArgs& a = b.w;
@@ -58,79 +56,8 @@ __global__ void __launch_bounds__(256) k_w4_sites(W4Args b) {
 }
 
 __global__ void __launch_bounds__(256) k_w4_pairs(W4Args b) {
-    const WaterArgs& a = b.w;
-    if (a.devflags[DEVFLAG_FROZEN]) return;                 // a frame that will be evaluated again
-    __shared__ double sx[W4_TILE], sy[W4_TILE], sz[W4_TILE];        // charge sites
-    __shared__ unsigned char so[W4_TILE];
-    const int tid = threadIdx.x;
-    const int I = (int)(blockIdx.x / (unsigned)a.slices), s = (int)(blockIdx.x % (unsigned)a.slices);
-    const int box = blockIdx.y;
-    const int npb = a.bx.n_boxes > 1 ? a.bx.n_per_box : a.n;
-    const size_t a0 = (size_t)box * (size_t)npb;            // the caller's order is box-major
-    if (I >= a.tiles) return;                               // (uniform; cannot happen with the launcher's grid)
-    const int il = I * W4_TILE + tid;                       // atom of this thread inside its box
-    const bool vi = il < npb;
-    const long long jb = (long long)s * a.chunk;
-    const int je = (int)(jb + a.chunk < (long long)npb ? jb + a.chunk : (long long)npb);
-    const double Lx = gamd_box_edge(a, box, 0), Ly = gamd_box_edge(a, box, 1), Lz = gamd_box_edge(a, box, 2);
-
-    double xi = 0.0, yi = 0.0, zi = 0.0;
-    bool oi = false;
-    if (vi) {
-        const double* q = b.sites + 3 * (a0 + (size_t)il);
-        xi = q[0]; yi = q[1]; zi = q[2];
-        oi = a.species[a0 + (size_t)il] != 0;
-    }
-    const double q_h = a.q_h, q_o = -(q_h + q_h);           // -2 q_h, exact
-    const double qi = oi ? q_o : q_h;
-    const int mi = il / 3;                                  // npb is a multiple of 3: molecules do not straddle boxes
-    // the thread's output row, held in vector registers from here on, as in k_water_pairs
-    double* out = a.part + (((size_t)box * (size_t)a.slices + (size_t)s) * (size_t)npb + (size_t)il) * WATER_PART;
-    asm volatile("" : "+v"(out));
-    double fx = 0.0, fy = 0.0, fz = 0.0, ec = 0.0, cnt = 0.0;
-    for (long long base = jb; base < je; base += W4_TILE) {
-        __syncthreads();                                    // the previous chunk has been read
-        const int nj = (int)(je - base < W4_TILE ? je - base : W4_TILE);
-        if (tid < nj) {
-            const size_t j = a0 + (size_t)base + (size_t)tid;
-            const double* q = b.sites + 3 * j;
-            sx[tid] = q[0]; sy[tid] = q[1]; sz[tid] = q[2];
-            so[tid] = a.species[j] != 0 ? 1 : 0;
-        }
-        __syncthreads();
-        if (!vi) continue;
-        const int self = (int)((long long)il - base);       // this atom's own slot in the chunk, if it is there
-        const int mol0 = (int)((long long)mi * 3 - base);   // ... and its molecule's first
-        for (int jj = 0; jj < nj; ++jj) {
-            double dx = xi - sx[jj], dy = yi - sy[jj], dz = zi - sz[jj];
-            dx = dx - Lx * rint(dx / Lx);
-            dy = dy - Ly * rint(dy / Ly);
-            dz = dz - Lz * rint(dz / Lz);
-            const double r2 = (dx * dx + dy * dy) + dz * dz;
-            if (jj == self) continue;
-            const bool same = jj >= mol0 && jj < mol0 + 3;
-            if (!same && !(r2 < a.rc2)) continue;
-            const bool oj = so[jj] != 0;
-            const double qq = a.coul * (qi * (oj ? q_o : q_h));
-            const double r = sqrt(r2);
-            const double ir2 = 1.0 / r2;
-            const double ar = a.alpha * r;
-            const double gs = a.two_a_rpi * exp(-(ar * ar));        // -r d/dr of erfc(alpha r), over r
-            double fs;
-            if (same) {                                     // U_excl: -q_i q_j erf(alpha r) / r
-                const double t = erf(ar) / r;
-                ec += -(qq * t);
-                fs = (qq * (gs - t)) * ir2;
-            } else {                                        // U_real: q_i q_j erfc(alpha r) / r
-                const double t = erfc(ar) / r;
-                ec += qq * t;
-                fs = (qq * (t + gs)) * ir2;
-                cnt += 1.0;
-            }
-            fx += fs * dx; fy += fs * dy; fz += fs * dz;
-        }
-    }
-    if (vi) { out[0] = fx; out[1] = fy; out[2] = fz; out[3] = 0.0; out[4] = ec; out[5] = cnt; }   // u_LJ: k_w4_lj's
+    if (b.w.devflags[DEVFLAG_FROZEN]) return;               // a frame that will be evaluated again
+    gamd_water_walk<WATER_PART, false>(b.w, GamdPosF64{b.sites});       // u_LJ: k_w4_lj's
 }
 
 // the Lennard-Jones pass over oxygens: thread t of workgroup (I, s) keeps the oxygen of molecule I * 256 + t (atom 3 m of the
@@ -138,15 +65,15 @@ __global__ void __launch_bounds__(256) k_w4_pairs(W4Args b) {
 __global__ void __launch_bounds__(256) k_w4_lj(W4Args b) {
     const WaterArgs& a = b.w;
     if (a.devflags[DEVFLAG_FROZEN]) return;
-    __shared__ double sx[W4_TILE], sy[W4_TILE], sz[W4_TILE];
-    __shared__ unsigned char so[W4_TILE];
+    __shared__ double sx[GAMD_PASS_TILE], sy[GAMD_PASS_TILE], sz[GAMD_PASS_TILE];
+    __shared__ unsigned char so[GAMD_PASS_TILE];
     const int tid = threadIdx.x;
     const int I = (int)(blockIdx.x / (unsigned)a.slices), s = (int)(blockIdx.x % (unsigned)a.slices);
     const int box = blockIdx.y;
     const int npb = a.bx.n_boxes > 1 ? a.bx.n_per_box : a.n, nm = npb / 3;
     const size_t a0 = (size_t)box * (size_t)npb;
-    const int ml = I * W4_TILE + tid;                       // molecule of this thread inside its box
-    if (I * W4_TILE >= nm) return;                          // (uniform; cannot happen with the launcher's grid)
+    const int ml = I * GAMD_PASS_TILE + tid;                       // molecule of this thread inside its box
+    if (I * GAMD_PASS_TILE >= nm) return;                          // (uniform; cannot happen with the launcher's grid)
     const bool vi = ml < nm;
     const long long jb = (long long)s * b.mchunk;
     const int je = (int)(jb + b.mchunk < (long long)nm ? jb + b.mchunk : (long long)nm);
@@ -159,9 +86,9 @@ __global__ void __launch_bounds__(256) k_w4_lj(W4Args b) {
         oi = a.species[a0 + 3 * (size_t)ml] != 0;
     }
     double lx = 0.0, ly = 0.0, lz = 0.0, elj = 0.0;
-    for (long long base = jb; base < je; base += W4_TILE) {
+    for (long long base = jb; base < je; base += GAMD_PASS_TILE) {
         __syncthreads();                                    // the previous chunk has been read
-        const int nj = (int)(je - base < W4_TILE ? je - base : W4_TILE);
+        const int nj = (int)(je - base < GAMD_PASS_TILE ? je - base : GAMD_PASS_TILE);
         if (tid < nj) {
             const size_t j = a0 + 3 * ((size_t)base + (size_t)tid);
             const float* p = a.x + 3 * j;
@@ -179,18 +106,9 @@ __global__ void __launch_bounds__(256) k_w4_lj(W4Args b) {
             const double r2 = (dx * dx + dy * dy) + dz * dz;
             if (jj == self || so[jj] == 0 || !(r2 < a.rc2)) continue;  // the cutoff test on the O-O distance
             const double ir2 = 1.0 / r2;
-            const double2 lj = gamd_lj_term(a.sig2, a.eps4, 6.0 * a.eps4, a.u0, ir2);   // 6 (4 epsilon) = 24 epsilon bit for bit
-            double u = lj.x, ru = lj.y;
-            if (a.rs >= 0.0) {
-                const double r = sqrt(r2);
-                if (r > a.rs) {
-                    const double2 sw = gamd_lj_switch(a.rs, a.inv_w, r);
-                    ru = ru * sw.x + ((u * sw.y) * r);
-                    u = u * sw.x;
-                }
-            }
-            elj += u;
-            const double fl = -(ru * ir2);
+            const double2 lj = gamd_lj_pair_r2(a, 6.0 * a.eps4, ir2, r2);               // 6 (4 epsilon) = 24 epsilon bit for bit
+            elj += lj.x;
+            const double fl = -(lj.y * ir2);
             lx += fl * dx; ly += fl * dy; lz += fl * dz;
         }
     }
@@ -201,91 +119,13 @@ __global__ void __launch_bounds__(256) k_w4_lj(W4Args b) {
 }
 
 __global__ void __launch_bounds__(256) k_w4_rho(W4Args b) {
-    const WaterArgs& a = b.w;
-    if (a.devflags[DEVFLAG_FROZEN]) return;
-    __shared__ double sx[W4_TILE], sy[W4_TILE], sz[W4_TILE], sq[W4_TILE];
-    __shared__ double red[4][2][64];                        // [wave][re, im][lane]
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int box = blockIdx.z, npb = a.bx.n_boxes > 1 ? a.bx.n_per_box : a.n, a0 = box * npb, a1 = a0 + npb;
-    const int k = blockIdx.y * 64 + lane;
-    const bool vk = k < a.n_k;
-    const double nx = vk ? (double)a.kvec[3 * (size_t)k] : 0.0, ny = vk ? (double)a.kvec[3 * (size_t)k + 1] : 0.0,
-                 nz = vk ? (double)a.kvec[3 * (size_t)k + 2] : 0.0;
-    const double Lx = gamd_box_edge(a, box, 0), Ly = gamd_box_edge(a, box, 1), Lz = gamd_box_edge(a, box, 2);
-    double re = 0.0, im = 0.0;
-    for (int base = a0 + blockIdx.x * W4_TILE; base < a1; base += gridDim.x * W4_TILE) {
-        __syncthreads();                                    // the previous chunk has been read
-        const int i = base + tid;
-        if (i < a1) {
-            sx[tid] = water_frac(b.sites[3 * (size_t)i], Lx);
-            sy[tid] = water_frac(b.sites[3 * (size_t)i + 1], Ly);
-            sz[tid] = water_frac(b.sites[3 * (size_t)i + 2], Lz);
-            sq[tid] = a.species[i] != 0 ? a.q_o : a.q_h;
-        }
-        __syncthreads();
-        const int cnt = a1 - base < W4_TILE ? a1 - base : W4_TILE;
-        for (int j = w; j < cnt; j += 4) {                  // (wave-uniform: one LDS address per wave)
-            const double ph = (nx * sx[j] + ny * sy[j]) + nz * sz[j];
-            double sn, cs;
-            sincospi(2.0 * ph, &sn, &cs);
-            re += sq[j] * cs; im -= sq[j] * sn;
-        }
-    }
-    red[w][0][lane] = re; red[w][1][lane] = im;
-    __syncthreads();
-    if (w == 0 && vk) {
-        double* out = a.rho_partial + (((size_t)box * a.rho_blocks + blockIdx.x) * (size_t)a.n_k + (size_t)k) * 2;
-        out[0] = (red[0][0][lane] + red[1][0][lane]) + (red[2][0][lane] + red[3][0][lane]);
-        out[1] = (red[0][1][lane] + red[1][1][lane]) + (red[2][1][lane] + red[3][1][lane]);
-    }
+    if (b.w.devflags[DEVFLAG_FROZEN]) return;
+    gamd_water_rho(b.w, GamdPosF64{b.sites});
 }
 
 __global__ void __launch_bounds__(256) k_w4_recip(W4Args b) {
-    const WaterArgs& a = b.w;
-    if (a.devflags[DEVFLAG_FROZEN]) return;
-    __shared__ double kn[3][W4_TILE], ks_re[W4_TILE], ks_im[W4_TILE], ks_a[W4_TILE];
-    const int tid = threadIdx.x;
-    const int I = (int)(blockIdx.x / (unsigned)a.kslices), s = (int)(blockIdx.x % (unsigned)a.kslices);
-    const int box = blockIdx.y;
-    const int npb = a.bx.n_boxes > 1 ? a.bx.n_per_box : a.n;
-    const size_t a0 = (size_t)box * (size_t)npb;
-    if (I >= a.tiles) return;                               // (uniform; cannot happen with the launcher's grid)
-    const int il = I * W4_TILE + tid;
-    const bool vi = il < npb;
-    const long long kb = (long long)s * a.kchunk;
-    const int ke = (int)(kb + a.kchunk < (long long)a.n_k ? kb + a.kchunk : (long long)a.n_k);
-    double six = 0.0, siy = 0.0, siz = 0.0;
-    if (vi) {
-        const double* p = b.sites + 3 * (a0 + (size_t)il);
-        six = water_frac(p[0], gamd_box_edge(a, box, 0));
-        siy = water_frac(p[1], gamd_box_edge(a, box, 1));
-        siz = water_frac(p[2], gamd_box_edge(a, box, 2));
-    }
-    double gx = 0.0, gy = 0.0, gz = 0.0;
-    for (long long base = kb; base < ke; base += W4_TILE) {
-        __syncthreads();                                    // the previous chunk has been read
-        const int nk = (int)(ke - base < W4_TILE ? ke - base : W4_TILE);
-        if (tid < nk) {
-            const size_t k = (size_t)base + (size_t)tid;
-            kn[0][tid] = (double)a.kvec[3 * k]; kn[1][tid] = (double)a.kvec[3 * k + 1]; kn[2][tid] = (double)a.kvec[3 * k + 2];
-            const double* p = a.sk + ((size_t)box * (size_t)a.n_k + k) * 3;
-            ks_re[tid] = p[0]; ks_im[tid] = p[1]; ks_a[tid] = p[2];
-        }
-        __syncthreads();
-        if (!vi) continue;
-        for (int kk = 0; kk < nk; ++kk) {
-            const double nx = kn[0][kk], ny = kn[1][kk], nz = kn[2][kk];
-            const double ph = (nx * six + ny * siy) + nz * siz;
-            double sn, cs;
-            sincospi(2.0 * ph, &sn, &cs);
-            const double wk = ks_a[kk] * (ks_re[kk] * sn + ks_im[kk] * cs);
-            gx += wk * nx; gy += wk * ny; gz += wk * nz;
-        }
-    }
-    if (vi) {
-        double* out = a.rpart + (((size_t)box * (size_t)a.kslices + (size_t)s) * (size_t)npb + (size_t)il) * 3;
-        out[0] = gx; out[1] = gy; out[2] = gz;
-    }
+    if (b.w.devflags[DEVFLAG_FROZEN]) return;
+    gamd_water_recip(b.w, GamdPosF64{b.sites});
 }
 
 // the box's constants of the per-atom passes
@@ -389,18 +229,15 @@ __global__ void __launch_bounds__(256) k_w4_drive(W4Args b, float* __restrict__ 
     f_out[3 * i] = (float)F[0]; f_out[3 * i + 1] = (float)F[1]; f_out[3 * i + 2] = (float)F[2];
 }
 
-// what both launchers check, and the five launches they share: sites, pairs, rho, sk, recip
-int w4_launch_passes(const W4Args& b, hipStream_t st) {
+// what both launchers check, and the five launches they share: sites, pairs, rho, sk, recip; *gp = the rows' geometry
+int w4_launch_passes(const W4Args& b, PassGeom* gp, hipStream_t st) {
     const WaterArgs& a = b.w;
-    const int nb = a.bx.n_boxes > 1 ? a.bx.n_boxes : 1, npb = a.bx.n_boxes > 1 ? a.bx.n_per_box : a.n;
-    const long long T = (npb + W4_TILE - 1) / W4_TILE;
-    if (npb < 3 || npb % 3 || nb > 65535 || a.tiles != (int)T || a.slices < 1 || a.chunk < 1) return -1;
-    if ((long long)a.slices * a.chunk < npb || T * a.slices > 0x7fffffll) return -1;   // the slices cover a row; grid.x * 256 threads stay below 2^31
-    if (a.n_k < 1 || a.n_k > (1 << 17) || a.kslices < 1 || a.kchunk < 1 || (long long)a.kslices * a.kchunk < a.n_k || T * a.kslices > 0x7fffffll) return -1;
-    if (a.kblocks != (a.n_k + 255) / 256 || a.rho_blocks < 1 || a.rho_blocks > 65535) return -1;
+    if (pass_geometry(a, 3, gp) || pass_k_geometry(a, gp->T, true)) return -1;
+    const int nb = gp->nb, npb = gp->npb;
+    const long long T = gp->T;
     if (!a.x || !a.species || !a.kvec || !a.part || !a.rho_partial || !a.sk || !a.ublk || !a.rpart || !a.f_cl || !a.devflags) return -1;
     if (!b.sites || !b.ljpart || !(b.w_h > 0.0) || !(b.w_h < 0.5) || b.mchunk < 1 || (long long)a.slices * b.mchunk < npb / 3) return -1;
-    const long long Tm = (npb / 3 + W4_TILE - 1) / W4_TILE;
+    const long long Tm = (npb / 3 + GAMD_PASS_TILE - 1) / GAMD_PASS_TILE;
     hipLaunchKernelGGL(k_w4_sites, dim3((unsigned)T, nb), dim3(256), 0, st, b); GAMD_CHECK_LAUNCH();
     hipLaunchKernelGGL(k_w4_pairs, dim3((unsigned)(T * a.slices), nb), dim3(256), 0, st, b); GAMD_CHECK_LAUNCH();
     hipLaunchKernelGGL(k_w4_lj, dim3((unsigned)(Tm * a.slices), nb), dim3(256), 0, st, b); GAMD_CHECK_LAUNCH();
@@ -414,18 +251,17 @@ int w4_launch_passes(const W4Args& b, hipStream_t st) {
 
 int launch_w4_classical(const W4Args& b, hipStream_t st) {
     const WaterArgs& a = b.w;
-    const int nb = a.bx.n_boxes > 1 ? a.bx.n_boxes : 1;
+    PassGeom g;
     if (a.blocks < 1 || a.blocks > 65535 || a.slot < 0 || !a.blk || !a.rows) return -1;
-    if (int r = w4_launch_passes(b, st)) return r;
-    hipLaunchKernelGGL(k_w4_atoms, dim3(a.blocks, nb), dim3(256), 0, st, b); GAMD_CHECK_LAUNCH();
+    if (int r = w4_launch_passes(b, &g, st)) return r;
+    hipLaunchKernelGGL(k_w4_atoms, dim3(a.blocks, g.nb), dim3(256), 0, st, b); GAMD_CHECK_LAUNCH();
     return launch_water_final(a, st);
 }
 
 int launch_w4_drive(const W4Args& b, float* f_out, hipStream_t st) {
-    const WaterArgs& a = b.w;
-    const int nb = a.bx.n_boxes > 1 ? a.bx.n_boxes : 1, npb = a.bx.n_boxes > 1 ? a.bx.n_per_box : a.n;
+    PassGeom g;
     if (!f_out) return -1;
-    if (int r = w4_launch_passes(b, st)) return r;
-    hipLaunchKernelGGL(k_w4_drive, dim3((unsigned)((npb + W4_TILE - 1) / W4_TILE), nb), dim3(256), 0, st, b, f_out); GAMD_CHECK_LAUNCH();
+    if (int r = w4_launch_passes(b, &g, st)) return r;
+    hipLaunchKernelGGL(k_w4_drive, dim3((unsigned)g.T, g.nb), dim3(256), 0, st, b, f_out); GAMD_CHECK_LAUNCH();
     return 0;
 }

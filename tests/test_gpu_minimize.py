@@ -16,6 +16,8 @@ What is asserted, and why the bars are what they are
   a lattice: every frame of 12 steps carries fp32(classical_forces(x)) bit for bit, and three steps agree with the oracle's
   float64 integrators within that file's bars (1e-5 on x, 1e-4 on v) after the same CPU pre-check (an fp32 emulation against
   the float64 replay), which passes on the minimised start: rel_err x 1.6e-7 / v 2.5e-7 (BAOAB), 8.4e-8 / 1.7e-7 (NHC).
+* energy_start equals the energy classical_forces gives on the same fp32 start, bit for bit (258 atoms; a two-box handle): the
+  minimiser's pair pass and the observer's are one walk, and the sums above it take the same order.  No tolerance is involved.
 * Same bits from two calls, a fresh handle, check_every = 1, 64 and 1000, the checked library, and for each box of a two-box
   handle whose boxes stop at different iterations.
 
@@ -226,6 +228,22 @@ def test_each_box_of_a_two_box_handle_gets_the_bits_it_gets_alone():
         sl = slice(258 * b, 258 * (b + 1))
         assert np.array_equal(_i32(x[sl]), _i32(x1)) and np.array_equal(_i32(f[sl]), _i32(f1)), f"box {b}"
         assert np.array_equal(_i64(x64[sl]), _i64(x641)) and np.array_equal(_i64(res.rows[b]), _i64(r1.rows[0])), f"box {b}"
+
+
+def test_energy_start_is_the_classical_energy_of_the_same_fp32_start_bit_for_bit():
+    """k_min_pairs and k_classical_pairs are one walk (gamd_lj_walk): on the same fp32 start — widened by the one, by k_min_init
+    for the other — the same slices, atom-to-thread assignment, block count and tree, and 0.5 * the in-order block sum give the
+    same double.  258 atoms (two row tiles, the second partial) alone and in a two-box handle with different edges."""
+    (xa, ba), (xb, bb) = _golden_start(), _lattice_start()
+    boxes = np.array([[ba] * 3, [bb] * 3], dtype=np.float32)
+    for x0, box, nb in ((xa, None, 1), (np.concatenate([xa, xb]), boxes, 2)):
+        eng = _seeded_engine(258, float(ba), n_boxes=nb)
+        energy = eng.classical_forces(x0, box=box)[1]
+        res = _minimize(eng, x0, box=box, tolerance=TOL, max_iter=1)[0]
+        eng.close()
+        print(f"{nb} box(es): energy_start {res.energy_start.tolist()}, classical_forces {np.asarray(energy).tolist()}")
+        assert np.isfinite(energy).all() and len(energy) == nb
+        assert np.array_equal(_i64(res.energy_start), _i64(energy))
 
 
 CHILD = r"""

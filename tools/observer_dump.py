@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Everything the five run observers hand back, for five short runs, as one .npz — to set two builds of the library against
-each other bit for bit.
+"""Everything the five run observers, the two classical force sources and the two minimisers hand back, for short runs, as one
+.npz — to set two builds of the library against each other bit for bit.
 
     GAMD_LIB=/path/to/libgamd_hip.so python tools/observer_dump.py out.npz      (one process per library: GAMD_LIB is read
     python tools/observer_dump.py --compare a.npz b.npz                          when gamd_amd._lib is imported)
@@ -17,8 +17,19 @@ each of the others and drops rows.
   e  two boxes of 86 rigid TIP3P molecules (258 atoms: two row tiles, molecule 85 straddles the tile edge at atom 256) with
      different positions and edges, 16 steps, the water classical observer alone at the interval 3; then
      water_classical_forces on the final positions, in bohr
+  f  LJ force source: 258 atoms on the workload's lattice (two row tiles, the second partial), shifted and switched, 12 driven
+     steps with every frame recorded and the classical observer at the interval 5
+  g  water force source, 3-site: e's two boxes, 12 driven rigid steps, every frame recorded, the observer at the interval 3
+  h  the same with the M-site (m_site = 0.1, gamd_water_msite); then water_classical_forces on the final positions
+  i  gamd_minimize: 258 atoms (the lj258_seed0 snapshot), and a two-box handle (the snapshot and the lattice, different edges):
+     40 iterations towards a tolerance they do not reach, with check_every = 1 and 16
+  j  gamd_water_minimize: 86 molecules in a box with three different edges, the same 40 iterations and check_every
+Between them every kernel of classical.hip, drive.hip, minimize.hip, water_classical.hip, water_drive.hip, water_msite.hip and
+water_minimize.hip writes into the dump: a partial tile, a molecule across a tile edge, more than one slice, two boxes, and a
+k-vector list longer than one box needs.
 Written per case: final x, v, f and every attribute of report_read(), traj_read(), structure_read() and
-classical_read(forces=True) / water_classical_read(forces=True); for a and e what the call outside the run returned.
+classical_read(forces=True) / water_classical_read(forces=True); for a, e and h what the call outside the run returned; for i
+and j x, f, x64 and the rows of every call, and the observer's f_cl behind the last.
 """
 import os
 import sys
@@ -77,8 +88,8 @@ def _lj_outside(case, x):
     return call
 
 
-def _water_two_boxes(out):
-    """case e"""
+def _two_water_boxes():
+    """e's system: (case, engine, x, v, f, boxes, species)"""
     import gamd_oracle as orc
     from gamd_amd import workloads as wl
     from gamd_amd.engine import GamdForce
@@ -96,15 +107,85 @@ def _water_two_boxes(out):
     x = torch.from_numpy(np.concatenate([case.pos, other])).float().cuda()
     v = torch.from_numpy(np.concatenate([case.v0, v1])).float().cuda()
     f = eng.forward(x, box=boxes, species=species, denormalize=True).clone()
-    eng.water_classical_configure(3, max_samples=3, **_water_kw(boxes))
-    eng.md_run(x, v, f, 16, gamma_per_ps=25.0, seed=11, box=boxes, **{**case.md, "species": species})
+    return case, eng, x, v, f, boxes, species
 
-    def outside(eng):
+
+def _water_outside(x, species, boxes, **kw):
+    def call(eng):
         length, unit = _bohr()
-        eng.water_classical_configure(0, **_water_kw(boxes, unit))
+        eng.water_classical_configure(0, **_water_kw(boxes, unit), **kw)
         fo, rd = eng.water_classical_forces((x.double() * unit).float(), species, box=boxes * unit, length_per_nm=length)
         return {"eval.forces": fo.cpu().numpy(), **{f"eval.{k}": val for k, val in vars(rd).items() if val is not None}}
-    _collect(out, "e", eng, x, v, f, observers=(), outside=outside)
+    return call
+
+
+def _water_two_boxes(out):
+    """case e"""
+    case, eng, x, v, f, boxes, species = _two_water_boxes()
+    eng.water_classical_configure(3, max_samples=3, **_water_kw(boxes))
+    eng.md_run(x, v, f, 16, gamma_per_ps=25.0, seed=11, box=boxes, **{**case.md, "species": species})
+    _collect(out, "e", eng, x, v, f, observers=(), outside=_water_outside(x, species, boxes))
+
+
+DRIVEN = 12
+
+
+def _lj_source(out):
+    """case f"""
+    from test_gpu_classical_drive import _Lj258
+    case = _Lj258()
+    eng, x, v, f = case.make()
+    eng.classical_configure(5, max_samples=3)            # the defaults: shifted, switched over the last sigma
+    eng.md_force_source("classical")
+    f = eng.classical_forces(x)[0].float().contiguous()
+    eng.traj_configure(1, max_frames=DRIVEN, fields=("x", "v", "f"))
+    case.run(eng, x, v, f, DRIVEN)
+    _collect(out, "f", eng, x, v, f, observers=("traj",))
+
+
+def _water_source(out, name, **kw):
+    """cases g and h"""
+    case, eng, x, v, f, boxes, species = _two_water_boxes()
+    eng.water_classical_configure(3, max_samples=3, **_water_kw(boxes), **kw)
+    eng.md_force_source("water_classical")
+    f = eng.water_classical_forces(x, species, box=boxes)[0].float().contiguous()
+    eng.traj_configure(1, max_frames=DRIVEN, fields=("x", "v", "f"))
+    eng.md_run(x, v, f, DRIVEN, gamma_per_ps=25.0, seed=11, box=boxes, **{**case.md, "species": species})
+    _collect(out, name, eng, x, v, f, observers=("traj",), outside=_water_outside(x, species, boxes, **kw) if kw else None)
+
+
+def _minimise_calls(out, name, eng, call, read):
+    """40 iterations towards a tolerance they do not reach, looked at after every one and after every 16"""
+    for every in (1, 16):
+        res, x = call(tolerance=1e-300, max_iter=40, check_every=every)
+        got = {"x": x, "f": res.f, "x64": res.x64}
+        out.update({f"{name}/every{every}.{k}": val.cpu().numpy() for k, val in got.items()})
+        out[f"{name}/every{every}.rows"] = np.asarray(res.rows)
+        out[f"{name}/every{every}.status"] = np.asarray(res.status)
+    out[f"{name}/f_cl"] = np.asarray(read(forces=True).forces)
+    eng.close()
+
+
+def _minimisers(out):
+    """cases i and j"""
+    from test_gpu_classical_drive import _seeded_engine
+    from test_gpu_minimize import _golden_start, _lattice_start
+    from test_gpu_water_minimize import EDGES, _start, _water_engine
+    (xa, ba), (xb, bb) = _golden_start(), _lattice_start()
+    for name, x0, box, nb in (("i1", xa, None, 1), ("i2", np.concatenate([xa, xb]), np.array([[ba] * 3, [bb] * 3], dtype=np.float32), 2)):
+        eng = _seeded_engine(258, float(ba), n_boxes=nb)
+
+        def call(x0=x0, box=box, eng=eng, **kw):
+            x = torch.from_numpy(np.ascontiguousarray(x0, dtype=np.float32)).cuda()
+            return eng.minimize(x, box=box, return_x64=True, **kw), x
+        _minimise_calls(out, name, eng, call, eng.classical_read)
+    x0, box, species = _start(86, edges=EDGES)
+    eng = _water_engine(86, box, 0.48 * float(np.min(box)))
+
+    def call(**kw):
+        x = torch.from_numpy(x0).cuda()
+        return eng.water_minimize(x, species, box=box, return_x64=True, **kw), x
+    _minimise_calls(out, "j", eng, call, eng.water_classical_read)
 
 
 def dump(path):
@@ -127,6 +208,10 @@ def dump(path):
     _collect(out, "d", eng, x, v, f, {"resumed": eng.sync_status()})
     assert out["d/resumed"] == 1, "case d was meant to outgrow its edge buffer"
     _water_two_boxes(out)
+    _lj_source(out)
+    _water_source(out, "g")
+    _water_source(out, "h", m_site=0.1)
+    _minimisers(out)
     np.savez(path, **out)
     print(f"{path}: {len(out)} entries from {os.environ.get('GAMD_LIB', 'the default library')}")
 
