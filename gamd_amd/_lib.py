@@ -76,6 +76,7 @@ MINIMIZE_ROW = 8                                            # GAMD_MINIMIZE_ROW:
 MINIMIZE_STATE = ("converged", "max_iter", "failed")        # GAMD_MIN_*: a row's state and the call's return value
 CLASSICAL_ROW = 9                                           # GAMD_CLASSICAL_ROW: doubles per box and row of gamd_classical_read
 WATER_ROW = 12                                              # GAMD_WATER_ROW: doubles per box and row of gamd_water_read
+WATER_VIRIAL_ROW = 6                                        # GAMD_WATER_VIRIAL_ROW: doubles per box and row of gamd_water_virial_read
 TRAJ_FIELDS = {"x": 1, "v": 2, "f": 4, "image": 8}          # GAMD_TRAJ_*
 FORCE_SOURCE = {"network": 0, "classical": 1}               # GAMD_FORCE_*
 WATER_FORCE_SOURCE = {"water_classical": 2}                 # GAMD_FORCE_WATER_CLASSICAL (GAMD_KIND_WATER handles)
@@ -127,6 +128,9 @@ SYMBOLS = {
     "gamd_water_reset": (_i32, [_vp]),
     "gamd_water_read": (_i32, [_vp, _vp, _vp, _vp, _i64, C.POINTER(_i64), C.POINTER(_i64), _vp, _i64]),
     "gamd_water_eval": (_i32, [_vp, _vp, _vp, C.POINTER(C.c_float), C.c_float, _vp, _vp, _vp]),
+    "gamd_water_virial": (_i32, [_vp, _i32]),
+    "gamd_water_virial_read": (_i32, [_vp, _vp, _vp, _i64, C.POINTER(_i64)]),
+    "gamd_water_virial_eval": (_i32, [_vp, _vp, _vp, _vp, C.POINTER(C.c_float), C.c_float, C.c_double, C.c_double, _vp, _vp, _vp]),
     "gamd_water_minimize": (_i32, [_vp, _vp, _vp, C.POINTER(C.c_float), C.c_float, C.c_double, C.c_double, _vp, _vp,
                                    C.POINTER(GamdMinimizeParams), _vp, _vp]),
     "gamd_profile": (_i32, [_vp, _vp, _vp, C.POINTER(C.c_float), _vp, _vp, C.c_char_p, C.c_size_t,

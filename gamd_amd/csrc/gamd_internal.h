@@ -720,6 +720,31 @@ int launch_w4_classical(const W4Args& a, hipStream_t st);
 // ... the first six and k_w4_drive: launch_water_drive's f_cl and f_out (the energies of the pair pass are computed and not read)
 int launch_w4_drive(const W4Args& a, float* f_out, hipStream_t st);
 
+// ---- molecular virial of the water classical potential (water_virial.hip) ------------------------------
+// The virial log of gamd_water_virial: launched BEHIND launch_water_classical / launch_w4_classical
+// of the same frame and argument block `w`, whose f_cl (the atoms' total classical forces) and sk ({Re S, Im S, A}) it reads;
+// nothing of theirs is written.  w_h = 0: the 3-site walk on w.x; else the charge-site walk on `sites` and the O-O pass with
+// mchunk molecules per slice.  v (may be null: KE_com = 0) are the frame's velocities, length unit / ps; masses in amu.
+// (No kernel uses a value it read from memory as an address: the checked build has nothing to range-check here.)
+enum { WATER_VIR_PART = 2,     // per atom and pair slice: sum -(r u_LJ'(r)), sum fs_coul r^2 of the atom's row
+       WATER_VIR_ACC = 4,      // per box and block: sum w_LJ, sum w_coul, sum s.F (kJ/mol), sum |P_mol|^2 / M (kJ/mol)
+       WATER_VIR_ROW = 6 };    // per box: W_LJ, W_coul,pair, W_recip, W_intra, KE_com, W_mol = ((W_LJ + W_coul,pair) + W_recip) - W_intra
+struct WVirArgs {
+    WaterArgs w;
+    double w_h;                // the M-site's hydrogen weight, 0 = 3-site
+    int mchunk;                // w_h != 0: molecules per slice of the Lennard-Jones pass, as W4Args
+    const double* sites;       // w_h != 0: [n][3] the charge sites k_w4_sites left
+    const float* v;            // [n][3] or null
+    double mass_o, mass_h;     // amu
+    double* vpart;             // [n_boxes][slices][n_per_box][WATER_VIR_PART]
+    double* vljpart;           // w_h != 0: [n_boxes][slices][n_per_box / 3] the oxygen's sum -(r u_LJ'(r))
+    double* vublk;             // [n_boxes][kblocks]: block sums of A |S|^2 (1 - k^2 / 2 alpha^2)
+    double* vblk;              // [n_boxes][blocks][WATER_VIR_ACC]
+    double* vrows;             // [...][n_boxes][WATER_VIR_ROW], the row of w.slot
+};
+// k_wvir_pairs (or k_wvir_pairs4 and k_wvir_lj4), k_wvir_sk, k_wvir_mols, k_wvir_final
+int launch_water_virial(const WVirArgs& a, hipStream_t st);
+
 // ---- energy minimiser (minimize.hip) ----------------------------------------------------------------
 // FIRE under the Lennard-Jones potential of classical.hip, per box, all state in double.  `c` carries
 // the potential's constants, the geometry of the pair pass and its work buffers (part, blk) as for ClassicalArgs, with

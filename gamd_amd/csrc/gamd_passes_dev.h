@@ -1,6 +1,6 @@
 // gamd_passes_dev.h — the ONE body of every pass the classical potentials' consumers share (DESIGN.md sections 4.9 - 4.13): the
 // Lennard-Jones tile walk (classical.hip, drive.hip), the water tile walk (water_classical.hip, water_drive.hip,
-// water_msite.hip), the rho(k) pass (water_classical.hip, water_minimize.hip, water_msite.hip), the reciprocal force pass
+// water_msite.hip; water_virial.hip with the virial's accumulators), the rho(k) pass (water_classical.hip, water_minimize.hip, water_msite.hip), the reciprocal force pass
 // (water_classical.hip, water_msite.hip), and FIRE's scalar part (minimize.hip, water_minimize.hip).  A kernel is its gate plus
 // one call; what it chooses is a compile-time parameter: where positions come from (a loader below), which accumulators it
 // keeps (NOUT), whether the O-O Lennard-Jones term is in the water walk.  Three kernels of the minimisers measured slower on
@@ -100,9 +100,12 @@ __device__ __forceinline__ void gamd_lj_walk(const ClassicalArgs& a, const Pos p
 // (WATER_PART stride): NOUT = 3 the force source, 6 the observer and the M-site pass, whose `pos` are the charge sites and
 // whose Lennard-Jones term is k_w4_lj's (LJ = false: u_LJ is stored as 0).  (k_wmin_pairs, water_minimize.hip, carries this
 // text written out with {F, u_LJ, u_coul} kept.)
-template <int NOUT, bool LJ, typename Pos>
-__device__ __forceinline__ void gamd_water_walk(const WaterArgs& a, const Pos pos) {
-    static_assert(NOUT == 3 || NOUT == WATER_PART, "forces; + u_LJ, u_coul and pairs");
+// VIR (water_virial.hip) is the walk with the virial's accumulators INSTEAD of the others: the same pairs by the same tests,
+// per atom and slice {w_LJ, w_coul} = {sum -(r u_LJ'(r)), sum fs_coul r^2} into `vpart` (WATER_VIR_PART stride), fs_coul r^2
+// being the bracket the force scalar above is built from, on either branch.  Nothing of a.part is touched.
+template <int NOUT, bool LJ, bool VIR = false, typename Pos>
+__device__ __forceinline__ void gamd_water_walk(const WaterArgs& a, const Pos pos, double* vpart = nullptr) {
+    static_assert(VIR ? NOUT == 0 : (NOUT == 3 || NOUT == WATER_PART), "forces; + u_LJ, u_coul and pairs; or the virial alone");
     __shared__ double sx[GAMD_PASS_TILE], sy[GAMD_PASS_TILE], sz[GAMD_PASS_TILE];
     __shared__ unsigned char so[GAMD_PASS_TILE];
     const int tid = threadIdx.x;
@@ -128,9 +131,11 @@ __device__ __forceinline__ void gamd_water_walk(const WaterArgs& a, const Pos po
     const int mi = il / 3;                                  // npb is a multiple of 3: molecules do not straddle boxes
     // the thread's output row, held in vector registers from here on: left to the compiler, its uniform part stays in scalar
     // registers across the loop, which the potential's constants fill already (four scalar spills otherwise)
-    double* out = a.part + (((size_t)box * (size_t)a.slices + (size_t)s) * (size_t)npb + (size_t)il) * WATER_PART;
+    double* out = VIR ? vpart + (((size_t)box * (size_t)a.slices + (size_t)s) * (size_t)npb + (size_t)il) * WATER_VIR_PART
+                      : a.part + (((size_t)box * (size_t)a.slices + (size_t)s) * (size_t)npb + (size_t)il) * WATER_PART;
     asm volatile("" : "+v"(out));
     double fx = 0.0, fy = 0.0, fz = 0.0, elj = 0.0, ec = 0.0, cnt = 0.0;
+    double wlj = 0.0, wc = 0.0;                             // VIR only
     for (long long base = jb; base < je; base += GAMD_PASS_TILE) {
         __syncthreads();                                    // the previous chunk has been read
         const int nj = (int)(je - base < GAMD_PASS_TILE ? je - base : GAMD_PASS_TILE);
@@ -163,24 +168,28 @@ __device__ __forceinline__ void gamd_water_walk(const WaterArgs& a, const Pos po
                 const double t = erf(ar) / r;
                 if constexpr (NOUT >= 6) ec += -(qq * t);
                 fs = (qq * (gs - t)) * ir2;
+                if constexpr (VIR) wc += qq * (gs - t);
             } else {                                        // U_real: q_i q_j erfc(alpha r) / r
                 const double t = erfc(ar) / r;
                 if constexpr (NOUT >= 6) ec += qq * t;
                 fs = (qq * (t + gs)) * ir2;
+                if constexpr (VIR) wc += qq * (t + gs);
                 if constexpr (NOUT >= 6) cnt += 1.0;
                 if constexpr (LJ) {
                     if (oi && oj) {                         // the Lennard-Jones walk's term
                         const double2 lj = gamd_lj_pair_r(a, 6.0 * a.eps4, ir2, r);     // 6 (4 epsilon) = 24 epsilon bit for bit
                         if constexpr (NOUT >= 6) elj += lj.x;
                         fs = fs + -(lj.y * ir2);
+                        if constexpr (VIR) wlj += -lj.y;    // gamd_lj_walk's w
                     }
                 }
             }
-            fx += fs * dx; fy += fs * dy; fz += fs * dz;
+            if constexpr (!VIR) { fx += fs * dx; fy += fs * dy; fz += fs * dz; }
         }
     }
     if (vi) {
-        out[0] = fx; out[1] = fy; out[2] = fz;
+        if constexpr (VIR) { out[0] = LJ ? wlj : 0.0; out[1] = wc; }
+        else { out[0] = fx; out[1] = fy; out[2] = fz; }
         if constexpr (NOUT >= 6) { out[3] = LJ ? elj : 0.0; out[4] = ec; out[5] = cnt; }
     }
 }

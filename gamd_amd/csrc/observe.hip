@@ -103,6 +103,10 @@ struct WaterClassical : PotentialLog {
     DevBuf kvec, rho_partial, sk, ublk;// ... per k-vector
     double w_h = 0.0;                  // gamd_water_msite: the hydrogens' weight of the TIP4P M-site, 0 = 3-site
     DevBuf sites, ljpart;              // w_h != 0: per atom, and per atom and pair slice (water_msite.hip)
+    bool virial = false;               // gamd_water_virial: every sample also writes its row of vrows (water_virial.hip)
+    bool vwork = false;                // the virial's work buffers are wanted: the log has been on, or gamd_water_virial_eval called
+    DevBuf vrows;                      // the virial log, slot for slot with rows
+    DevBuf vpart, vljpart, vublk, vblk, veval_rows;     // one evaluation, and the eval call's row
 };
 
 // energy minimiser (gamd_minimize, minimize.hip): no observer — no clock, no entry in observer_list() — but a user of the
@@ -203,6 +207,14 @@ ObsBufs water_bufs(gamd_handle* h) {
     const size_t m = wc.w_h != 0.0 ? 1 : 0;
     t.push_back({&wc.sites, m * sizeof(double) * 3 * n, false});
     t.push_back({&wc.ljpart, m * sizeof(double) * W4_LJ * (n / 3) * (size_t)classical_slices(h), false});
+    // the virial log's own: nothing until gamd_water_virial / gamd_water_virial_eval asks
+    const size_t v = wc.vwork ? 1 : 0;
+    t.push_back({&wc.vrows, (wc.virial ? 1 : 0) * sizeof(double) * WATER_VIR_ROW * nb * (size_t)wc.max_samples, true});
+    t.push_back({&wc.vpart, v * sizeof(double) * WATER_VIR_PART * n * (size_t)classical_slices(h), false});
+    t.push_back({&wc.vljpart, v * m * sizeof(double) * (n / 3) * (size_t)classical_slices(h), false});
+    t.push_back({&wc.vublk, v * sizeof(double) * nb * ((K + 255) / 256), false});
+    t.push_back({&wc.vblk, v * sizeof(double) * WATER_VIR_ACC * nb * (size_t)classical_blocks(h), false});
+    t.push_back({&wc.veval_rows, v * sizeof(double) * WATER_VIR_ROW * nb, false});
     return t;
 }
 
@@ -432,6 +444,7 @@ struct LjPotential {
     }
     static void species(Args&, const uint8_t*) {}
     static int launch(const gamd_handle*, const Args& a, hipStream_t st) { return launch_classical(a, st); }
+    static int sample_extra(const gamd_handle*, const Args&, const Particles&, hipStream_t) { return 0; }
     static int check_box(gamd_handle* h, const float* box, const uint8_t*) { return potential_check_box(h, state(h), who, box); }
     // a force source as well (potential_drive): the forces alone, rounded to fp32, into the run's f
     static int drive(const gamd_handle*, const Args& a, float* f_out, hipStream_t st) { return launch_classical_drive(a, f_out, st); }
@@ -472,6 +485,20 @@ struct WaterPotential {
     static int launch(const gamd_handle* h, const Args& a, hipStream_t st) {
         return state(h).w_h != 0.0 ? launch_w4_classical(msite(h, a), st) : launch_water_classical(a, st);
     }
+    // the virial's kernels behind launch() on the same argument block (water_virial.hip): the row of a.slot into `vrows`
+    static int virial(const gamd_handle* h, const Args& a, const float* v, double mass_o, double mass_h, double* vrows, hipStream_t st) {
+        const WaterClassical& wc = state(h);
+        const bool m = wc.w_h != 0.0;
+        return launch_water_virial(WVirArgs{a, wc.w_h, (classical_chunk(h) + 2) / 3, m ? wc.sites.as<double>() : nullptr, v, mass_o, mass_h,
+                                            wc.vpart.as<double>(), m ? wc.vljpart.as<double>() : nullptr, wc.vublk.as<double>(),
+                                            wc.vblk.as<double>(), vrows}, st);
+    }
+    // what a sample of a run adds while the virial log is on: v behind the step's second half, the reporter's masses
+    static int sample_extra(const gamd_handle* h, const Args& a, const Particles& pt, hipStream_t st) {
+        const WaterClassical& wc = state(h);
+        if (!wc.virial) return 0;
+        return virial(h, a, pt.v, pt.mass, pt.mass_h > 0.0 ? pt.mass_h : pt.mass, wc.vrows.as<double>(), st);
+    }
     // species, 2 r_cut <= every edge, a k-vector list of at most 131 072 triples for these boxes (built and uploaded here when
     // the boxes need another one than the list in force)
     static int check_box(gamd_handle* h, const float* box, const uint8_t* species_dev) {
@@ -502,6 +529,7 @@ int potential_sample(gamd_handle* h, long long s) {
     a.g = pl.clock.completed(s);
     a.slot = pl.clock.ordinal(s);
     if (int r = P::launch(h, a, p.st)) return fail(-1, "%s observer launch failed (%d)", P::who, r);
+    if (int r = P::sample_extra(h, a, pending_particles(p), p.st)) return fail(-1, "%s observer launch failed (%d)", P::who, r);
     pl.evaluated = true;
     return 0;
 }
@@ -651,10 +679,11 @@ int potential_read(gamd_handle* h, void* stream, int64_t* steps, double* rows, i
     return 0;
 }
 
-// the kernels of a sample on given positions, outside a run: the forces to f_out_dev (may be null), the row of every box to `row`
-template <typename P>
+// the kernels of a sample on given positions, outside a run: the forces to f_out_dev (may be null), the row of every box to `row`;
+// extra(a, st) enqueues what the caller adds behind them on the same argument block
+template <typename P, typename Extra>
 int potential_eval(gamd_handle* h, const float* pos_dev, const uint8_t* species_dev, const float* box, float length_per_nm,
-                   double* f_out_dev, std::vector<double>& row, void* stream) {
+                   double* f_out_dev, std::vector<double>& row, void* stream, Extra extra) {
     if (!h) return fail(-22, "null handle");
     if (!pos_dev || !box) return fail(-22, "null argument");
     PotentialLog& pl = P::state(h);
@@ -675,6 +704,7 @@ int potential_eval(gamd_handle* h, const float* pos_dev, const uint8_t* species_
     a.x = pos_dev; a.f = nullptr; P::species(a, species_dev);
     a.rows = pl.eval_rows.as<double>(); a.steps = nullptr; a.slot = 0; a.g = 0;
     if (int r = P::launch(h, a, st)) return fail(-1, "%s potential launch failed (%d)", P::who, r);
+    if (int r = extra(a, st)) return fail(-1, "%s potential launch failed (%d)", P::who, r);
     pl.evaluated = true;
     if (f_out_dev) HIP_TRY(hipMemcpyAsync(f_out_dev, pl.f_cl.p, sizeof(double) * 3 * (size_t)h->n, hipMemcpyDeviceToDevice, st));
     row = std::vector<double>(P::ROW * nb);
@@ -685,6 +715,13 @@ int potential_eval(gamd_handle* h, const float* pos_dev, const uint8_t* species_
         if (std::isnan(row[P::ROW * b + P::FROZEN_COL]))
             return fail(-1, "%s_eval: the handle is frozen by a neighbour-buffer overflow (call gamd_sync_status)", P::api);
     return 0;
+}
+
+template <typename P>
+int potential_eval(gamd_handle* h, const float* pos_dev, const uint8_t* species_dev, const float* box, float length_per_nm,
+                   double* f_out_dev, std::vector<double>& row, void* stream) {
+    return potential_eval<P>(h, pos_dev, species_dev, box, length_per_nm, f_out_dev, row, stream,
+                             [](const typename P::Args&, hipStream_t) { return 0; });
 }
 
 // What a minimiser supplies besides the potential it builds on: its name in the error texts, its argument block (the
@@ -899,6 +936,7 @@ static_assert(sizeof(gamd_water_params) == 88 && offsetof(gamd_water_params, q_h
               offsetof(gamd_water_params, shift) == 56 && offsetof(gamd_water_params, alpha) == 64 && offsetof(gamd_water_params, coulomb_const) == 80,
               "gamd_water_params layout is part of the C ABI (gamd_amd/_lib.py mirrors it)");
 static_assert(GAMD_WATER_ROW == WATER_ROW, "the row of gamd_water_read is the kernels' row");
+static_assert(GAMD_WATER_VIRIAL_ROW == WATER_VIR_ROW, "the row of gamd_water_virial_read is the kernels' row");
 static_assert(sizeof(gamd_minimize_params) == 88 && offsetof(gamd_minimize_params, max_iter) == 8 && offsetof(gamd_minimize_params, dt_start) == 24 &&
               offsetof(gamd_minimize_params, max_step) == 72 && offsetof(gamd_minimize_params, n_min) == 80,
               "gamd_minimize_params layout is part of the C ABI (gamd_amd/_lib.py mirrors it)");
@@ -1199,6 +1237,80 @@ int32_t gamd_water_eval(gamd_handle* h, const float* pos_dev, const uint8_t* spe
     std::vector<double> row;
     if (int r = potential_eval<WaterPotential>(h, pos_dev, species_dev, box, length_per_nm, f_out_dev, row, stream)) return r;
     if (rows) std::memcpy(rows, row.data(), sizeof(double) * row.size());
+    return 0;
+}
+
+int32_t gamd_water_virial(gamd_handle* h, int32_t on) {
+    if (!h) return fail(-22, "null handle");
+    if (h->cfg.kind != GAMD_KIND_WATER)
+        return fail(-22, "gamd_water_virial: a GAMD_KIND_LJ handle has no molecules (GAMD_KIND_WATER handles only; the row of "
+                         "gamd_classical_read carries the Lennard-Jones virial)");
+    WaterClassical& wc = h->obs->wc;
+    if (!wc.params_set) return fail(-22, "gamd_water_virial needs the parameters of a gamd_water_configure call (interval 0 will do)");
+    if (h->pending.active) return fail(-22, "an MD run is still enqueued: call gamd_sync_status before gamd_water_virial");
+    if (!on) { wc.virial = false; return 0; }               // off: what was logged stays readable
+    const bool before = wc.virial, work_before = wc.vwork;
+    wc.virial = wc.vwork = true;
+    DeviceGuard guard(h->dev);
+    InitStream init(h->init_stream);
+    const size_t want = sizeof(double) * WATER_VIR_ROW * (size_t)h->n_boxes * (size_t)wc.max_samples;
+    if (wc.vrows.bytes != want) wc.vrows.release();
+    if (bufs_ensure_work(water_bufs(h)) || (want && wc.vrows.ensure(want, true))) {
+        wc.virial = before; wc.vwork = work_before;
+        return fail(-12, "gamd_water_virial: allocation failed");
+    }
+    if (wc.vrows.p) {
+        HIP_TRY(hipMemsetAsync(wc.vrows.p, 0, wc.vrows.bytes, tl_init_stream));
+        HIP_TRY(hipStreamSynchronize(tl_init_stream));
+    }
+    return 0;
+}
+
+int32_t gamd_water_virial_read(gamd_handle* h, void* stream, double* rows, int64_t max_rows, int64_t* n_rows) {
+    if (!h) return fail(-22, "null handle");
+    if (max_rows < 0) return fail(-22, "max_rows is negative");
+    if (h->cfg.kind != GAMD_KIND_WATER) return fail(-22, "gamd_water_virial_read: GAMD_KIND_WATER handles only");
+    const WaterClassical& wc = h->obs->wc;
+    if (!wc.vrows.p) return fail(-22, "gamd_water_virial_read: the virial log has not been on (gamd_water_virial) since the rows were allocated");
+    DeviceGuard guard(h->dev);
+    hipStream_t st = (hipStream_t)stream;
+    const long long nb = h->n_boxes;
+    const long long kept = std::min<long long>(wc.clock.taken(wc.steps.p != nullptr), wc.max_samples);
+    const long long n_copy = std::min<long long>(kept, max_rows);
+    if (n_copy > 0 && rows)
+        HIP_TRY(hipMemcpyAsync(rows, wc.vrows.p, sizeof(double) * (size_t)(n_copy * nb * WATER_VIR_ROW), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (int t = check_traps(h)) return t;
+    if (n_rows) *n_rows = kept;
+    return 0;
+}
+
+int32_t gamd_water_virial_eval(gamd_handle* h, const float* pos_dev, const uint8_t* species_dev, const float* vel_dev,
+                               const float* box, float length_per_nm, double mass_o_amu, double mass_h_amu, double* rows,
+                               double* water_rows, void* stream) {
+    if (!h) return fail(-22, "null handle");
+    if (!(mass_o_amu > 0.0) || !(mass_h_amu > 0.0) || !std::isfinite(mass_o_amu) || !std::isfinite(mass_h_amu))
+        return fail(-22, "gamd_water_virial_eval: mass_o_amu = %g, mass_h_amu = %g: a mass is not positive", mass_o_amu, mass_h_amu);
+    if (h->cfg.kind != GAMD_KIND_WATER) return fail(-22, "gamd_water_virial_eval: a GAMD_KIND_LJ handle has no molecules (GAMD_KIND_WATER handles only)");
+    WaterClassical& wc = h->obs->wc;
+    if (h->pending.active) return fail(-22, "an MD run is still enqueued: call gamd_sync_status before gamd_water_virial_eval");
+    wc.vwork = true;                                        // the work buffers are ensured with the potential's (potential_eval)
+    std::vector<double> row;
+    const size_t nv = WATER_VIR_ROW * (size_t)h->n_boxes;
+    int r = potential_eval<WaterPotential>(h, pos_dev, species_dev, box, length_per_nm, nullptr, row, stream,
+                                           [&](const WaterArgs& a, hipStream_t st) {
+        // a frozen handle's kernels return at once (potential_eval answers for that)
+        if (hipMemsetAsync(wc.veval_rows.p, 0xff, sizeof(double) * nv, st) != hipSuccess) return -2;
+        return WaterPotential::virial(h, a, vel_dev, mass_o_amu, mass_h_amu, wc.veval_rows.as<double>(), st);
+    });
+    if (r) return r;
+    if (water_rows) std::memcpy(water_rows, row.data(), sizeof(double) * row.size());
+    if (rows) {
+        DeviceGuard guard(h->dev);
+        hipStream_t st = (hipStream_t)stream;
+        HIP_TRY(hipMemcpyAsync(rows, wc.veval_rows.p, sizeof(double) * nv, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
     return 0;
 }
 

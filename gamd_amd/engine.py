@@ -285,6 +285,46 @@ KJ_PER_KCAL = 4.184
 BAR_PER_KJ_MOL_NM3 = 16.6053906717          # 1 kJ/mol/nm^3 = 1e3 / (6.02214076e23 * 1e-27) Pa = 16.6053906717 bar
 
 
+def lj_dispersion_correction(n_sites: int, volume_nm3: float, sigma: float, epsilon: float, r_cut: float,
+                             r_switch: float = 0.0, order: int = 64) -> Tuple[float, float]:
+    """(U_lrc, W_lrc) in kJ/mol: the long-range dispersion correction of ``n_sites`` Lennard-Jones sites at uniform density in
+    ``volume_nm3`` for the switched 12-6 potential the observers evaluate, and its virial W_lrc = 3 U_lrc (U_lrc scales as
+    1 / V, so -dU/dlnV^(1/3) = 3 U).  U_lrc = 2 pi n^2 / V * integral over r >= r_switch of [u_LJ(r) - u_used(r)] r^2 dr:
+    beyond ``r_cut`` u_used = 0 and the integral is the closed form 4 eps (sigma^12 / (9 r_c^9) - sigma^6 / (3 r_c^3)); on the
+    switch interval u_LJ - u_used = u_LJ (1 - S) with S(t) = 1 - t^3 (6 t^2 - 15 t + 10), t = (r - r_s) / (r_c - r_s), taken by
+    Gauss-Legendre quadrature of ``order`` points (a smooth integrand: 64 points are exact to rounding).  ``sigma``,
+    ``r_cut``, ``r_switch`` in nm, ``epsilon`` in kJ/mol; ``r_switch`` = 0 or >= r_cut: no switching.  Host only; it concerns
+    energy and pressure, never forces.  Not defined for a shifted potential (the shift is a constant inside the cutoff, whose
+    'correction' would grow with the volume): the ``pressure`` methods refuse that."""
+    n, vol, sig, eps, rc, rs = float(n_sites), float(volume_nm3), float(sigma), float(epsilon), float(r_cut), float(r_switch)
+    if not (vol > 0.0 and sig > 0.0 and rc > 0.0):
+        raise ValueError("volume_nm3, sigma and r_cut must be positive")
+    s6 = sig ** 6
+    tail = 4.0 * eps * (s6 * s6 / (9.0 * rc ** 9) - s6 / (3.0 * rc ** 3))
+    inner = 0.0
+    if 0.0 < rs < rc:
+        t, w = np.polynomial.legendre.leggauss(int(order))
+        r = 0.5 * (rc - rs) * t + 0.5 * (rc + rs)
+        u = (r - rs) / (rc - rs)
+        one_minus_s = u ** 3 * ((6.0 * u - 15.0) * u + 10.0)
+        s6r = s6 / r ** 6
+        inner = 0.5 * (rc - rs) * float(np.sum(w * (4.0 * eps * (s6r * s6r - s6r)) * one_minus_s * r * r))
+    u_lrc = 2.0 * np.pi * n * n / vol * (tail + inner)
+    return float(u_lrc), float(3.0 * u_lrc)
+
+
+def _dispersion_virial(lj, n_sites: int, vol: np.ndarray) -> np.ndarray:
+    """[B] W_lrc of the potential ``lj`` (what classical_read / water_classical_read attach: sigma, epsilon, r_cut, r_switch in
+    the engine's length unit, shift, length_per_nm) for the volumes ``vol`` [B] in nm^3"""
+    if lj is None:
+        raise ValueError("dispersion=True needs the potential's parameters: read the log through classical_read / water_classical_read")
+    if lj["shift"]:
+        raise ValueError("the long-range dispersion correction is not defined for a shifted potential (shift=True)")
+    ln = float(lj["length_per_nm"]) or 10.0
+    return np.array([lj_dispersion_correction(n_sites, v, lj["sigma"] / ln, lj["epsilon"], lj["r_cut"] / ln, lj["r_switch"] / ln)[1]
+                     for v in vol], dtype=np.float64)
+
+
 class RunClassical:
     """What the classical observer logged (GamdForce.classical_read).  Host-only: plain arrays in, plain arrays out.
 
@@ -319,12 +359,19 @@ class RunClassical:
             rel = np.where(self.sum_norm_cl > 0, mae / (self.sum_norm_cl / n), np.nan)
         return {"mae": float(unit) * mae, "rmse": float(unit) * np.sqrt(self.sum_sq / (3.0 * n)), "cosine": cos, "relative_mae": rel}
 
-    def pressure(self, ke, volumes) -> np.ndarray:
+    lj = None          # the potential's parameters, attached by the engine's read calls (``dispersion`` needs them)
+
+    def pressure(self, ke, volumes, dispersion: bool = False) -> np.ndarray:
         """[S, B] virial pressure in bar: (2 KE + W) / (3 V) with KE [S, B] in kJ/mol (RunReport.ke of the same samples),
-        ``volumes`` scalar or [B] in nm^3; 1 kJ/mol/nm^3 = 16.6053906717 bar.  No long-range correction."""
+        ``volumes`` scalar or [B] in nm^3; 1 kJ/mol/nm^3 = 16.6053906717 bar.  ``dispersion``: add W_lrc / (3 V), the
+        long-range dispersion correction of ``lj_dispersion_correction`` for n_atoms sites (ValueError for a shifted
+        potential); off by default, and then no long-range correction is applied."""
         ke = np.asarray(ke, dtype=np.float64).reshape(self.virial.shape)
         vol = np.broadcast_to(np.asarray(volumes, dtype=np.float64).reshape(-1), (self.virial.shape[1],))
-        return BAR_PER_KJ_MOL_NM3 * (2.0 * ke + self.virial) / (3.0 * vol[None, :])
+        p = BAR_PER_KJ_MOL_NM3 * (2.0 * ke + self.virial) / (3.0 * vol[None, :])
+        if dispersion:
+            p = p + BAR_PER_KJ_MOL_NM3 * _dispersion_virial(self.lj, self.n_atoms, vol)[None, :] / (3.0 * vol[None, :])
+        return p
 
     def write_state_data(self, report: "RunReport", path, dt_ps: float, separator: str = "\t",
                          driver_step_convention: bool = False, box: int = 0) -> None:
@@ -362,18 +409,48 @@ class RunWaterClassical(RunClassical):
     Ewald sum of the different-molecule pairs inside r_cut plus the same-molecule erf correction), u_recip, u_self, pairs
     (different-molecule pairs inside r_cut), the force-error sums and ``excluded`` of RunClassical, and sum_q, the sum of the
     charges in e: exactly 0.0 unless the species vector is not one O and two H per molecule.  ``energy`` is the sum of the four
-    Coulomb terms plus u_lj, added as ((u_real + u_recip) + u_self) + u_lj.  No virial and no pressure: with rigid
-    molecules the atomic virial is not the pressure.  ``force_errors`` and ``write_state_data`` are RunClassical's."""
+    Coulomb terms plus u_lj, added as ((u_real + u_recip) + u_self) + u_lj.  The rows hold no virial: with rigid molecules
+    the atomic virial is not the pressure.  ``force_errors`` and ``write_state_data`` are RunClassical's.
+
+    With the virial log armed (``water_classical_configure(..., virial=True)``) ``virial_rows`` [S, B, 6] come with the rows,
+    slot for slot: ``virial_terms`` = dict of w_lj, w_coul (the pair terms, real space and exclusion), w_recip, w_intra
+    (sum over molecules of s_a . F_a about the centre of mass), each [S, B] in kJ/mol; ``ke_com`` [S, B] the kinetic energy
+    of the molecules' centres of mass; ``virial`` [S, B] the molecular virial W_mol = w_lj + w_coul + w_recip - w_intra as the
+    device added it.  Without them the three are None."""
 
     COLUMNS = ("u_lj", "u_real", "u_recip", "u_self", "pairs", "sum_abs", "sum_sq", "sum_cos", "sum_norm_cl", "sum_norm",
                "excluded", "sum_q")
+    VIRIAL_COLUMNS = ("w_lj", "w_coul", "w_recip", "w_intra", "ke_com", "w_mol")
 
-    def __init__(self, steps, rows, n_atoms: int, dropped: int = 0, forces=None):
+    def __init__(self, steps, rows, n_atoms: int, dropped: int = 0, forces=None, virial_rows=None):
         super().__init__(steps, rows, n_atoms, dropped, forces)
         self.energy = ((self.u_real + self.u_recip) + self.u_self) + self.u_lj
+        self.set_virial_rows(virial_rows)
 
-    def pressure(self, ke, volumes):
-        raise NotImplementedError("the water classical observer logs no virial: with rigid molecules the atomic virial is not the pressure")
+    def set_virial_rows(self, virial_rows) -> None:
+        """Attach (or with None drop) the virial rows [S, B, 6] of the same samples."""
+        self.virial = self.virial_terms = self.ke_com = None
+        if virial_rows is not None:
+            vr = np.asarray(virial_rows, dtype=np.float64)
+            if vr.shape != self.u_lj.shape + (len(self.VIRIAL_COLUMNS),):
+                raise ValueError(f"virial_rows must be {self.u_lj.shape + (len(self.VIRIAL_COLUMNS),)}, got {vr.shape}")
+            self.virial_terms = {name: vr[:, :, k].copy() for k, name in enumerate(self.VIRIAL_COLUMNS[:4])}
+            self.ke_com, self.virial = vr[:, :, 4].copy(), vr[:, :, 5].copy()
+
+    def pressure(self, ke, volumes, dispersion: bool = False):
+        """[S, B] pressure of the rigid molecules in bar: (2 KE_com + W_mol) / (3 V), ``volumes`` scalar or [B] in nm^3.
+        ``ke`` None: the logged ``ke_com``; otherwise [S, B] centre-of-mass kinetic energies in kJ/mol (NOT RunReport.ke,
+        which holds the rotations too).  ``dispersion``: add W_lrc / (3 V) for the n_atoms / 3 oxygens (ValueError for a
+        shifted potential).  NotImplementedError without logged virial rows."""
+        if self.virial is None:
+            raise NotImplementedError("the water classical observer logged no virial rows (with rigid molecules the atomic virial is not "
+                                      "the pressure): arm the molecular virial with water_classical_configure(..., virial=True)")
+        ke = self.ke_com if ke is None else np.asarray(ke, dtype=np.float64).reshape(self.virial.shape)
+        vol = np.broadcast_to(np.asarray(volumes, dtype=np.float64).reshape(-1), (self.virial.shape[1],))
+        p = BAR_PER_KJ_MOL_NM3 * (2.0 * ke + self.virial) / (3.0 * vol[None, :])
+        if dispersion:
+            p = p + BAR_PER_KJ_MOL_NM3 * _dispersion_virial(self.lj, self.n_atoms // 3, vol)[None, :] / (3.0 * vol[None, :])
+        return p
 
 
 class MinimizeResult:
@@ -987,6 +1064,8 @@ class GamdForce:
         p = GamdClassicalParams(int(interval), int(max_samples), float(sigma), float(epsilon), r_cut, r_switch, int(bool(shift)), 0)
         check(self._lib.gamd_classical_configure(self._h, C.byref(p)), "gamd_classical_configure")
         self._classical_set = True
+        self._classical_lj = dict(sigma=float(sigma), epsilon=float(epsilon), r_cut=r_cut, r_switch=r_switch, shift=bool(shift),
+                                  length_per_nm=0.0)
 
     def classical_reset(self) -> None:
         """Step count and rows back to zero; parameters and configuration stay."""
@@ -1010,7 +1089,9 @@ class GamdForce:
     def classical_read(self, forces: bool = False) -> "RunClassical":
         """Synchronise and fetch what the classical observer has logged since it was configured or reset; ``forces``: also
         the classical forces of the last sample."""
-        return self._potential_read("gamd_classical_read", _lib.CLASSICAL_ROW, RunClassical, forces)
+        rc = self._potential_read("gamd_classical_read", _lib.CLASSICAL_ROW, RunClassical, forces)
+        rc.lj = getattr(self, "_classical_lj", None)
+        return rc
 
     def classical_forces(self, pos: ArrayLike, box=None, length_per_nm: float = 0.0):
         """The classical potential of the last ``classical_configure`` (with the defaults and interval 0 when there was
@@ -1065,7 +1146,7 @@ class GamdForce:
                                   epsilon_o: float = 0.635968, r_cut: Optional[float] = None, r_switch: float = 0.0,
                                   shift: bool = False, ewald_tol: float = 1e-10, alpha: Optional[float] = None,
                                   k_cut: Optional[float] = None, coulomb_const: float = COULOMB_KJ_NM,
-                                  length_per_nm: float = 0.0, m_site: float = 0.0) -> None:
+                                  length_per_nm: float = 0.0, m_site: float = 0.0, virial: bool = False) -> None:
         """While configured, every ``interval``-th completed step of md_run / md_run_nhc (counted across calls, by a counter
         of its own) evaluates the classical potential of 3-site water in double on the device — O-O Lennard-Jones plus
         point charges q_H and q_O = -2 q_H by a plain Ewald sum (real space inside ``r_cut``, same-molecule exclusion,
@@ -1094,9 +1175,15 @@ class GamdForce:
         3.16435 Angstrom, epsilon_O = 0.680946 kJ/mol, w = 0.106676721) is meant to be OpenMM's ``tip4pew.xml``; these values
         too were written down from memory and are UNVERIFIED.  ``sigma_o`` given explicitly is in the engine's length unit.
 
-        The sum is the limit OpenMM's PME approximates, not PME.  Not built: PME, the long-range dispersion correction, a
-        virial, a 4-site minimiser; no parity with OpenMM is claimed.  Check the parameters against your OpenMM system
-        before comparing energies."""
+        ``virial`` arms the molecular virial log: every sample then also writes W_lj, W_coul, W_recip, W_intra, the
+        centre-of-mass kinetic energy and W_mol per box (``RunWaterClassical.virial``, ``.virial_terms``, ``.ke_com``,
+        ``.pressure``), by kernels of their own behind the observer's, which change nothing the observer, a force source or
+        the trajectory computes.  Every call states it: the default switches the log off.
+
+        The sum is the limit OpenMM's PME approximates, not PME.  Not built: PME, a 4-site minimiser, the pressure tensor,
+        a barostat; the long-range dispersion correction is ``lj_dispersion_correction`` on the host (``pressure(...,
+        dispersion=True)``).  No parity with OpenMM is claimed.  Check the parameters against your OpenMM system before
+        comparing energies."""
         unit = float(np.float32(length_per_nm)) / 10.0 if length_per_nm else 1.0     # the fp32 value the library holds
         sigma_o = 3.15075 * unit if sigma_o is None else float(sigma_o)
         r_cut = 9.5 * unit if r_cut is None else float(r_cut)
@@ -1110,7 +1197,11 @@ class GamdForce:
                             int(bool(shift)), 0, float(alpha), float(k_cut), float(coulomb_const))
         check(self._lib.gamd_water_configure(self._h, C.byref(p)), "gamd_water_configure")
         check(self._lib.gamd_water_msite(self._h, float(m_site)), "gamd_water_msite")
+        check(self._lib.gamd_water_virial(self._h, int(bool(virial))), "gamd_water_virial")
         self._water_set = True
+        self._water_virial = bool(virial)
+        self._water_lj = dict(sigma=sigma_o, epsilon=float(epsilon_o), r_cut=r_cut, r_switch=float(r_switch), shift=bool(shift),
+                              length_per_nm=float(length_per_nm))
 
     def water_classical_reset(self) -> None:
         """Step count and rows back to zero; parameters and configuration stay."""
@@ -1119,7 +1210,52 @@ class GamdForce:
     def water_classical_read(self, forces: bool = False) -> "RunWaterClassical":
         """Synchronise and fetch what the water classical observer has logged since it was configured or reset; ``forces``:
         also the classical forces of the last sample."""
-        return self._potential_read("gamd_water_read", _lib.WATER_ROW, RunWaterClassical, forces)
+        rc = self._potential_read("gamd_water_read", _lib.WATER_ROW, RunWaterClassical, forces)
+        rc.lj = getattr(self, "_water_lj", None)
+        if getattr(self, "_water_virial", False) and rc.steps.shape[0] > 0:
+            vr = np.zeros((rc.steps.shape[0], self.n_boxes, _lib.WATER_VIRIAL_ROW), dtype=np.float64)
+            n_rows = C.c_int64()
+            check(self._lib.gamd_water_virial_read(self._h, self._stream(), vr.ctypes.data_as(C.c_void_p), vr.shape[0],
+                                                   C.byref(n_rows)), "gamd_water_virial_read")
+            rc.set_virial_rows(vr[:n_rows.value])
+        return rc
+
+    def _species_flags(self, species) -> Optional[torch.Tensor]:
+        if species is None:
+            return None
+        s = torch.as_tensor(species).reshape(-1).to(device=self.device)
+        if s.numel() == self.n and self.n_boxes > 1:
+            s = s.repeat(self.n_boxes)
+        if s.numel() != self.n_total:
+            raise ValueError("species must have one entry per atom")
+        return (s != 0).to(torch.uint8).contiguous()
+
+    def water_classical_virial(self, pos: ArrayLike, species, vel: Optional[ArrayLike] = None, box=None, length_per_nm: float = 0.0,
+                               mass_o_amu: float = 15.99943, mass_h_amu: float = 1.007947):
+        """The molecular virial of the water classical potential of the last ``water_classical_configure`` on given positions
+        (and velocities ``vel`` [N, 3] in length unit / ps, fp32 as the library reads them; None: KE_com = 0), outside any
+        run and whether or not the log is armed: a RunWaterClassical of one row whose ``virial``, ``virial_terms`` and
+        ``ke_com`` are filled, so ``.pressure(None, volumes)`` is the pressure of the frame.  Arguments as
+        ``water_classical_forces``; the masses are those a run would be given as mass_amu / mass_h_amu.  Synchronises."""
+        if not getattr(self, "_water_set", False):
+            self.water_classical_configure(0, length_per_nm=length_per_nm)
+        p = self._dev_pos(pos)
+        flags = self._species_flags(species)
+        v = None
+        if vel is not None:
+            v = torch.as_tensor(vel, dtype=torch.float32).to(device=self.device).reshape(-1, 3).contiguous()
+            if v.shape[0] != self.n_total:
+                raise ValueError("vel must have one row per atom")
+        row = np.zeros((1, self.n_boxes, _lib.WATER_ROW), dtype=np.float64)
+        vrow = np.zeros((1, self.n_boxes, _lib.WATER_VIRIAL_ROW), dtype=np.float64)
+        check(self._lib.gamd_water_virial_eval(self._h, C.c_void_p(p.data_ptr()), C.c_void_p(flags.data_ptr()) if flags is not None else None,
+                                               C.c_void_p(v.data_ptr()) if v is not None else None, self._box_arg(box),
+                                               float(length_per_nm), float(mass_o_amu), float(mass_h_amu),
+                                               vrow.ctypes.data_as(C.c_void_p), row.ctypes.data_as(C.c_void_p), self._stream()),
+              "gamd_water_virial_eval")
+        rc = RunWaterClassical([0], row, self.n, virial_rows=vrow)
+        rc.lj = getattr(self, "_water_lj", None)
+        return rc
 
     def water_classical_forces(self, pos: ArrayLike, species, box=None, length_per_nm: float = 0.0):
         """The water classical potential of the last ``water_classical_configure`` (with the defaults and interval 0 when

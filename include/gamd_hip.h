@@ -532,7 +532,7 @@ int32_t gamd_classical_eval(gamd_handle* h, const float* pos_dev, const float* b
  * gamd_water_configure (interval 0 will do).
  * gamd_water_minimize (below) relaxes a start and leaves x and f as this source expects them.  With gamd_water_msite the
  * source drives the 4-site (TIP4P) form of the potential by seven launches; a start is then minimised with w_h = 0 (see there).
- * Not built: PME, long-range dispersion, the 4-site minimiser.  The default parameters of gamd_water_configure remain UNVERIFIED
+ * Not built: PME, the 4-site minimiser, a barostat.  The default parameters of gamd_water_configure remain UNVERIFIED
  * against OpenMM. */
 enum { GAMD_FORCE_NETWORK = 0, GAMD_FORCE_CLASSICAL = 1, GAMD_FORCE_WATER_CLASSICAL = 2 };
 int32_t gamd_md_force_source(gamd_handle* h, int32_t source);
@@ -555,8 +555,8 @@ int32_t gamd_md_force_source(gamd_handle* h, int32_t source);
  * list per handle, built for the longest edge of the boxes of the run or call and sorted by (|n|^2, n_x, n_y, n_z); a box gives
  * the vectors beyond its own k_cut the weight A = 0.  At most 131 072 triples: a longer list is refused with -22 (the message
  * names k_cut).  The TIP4P M-site is set by gamd_water_msite (below): until then a handle evaluates the 3-site form of the
- * parameters it is given.  Not included: the long-range dispersion correction, and any virial or pressure (with rigid molecules
- * the atomic virial is not the pressure).
+ * parameters it is given.  The row holds no virial: with rigid molecules the atomic virial is not the pressure, and the
+ * molecular virial is a log of its own (gamd_water_virial, below).
  * Sample point, step counter, rows, resume rule and the off state are those of the classical observer above.  A row holds, per
  * box: U_LJ, U_real + U_excl, U_recip, U_self, the different-molecule pairs inside r_cut, the five force-error sums of f against
  * the classical force in the order of gamd_classical_params, the atoms left out of the cosine, and sum_i q_i, which is exactly
@@ -630,10 +630,50 @@ int32_t gamd_water_eval(gamd_handle* h, const float* pos_dev, const uint8_t* spe
  * run, w_h not finite, negative or >= 0.5.  -12 when the extra work buffers cannot be allocated: they are ensured here or at
  * run entry, never inside a run.  Device memory added while w_h != 0: 24 B per atom (the sites) and 32 B per molecule and pair
  * slice (the oxygen's Lennard-Jones force and energy, apart from the site force).
- * Not built: PME, the long-range dispersion correction, a virial, the 4-site minimiser.  The TIP4P-Ew parameters the Python
+ * Not built: PME, the 4-site minimiser (the molecular virial is gamd_water_virial below; the long-range dispersion correction
+ * is a host function of the Python package).  The TIP4P-Ew parameters the Python
  * package offers (q_H = 0.52422 e, sigma_O = 3.16435 Angstrom, epsilon_O = 0.680946 kJ/mol, w_h = 0.106676721) were written
  * down from memory and are UNVERIFIED against OpenMM's tip4pew.xml; no parity with OpenMM is claimed. */
 int32_t gamd_water_msite(gamd_handle* h, double w_h);
+
+/* The molecular virial of the water classical potential, and with it the scalar pressure of a box of rigid molecules (with
+ * rigid molecules the atomic virial is not the pressure: the constraint forces carry the rest).  Per box, all sums in double,
+ * every term in kJ/mol:
+ *     W_LJ        = sum over the pairs of U_LJ of -(r u'(r)), u the switched, shifted form in force
+ *     W_coul,pair = sum over the pairs of U_real and of U_excl of fs_coul r^2, fs_coul the Coulomb part of the force scalar
+ *                   F_ij = fs d: C q_i q_j (erfc(alpha r) / r + g) or C q_i q_j (g - erf(alpha r) / r),
+ *                   g = (2 alpha / sqrt(pi)) exp(-alpha^2 r^2); charge sites with an M-site, O-O distances for W_LJ
+ *     W_recip     = (4 pi C / V) sum_k A(k) |S(k)|^2 (1 - k^2 / (2 alpha^2)), k-vectors, A and S(k) those of U_recip
+ *     W_intra     = sum over molecules and their atoms a of s_a . F_a / length_per_nm, F_a the atom's total classical force
+ *                   (kJ/mol/nm, behind the M-site redistribution) and s_a = r_a - R_mol from the minimum-image vectors
+ *                   d_k = H_k - O alone: s_O = -(m_H / M)(d_1 + d_2), s_Hk = d_k + s_O, M = m_O + 2 m_H
+ *     KE_com      = sum over molecules of |m_O v_O + m_H (v_H1 + v_H2)|^2 / (2 M), velocities over length_per_nm (nm/ps), amu
+ *     W_mol       = ((W_LJ + W_coul,pair) + W_recip) - W_intra
+ * and P = (2 KE_com + W_mol) / (3 V) (times 16.6053906717 for bar with V in nm^3).  The pressure tensor, a barostat and the
+ * atomic virial with constraint forces are not built.
+ * gamd_water_virial(h, 1) arms the virial log of the water classical observer, gamd_water_virial(h, 0) switches it off; call it
+ * between runs, behind gamd_water_configure.  While it is on, every sample the observer takes also writes a row
+ * {W_LJ, W_coul,pair, W_recip, W_intra, KE_com, W_mol} per box in the same slot as its GAMD_WATER_ROW row, from the same frame
+ * (x and f_cl of the sample, v behind the step's second half, the run's mass_amu / mass_h_amu: as the run reporter's KE), by
+ * four more launches behind the observer's (five with an M-site) that write nothing the observer or a force source reads: rows
+ * of gamd_water_read, f_cl and the trajectory are bit for bit what they are with the log off, and with it off every entry point
+ * launches exactly what it did.  Same resume rule: a sample evaluated twice writes the same bits twice.  The rows are cleared by
+ * gamd_water_configure (interval > 0) and gamd_water_reset, and by switching the log on.
+ * -22, with a message: a null handle, a GAMD_KIND_LJ handle, no accepted gamd_water_configure, a pending run (the state is left
+ * as it was).  -12 when the buffers cannot be allocated.  Device memory while on: 16 B per atom and pair slice, 8 B per molecule
+ * and pair slice with an M-site, 48 B per box and row. */
+enum { GAMD_WATER_VIRIAL_ROW = 6 };
+int32_t gamd_water_virial(gamd_handle* h, int32_t on);
+/* rows HOST double [max_rows][n_boxes][GAMD_WATER_VIRIAL_ROW], slot for slot the samples of gamd_water_read (whose steps are
+ * theirs); *n_rows = the rows kept.  A slot sampled while the log was off holds zeros.  -22 while the log has never been on. */
+int32_t gamd_water_virial_read(gamd_handle* h, void* stream, double* rows, int64_t max_rows, int64_t* n_rows);
+/* The same kernels outside a run, behind those of gamd_water_eval on the same arguments (armed or not): vel_dev float
+ * [n_boxes * n_atoms][3] DEVICE in length unit / ps, or NULL (KE_com = 0); mass_o_amu, mass_h_amu > 0; rows HOST double
+ * [n_boxes][GAMD_WATER_VIRIAL_ROW]; water_rows HOST double [n_boxes][GAMD_WATER_ROW] or NULL: gamd_water_eval's rows of the same
+ * call.  Refusals as gamd_water_eval, and -22 for a mass that is not positive and finite. */
+int32_t gamd_water_virial_eval(gamd_handle* h, const float* pos_dev, const uint8_t* species_dev, const float* vel_dev,
+                               const float* box, float length_per_nm, double mass_o_amu, double mass_h_amu, double* rows,
+                               double* water_rows, void* stream);
 
 /* Energy minimiser: every reference driver relaxes its start in front of the first step (minimizeEnergy(tolerance = 1 kJ/mol),
  * dataset/generate_lj_data.py:83; minimizeEnergy(1e-6), LJ/test_script/test_langevin.py:84, test_nosehoover.py:88).

@@ -2,7 +2,7 @@
 """What a sample of the water classical observer costs: the per-step device times of sampled and unsampled steps of ONE run on ONE handle.
 
     python tools/water_classical_cost.py [--steps 200] [--interval 10] [--rounds 3] [--ewald-tol 1e-10] [--workloads c3 w774] [--plain]
-                                           [--m-site W]
+                                           [--m-site W] [--virial]
 
 On the C3 workload (1 390 rigid TIP3P molecules = 4 170 atoms) and the 774-atom box (258 molecules), in skin mode as bench.py
 runs the water workloads, per-step device times come from gamd_timing_read_steps over a warmed run of --steps steps with the
@@ -12,6 +12,8 @@ second half (and, in skin mode, that second half launched on its own) falls into
 and round: p50 of the unsampled steps, p50 of the sampled steps, their difference (the cost of one sample), and the same run's
 p50 with the observer off on the same handle; then the medians over the rounds.  A record, not a pass/fail bar.
 --m-site W (TIP4P-Ew: 0.106676721) samples the 4-site form of the potential with the package's TIP4PEW parameters instead.
+--virial adds a third run per round with the molecular virial log armed (gamd_water_virial) and prints what a sampled step costs
+with it against without it.
 --plain times the same runs without touching the observer's entry points at all: the tool then also runs in a checkout of a
 commit that does not have them (copy it into that checkout's tools/), which is how the unsampled steps of an armed run are set
 against the parent commit's library on one machine.
@@ -51,6 +53,7 @@ def main():
     ap.add_argument("--ewald-tol", type=float, default=1e-10)
     ap.add_argument("--workloads", nargs="+", default=["c3", "w774"], choices=["c3", "w774"])
     ap.add_argument("--m-site", type=float, default=0.0, help="the hydrogens' weight of the TIP4P M-site with the TIP4PEW parameters; 0: 3-site water")
+    ap.add_argument("--virial", action="store_true", help="a third run per round with the molecular virial log armed")
     ap.add_argument("--plain", action="store_true", help="observer-off runs only, without calling the observer's entry points")
     args = ap.parse_args()
     if args.interval < 2 or args.steps % args.interval:
@@ -66,16 +69,24 @@ def main():
         done, rows = 50, []
         for rnd in range(args.rounds):
             res = {}
-            for name, interval in ((("off", 0),) if args.plain else (("off", 0), ("on", args.interval))):
+            modes = (("off", 0),) if args.plain else (("off", 0), ("on", args.interval)) + ((("vir", args.interval),) if args.virial else ())
+            for name, interval in modes:
                 if not args.plain:
-                    eng.water_classical_configure(interval, ewald_tol=args.ewald_tol, **pot)
+                    eng.water_classical_configure(interval, ewald_tol=args.ewald_tol, **pot, **(dict(virial=True) if name == "vir" else {}))
                 eng.timing_enable(True)
                 eng.md_run(x, v, f, args.steps, first_step=done, **md)
                 ms = eng.timing_read_steps()
                 eng.timing_enable(False)
                 done += args.steps
                 assert ms.shape[0] == args.steps
-                if interval:
+                if name == "vir":
+                    rd = eng.water_classical_read()
+                    assert rd.steps.shape[0] == args.steps // interval and np.isfinite(rd.virial).all()
+                    sampled = (np.arange(1, args.steps + 1) % interval) == 0
+                    res["vir_unsampled_p50_ms"] = float(np.percentile(ms[~sampled], 50))
+                    res["vir_sampled_p50_ms"] = float(np.percentile(ms[sampled], 50))
+                    res["w_mol_last"] = float(rd.virial[-1, 0])
+                elif interval:
                     rd = eng.water_classical_read()
                     assert rd.steps.shape[0] == args.steps // interval and (rd.sum_q == 0.0).all()
                     sampled = (np.arange(1, args.steps + 1) % interval) == 0      # the clock restarts at every configure
@@ -103,6 +114,10 @@ def main():
                   f"{1e3 * (r['sampled_p50_ms'] - r['unsampled_p50_ms']):.1f} | {1e3 * (r['mean_ms'] - r['off_mean_ms']):+.2f} |")
         print(f"\nmedian over rounds: a sampled step {med('sampled_p50_ms'):.4f} ms against {med('unsampled_p50_ms'):.4f} ms unsampled "
               f"({1e3 * (med('sampled_p50_ms') - med('unsampled_p50_ms')):+.1f} us per sample); observer off {med('off_p50_ms'):.4f} ms")
+        if args.virial:
+            print(f"virial log armed: a sampled step {med('vir_sampled_p50_ms'):.4f} ms ({1e3 * (med('vir_sampled_p50_ms') - med('sampled_p50_ms')):+.1f} us "
+                  f"against the observer alone), unsampled {med('vir_unsampled_p50_ms'):.4f} ms; per round sampled: "
+                  + " ".join(f"{r['vir_sampled_p50_ms']:.4f}" for r in rows) + ", unsampled: " + " ".join(f"{r['vir_unsampled_p50_ms']:.4f}" for r in rows))
     print("RESULT " + json.dumps(out), flush=True)
 
 
