@@ -1,21 +1,20 @@
-// gamd_api.hip — the weight upload, the force evaluation, the MD driver and their extern "C" entry points of include/gamd_hip.h
-// (the handle itself is in gamd_host.h, weight packing in gamd_weights_host.h; the run observers' entry points are in observe.hip).
+// gamd_api.hip — the handle's lifetime, the weight upload, the MD driver and the extern "C" entry points of include/gamd_hip.h
+// (the handle itself is in gamd_host.h, the kernel route in gamd_route_host.h, weight packing in gamd_weights_host.h, the force
+// evaluation in forward.hip; the run observers' entry points are in observe.hip).
 #include "gamd_host.h"
 
 #include <algorithm>
 #include <cmath>
 #include <cstddef>
-#include <cstdlib>
 #include <cstring>
+#include <memory>
+#include <optional>
 
 static_assert(sizeof(gamd_config) == 96 && offsetof(gamd_config, n_boxes) == 88 && offsetof(gamd_config, edge_capacity) == 40,
               "gamd_config layout is part of the C ABI (gamd_amd/_lib.py mirrors it)");
 static_assert(WH_FRAG_FLOATS == GAMD_WFRAG_FLOATS, "gamd_weights_host.h restates the size of a packed 128x128 weight");
 
 namespace {
-
-// batches never take the single-workgroup small-system path of neighbor.hip (k_step_small / k_filter_fill_small)
-bool small_path(const gamd_handle* h) { return h->use_small; }
 
 // centre-of-mass motion removal (MdCom): per-box, per-block momentum sums
 int fill_com(gamd_handle* h, int enabled, MdCom* c) {
@@ -43,13 +42,13 @@ int alloc_edges(gamd_handle* h, long long e_cap) {
     r |= h->erow.ensure(sizeof(int) * ec, true);
     r |= h->chunk_piece.ensure(sizeof(int) * (ec / GAMD_CHUNK + 2), true);
     r |= h->chunk_mask.ensure(sizeof(unsigned) * (ec / GAMD_CHUNK + 2), true);
-    r |= h->e_frag.ensure(sizeof(float) * 4096 * (size_t)h->EHT * (ec / GAMD_TILE + 1), false);
-    if (h->ln_fold) r |= h->e_rstd.ensure(sizeof(float) * 64 * (ec / GAMD_TILE + 1), false);
-    r |= h->partial.ensure(sizeof(float) * (size_t)h->H * (ec / GAMD_CHUNK + (size_t)h->n + 2), false);
+    r |= h->e_frag.ensure(sizeof(float) * 4096 * (size_t)h->rt.EHT * (ec / GAMD_TILE + 1), false);
+    if (h->rt.ln_fold) r |= h->e_rstd.ensure(sizeof(float) * 64 * (ec / GAMD_TILE + 1), false);
+    r |= h->partial.ensure(sizeof(float) * (size_t)h->rt.H * (ec / GAMD_CHUNK + (size_t)h->n + 2), false);
     h->piece_cap = (long long)(ec / GAMD_CHUNK + (size_t)h->n + 2);
-    if (h->update_edge) {                        // e_emb rows of one layer and the updated embedding tiles (H == Eh)
-        r |= h->e_emb.ensure(sizeof(float) * (size_t)h->H * ec, false);
-        r |= h->e_frag2.ensure(sizeof(float) * 4096 * (size_t)h->EHT * (ec / GAMD_TILE + 1), false);
+    if (h->rt.update_edge) {                        // e_emb rows of one layer and the updated embedding tiles (H == Eh)
+        r |= h->e_emb.ensure(sizeof(float) * (size_t)h->rt.H * ec, false);
+        r |= h->e_frag2.ensure(sizeof(float) * 4096 * (size_t)h->rt.EHT * (ec / GAMD_TILE + 1), false);
     }
     if (h->cfg.keep_stages) r |= h->feat_dbg.ensure(sizeof(float) * 48 * ec, true);
     if (r) return fail(-12, "edge buffer allocation failed for capacity %lld", e_cap);
@@ -64,26 +63,8 @@ int alloc_edges(gamd_handle* h, long long e_cap) {
     return 0;
 }
 
-// ---- the candidate radius of the Verlet-skin reuse, in fp32 ---------------------------------------------------------------
-// Reuse rests on the triangle inequality: a pair that is an edge now (D1 <= rc) and whose atoms have each moved at most skin / 2
-// since the build was at most rc + skin apart then (D0 <= D1 + 2 skin / 2), so it is in the candidate rows.  Every one of these
-// four statements is decided by an fp32 predicate over wrapped coordinates, and each predicate sees the true minimum-image
-// distance D only up to an ABSOLUTE error that scales with the box edge L, not with D.  With eps = 2^-24 (half an ulp, relative):
-//   per component (gamd_min_image_wrapped on d = pc - pb, both in [0, L]):  d: eps L;  d + L/2: 1.5 eps L (|.| <= 1.5 L);
-//     +/- L: eps L;  - L/2: 0.5 eps L   -> |r~ - r| <= 4 eps L   (a different image near +/- L/2 has the same |r| to that error)
-//   vector:  | |r~| - D | <= sqrt(3) 4 eps L  < 7 eps L
-//   squares and sums: three roundings per term, (1 + 3 eps) on d2, 1.5 eps D <= 1.3 eps L on the root (D <= sqrt(3) L / 2)
-//   the threshold itself (rc2, skin_half2 rounded; the torch flavour's rounded sqrt):  <= eps D < 1 eps L
-//   => each predicate decides "D~ < T" for some D~ with |D~ - D| <= E,  E = 10 eps L.
-// Chain:  edge now => D1 <= rc + E;  not moved (twice) => each displacement <= skin / 2 + E;  so D0 <= rc + skin + 3 E, and the
-// build's predicate sees D0~ <= rc + skin + 4 E.  The candidate radius must exceed that: rc + skin + 40 eps L, and 48 eps L once
-// its own two roundings (rc_build, rc2_build) and a strict '<' are paid for.  L is the longest edge of any box of the handle
-// (NbrArgs carries one radius for the whole batch).  At L = 30 / 150 / 1000 the margin is 8.6e-5 / 4.3e-4 / 2.9e-3: with
-// rc + skin = 8.75 that is 1e-5 ... 3e-4 of the radius, 3e-5 ... 1e-3 of the candidates.  The exact filter and the move test are
-// unchanged, so the edge set and the CSR order are what they were.  Without the margin a reuse step can miss an edge
-// (tests/test_gpu_nbr_cutoff.py, profiles/nbr_cutoff_parity.md: 76-80 of 80 constructed pairs).
-constexpr double GAMD_SKIN_MARGIN_EPS = 48.0 / 16777216.0;             // 48 x 2^-24, times the longest box edge
-// The cell grid must hold the enlarged radius: a candidate pair is at most rc_build + E apart along every axis, and cell_coord
+// The cell grid must hold the enlarged candidate radius (GAMD_SKIN_MARGIN_EPS, forward.hip: rc_build = rc + skin + 48 eps L, each
+// fp32 predicate off by at most E = 10 eps L): a candidate pair is at most rc_build + E apart along every axis, and cell_coord
 // (p * (nc / L), two roundings, |p nc / L| <= nc) places an atom up to 3 eps L from where it is, so two candidates land in the same
 // or in adjacent cells when the cells are rc + skin + (48 + 10 + 6) eps L wide.  The 1.0001 factor gives more than that while
 // 64 eps L <= 1e-4 (rc + skin), i.e. up to L = 26 (rc + skin); beyond that the second term takes over.  Without a skin the
@@ -147,64 +128,6 @@ int set_box(gamd_handle* h, const float* box, hipStream_t st = nullptr) {
     return 0;
 }
 
-NbrArgs nbr_args(gamd_handle* h, const float* pos_dev, const uint8_t* species_dev) {
-    NbrArgs a{};
-    a.n = h->n;
-    a.flavour = h->cfg.nbr_flavour;
-    for (int d = 0; d < 3; ++d) {
-        a.box[d] = h->box[d];
-        a.half[d] = 0.5f * h->box[d];
-        a.nc[d] = h->nc[d];
-    }
-    a.rc = h->cfg.cutoff;
-    a.rc2 = (float)((double)h->cfg.cutoff * (double)h->cfg.cutoff);   // graph_utils.py:59 cutoff ** 2
-    a.ncell = h->ncell;
-    a.bx = box_ref(h);
-    a.box_shift = h->box_shift.as<int>();
-    a.e_cap = h->e_cap;
-    a.pos = pos_dev;
-    a.species = species_dev;
-    a.feat = h->feat_dev;
-    a.self_loop = h->cfg.self_loop_mode == GAMD_SELF_LOOP_APPEND_ZERO_FEATURE ? 1 : 0;
-    a.devflags = h->devflags.as<int>();
-    a.pos_w = h->pos_w.as<float4>();
-    a.pos_s = h->pos_s.as<float4>();
-    a.cell_of = h->cell_of.as<int>();
-    a.ncell_cap = h->ncell_cap;
-    a.cell_cnt = h->counters.as<int>() + CNT_COUNT;
-    a.cell_fill = h->counters.as<int>() + CNT_COUNT + h->ncell_cap;
-    a.cell_start = h->cell_start.as<int>();
-    a.perm = h->perm.as<int>();
-    a.inv_perm = h->inv_perm.as<int>();
-    a.deg = h->deg.as<int>();
-    a.row_ptr = h->row_ptr.as<int>();
-    a.na_excl = h->na_excl.as<int>();
-    a.col = h->col.as<int>();
-    a.erow = h->erow.as<int>();
-    a.chunk_piece = h->chunk_piece.as<int>();
-    a.chunk_mask = h->chunk_mask.as<unsigned>();
-    a.counters = h->cur_counters ? h->cur_counters : h->counters.as<int>();
-    a.sticky = h->sticky_dev;
-    if (h->skin > 0.f) {
-        a.skin_half2 = 0.25f * h->skin * h->skin;
-        // rc + skin plus the rounding margin (GAMD_SKIN_MARGIN_EPS above): summed in double, rounded once
-        a.rc_build = (float)((double)h->cfg.cutoff + (double)h->skin + GAMD_SKIN_MARGIN_EPS * (double)h->box_max);
-        a.rc2_build = (float)((double)a.rc_build * (double)a.rc_build);
-        a.cand_deg = h->cand_deg.as<int>();
-        a.cand_ptr = h->cand_ptr.as<int>();
-        a.cand_col = h->cand_col.as<int>();
-        a.cand_cap = h->cand_cap;
-        // fixed-width candidate rows (neighbor.hip): the width follows the capacity (alloc_candidates keeps cand_cap >= n, so
-        // the width is at least 1: a buffer that is too small shows up as rows longer than the stride = the overflow -> regrow
-        // protocol, not as a zero stride)
-        a.use_small = small_path(h) ? 1 : 0;
-        a.cand_stride = (int)std::max<long long>(1, std::min<long long>(h->cand_cap / h->n, 1 << 20));
-    }
-    return a;
-}
-
-struct EdgeList { const int* centre; const int* neigh; long long n; };
-
 // rigid-water block shared by both integrators; returns 0 or an error code (message set)
 int fill_rigid(const gamd_handle* h, int rigid_water, float mass_o, float mass_h, float r_oh, float r_hh,
                int* use_rigid, RigidWater* g) {
@@ -218,250 +141,6 @@ int fill_rigid(const gamd_handle* h, int rigid_water, float mass_o, float mass_h
     g->m_o = mass_o; g->m_h = mass_h;
     g->rc = (float)rc; g->ra = (float)ra; g->rb = (float)(t - ra);
     *use_rigid = 1;
-    return 0;
-}
-
-int enqueue_forward(gamd_handle* h, const float* pos_dev, const uint8_t* species_dev, float* out_norm_dev,
-                    float* out_denorm_dev, hipStream_t st, hipEvent_t* evs, int* n_ev, std::vector<std::string>* labels,
-                    const EdgeList* el = nullptr, const MdFuse* fuse = nullptr, bool copy_counters = true, bool l0_reuse = false,
-                    bool drive = false) {
-    auto mark = [&](const char* label) {
-        if (evs) { (void)hipEventRecord(evs[*n_ev], st); ++*n_ev; labels->push_back(label); }
-    };
-    int r;
-    mark("begin");
-    // Verlet-skin reuse: ping-pong counter blocks instead of a memset node per call; n <= 1024: 4 neighbour launches per call
-    // with the integrator halves folded in (neighbor.hip)
-    const bool pingpong = !el && h->skin > 0.f;
-    int* counters_next = nullptr;
-    if (pingpong) {
-        h->cnt_parity ^= 1;
-        h->cur_counters = h->cnt2.as<int>() + h->cnt_parity * CNT_COUNT;
-        counters_next = h->cnt2.as<int>() + (1 - h->cnt_parity) * CNT_COUNT;
-    } else {
-        h->cur_counters = h->counters.as<int>();
-    }
-    NbrArgs na = nbr_args(h, pos_dev, species_dev);
-    na.counters_next = counters_next;
-    if (el) {
-        if ((r = launch_csr_from_edges(na, el->centre, el->neigh, el->n, h->tmp_eid.as<int>(), st)))
-            return fail(-1, "edge-list CSR launch failed (%d)", r);
-        h->cand_valid = false;                                    // atom order changed under the candidate list
-    } else if (h->skin > 0.f) {
-        na.ref_pos = h->ref_pos.as<float4>();
-        na.force_rebuild = h->cand_valid ? 0 : 1;
-        // rebuilds so far (host-mapped counter, lags the stream by what is enqueued) against calls so far: the one-workgroup
-        // cell build costs ~70 us more per rebuild at 10^4 atoms and saves three gated launches (~14 us) on every other step
-        ++h->skin_calls;
-        na.cells_one_wg = (h->skin_calls < 32 || 6ll * h->sticky_host[STICKY_REBUILDS] < h->skin_calls) ? 1 : 0;
-        if (fuse && !pingpong) return fail(-1, "internal: integrator halves can only be fused into the skin path");
-        if ((r = launch_neighbor_skin(na, st, fuse))) return fail(-1, "neighbor (skin) launch failed (%d)", r);
-        h->cand_valid = true;
-    } else if ((r = launch_neighbor_build(na, st))) return fail(-1, "neighbor build launch failed (%d)", r);
-    mark("neighbor_build");
-
-    // classical force source (a step of an enqueued MD run, gamd_md_force_source): the neighbour stage above stays — the fused
-    // integrator halves, the observers' edge list and pos_s, and the freeze / resume machinery hang on it — and the potential's
-    // launches (two for Lennard-Jones, five for water) stand where encoder, conv layers and decoder would
-    if (drive) {
-        if ((r = drive_enqueue(h))) return r;
-        if (copy_counters)
-            HIP_TRY(hipMemcpyAsync(h->counters_host, h->cur_counters, sizeof(int) * CNT_COUNT, hipMemcpyDeviceToHost, st));
-        return 0;
-    }
-
-    EncArgs ea{};
-    ea.counters = h->cur_counters;
-    ea.devflags = h->devflags.as<int>();
-    ea.pos_s = h->pos_s.as<float4>();
-    ea.col = h->col.as<int>();
-    ea.erow = h->erow.as<int>();
-    ea.bond_nbr = h->has_bonds ? h->bond_nbr.as<int>() : nullptr;
-    ea.perm = h->perm.as<int>();
-    ea.row_ptr = h->row_ptr.as<int>();
-    ea.self_loop = na.self_loop;
-    ea.zero_row = h->n;
-    for (int d = 0; d < 3; ++d) { ea.box[d] = h->box[d]; ea.half[d] = 0.5f * h->box[d]; }
-    ea.bx = box_ref(h);
-    ea.length_mean = h->length_mean;
-    ea.length_std = h->length_std;
-    ea.gamma = (float)(1.0 / 0.025);             // RBFExpansion(high=1, gap=0.025): gamma = 1/gap (nn_module.py:240)
-    ea.ln_inv_width = 1.0f / (float)h->Eh_true;
-    ea.ln_n_pad = (float)(h->Eh - h->Eh_true);
-    ea.n_feat = h->n_feat;
-    ea.n_ksteps = (h->n_feat + 1) / 2;
-    ea.centers = h->centers;
-    ea.rbf = h->rbf;
-    ea.w1p = h->enc_w1p; ea.w2p = h->enc_w2p; ea.w3p = h->enc_w3p;
-    ea.b1 = h->enc_b1; ea.b2 = h->enc_b2; ea.b3 = h->enc_b3;
-    ea.ln_g = h->enc_lng; ea.ln_b = h->enc_lnb;
-    ea.e_format = !h->wide_enc ? 0 : h->cfg.edge_dtype == GAMD_EDGE_F16X3 ? 2 : h->cfg.edge_dtype == GAMD_EDGE_BF16 ? 1 : 0;
-    ea.e_frag = h->e_frag.as<float>();
-    ea.e_cap = h->e_cap;
-    ea.sticky = h->sticky_dev;
-    ea.feat_dbg = h->cfg.keep_stages ? h->feat_dbg.as<float>() : nullptr;
-    ea.rstd_out = h->ln_fold ? h->e_rstd.as<float>() : nullptr;
-    // fp32 path, few tiles (measured crossover ~500 tiles, half a tile per SIMD): the latency-oriented kernels, one tile
-    // per 4-wave workgroup (conv_edge_small.hip, k_edge_encode_small).  They are bit-identical to the throughput kernels, so
-    // the choice (from the last known edge count, or the density estimate before the first call) never shows in the results.
-    int small_tiles = 0;
-    if (h->cfg.edge_dtype == GAMD_EDGE_F32) {
-        const long long e_est = el ? el->n + (na.self_loop ? h->n : 0)
-                                   : (h->counters_host[CNT_E] > 0 ? (long long)h->counters_host[CNT_E] : (long long)((double)h->e_cap / 1.5));
-        const long long tiles = (e_est + GAMD_TILE - 1) / GAMD_TILE;
-        if (tiles <= h->small_tile_limit) small_tiles = (int)std::max<long long>(1, std::min<long long>(tiles + tiles / 8 + 1, 4096));
-    }
-    // Generic-width fp32 conv kernel on 16-edge work units (k_conv_edge_wide16, bit-identical to k_conv_edge_wide): opt-in through
-    // GAMD_KSEL_FORCE_HALF_QUANTUM.  The idea — with t tiles per SIMD the launch takes ceil(2 t) / 2 tile quanta instead of ceil(t):
-    // 1.5 instead of 2 at the DFT-water size — holds for the matrix time (61 against 82 us) but not for the launch: one wave per
-    // SIMD pays the barrier, the 64 KiB weight copy and its vector work per 8 192-cycle phase instead of per 32 768-cycle phase
-    // pair, ~2.7 us x 18 phases (110 us against 107, profiles/r06_experiments.md).  Not chosen automatically.
-    const bool half_quantum = h->wide_conv && h->cfg.edge_dtype == GAMD_EDGE_F32 && (h->cfg.kernel_select & GAMD_KSEL_FORCE_HALF_QUANTUM) != 0;
-    bool tev_full = false;
-    auto tev_begin = [&](int kind) -> int {
-        if (!h->timing) return 0;
-        if (h->tev_used + 2 > h->tev.size()) {
-            if (h->tev.size() >= 8 * gamd_handle::EVENT_POOL_CAP) { tev_full = true; return 0; }   // pool full: not timed any more
-            for (int k = 0; k < 256; ++k) { hipEvent_t e; HIP_TRY(hipEventCreate(&e)); h->tev.push_back(e); h->tev_kind.push_back(0); }
-        }
-        h->tev_kind[h->tev_used] = kind;
-        HIP_TRY(hipEventRecord(h->tev[h->tev_used], st));
-        return 0;
-    };
-    auto tev_end = [&]() -> int {
-        if (!h->timing || tev_full) return 0;
-        HIP_TRY(hipEventRecord(h->tev[h->tev_used + 1], st));
-        h->tev_used += 2;
-        return 0;
-    };
-    if ((r = tev_begin(100))) return r;                         // kind 100: edge encoder
-    r = h->DT > 1 ? launch_edge_encode_wide_d(ea, h->EHT, h->DT, h->n_cu, st)
-        : h->wide_enc ? launch_edge_encode_wide(ea, h->EHT, h->n_cu, st)
-        : h->cfg.edge_dtype == GAMD_EDGE_BF16 ? launch_edge_encode_bf16(ea, h->n_cu, st)
-        : h->cfg.edge_dtype == GAMD_EDGE_F16X3 ? launch_edge_encode_f16x3(ea, h->n_cu, st)
-        : small_tiles > 0 ? launch_edge_encode_small(ea, small_tiles, st) : launch_edge_encode(ea, h->n_cu, st);
-    if (r) return fail(-1, "edge encode launch failed (%d)", r);
-    if ((r = tev_end())) return r;
-    mark("edge_encode");
-
-    const size_t nh = (size_t)h->n * (size_t)h->H;
-    auto node = [&](const NodeArgs& na_) {
-        return h->DT > 1 ? launch_node_wide_d(na_, h->HT, h->DT, st) : h->wide_conv ? launch_node_wide(na_, h->HT, st) : launch_node(na_, st);
-    };
-    auto hptr = [&](int l) { return h->hbuf.as<float>() + (h->cfg.keep_stages ? (size_t)l * nh : (size_t)(l & 1) * nh); };
-
-    NodeArgs no{};
-#ifdef GAMD_PROFILING
-    { static const bool node_time = getenv("GAMD_NODE_TIME") != nullptr; if (node_time) no.tdbg = h->tdbg.as<long long>(); }
-#endif
-    no.counters = h->cur_counters;
-    no.devflags = h->devflags.as<int>();
-    no.sticky = h->sticky_dev;
-    no.n = h->n;
-    no.pos_s = h->pos_s.as<float4>();
-    no.node_emb = h->node_emb; no.enc_w = h->nenc_w; no.enc_b = h->nenc_b;
-    no.row_ptr = h->row_ptr.as<int>(); no.na_excl = h->na_excl.as<int>(); no.deg = h->deg.as<int>();
-    no.col = (h->l0_hoist && h->n_boxes > 1) ? h->col.as<int>() : nullptr;     // post(0) of the layer-0 form: box padding
-    no.partial = h->partial.as<float>();
-    no.piece_cap = h->piece_cap;
-    no.P_in = h->P.as<float>();
-    no.hn_perm = (!h->wide_conv && h->cfg.edge_dtype == GAMD_EDGE_F16X3) ? 1 : 0;
-    no.tab16 = (!h->wide_conv && h->cfg.edge_dtype == GAMD_EDGE_BF16) ? 1 : 0;       // conv_edge_bf16.hip gathers fp16 rows
-    no.hn_out = h->hn.as<float>(); no.S_out = h->S.as<float>(); no.D_out = h->D.as<float>(); no.P_out = h->P.as<float>();
-    no.dec_w1p = h->dec_w1p; no.dec_b1 = h->dec_b1; no.dec_w2 = h->dec_w2; no.dec_b2 = h->dec_b2;
-    no.ln_inv_width = 1.0f / (float)h->H_true;
-    no.ln_n_pad = (float)(h->H - h->H_true);
-    no.norm_bn = h->norm_bn;
-    no.f16x3 = h->node_f16 ? 1 : 0;
-    no.scale = (float)std::sqrt(h->scaler_var);
-    no.shift = (float)h->scaler_mean;
-    no.perm = h->perm.as<int>();
-    no.forces_norm = out_norm_dev ? out_norm_dev : h->f_norm.as<float>();
-    no.forces = out_denorm_dev;
-
-    // layer 0 owns its tables in skin mode (see gamd_handle::l0_*); l0_reuse (steps of an enqueued MD run behind its first: same
-    // species buffer, same weights): the launch returns at once unless this step rebuilt the candidate list
-    const bool l0 = h->skin > 0.f && !el;
-    float* const h0 = (l0 && !h->cfg.keep_stages) ? h->l0_h.as<float>() : hptr(0);
-    no.mode = 0;
-    no.pre = h->layers[0].node;
-    no.h_out = h0;
-    if (l0) { no.hn_out = h->l0_hn.as<float>(); no.S_out = h->l0_S.as<float>(); no.D_out = h->l0_D.as<float>(); no.P_out = h->l0_P.as<float>(); }
-    no.l0_gate = (l0 && l0_reuse) ? 1 : 0;
-    if ((r = node(no))) return fail(-1, "node(0) launch failed (%d)", r);
-    no.l0_gate = 0;
-    no.hn_out = h->hn.as<float>(); no.S_out = h->S.as<float>(); no.D_out = h->D.as<float>(); no.P_out = h->P.as<float>();
-    mark("node_first");
-
-
-    for (int l = 0; l < h->L; ++l) {
-        ConvEdgeArgs ca{};
-        ca.counters = h->cur_counters;
-        ca.devflags = h->devflags.as<int>();
-        ca.col = h->col.as<int>(); ca.erow = h->erow.as<int>();
-        ca.chunk_piece = h->chunk_piece.as<int>(); ca.chunk_mask = h->chunk_mask.as<unsigned>();
-        // update_edge_emb: layers after the first read the previous layer's LayerNorm(e_emb) (nn_module.py:145-146)
-        ca.e_frag = (h->update_edge && l > 0) ? h->e_frag2.as<float>() : h->e_frag.as<float>();
-        ca.emb_out = (h->update_edge && l + 1 < h->L) ? h->e_emb.as<float>() : nullptr;
-        ca.hn = h->hn.as<float>(); ca.S = h->S.as<float>(); ca.D = h->D.as<float>();
-        if (l0 && l == 0) { ca.hn = h->l0_hn.as<float>(); ca.S = h->l0_S.as<float>(); ca.D = h->l0_D.as<float>(); }
-        const LayerDev& ld = h->layers[l];
-        ca.w1p = ld.w1p; ca.w2p = ld.w2p; ca.w3p = ld.w3p; ca.w4p = ld.w4p; ca.w16p = ld.w16p;
-        ca.b1 = ld.b1; ca.b3 = ld.b3; ca.b4 = ld.b4;
-        // layer-0 form: three GEMMs per edge, phi_edge's part applied per atom by post(0) (timed as conv layer 0 all the same)
-        const bool hoist = l == 0 && h->l0_hoist;
-        if (hoist) { ca.w3p = ld.w3p_l0; ca.b3 = ld.b3_l0; }
-        ca.e_rstd = h->ln_fold ? h->e_rstd.as<float>() : nullptr;
-        ca.partial = h->partial.as<float>();
-        ca.piece_cap = h->piece_cap;
-        ca.sticky = h->sticky_dev;
-        ca.e_cap = h->e_cap;
-        ca.zero_row = h->n;
-#ifdef GAMD_CHECKED
-        // fault injection for tests/test_gpu_checked.py: the conv kernels are told that the node tables end at row 0, so the
-        // first source index above it must be reported (GAMD_CHK_CONV_SRC) and clamped
-        { static const bool inject = getenv("GAMD_CHK_INJECT") != nullptr; if (inject) ca.zero_row = 0; }
-#endif
-        ca.tdbg = h->tdbg.as<long long>();
-        if ((r = tev_begin(l))) return r;                        // kind l: conv-layer edge kernel of layer l
-        r = h->DT > 1 ? launch_conv_edge_wide_d(ca, h->EHT, h->HT, h->DT, h->n_cu, st)
-            : h->wide_conv ? (h->cfg.edge_dtype == GAMD_EDGE_F16X3 ? launch_conv_edge_f16x3_wide(ca, h->EHT, h->HT, h->n_cu, st)
-                            : h->cfg.edge_dtype == GAMD_EDGE_BF16 ? launch_conv_edge_bf16_wide(ca, h->EHT, h->HT, h->n_cu, st)
-                            : (half_quantum && ca.w16p && !ca.emb_out) ? launch_conv_edge_wide16(ca, h->EHT, h->HT, h->n_cu, st)
-                            : small_tiles > 0 ? launch_conv_edge_small_wide(ca, h->EHT, h->HT, small_tiles, st)
-                                              : launch_conv_edge_wide(ca, h->EHT, h->HT, h->n_cu, st))
-            : h->cfg.edge_dtype == GAMD_EDGE_BF16 ? launch_conv_edge_bf16(ca, h->n_cu, st)
-            : h->cfg.edge_dtype == GAMD_EDGE_F16X3 ? launch_conv_edge_f16x3(ca, h->n_cu, st)
-            : hoist ? (small_tiles > 0 ? launch_conv_edge_small_l0(ca, small_tiles, st) : launch_conv_edge_l0(ca, h->n_cu, st))
-            : small_tiles > 0 ? launch_conv_edge_small(ca, small_tiles, st) : launch_conv_edge(ca, h->n_cu, st);
-        if (r) return fail(-1, "conv edge launch failed (%d)", r);
-        if ((r = tev_end())) return r;
-        mark("conv_edge");
-        if (ca.emb_out) {
-            EdgeUpdateArgs ua{};
-            ua.counters = h->cur_counters; ua.devflags = h->devflags.as<int>(); ua.e_cap = h->e_cap;
-            ua.emb = ca.emb_out; ua.ln_g = ld.e_ln_g; ua.ln_b = ld.e_ln_b;
-            ua.ln_inv_width = 1.0f / (float)h->Eh_true;
-            ua.ln_n_pad = (float)(h->Eh - h->Eh_true);
-            ua.e_frag_out = h->e_frag2.as<float>();
-            if ((r = launch_edge_update(ua, h->HT, small_tiles > 0 ? std::max(1, small_tiles / 4) : 2 * h->n_cu, st)))
-                return fail(-1, "edge update launch failed (%d)", r);
-            mark("edge_update");
-        }
-
-        no.mode = (l == h->L - 1) ? 2 : 1;
-        no.post = ld.node;
-        if (l + 1 < h->L) no.pre = h->layers[l + 1].node;
-        no.h_in = l == 0 ? h0 : hptr(l);
-        no.P_in = (l0 && l == 0) ? h->l0_P.as<float>() : h->P.as<float>();
-        no.h_out = hptr(l + 1);
-        if ((r = node(no))) return fail(-1, "node launch failed (%d)", r);
-        mark(no.mode == 2 ? "node_last_decode" : "node_mid");
-    }
-    // inside an enqueued MD run only the last step's counters are fetched (an overflow in any step reaches the host
-    // through the mapped sticky flags): one copy node less per step
-    if (copy_counters)
-        HIP_TRY(hipMemcpyAsync(h->counters_host, h->cur_counters, sizeof(int) * CNT_COUNT, hipMemcpyDeviceToHost, st));
     return 0;
 }
 
@@ -512,10 +191,19 @@ int step_event(gamd_handle* h, hipStream_t st, bool closes = false) {
     return 0;
 }
 
+// the force evaluation of step s of the pending MD run (of the steps enqueued from s_begin on): f from x, by the run's force source
+int step_forces(gamd_handle* h, long long s, long long s_begin, const MdFuse* fuse = nullptr) {
+    const MdPending& p = h->pending;
+    ForwardCall c{p.x, p.species, nullptr, p.f, p.st, nullptr, fuse};
+    c.copy_counters = s + 1 == p.n_steps;
+    c.l0_reuse = s > s_begin;
+    StageClock clock{h, p.st};
+    return enqueue_forward(h, c, clock, h->force_source != GAMD_FORCE_NETWORK);     // (cannot change while the run is pending)
+}
+
 // steps [s_begin, n_steps) of the pending MD run; skip_first: the first half of step s_begin has already been done
 int enqueue_md_steps(gamd_handle* h, long long s_begin, bool skip_first) {
     MdPending& p = h->pending;
-    const bool drive = h->force_source != GAMD_FORCE_NETWORK;        // cannot change while the run is pending
     int r;
     // Skin mode, BAOAB (free atoms or rigid water): the B of step s-1 and the B A O A of step s ride in the first kernel of step s's force
     // evaluation (k_step_small / k_skin_check): 2 launches less per step; the last B is launched on its own.
@@ -548,9 +236,7 @@ int enqueue_md_steps(gamd_handle* h, long long s_begin, bool skip_first) {
                 }
             }
             const MdFuse fuse{&p.m, do_second, do_first};
-            if ((r = enqueue_forward(h, p.x, p.species, nullptr, p.f, p.st, nullptr, nullptr, nullptr, nullptr, &fuse,
-                                     s + 1 == p.n_steps, s > s_begin, drive)))
-                return r;
+            if ((r = step_forces(h, s, s_begin, &fuse))) return r;
             if (s + 1 < p.n_steps && observers_sampled(h, s)) {        // a sampled step completes its B before the sample
                 if ((r = launch_baoab_second(p.m, p.st))) return fail(-1, "integrator launch failed (%d)", r);
                 if ((r = observers_enqueue(h, s))) return r;
@@ -565,20 +251,12 @@ int enqueue_md_steps(gamd_handle* h, long long s_begin, bool skip_first) {
     }
     for (long long s = s_begin; s < p.n_steps; ++s) {
         if ((r = step_event(h, p.st))) return r;
-        const bool first = !(skip_first && s == s_begin);
-        const bool last = s + 1 == p.n_steps;
-        if (p.kind == 0) {
-            p.m.step = p.first_step + (unsigned long long)s;
-            p.m.step_index = (int)s;
-            if (first && (r = launch_baoab_first(p.m, p.st))) return fail(-1, "integrator launch failed (%d)", r);
-            if ((r = enqueue_forward(h, p.x, p.species, nullptr, p.f, p.st, nullptr, nullptr, nullptr, nullptr, nullptr, last, s > s_begin, drive))) return r;
-            if ((r = launch_baoab_second(p.m, p.st))) return fail(-1, "integrator launch failed (%d)", r);
-        } else {
-            p.a.step_index = (int)s;
-            if (first && (r = launch_nhc_first(p.a, p.st))) return fail(-1, "integrator launch failed (%d)", r);
-            if ((r = enqueue_forward(h, p.x, p.species, nullptr, p.f, p.st, nullptr, nullptr, nullptr, nullptr, nullptr, last, s > s_begin, drive))) return r;
-            if ((r = launch_nhc_second(p.a, p.st))) return fail(-1, "integrator launch failed (%d)", r);
-        }
+        const bool first = !(skip_first && s == s_begin), baoab = p.kind == 0;
+        if (baoab) { p.m.step = p.first_step + (unsigned long long)s; p.m.step_index = (int)s; }
+        else p.a.step_index = (int)s;
+        if (first && (r = baoab ? launch_baoab_first(p.m, p.st) : launch_nhc_first(p.a, p.st))) return fail(-1, "integrator launch failed (%d)", r);
+        if ((r = step_forces(h, s, s_begin))) return r;
+        if ((r = baoab ? launch_baoab_second(p.m, p.st) : launch_nhc_second(p.a, p.st))) return fail(-1, "integrator launch failed (%d)", r);
         if ((r = observers_enqueue(h, s))) return r;
     }
     return step_event(h, p.st, true);
@@ -598,6 +276,29 @@ int fill_run_args(gamd_handle* h, const Params* p, const float* box, const uint8
     if ((r = fill_com(h, p->remove_cm_motion, &a->com))) return r;
     a->devflags = h->devflags.as<int>();
     return 0;
+}
+
+// The top of gamd_md_run / gamd_md_run_nhc: every refusal the two share, in the order a bad call meets them (an integrator's own
+// refusal texts `own_after_steps`, `own_after_inputs`, null when it has none to make, keep their places), then the guards of the
+// entry point, which live in `scope` until it returns, and the box.
+struct RunScope { std::optional<DeviceGuard> device; std::optional<InitStream> init; };
+int begin_run(gamd_handle* h, bool pointers_given, long long n_steps, const uint8_t* species_dev, const float* box, int rigid_water,
+              hipStream_t st, RunScope& scope, const char* own_after_steps = nullptr, const char* own_after_inputs = nullptr) {
+    int r;
+    if ((r = check_ready(h))) return r;
+    if (!pointers_given) return fail(-22, "null argument");
+    if (n_steps < 0 || n_steps > 0x3fffffff) return fail(-22, "n_steps out of range");
+    if (own_after_steps) return fail(-22, "%s", own_after_steps);
+    if ((r = check_model_inputs(h, species_dev))) return r;
+    if (own_after_inputs) return fail(-22, "%s", own_after_inputs);
+    if ((r = observers_check_run(h, box, species_dev))) return r;
+    if (h->force_source == GAMD_FORCE_WATER_CLASSICAL && !rigid_water)
+        return fail(-22, "the water classical force source needs rigid_water: the potential has no bond or angle term (same-molecule "
+                         "pairs are excluded), so only the constraints hold a molecule together");
+    if (h->force_source != GAMD_FORCE_NETWORK && (r = drive_check_run(h, box, species_dev))) return r;
+    scope.device.emplace(h->dev);
+    scope.init.emplace(st);
+    return set_box(h, box, st);
 }
 
 // ... and once the run is certain to be enqueued (pending.kind and its argument block are set)
@@ -647,32 +348,18 @@ int32_t gamd_create(const gamd_config* cfg, gamd_handle** out) {
     DeviceGuard guard(cfg->device);            // the caller's current device is restored on every return path
     hipDeviceProp_t prop;
     HIP_TRY(hipGetDeviceProperties(&prop, cfg->device));
-    // Widths as build_model hands them to the model constructors (nn_module.py:561-601, :410-460, :266-320).  The kernels work
-    // in 128-wide blocks: narrower (or in-between) widths are zero-padded by gamd_finalize_weights — padded features stay
-    // exact zeros through every Linear / SiLU / GELU, and the two LayerNorms divide by the true width.
-    const int H_true = cfg->encoding_size ? cfg->encoding_size : 128, Eh_true = cfg->edge_embedding_dim ? cfg->edge_embedding_dim : 128;
-    const int D_true = cfg->hidden_dim ? cfg->hidden_dim : 128;
-    if (H_true < 1 || H_true > 256 || Eh_true < 1 || Eh_true > 256)
-        return fail(-22, "encoding_size and edge_embedding_dim must be in [1, 256] (got %d, %d)", H_true, Eh_true);
-    if (D_true < 1 || D_true > 256) return fail(-22, "hidden_dim must be in [1, 256] (got %d)", D_true);
-    const int Dp = D_true <= 128 ? 128 : 256;
-    // hidden_dim above 128: two 128-blocks per D-wide operand, the fp32 kernels of wide_d.hip
-    if (Dp > 128 && cfg->edge_dtype != GAMD_EDGE_F32)
-        return fail(-22, "hidden_dim above 128 is built for edge_dtype f32 only (got hidden_dim %d)", D_true);
-    const int H = H_true <= 128 ? 128 : 256, Eh = Eh_true <= 128 ? 128 : 256;
-    const bool exact128 = H_true == 128 && Eh_true == 128 && D_true == 128;
-    const bool generic = H != 128 || Eh != 128 || cfg->no_expand_edge;
-    // reduced-precision edge MLPs (bf16, fp32-grade split-fp16) exist for every width and both feature sets: 128 / 128 / 128
-    // expanded runs the specialised kernels, anything else wide.hip's encoder writing the operands + wide_lp.hip
-    if (cfg->edge_dtype != GAMD_EDGE_F32 && H == 256 && (long long)cfg->n_atoms * n_boxes > (1ll << 22) - 2)
+    // widths, kernel families and their refusals: gamd_route_host.h (update_edge is known once the weights are there)
+    const Route rt = gamd_route(route_config(*cfg), false);
+    if (rt.err) return fail(rt.err, "%s", rt.msg);
+    if (!rt.f32 && rt.H == 256 && (long long)cfg->n_atoms * n_boxes > (1ll << 22) - 2)
         return fail(-22, "bf16 / split-fp16 with encoding_size > 128: at most 2^22 - 2 atoms per handle (32-bit byte offsets into hn)");
-    gamd_handle* h = new gamd_handle();
+    std::unique_ptr<gamd_handle, int32_t (*)(gamd_handle*)> owner(new gamd_handle(), gamd_destroy);    // destroyed on every return but the last
+    gamd_handle* const h = owner.get();
     h->obs = observers_new();
     h->cfg = *cfg;
     h->dev = cfg->device;
     if (hipStreamCreateWithFlags(&h->init_stream, hipStreamNonBlocking) != hipSuccess) {
         h->init_stream = nullptr;
-        gamd_destroy(h);
         return fail(-12, "stream creation failed");
     }
     InitStream init(h->init_stream);
@@ -680,22 +367,9 @@ int32_t gamd_create(const gamd_config* cfg, gamd_handle** out) {
     h->n_per_box = cfg->n_atoms;
     h->n = cfg->n_atoms * n_boxes;
     h->L = cfg->n_layers;
-    h->H = H; h->Eh = Eh; h->HT = H / 128; h->EHT = Eh / 128;
-    h->H_true = H_true; h->Eh_true = Eh_true; h->D_true = D_true;
-    h->Dp = Dp; h->DT = Dp / 128;
+    h->rt = rt;
     h->skin = cfg->neighbor_skin;
-    if (cfg->small_tile_limit != 0) h->small_tile_limit = cfg->small_tile_limit < 0 ? -1 : cfg->small_tile_limit;
-    const bool forced = (cfg->kernel_select & GAMD_KSEL_FORCE_GENERIC_WIDTH) && cfg->edge_dtype == GAMD_EDGE_F32;
-    // bf16 / split-fp16 outside 128 / 128 / 128 expanded: encoder, conv and node kernels all take the generic-width route
-    const bool lp_generic = cfg->edge_dtype != GAMD_EDGE_F32 && (generic || !exact128);
-    h->wide_enc = generic || forced || lp_generic || Dp > 128;
-    h->wide_conv = H != 128 || Eh != 128 || forced || lp_generic || Dp > 128;
-    // Folded edge LayerNorm (gamd_ln_fold_host.h): the fp32 128-wide kernels without appended self loops; not with keep_stages
-    // (e is then a stage the getters hand out), not under GAMD_KSEL_NO_LN_FOLD, not for update_edge_emb models (which
-    // gamd_finalize_weights moves to the generic-width kernels)
-    h->ln_fold = cfg->edge_dtype == GAMD_EDGE_F32 && !h->wide_enc && !h->wide_conv && cfg->self_loop_mode == GAMD_SELF_LOOP_DGL07_NOOP &&
-                 !cfg->keep_stages && !(cfg->kernel_select & GAMD_KSEL_NO_LN_FOLD);
-    h->n_feat = (cfg->no_expand_edge ? 4 : 44) + (cfg->use_bond ? 1 : 0);
+    h->small_tile_limit = route_tile_limit(cfg->small_tile_limit);
     h->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     const size_t n = (size_t)h->n;
     int r = 0;
@@ -713,16 +387,16 @@ int32_t gamd_create(const gamd_config* cfg, gamd_handle** out) {
     r |= h->deg.ensure(sizeof(int) * n, true);
     r |= h->row_ptr.ensure(sizeof(int) * (n + 1), true);
     r |= h->na_excl.ensure(sizeof(int) * (n + 1), true);
-    const size_t nh = n * (size_t)H * sizeof(float), nd = n * (size_t)Dp * sizeof(float), zd = (size_t)Dp * sizeof(float);
+    const size_t nh = n * (size_t)rt.H * sizeof(float), nd = n * (size_t)rt.Dp * sizeof(float), zd = (size_t)rt.Dp * sizeof(float);
     r |= h->hbuf.ensure(nh * (cfg->keep_stages ? (size_t)h->L + 1 : 2), true);
     // one extra, all-zero row (index n) behind the node tables the conv-layer edge kernel gathers from: the padding
     // slots of the last 32-edge tile point at it, so their messages are exact zeros without a per-element mask
-    r |= h->hn.ensure(nh + (size_t)H * sizeof(float), true);
+    r |= h->hn.ensure(nh + (size_t)rt.H * sizeof(float), true);
     r |= h->S.ensure(nd + zd, true);
     r |= h->D.ensure(nd + zd, true);
     r |= h->P.ensure(nd, true);
     if (cfg->neighbor_skin > 0.f) {
-        r |= h->l0_hn.ensure(nh + (size_t)H * sizeof(float), true);
+        r |= h->l0_hn.ensure(nh + (size_t)rt.H * sizeof(float), true);
         r |= h->l0_S.ensure(nd + zd, true);
         r |= h->l0_D.ensure(nd + zd, true);
         r |= h->l0_P.ensure(nd, true);
@@ -733,38 +407,30 @@ int32_t gamd_create(const gamd_config* cfg, gamd_handle** out) {
     r |= h->tdbg.ensure(sizeof(long long) * 16 * 8 * 1024, true);
     r |= h->devflags.ensure(sizeof(int) * DEVFLAG_COUNT, true);
     r |= h->cnt2.ensure(sizeof(int) * 2 * CNT_COUNT, true);
-    if (r) { gamd_destroy(h); return fail(-12, "device allocation failed"); }
+    if (r) return fail(-12, "device allocation failed");
     {
         const int no_atom = -2;
-        if (init_upload(h->perm.as<int>() + n, &no_atom, sizeof(int)) != hipSuccess) {
-            gamd_destroy(h);
-            return fail(-1, "device copy failed");
-        }
+        if (init_upload(h->perm.as<int>() + n, &no_atom, sizeof(int)) != hipSuccess) return fail(-1, "device copy failed");
     }
-    if ((r = clear_devflags(h))) { gamd_destroy(h); return r; }
-    if (hipHostMalloc((void**)&h->counters_host, sizeof(int) * CNT_COUNT) != hipSuccess) {
-        gamd_destroy(h);
-        return fail(-12, "pinned allocation failed");
-    }
+    if ((r = clear_devflags(h))) return r;
+    if (hipHostMalloc((void**)&h->counters_host, sizeof(int) * CNT_COUNT) != hipSuccess) return fail(-12, "pinned allocation failed");
     memset(h->counters_host, 0, sizeof(int) * CNT_COUNT);
     if (hipHostMalloc((void**)&h->sticky_host, sizeof(int) * STICKY_COUNT, hipHostMallocMapped) != hipSuccess ||
-        hipHostGetDevicePointer((void**)&h->sticky_dev, h->sticky_host, 0) != hipSuccess) {
-        gamd_destroy(h);
+        hipHostGetDevicePointer((void**)&h->sticky_dev, h->sticky_host, 0) != hipSuccess)
         return fail(-12, "mapped host allocation failed");
-    }
     memset(h->sticky_host, 0, sizeof(int) * STICKY_COUNT);
     if (h->skin > 0.f) {
         int rr = 0;
         rr |= h->ref_pos.ensure(sizeof(float4) * n, true);
         rr |= h->cand_deg.ensure(sizeof(int) * n, true);
         rr |= h->cand_ptr.ensure(sizeof(int) * (n + 1), true);
-        if (rr) { gamd_destroy(h); return fail(-12, "device allocation failed"); }
+        if (rr) return fail(-12, "device allocation failed");
     }
     {
         std::vector<float> all((size_t)n_boxes * 3);              // every box starts with the constructor's box
         for (int b = 0; b < n_boxes; ++b)
             for (int d = 0; d < 3; ++d) all[(size_t)3 * b + d] = cfg->box[d];
-        if ((r = set_box(h, all.data()))) { gamd_destroy(h); return r; }
+        if ((r = set_box(h, all.data()))) return r;
     }
     {
         // Small-system path (k_step_small: skin check, integrator halves and — on the steps that need it — the cell build of a
@@ -782,9 +448,9 @@ int32_t gamd_create(const gamd_config* cfg, gamd_handle** out) {
         ecap = (long long)(1.5 * per_atom * (double)h->n) + 1024 + 16ll * n_boxes;
     }
     if (cfg->self_loop_mode) ecap += h->n;
-    if ((r = alloc_edges(h, ecap))) { gamd_destroy(h); return r; }
-    if (hipStreamSynchronize(h->init_stream) != hipSuccess) { gamd_destroy(h); return fail(-1, "device synchronisation failed"); }
-    *out = h;                                  // every initialising memset / copy has landed: any stream may use the handle
+    if ((r = alloc_edges(h, ecap))) return r;
+    if (hipStreamSynchronize(h->init_stream) != hipSuccess) return fail(-1, "device synchronisation failed");
+    *out = owner.release();                    // every initialising memset / copy has landed: any stream may use the handle
     return 0;
 }
 
@@ -796,7 +462,7 @@ int32_t gamd_destroy(gamd_handle* h) {
     h->cnt2.release();
     DevBuf* bufs[] = {&h->boxes_dev, &h->box_shift, &h->wblob, &h->pos_w, &h->pos_s, &h->cell_of, &h->perm, &h->inv_perm, &h->deg, &h->row_ptr,
                       &h->na_excl, &h->bond_nbr, &h->hbuf, &h->hn, &h->S, &h->D, &h->P, &h->l0_h, &h->l0_hn, &h->l0_S, &h->l0_D, &h->l0_P, &h->f_norm, &h->f_den,
-                      &h->cell_cnt, &h->cell_fill, &h->cell_start, &h->col, &h->erow, &h->chunk_piece,
+                      &h->cell_start, &h->col, &h->erow, &h->chunk_piece,
                       &h->chunk_mask, &h->e_frag, &h->e_rstd, &h->e_emb, &h->e_frag2, &h->partial, &h->feat_dbg, &h->counters, &h->tdbg, &h->tmp_eid, &h->ke_partial, &h->com_partial,
                       &h->ref_pos, &h->cand_deg, &h->cand_ptr, &h->cand_col};
     for (DevBuf* b : bufs) b->release();
@@ -824,29 +490,20 @@ int32_t gamd_load_weight(gamd_handle* h, const char* name, const float* data, co
     return 0;
 }
 
-// Transformation and packing are pack_weights (gamd_weights_host.h, host only); here: its flags onto the handle, the upload,
-// and its offset tables turned into the device pointers of the same names.
+// Transformation and packing are pack_weights (gamd_weights_host.h, host only); here: the route now that the state_dict is known,
+// the upload, and the offset tables turned into the device pointers of the same names.
 int32_t gamd_finalize_weights(gamd_handle* h) {
     if (!h) return fail(-22, "null handle");
     DeviceGuard guard(h->dev);
     InitStream init(h->init_stream);
-    WeightSpec spec;
-    spec.kind = h->cfg.kind; spec.edge_dtype = h->cfg.edge_dtype; spec.no_expand_edge = h->cfg.no_expand_edge;
-    spec.self_loop_mode = h->cfg.self_loop_mode; spec.kernel_select = h->cfg.kernel_select;
-    spec.n_layers = h->L; spec.n_feat = h->n_feat;
-    spec.H_true = h->H_true; spec.Eh_true = h->Eh_true; spec.D_true = h->D_true;
-    spec.H = h->H; spec.Eh = h->Eh; spec.Dp = h->Dp;
-    spec.wide_enc = h->wide_enc; spec.wide_conv = h->wide_conv; spec.ln_fold = h->ln_fold;
-    const PackedWeights pw = pack_weights(spec, h->host_w);
+    const RouteConfig rc = route_config(h->cfg);
+    const Route rt = gamd_route(rc, route_update_edge(h->host_w));
+    const PackedWeights pw = pack_weights(rc, rt, h->L, h->host_w);
     if (pw.err) return fail(pw.err, "%s", pw.msg);
-    h->node_f16 = pw.node_f16;
-    h->wide_enc = pw.wide_enc; h->wide_conv = pw.wide_conv; h->ln_fold = pw.ln_fold;
-    if (pw.update_edge != h->update_edge) {                      // e_emb / e_frag2 come and go with it
-        h->update_edge = pw.update_edge;
-        if (alloc_edges(h, h->e_cap)) return -12;
-    }
+    const bool regrow = rt.update_edge != h->rt.update_edge;     // e_emb / e_frag2 come and go with it
+    h->rt = rt;
+    if (regrow && alloc_edges(h, h->e_cap)) return -12;
     h->norm_bn = pw.norm_bn ? 1 : 0;
-    h->l0_hoist = pw.l0_hoist;
     h->length_mean = pw.length_mean;
     h->length_std = pw.length_std;
     h->rbf = RbfGrid{pw.rbf.uniform, pw.rbf.c0, pw.rbf.delta, pw.rbf.A, pw.rbf.B, pw.rbf.C};
@@ -959,7 +616,9 @@ int32_t gamd_forces_async(gamd_handle* h, const float* pos_dev, const uint8_t* s
     InitStream init((hipStream_t)stream);
     if ((r = set_box(h, box, (hipStream_t)stream))) return r;
     h->pending.active = false;
-    return enqueue_forward(h, pos_dev, species_dev, out_norm_dev, out_denorm_dev, (hipStream_t)stream, nullptr, nullptr, nullptr);
+    const ForwardCall c{pos_dev, species_dev, out_norm_dev, out_denorm_dev, (hipStream_t)stream};
+    StageClock clock{h, c.st};
+    return enqueue_forward(h, c, clock);
 }
 
 int32_t gamd_sync_status(gamd_handle* h, void* stream) {
@@ -1082,10 +741,11 @@ int32_t gamd_forces_edges(gamd_handle* h, const float* pos_dev, const uint8_t* s
     }
     if (h->tmp_eid.ensure(sizeof(int) * ((size_t)std::max<long long>(total, 1) + 64), false))
         return fail(-12, "edge scratch allocation failed");
-    EdgeList el{centre_dev, neigh_dev, (long long)n_edges};
-    if ((r = enqueue_forward(h, pos_dev, species_dev, out_norm_dev, out_denorm_dev, (hipStream_t)stream, nullptr, nullptr,
-                             nullptr, &el)))
-        return r;
+    const EdgeList el{centre_dev, neigh_dev, (long long)n_edges};
+    ForwardCall c{pos_dev, species_dev, out_norm_dev, out_denorm_dev, (hipStream_t)stream};
+    c.edges = &el;
+    StageClock clock{h, c.st};
+    if ((r = enqueue_forward(h, c, clock))) return r;
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
     h->sticky_host[STICKY_EDGE_OVERFLOW] = 0;
     if (h->counters_host[CNT_OVERFLOW]) {
@@ -1127,16 +787,16 @@ int32_t gamd_debug_get(gamd_handle* h, int32_t what, void* host_out, size_t byte
     else if (what == GAMD_DBG_ROWPTR) { src = h->row_ptr.p; avail = sizeof(int) * (n + 1); }
     else if (what == GAMD_DBG_COL) { src = h->col.p; avail = sizeof(int) * E; }
     else if (what == GAMD_DBG_EFRAG) {
-        if (h->ln_fold) return fail(-22, "EFRAG needs keep_stages=1 on this handle: the edge LayerNorm is folded into the conv layers and e is never formed");
-        src = h->e_frag.p; avail = sizeof(float) * 4096 * (size_t)h->EHT * ((E + 31) / 32);
+        if (h->rt.ln_fold) return fail(-22, "EFRAG needs keep_stages=1 on this handle: the edge LayerNorm is folded into the conv layers and e is never formed");
+        src = h->e_frag.p; avail = sizeof(float) * 4096 * (size_t)h->rt.EHT * ((E + 31) / 32);
     } else if (what == GAMD_DBG_FEAT) {
         if (!h->cfg.keep_stages) return fail(-22, "FEAT needs keep_stages=1");
         src = h->feat_dbg.p; avail = sizeof(float) * 48 * E;
     } else if (what >= GAMD_DBG_H0 && what <= GAMD_DBG_H0 + h->L) {
         if (!h->cfg.keep_stages) return fail(-22, "H_l needs keep_stages=1");
-        src = h->hbuf.as<float>() + (size_t)(what - GAMD_DBG_H0) * n * (size_t)h->H; avail = sizeof(float) * n * (size_t)h->H;
+        src = h->hbuf.as<float>() + (size_t)(what - GAMD_DBG_H0) * n * (size_t)h->rt.H; avail = sizeof(float) * n * (size_t)h->rt.H;
     } else if (what == GAMD_DBG_PARTIAL) {
-        src = h->partial.p; avail = sizeof(float) * (size_t)h->H * (size_t)std::max(0, h->counters_host[CNT_PIECES]);
+        src = h->partial.p; avail = sizeof(float) * (size_t)h->rt.H * (size_t)std::max(0, h->counters_host[CNT_PIECES]);
     } else if (what == GAMD_DBG_CYCLES) { src = h->tdbg.p; avail = sizeof(long long) * 16 * 8 * (size_t)h->n_cu;
     } else return fail(-22, "unknown debug tensor %d", what);
     if (bytes < avail) return fail(-22, "host buffer too small: %zu < %zu", bytes, avail);
@@ -1147,19 +807,9 @@ int32_t gamd_debug_get(gamd_handle* h, int32_t what, void* host_out, size_t byte
 int32_t gamd_md_run(gamd_handle* h, float* x_dev, float* v_dev, float* f_dev, const uint8_t* species_dev,
                     const float* box, const gamd_md_params* p, int64_t n_steps, void* stream) {
     int r;
-    if ((r = check_ready(h))) return r;
-    if (!x_dev || !v_dev || !f_dev || !box || !p) return fail(-22, "null argument");
-    if (n_steps < 0 || n_steps > 0x3fffffff) return fail(-22, "n_steps out of range");
-    if ((r = check_model_inputs(h, species_dev))) return r;
-    if ((r = observers_check_run(h, box, species_dev))) return r;
-    if (h->force_source == GAMD_FORCE_WATER_CLASSICAL && !p->rigid_water)
-        return fail(-22, "the water classical force source needs rigid_water: the potential has no bond or angle term (same-molecule "
-                         "pairs are excluded), so only the constraints hold a molecule together");
-    if (h->force_source != GAMD_FORCE_NETWORK && (r = drive_check_run(h, box, species_dev))) return r;
-    DeviceGuard guard(h->dev);
-    InitStream init((hipStream_t)stream);
-    if ((r = set_box(h, box, (hipStream_t)stream))) return r;
     hipStream_t st = (hipStream_t)stream;
+    RunScope scope;
+    if ((r = begin_run(h, x_dev && v_dev && f_dev && box && p, n_steps, species_dev, box, p ? p->rigid_water : 0, st, scope))) return r;
     MdArgs m{};
     m.x = x_dev; m.v = v_dev; m.f = f_dev;
     if (!(p->mass_amu > 0.f)) return fail(-22, "mass_amu must be positive");
@@ -1191,26 +841,19 @@ int32_t gamd_md_force_source(gamd_handle* h, int32_t source) {
 int32_t gamd_md_run_nhc(gamd_handle* h, float* x_dev, float* v_dev, float* f_dev, const uint8_t* species_dev,
                         const float* box, const gamd_nhc_params* p, double* chain_state_dev, int64_t n_steps, void* stream) {
     int r;
-    if ((r = check_ready(h))) return r;
-    if (!x_dev || !v_dev || !f_dev || !box || !p || !chain_state_dev) return fail(-22, "null argument");
-    if (n_steps < 0 || n_steps > 0x3fffffff) return fail(-22, "n_steps out of range");
-    if (p->chain_length < 1 || p->chain_length > 16) return fail(-22, "chain_length must be in [1, 16]");
-    if ((r = check_model_inputs(h, species_dev))) return r;
+    hipStream_t st = (hipStream_t)stream;
     static const double YS1[] = {1.0};
     static const double YS3[] = {0.8289815435887510, -0.6579630871775020, 0.8289815435887510};
     static const double YS5[] = {0.2967324292201065, 0.2967324292201065, -0.1869297168804260, 0.2967324292201065,
                                  0.2967324292201065};                       // hack_integrator.py:183-187
-    const double* ys = p->num_yoshidasuzuki == 1 ? YS1 : p->num_yoshidasuzuki == 3 ? YS3 : p->num_yoshidasuzuki == 5 ? YS5 : nullptr;
-    if (!ys) return fail(-22, "Invalid Yoshida-Suzuki value. Allowed values are: 1,3,5");
-    if ((r = observers_check_run(h, box, species_dev))) return r;
-    if (h->force_source == GAMD_FORCE_WATER_CLASSICAL && !p->rigid_water)
-        return fail(-22, "the water classical force source needs rigid_water: the potential has no bond or angle term (same-molecule "
-                         "pairs are excluded), so only the constraints hold a molecule together");
-    if (h->force_source != GAMD_FORCE_NETWORK && (r = drive_check_run(h, box, species_dev))) return r;
-    DeviceGuard guard(h->dev);
-    InitStream init((hipStream_t)stream);
-    if ((r = set_box(h, box, (hipStream_t)stream))) return r;
-    hipStream_t st = (hipStream_t)stream;
+    const double* ys = !p ? nullptr : p->num_yoshidasuzuki == 1 ? YS1 : p->num_yoshidasuzuki == 3 ? YS3 : p->num_yoshidasuzuki == 5 ? YS5 : nullptr;
+    // the chain's own two refusals keep their places among the shared ones: behind the step count, behind the model's inputs
+    const char* bad_chain = p && (p->chain_length < 1 || p->chain_length > 16) ? "chain_length must be in [1, 16]" : nullptr;
+    const char* bad_ys = ys ? nullptr : "Invalid Yoshida-Suzuki value. Allowed values are: 1,3,5";
+    RunScope scope;
+    if ((r = begin_run(h, x_dev && v_dev && f_dev && box && p && chain_state_dev, n_steps, species_dev, box, p ? p->rigid_water : 0, st, scope,
+                       bad_chain, bad_ys)))
+        return r;
     NhcArgs a{};
     a.x = x_dev; a.v = v_dev; a.f = f_dev;
     if (!(p->mass_amu > 0.f)) return fail(-22, "mass_amu must be positive");
@@ -1253,18 +896,18 @@ int32_t gamd_profile(gamd_handle* h, const float* pos_dev, const uint8_t* specie
     const int max_ev = 64;
     hipEvent_t evs[max_ev];
     for (int i = 0; i < max_ev; ++i) HIP_TRY(hipEventCreate(&evs[i]));
-    int n_ev = 0;
-    std::vector<std::string> labels;
-    r = enqueue_forward(h, pos_dev, species_dev, out_norm_dev, nullptr, st, evs, &n_ev, &labels);
+    const ForwardCall c{pos_dev, species_dev, out_norm_dev, nullptr, st};
+    StageClock clock{h, st, evs};
+    r = enqueue_forward(h, c, clock);
     if (r == 0) {
         HIP_TRY(hipStreamSynchronize(st));
         std::string all;
         int cnt = 0;
-        for (int i = 1; i < n_ev && cnt < max_ms; ++i, ++cnt) {
+        for (int i = 1; i < clock.n_ev && cnt < max_ms; ++i, ++cnt) {
             float t = 0.f;
             HIP_TRY(hipEventElapsedTime(&t, evs[i - 1], evs[i]));
             ms[cnt] = t;
-            all += labels[i];
+            all += clock.labels[i];
             all += "\n";
         }
         *n_out = cnt;

@@ -1,5 +1,5 @@
 // gamd_host.h — the handle and the host-side helpers shared by the host translation units of libgamd_hip.so (gamd_api.hip,
-// observe.hip).  Not part of the C ABI (include/gamd_hip.h) and not exported: hidden visibility, the dynamic symbols stay as they were.
+// forward.hip, observe.hip).  Not part of the C ABI (include/gamd_hip.h) and not exported: hidden visibility, the dynamic symbols stay as they were.
 #pragma once
 #include "../../include/gamd_hip.h"
 #include "gamd_common.h"
@@ -137,21 +137,14 @@ int drive_enqueue(gamd_handle* h);
 struct gamd_handle {
     gamd_config cfg{};
     int dev = 0;
-    int n = 0, L = 0, n_feat = 44, n_cu = 256;   // n: atoms of ALL boxes together (n_boxes * n_per_box)
+    int n = 0, L = 0, n_cu = 256;               // n: atoms of ALL boxes together (n_boxes * n_per_box)
     int n_boxes = 1, n_per_box = 0;              // gamd_config.n_boxes: independent boxes evaluated in one set of launches
     bool use_small = false;                      // skin mode: the single-workgroup small-system path of neighbor.hip (decided once)
     DevBuf boxes_dev, box_shift;                 // n_boxes > 1: per-box dimensions (BoxRef::boxes), scratch of the row scan
     std::vector<float> boxes_host;               // [n_boxes][3] as last set
-    int H = 128, Eh = 128, HT = 1, EHT = 1;      // node width, edge-embedding width (PADDED to 128-blocks) and their block counts
-    int H_true = 128, Eh_true = 128, D_true = 128;   // encoding_size, edge_embedding_dim, hidden_dim as given (<= the padded ones)
-    int Dp = 128, DT = 1;                        // hidden_dim padded to 128-blocks; DT = 2: the kernels of wide_d.hip (fp32)
+    Route rt;                                    // gamd_route_host.h: padded widths, family flags, one kernel enumerator per stage — set by
+                                                 // gamd_create, again by gamd_finalize_weights once the state_dict says update_edge or not
     int norm_bn = 0;                             // graph_conv.norm_layers are BatchNorm1d (running statistics in the state_dict)
-    bool update_edge = false;                    // update_edge_emb=True: conv.<l>.edge_layer_norm keys in the state_dict
-    bool node_f16 = false;                       // node.hip's GEMMs in split-fp16 (reduced-precision edge modes, 128-wide kernels)
-    bool wide_enc = false, wide_conv = false;    // generic-width kernels of wide.hip
-    bool l0_hoist = false;                       // LJ, fp32, 128-wide: layer 0 in its three-GEMM form (conv_edge.hip, node.hip post(0))
-    bool ln_fold = false;                        // fp32, 128-wide, no update_edge / appended loops / keep_stages: edge LayerNorm folded
-                                                 // into the encoder's norm and every layer's first matrix (gamd_ln_fold_host.h)
     long long small_tile_limit = 512;            // fp32 path: at most this many 32-edge tiles -> conv_edge_small.hip
     std::map<std::string, HostTensor> host_w;
     bool finalized = false;
@@ -176,7 +169,7 @@ struct gamd_handle {
     // (NodeArgs::l0_gate): the other layers' tables are overwritten layer by layer, these are not.
     DevBuf l0_h, l0_hn, l0_S, l0_D, l0_P;
     // cells
-    DevBuf cell_cnt, cell_fill, cell_start;
+    DevBuf cell_start;                           // (the per-cell counts and fill cursors live behind the counters: set_box)
     int ncell_cap = 0;
     // edges
     long long e_cap = 0;
@@ -218,7 +211,7 @@ struct gamd_handle {
     // live timing of the conv-edge kernel (gamd_timing_*)
     bool timing = false;
     std::vector<hipEvent_t> tev;     // pairs (start, stop)
-    std::vector<int> tev_kind;       // per pair: 0 = conv-layer edge kernel(s) of layer l, 1 = edge encoder; -(l+1) coded below
+    std::vector<int> tev_kind;       // per pair: l = the conv-layer edge kernel of layer l, 100 = the edge encoder (StageClock)
     size_t tev_used = 0;
     // one event at the top of every MD step of an enqueued run (and one behind the last): gamd_timing_read_steps
     std::vector<hipEvent_t> sev;
@@ -227,6 +220,34 @@ struct gamd_handle {
     size_t sev_used = 0;
     static constexpr size_t EVENT_POOL_CAP = 1u << 16;   // timing left on across a long run: recording stops here (never unbounded)
 };
+
+// ---- one force evaluation on a stream (forward.hip) ----------------------------------------------------------------------------
+struct EdgeList { const int* centre; const int* neigh; long long n; };
+struct ForwardCall {
+    const float* pos = nullptr;
+    const uint8_t* species = nullptr;
+    float* out_norm = nullptr;                 // null: the handle's f_norm
+    float* out_denorm = nullptr;               // null: not written
+    hipStream_t st = nullptr;
+    const EdgeList* edges = nullptr;           // the caller's edge list in place of a neighbour search
+    const MdFuse* fuse = nullptr;              // skin mode: integrator halves that ride in the neighbour stage's first kernel
+    bool copy_counters = true;                 // fetch this call's counter block behind the last launch
+    bool l0_reuse = false;                     // NodeArgs::l0_gate: node(0) returns at once unless this call rebuilt the candidates
+};
+struct StageClock {
+    gamd_handle* h;
+    hipStream_t st;
+    hipEvent_t* evs = nullptr;                 // gamd_profile: one event per mark, labels[i] names the stage in front of evs[i]
+    int n_ev = 0;
+    std::vector<std::string> labels;
+    bool full = false;                         // the gamd_timing_* pool is full: the rest of the call is not timed
+    void mark(const char* label);
+    int begin(int kind);                       // 100: the edge encoder, l: the conv-layer edge kernel of layer l
+    int end();
+};
+NbrArgs nbr_args(gamd_handle* h, const float* pos_dev, const uint8_t* species_dev);
+// neighbour stage, then the network — or, classical, drive_enqueue — then the counter copy
+int enqueue_forward(gamd_handle* h, const ForwardCall& c, StageClock& clock, bool classical = false);
 
 inline BoxRef box_ref(const gamd_handle* h) {
     BoxRef r{};

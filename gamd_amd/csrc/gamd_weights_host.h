@@ -6,6 +6,7 @@
 #pragma once
 #include "../../include/gamd_hip.h"
 #include "gamd_ln_fold_host.h"
+#include "gamd_route_host.h"
 
 #include <algorithm>
 #include <cmath>
@@ -158,15 +159,6 @@ inline void permute_f2(const HostTensor& w, const HostTensor& b, HostTensor& wo,
         }
 }
 
-// ---- what the packing depends on: gamd_config and the flags gamd_create has decided, nothing else -------------------------
-struct WeightSpec {
-    int kind = GAMD_KIND_LJ, edge_dtype = GAMD_EDGE_F32, no_expand_edge = 0, self_loop_mode = 0, kernel_select = 0;
-    int n_layers = 0, n_feat = 44;
-    int H_true = 128, Eh_true = 128, D_true = 128;   // the state_dict's widths
-    int H = 128, Eh = 128, Dp = 128;                 // padded to the kernels' 128-blocks
-    bool wide_enc = false, wide_conv = false, ln_fold = false;
-};
-
 // ---- what comes out: offsets into the blob, in floats, under the names of the pointers they become (LayerDev, NodeLayerW and
 //      the handle's enc_* / dec_* / node_* members: gamd_finalize_weights walks these lists).  WOFF_NONE: a null pointer ---------
 constexpr size_t WOFF_NONE = ~(size_t)0;
@@ -193,60 +185,40 @@ struct PackedWeights {
     std::vector<float> blob;
     std::vector<LayerOff> layers;
     GlobalOff g;
-    // derived flags (wide_enc / wide_conv / ln_fold: the spec's, after the update_edge override)
-    bool update_edge = false, norm_bn = false, l0_hoist = false, node_f16 = false, wide_enc = false, wide_conv = false, ln_fold = false;
+    bool norm_bn = false;                      // graph_conv.norm_layers are BatchNorm1d (running statistics in the state_dict)
     float length_mean = 0.f, length_std = 1.f;
     HostRbfGrid rbf;                           // uniform = 1 when edge_expand.centers is a uniform grid
 };
 
 class WeightPacker {
 public:
-    WeightPacker(const WeightSpec& spec, const std::map<std::string, HostTensor>& w)
-        : s(spec), w(w), H(spec.H), Eh(spec.Eh), HT(spec.H / 128), EHT(spec.Eh / 128), Ht(spec.H_true), Et(spec.Eh_true),
-          Dt(spec.D_true), Dp(spec.Dp), DT(spec.Dp / 128) {}
+    WeightPacker(const RouteConfig& cfg, const Route& route, int n_layers, const std::map<std::string, HostTensor>& w)
+        : s(cfg), rt(route), n_layers(n_layers), w(w), H(route.H), Eh(route.Eh), HT(route.HT), EHT(route.EHT), Ht(route.H_true),
+          Et(route.Eh_true), Dt(route.D_true), Dp(route.Dp), DT(route.DT) {}
 
     PackedWeights run() { if (pack()) out.blob = std::move(bb.host); return std::move(out); }
 
 private:
     bool pack() {
-        out.wide_enc = s.wide_enc; out.wide_conv = s.wide_conv; out.ln_fold = s.ln_fold;
-        // Reduced-precision edge modes (bf16, split-fp16): the node kernel's five GEMMs run in split-fp16 too
-        // (fp32-grade results at 3/16 of the fp32 matrix time, node.hip and wide.hip's k_node_wide)
-        out.node_f16 = s.edge_dtype != GAMD_EDGE_F32;
-        // update_edge_emb=True checkpoints (WaterMDDynamicBoxNet(update_edge=True), nn_module.py:91-92): every conv layer owns an
-        // edge_layer_norm; LayerNorm(in_edge_feats) is applied to e_emb of width in_node_feats (:141), so the two must agree.
-        // Served by the generic-width kernels (wide.hip) for any width.
-        out.update_edge = w.count("graph_conv.conv.0.edge_layer_norm.weight") != 0;
-        if (out.update_edge) {
-            if (Ht != Et) return refuse(-22, "update_edge_emb needs encoding_size == edge_embedding_dim (got %d, %d)", (int)Ht, (int)Et);
-            if (s.edge_dtype != GAMD_EDGE_F32 || s.self_loop_mode)
-                return refuse(-22, "update_edge_emb is built for the fp32 edge MLP without appended self loops");
-            out.wide_enc = out.wide_conv = true;
-            out.ln_fold = false;
-        }
-        const bool lp128 = s.edge_dtype != GAMD_EDGE_F32 && !out.wide_conv;   // 128 / 128 / 128 expanded: the specialised kernels
+        if (rt.err) return refuse(rt.err, "%s", rt.msg);
+        const bool lp128 = s.edge_dtype != GAMD_EDGE_F32 && !rt.wide_conv;   // 128 / 128 / 128 expanded: the specialised kernels
         bf16_edges = lp128 && s.edge_dtype == GAMD_EDGE_BF16;                 // (any other width / feature set: wide_lp.hip)
         f16x3_edges = lp128 && s.edge_dtype == GAMD_EDGE_F16X3;
         edge_fmt = s.edge_dtype == GAMD_EDGE_BF16 ? block_bf16 : s.edge_dtype == GAMD_EDGE_F16X3 ? block_f16x3 : block_f32;
         edge_slot = s.edge_dtype == GAMD_EDGE_BF16 ? WH_FRAG_FLOATS / 2 : WH_FRAG_FLOATS;
         // BatchNorm checkpoints carry running statistics next to norm_layers' weight and bias
         out.norm_bn = w.count("graph_conv.norm_layers.0.running_mean") != 0;
-        // Layer-0 form (conv_edge.hip): every atom of an LJ model enters layer 0 with the same row node_emb (nn_module.py:681), so
-        // hn0 = norm_layers[0](node_emb) is one row and phi_edge of the aggregated messages is M0 sum_j T3_j + d_i c0.  The fp32
-        // 128-wide kernels only; not for update_edge_emb models (their layers read e_emb) nor under GAMD_KSEL_NO_LAYER0_HOIST.
-        out.l0_hoist = s.kind == GAMD_KIND_LJ && s.edge_dtype == GAMD_EDGE_F32 && !out.wide_conv && DT == 1 && !out.update_edge &&
-                       !(s.kernel_select & GAMD_KSEL_NO_LAYER0_HOIST);
-        if (out.l0_hoist && !(emb0 = get("node_emb", {1, Ht}, {1, H}))) return false;
+        if (rt.l0_hoist && !(emb0 = get("node_emb", {1, Ht}, {1, H}))) return false;
         // Folded edge LayerNorm: B = C W_e3, c = C b_e3 (the centred last encoder Linear, in double) for the layers' first matrices
-        if (out.ln_fold) {
+        if (rt.ln_fold) {
             const HostTensor *w3 = get("edge_encoder.mlp_layer.4.weight", {Et, Dt}, {Eh, Dp}), *b3 = get("edge_encoder.mlp_layer.4.bias", {Et}, {Eh});
             fold_g = get("edge_layer_norm.weight", {Et}, {Eh});
             fold_b = get("edge_layer_norm.bias", {Et}, {Eh});
             if (out.err) return false;
             lnf_center(w3->data.data(), b3->data.data(), (int)Et, fold_B, fold_c);
         }
-        out.layers.assign((size_t)s.n_layers, LayerOff{});
-        for (int l = 0; l < s.n_layers; ++l)
+        out.layers.assign((size_t)n_layers, LayerOff{});
+        for (int l = 0; l < n_layers; ++l)
             if (!pack_layer(l)) return false;
         return pack_encoder_decoder();
     }
@@ -255,7 +227,9 @@ private:
         const HostTensor *ea0w, *ea0b, *ea2w, *ea2b, *sw, *sb, *dw, *db, *t1w, *t1b, *t3w, *t3b, *pdw, *pdb, *pew, *peb, *phw, *phb, *ng, *nb;
     };
 
-    const WeightSpec& s;
+    const RouteConfig& s;
+    const Route& rt;                           // the family flags and widths every branch below reads
+    const int n_layers;
     const std::map<std::string, HostTensor>& w;
     const int64_t H, Eh, HT, EHT;              // padded widths the kernels work in
     const int64_t Ht, Et, Dt;                  // the state_dict's widths
@@ -321,9 +295,9 @@ private:
     // node-side matrices: the 128-wide node kernel (node.hip) runs on 16x16x4 MFMAs with its own operand order; the
     // generic-width node kernel of wide.hip keeps the 32x32x2 fragment blocks
     size_t put_node(const HostTensor* t, int64_t OB, int64_t KB) {
-        if (out.wide_conv) return put_blocks(t, OB, KB, out.node_f16 ? block_f16x3 : block_f32);
+        if (rt.wide_conv) return put_blocks(t, OB, KB, rt.node_f16 ? block_f16x3 : block_f32);
         const size_t o = bb.add(WH_FRAG_FLOATS);
-        if (out.node_f16) pack16_f16x3(t->data.data(), reinterpret_cast<uint16_t*>(bb.host.data() + o));
+        if (rt.node_f16) pack16_f16x3(t->data.data(), reinterpret_cast<uint16_t*>(bb.host.data() + o));
         else pack16(t->data.data(), bb.host.data() + o);
         return o;
     }
@@ -448,7 +422,7 @@ private:
         } else {
             // one contiguous run of blocks: W1[:, kb] (EHT) | W2 | W3 | W4[ob, :] (HT) -- the order the kernels stream them
             // (hidden_dim above 128, wide_d.hip: W1[:, kb] (EHT) | W2[db, :] (DT) | W3[ob][db] (DT x DT) | W4[ob][db] (HT x DT))
-            if (out.ln_fold) {
+            if (rt.ln_fold) {
                 // A_l = W1 diag(gamma) B and the extra K step's fragment (a_l, 0) take W1's place, b1'_l = b1 + W1 beta takes b1's
                 std::vector<double> A, av, b1f;
                 lnf_layer(t.ea0w->data.data(), t.ea0b->data.data(), fold_g->data.data(), fold_b->data.data(), fold_B, fold_c, A, av, b1f);
@@ -466,7 +440,7 @@ private:
             o.w3p = put_blocks(t.t1w, DT, DT);
             if (DT > 1) {
                 o.w4p = put_blocks(t.t3w, HT, DT);
-            } else if (out.wide_conv) {
+            } else if (rt.wide_conv) {
                 o.w4p = put_blocks(t.t3w, HT, 1);
                 // the same run of blocks for the opt-in 16-edge kernel (wide16.hip): W1[:, kb] | W2 | W3 chained, W4[ob, :] not
                 o.w16p = bb.add((size_t)(EHT + 2 + HT) * WH_FRAG_FLOATS);
@@ -487,11 +461,11 @@ private:
         if (out.norm_bn && !fold_batchnorm(l, t)) return false;
         if (bf16_edges) scale_for_exp2(t);
         LayerOff& o = out.layers[(size_t)l];
-        if (l == 0 && out.l0_hoist) pack_layer0_form(t, o);
+        if (l == 0 && rt.l0_hoist) pack_layer0_form(t, o);
         pack_edge_matrices(t, o);
         o.b1 = put_vec(t.ea0b); o.b3 = put_vec(t.t1b); o.b4 = put_vec(t.t3b);
         o.node.ln_g = put_vec(t.ng); o.node.ln_b = put_vec(t.nb);
-        if (out.update_edge) {
+        if (rt.update_edge) {
             const std::string p = "graph_conv.conv." + std::to_string(l);
             const HostTensor *eg = get(p + ".edge_layer_norm.weight", {Et}, {Eh}), *eb = get(p + ".edge_layer_norm.bias", {Et}, {Eh});
             if (out.err) return false;
@@ -537,7 +511,7 @@ private:
     }
 
     bool pack_encoder_decoder() {
-        const int F = s.n_feat;
+        const int F = rt.n_feat;
         const bool expand = !s.no_expand_edge;
         GlobalOff& g = out.g;
         const HostTensor *e0w = get("edge_encoder.mlp_layer.0.weight", {Dt, (int64_t)F}, {Dp, (int64_t)F}), *e0b = get("edge_encoder.mlp_layer.0.bias", {Dt}, {Dp});
@@ -558,12 +532,12 @@ private:
         else if (f16x3_edges) pack_enc1_f16x3(e0w->data.data(), F, reinterpret_cast<uint16_t*>(e1));
         else pack_enc1(e0w->data.data(), F, e1);
         // generic-width encoder in the reduced-precision modes: its two 128-wide GEMMs run in split-fp16 (wide.hip, e_format != 0)
-        const bool enc_wide_f16 = out.wide_enc && s.edge_dtype != GAMD_EDGE_F32;
+        const bool enc_wide_f16 = rt.wide_enc && s.edge_dtype != GAMD_EDGE_F32;
         const bool lp128 = bf16_edges || f16x3_edges;
         g.enc_w2p = lp128 ? put_edge(e2w) : enc_wide_f16 ? put_blocks(e2w, 1, 1, block_f16x3) : put_blocks(e2w, DT, DT);
         HostTensor e4w_c = *e4w, e4b_c = *e4b;
         if (!bf16_edges && !f16x3_edges) { center_rows(*e4w, *e4b, e4w_c, e4b_c); }
-        if (out.ln_fold) {
+        if (rt.ln_fold) {
             // the encoder needs |B x2 + c| only: R of B = Q R (its six all-zero blocks left out) and Q^T c take W3's and b3's places
             std::vector<double> Rm, cq;
             lnf_qr(fold_B, fold_c, Rm, cq);
@@ -593,8 +567,10 @@ private:
     }
 };
 
-inline PackedWeights pack_weights(const WeightSpec& spec, const std::map<std::string, HostTensor>& weights) {
-    return WeightPacker(spec, weights).run();
+// route: gamd_route(cfg, route_update_edge(weights)); a refused route comes back as the packing's refusal
+inline bool route_update_edge(const std::map<std::string, HostTensor>& weights) { return weights.count("graph_conv.conv.0.edge_layer_norm.weight") != 0; }
+inline PackedWeights pack_weights(const RouteConfig& cfg, const Route& route, int n_layers, const std::map<std::string, HostTensor>& weights) {
+    return WeightPacker(cfg, route, n_layers, weights).run();
 }
 
 #pragma GCC visibility pop

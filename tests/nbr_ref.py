@@ -89,7 +89,7 @@ def moved_beyond(p, r, box, skin):
     return ~(s <= skin_half2(skin))
 
 
-MARGIN_ULPS = 48          # gamd_api.hip GAMD_SKIN_MARGIN_EPS: the margin is 48 x 2^-24 x the longest box edge
+MARGIN_ULPS = 48          # forward.hip GAMD_SKIN_MARGIN_EPS: the margin is 48 x 2^-24 x the longest box edge
 
 
 def skin_margin(l_max):
@@ -98,7 +98,7 @@ def skin_margin(l_max):
 
 def build_radius(rc, skin, l_max=None):
     """The candidate radius as float32.  l_max None: rc + skin as a float32 sum, the rule without a margin (exact
-    arithmetic's triangle inequality); l_max = the longest box edge: gamd_api.hip's rc + skin + skin_margin(l_max), summed
+    arithmetic's triangle inequality); l_max = the longest box edge: forward.hip's rc + skin + skin_margin(l_max), summed
     in double and rounded once."""
     if l_max is None:
         return F(F(rc) + F(skin))

@@ -295,7 +295,7 @@ def test_the_restated_host_and_kernel_lines_are_the_sources():
     # SiLU as x * rcp(1 + exp2(-log2 e x)) (_silu) and the unscaled, uncentred packing of the 128-wide split family
     assert "sk.nl2e = gamd_f32x2_t{-1.4426950408889634f, -1.4426950408889634f};" in _csrc("conv_edge_f16x3.hip")
     assert "const float e = __builtin_amdgcn_exp2f(x * -1.4426950408889634f);" in com and "return x * __builtin_amdgcn_rcpf(1.0f + e);" in com
-    assert "if (!bf16_edges && !f16x3_edges) {" in api and "out.node_f16 = s.edge_dtype != GAMD_EDGE_F32;" in api
+    assert "if (!bf16_edges && !f16x3_edges) {" in api and "r.node_f16 = c.edge_dtype != GAMD_EDGE_F32;" in _csrc("gamd_route_host.h")
     assert "if (LP) gemm128_f16x3<false>((const f16x8*)w2, lane, X, acc);" in _csrc("wide.hip")        # GEMM 1 of the wide encoder stays fp32
 
 

@@ -6,7 +6,7 @@
   b. each of five subtly wrong masks changes the edge set of at least one of those fixtures -- so the GPU tests on the same
      fixtures (tests/test_gpu_nbr_cutoff.py) would catch a kernel path that evaluated the mask that way;
   c. the skin-limit fixture is not vacuous: no atom counts as moved, and with the candidate radius rc + skin a reuse step
-     misses edges in general 3-D directions; with the margin of gamd_api.hip it misses none.
+     misses edges in general 3-D directions; with the margin of forward.hip it misses none.
 
 Figures: profiles/nbr_cutoff_parity.md."""
 import numpy as np
@@ -185,7 +185,7 @@ def test_the_skin_limit_fixture_is_not_vacuous(flavour, L):
     d -= b64 * np.round(d / b64)
     general = (np.abs(d) > 0.2 * np.linalg.norm(d, axis=1, keepdims=True)).all(axis=1)
     assert 2 * int(general.sum()) >= missed.size
-    # the derived margin (gamd_api.hip) closes every one of them
+    # the derived margin (forward.hip) closes every one of them
     fixed, rebuilt = nr.reuse_edges(wb, wn, box, rc, skin, flavour, nr.build_radius(rc, skin, l_max))
     assert not rebuilt and np.array_equal(nr.edge_keys(fixed, n), exact)
     # how much of the margin the fixture needs: the largest float64 build distance among the missed pairs

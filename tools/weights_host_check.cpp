@@ -3,8 +3,10 @@
 //   weights_host_check pack  <case file> <blob file>   run pack_weights, write the blob, print the canonical table
 //   weights_host_check arith <case file>               the same, then the host arithmetic of whatever this configuration
 //                                                      forms against a naive restatement in double; "arith: ok" at the end
-// Case file (little endian): 16 int32 of the WeightSpec in declaration order, int32 tensor count, then per tensor
-// int32 name length, the name, int32 ndim, int64 dims, float32 data.
+// Case file (little endian): 16 int32 — kind, edge_dtype, no_expand_edge, self_loop_mode, kernel_select, n_layers, n_feat, the
+// three true and the three padded widths, and wide_enc, wide_conv, ln_fold as the writer expects gamd_create to decide them —,
+// int32 tensor count, then per tensor int32 name length, the name, int32 ndim, int64 dims, float32 data.  The configuration is
+// read back out of the first ten; the widths and flags the route (gamd_route_host.h) derives from it must then be the file's.
 // Table: "blob <floats>", "flags ...", "scalars ..." (bit patterns), one "layer <l> name=offset ..." per layer and "global ...",
 // offsets in floats as the device pointers see them (node.wpep of a hoisted layer 0 is M0), -1 for a null pointer; a refusal
 // prints "error <code> <text>" instead.
@@ -12,15 +14,22 @@
 
 #include <cinttypes>
 
-static bool read_case(const char* path, WeightSpec& s, std::map<std::string, HostTensor>& w) {
+struct Case { RouteConfig cfg; int n_layers = 0; };
+static bool read_case(const char* path, Case& c, std::map<std::string, HostTensor>& w) {
     FILE* f = std::fopen(path, "rb");
     if (!f) return false;
     int32_t v[16], n = 0;
     bool ok = std::fread(v, 4, 16, f) == 16 && std::fread(&n, 4, 1, f) == 1;
     if (ok) {
+        RouteConfig& s = c.cfg;
         s.kind = v[0]; s.edge_dtype = v[1]; s.no_expand_edge = v[2]; s.self_loop_mode = v[3]; s.kernel_select = v[4];
-        s.n_layers = v[5]; s.n_feat = v[6]; s.H_true = v[7]; s.Eh_true = v[8]; s.D_true = v[9]; s.H = v[10]; s.Eh = v[11]; s.Dp = v[12];
-        s.wide_enc = v[13] != 0; s.wide_conv = v[14] != 0; s.ln_fold = v[15] != 0;
+        c.n_layers = v[5]; s.use_bond = v[6] & 1;                  // n_feat: 44 or 4, + 1 with bonds
+        s.encoding_size = v[7]; s.edge_embedding_dim = v[8]; s.hidden_dim = v[9];
+        s.keep_stages = gamd_route(s, false).ln_fold && !v[15];   // the one thing a configuration can add to keep the fold off
+        const Route r = gamd_route(s, false);
+        const int derived[9] = {r.n_feat, r.H_true, r.Eh_true, r.D_true, r.H, r.Eh, r.Dp, (int)r.wide_enc, (int)r.wide_conv};
+        ok = !r.err && std::equal(derived, derived + 9, v + 6) && (int)r.ln_fold == v[15];
+        if (!ok) std::fprintf(stderr, "the case file's widths and flags are not what gamd_route derives from its configuration\n");
     }
     for (int32_t i = 0; ok && i < n; ++i) {
         int32_t len = 0, ndim = 0;
@@ -45,10 +54,10 @@ static bool read_case(const char* path, WeightSpec& s, std::map<std::string, Hos
 static uint32_t bits(float x) { uint32_t u; memcpy(&u, &x, 4); return u; }
 static long long shown(size_t off) { return off == WOFF_NONE ? -1 : (long long)off; }
 
-static void print_table(const PackedWeights& p) {
+static void print_table(const Route& r, const PackedWeights& p) {
     std::printf("blob %zu\n", p.blob.size());
-    std::printf("flags update_edge=%d norm_bn=%d l0_hoist=%d node_f16=%d wide_enc=%d wide_conv=%d ln_fold=%d\n", (int)p.update_edge,
-                (int)p.norm_bn, (int)p.l0_hoist, (int)p.node_f16, (int)p.wide_enc, (int)p.wide_conv, (int)p.ln_fold);
+    std::printf("flags update_edge=%d norm_bn=%d l0_hoist=%d node_f16=%d wide_enc=%d wide_conv=%d ln_fold=%d\n", (int)r.update_edge,
+                (int)p.norm_bn, (int)r.l0_hoist, (int)r.node_f16, (int)r.wide_enc, (int)r.wide_conv, (int)r.ln_fold);
     std::printf("scalars length_mean=%08x length_std=%08x rbf=%d,%08x,%08x,%08x,%08x,%08x\n", bits(p.length_mean), bits(p.length_std),
                 p.rbf.uniform, bits(p.rbf.c0), bits(p.rbf.delta), bits(p.rbf.A), bits(p.rbf.B), bits(p.rbf.C));
     for (size_t l = 0; l < p.layers.size(); ++l) {
@@ -124,8 +133,8 @@ static void check_permute_f2() {
     std::printf("arith: permute_f2 is the permutation 32 q + s <- 4 s + q\n");
 }
 
-static int arith(const WeightSpec& s, const std::map<std::string, HostTensor>& w, const PackedWeights& p) {
-    const int H = s.H, Ht = s.H_true, Eh = s.Eh, Et = s.Eh_true, Dp = s.Dp, Dt = s.D_true, HT = H / 128, EHT = Eh / 128, DT = Dp / 128;
+static int arith(const Case& s, const Route& r, const std::map<std::string, HostTensor>& w, const PackedWeights& p) {
+    const int H = r.H, Ht = r.H_true, Eh = r.Eh, Et = r.Eh_true, Dp = r.Dp, Dt = r.D_true, HT = r.HT, EHT = r.EHT, DT = r.DT;
     const float* B = p.blob.data();
     const std::vector<int> pos128 = image_position([](const float* W, float* o, int ld) { pack128(W, o, ld); });
     const std::vector<int> pos16 = image_position([](const float* W, float* o, int ld) { pack16(W, o, ld); });
@@ -149,7 +158,7 @@ static int arith(const WeightSpec& s, const std::map<std::string, HostTensor>& w
     }
 
     // 2. layer-0 form: M0 = W_pe diag(hn0) W4, c0 = W_pe (hn0 * b4) as a plain triple loop in double, rounded once
-    if (p.l0_hoist) {
+    if (r.l0_hoist) {
         const auto &emb = T("node_emb"), &pe = T("graph_conv.conv.0.phi_edge.weight"), &w4 = T("graph_conv.conv.0.theta_edge.mlp_layer.3.weight"),
                    &b4 = T("graph_conv.conv.0.theta_edge.mlp_layer.3.bias");
         std::vector<double> hn0((size_t)Ht);
@@ -181,7 +190,7 @@ static int arith(const WeightSpec& s, const std::map<std::string, HostTensor>& w
     }
 
     // 3. the centred last encoder Linear (fp32 kernels without the fold): columns of W' and b' sum to 0 over the true rows
-    const bool fp32_blocks = s.edge_dtype == GAMD_EDGE_F32 && !p.ln_fold;
+    const bool fp32_blocks = r.f32 && !r.ln_fold;
     if (fp32_blocks) {
         const std::vector<float> w3 = unpack_blocks(B + p.g.enc_w3p, EHT, DT, pos128);
         const float* b3 = B + p.g.enc_b3;
@@ -201,7 +210,7 @@ static int arith(const WeightSpec& s, const std::map<std::string, HostTensor>& w
     }
 
     // 4. zero padding of every padded tensor, where all of them are fp32 block images: the generic-width fp32 kernels
-    if (fp32_blocks && p.wide_conv) {
+    if (fp32_blocks && r.wide_conv) {
         bool ok = true;
         auto vec = [&](size_t off, int n, int n_true) { for (int i = n_true; i < n; ++i) ok = ok && bits(B[off + (size_t)i]) == 0; };
         auto mat = [&](size_t off, int OB, int KB, int rt, int ct) { ok = ok && zero_outside(unpack_blocks(B + off, OB, KB, pos128), 128 * OB, 128 * KB, rt, ct); };
@@ -232,13 +241,14 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "usage: weights_host_check pack <case file> <blob file> | arith <case file>\n");
         return 2;
     }
-    WeightSpec spec;
+    Case c;
     std::map<std::string, HostTensor> w;
-    if (!read_case(argv[2], spec, w)) { std::fprintf(stderr, "cannot read case file %s\n", argv[2]); return 2; }
-    const PackedWeights p = pack_weights(spec, w);
+    if (!read_case(argv[2], c, w)) { std::fprintf(stderr, "cannot read case file %s\n", argv[2]); return 2; }
+    const Route r = gamd_route(c.cfg, route_update_edge(w));
+    const PackedWeights p = pack_weights(c.cfg, r, c.n_layers, w);
     if (p.err) { std::printf("error %d %s\n", p.err, p.msg); return 0; }
-    print_table(p);
-    if (mode == "arith") return arith(spec, w, p);
+    print_table(r, p);
+    if (mode == "arith") return arith(c, r, w, p);
     FILE* f = std::fopen(argv[3], "wb");
     if (!f || std::fwrite(p.blob.data(), sizeof(float), p.blob.size(), f) != p.blob.size()) { std::fprintf(stderr, "cannot write %s\n", argv[3]); return 2; }
     std::fclose(f);
