@@ -66,6 +66,10 @@ class GamdWaterParams(C.Structure):
                 ("reserved", C.c_int32), ("alpha", C.c_double), ("k_cut", C.c_double), ("coulomb_const", C.c_double)]
 
 
+class GamdWaterPmeParams(C.Structure):
+    _fields_ = [("order", C.c_int32), ("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32)]
+
+
 class GamdMinimizeParams(C.Structure):
     _fields_ = [("tolerance", C.c_double), ("max_iter", C.c_int64), ("check_every", C.c_int64), ("dt_start", C.c_double),
                 ("dt_max", C.c_double), ("f_inc", C.c_double), ("f_dec", C.c_double), ("alpha_start", C.c_double),
@@ -125,6 +129,7 @@ SYMBOLS = {
     "gamd_minimize": (_i32, [_vp, _vp, C.POINTER(C.c_float), C.c_float, _vp, _vp, C.POINTER(GamdMinimizeParams), _vp, _vp]),
     "gamd_water_configure": (_i32, [_vp, C.POINTER(GamdWaterParams)]),
     "gamd_water_msite": (_i32, [_vp, C.c_double]),
+    "gamd_water_pme": (_i32, [_vp, C.POINTER(GamdWaterPmeParams)]),
     "gamd_water_reset": (_i32, [_vp]),
     "gamd_water_read": (_i32, [_vp, _vp, _vp, _vp, _i64, C.POINTER(_i64), C.POINTER(_i64), _vp, _i64]),
     "gamd_water_eval": (_i32, [_vp, _vp, _vp, C.POINTER(C.c_float), C.c_float, _vp, _vp, _vp]),

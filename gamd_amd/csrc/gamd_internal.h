@@ -661,7 +661,10 @@ struct WaterArgs {
     long long slot;            // row of this sample
     long long g;               // completed MD steps at this sample
 };
-int launch_water_classical(const WaterArgs& a, hipStream_t st);
+// `pme` (gamd_water_pme; its w is `a` with kslices = 1 and kblocks = pme_blocks): launch_water_pme stands where the three
+// reciprocal launches are; null: the plain sum, launch for launch as it was
+struct PmeArgs;
+int launch_water_classical(const WaterArgs& a, hipStream_t st, const PmeArgs* pme = nullptr);
 // k_water_rho, k_water_sk, k_water_recip alone, with launch_water_classical's checks for them: a.rpart (and a.sk, a.ublk) from a.x
 int launch_water_recip(const WaterArgs& a, hipStream_t st);
 // k_water_sk alone (it reads no positions): a.sk and a.ublk from a.rho_partial, for the water minimiser's own rho and force passes
@@ -699,7 +702,7 @@ inline int pass_k_geometry(const WaterArgs& a, long long T, bool chunked) {
 // pass of water_classical.hip (tiles, slices and arithmetic of k_water_pairs; forces only) into a.part, launch_water_recip, then
 // per atom the pair slices and the k slices added in order from 0, f_cl to a.f_cl and (float)f_cl to f_out ([n][3], the
 // caller's atom order).  a.f, a.blk, a.rows, a.steps, a.slot and a.g are not used.  Five launches, plain stores.
-int launch_water_drive(const WaterArgs& a, float* f_out, hipStream_t st);
+int launch_water_drive(const WaterArgs& a, float* f_out, hipStream_t st, const PmeArgs* pme = nullptr);
 
 // ---- the TIP4P M-site in the water classical potential (water_msite.hip) ------------------------------
 // The potential of WaterArgs with the negative charge on a virtual site M = O' + w_h (d_1 + d_2) of every molecule
@@ -716,9 +719,31 @@ struct W4Args {
     double* ljpart;            // [n_boxes][slices][n_per_box / 3][W4_LJ]
 };
 // k_w4_sites, k_w4_pairs, k_w4_lj, k_w4_rho, k_water_sk, k_w4_recip, k_w4_atoms, k_water_final: launch_water_classical's row and f_cl
-int launch_w4_classical(const W4Args& a, hipStream_t st);
+int launch_w4_classical(const W4Args& a, hipStream_t st, const PmeArgs* pme = nullptr);
 // ... the first six and k_w4_drive: launch_water_drive's f_cl and f_out (the energies of the pair pass are computed and not read)
-int launch_w4_drive(const W4Args& a, float* f_out, hipStream_t st);
+int launch_w4_drive(const W4Args& a, float* f_out, hipStream_t st, const PmeArgs* pme = nullptr);
+
+// ---- smooth particle-mesh Ewald for the water classical potential (water_pme.hip) -----------------------
+// A second producer of w.rpart and w.ublk (gamd_water_pme): instead of k_water_rho, k_water_sk and
+// k_water_recip (or their site twins) the charges z (-2, +1) of the positions — w.x, or `sites` for the M-site form — are spread
+// on a grid of nx x ny x nz points per box in 64-bit integers, transformed, multiplied by the influence function and
+// transformed back, and the per-atom gradient sums are gathered into w.rpart with w.kslices = 1, scaled so that k_water_atoms,
+// k_wsrc_atoms, k_w4_atoms and k_w4_drive form the force with the arithmetic they have; the block sums of the reciprocal
+// energy go to w.ublk with w.kblocks = pme_blocks(nx, ny, nz), scaled so that k_water_final reads them unchanged.  Nothing of
+// w.kvec, w.rho_partial, w.sk, w.n_k, w.kchunk is read.  Ten launches on `st`: clear, spread, three line passes, the
+// convolution, three line passes, gather.
+struct PmeArgs {
+    WaterArgs w;
+    const double* sites;       // [n][3] the charge sites k_w4_sites left, or null: the fp32 positions w.x
+    int order;                 // 4 or 6
+    int nx, ny, nz;            // each of 8, 16, 32, 64, 128
+    unsigned long long* gq;    // [n_boxes][nx][ny][nz] the spread, quanta of 2^-50 q_H as two's complement (cleared every sample)
+    double* gc;                // [n_boxes][nx][ny][nz][2] the transform, (re, im)
+    const double* tw;          // [64][2] (cos, -sin)(2 pi j / 128)
+    const double* mod;         // [nx + ny + nz] the interpolation moduli of the three axes
+};
+inline int pme_blocks(int nx, int ny, int nz) { const long long g = (long long)nx * ny * nz / 256; return (int)(g < 128 ? g : 128); }
+int launch_water_pme(const PmeArgs& p, hipStream_t st);
 
 // ---- molecular virial of the water classical potential (water_virial.hip) ------------------------------
 // The virial log of gamd_water_virial: launched BEHIND launch_water_classical / launch_w4_classical

@@ -8,6 +8,7 @@
 // sample, one read call and one eval call (potential_*).
 #include "gamd_host.h"
 #include "gamd_minimize_host.h"
+#include "gamd_pme_dev.h"
 
 #include <algorithm>
 #include <array>
@@ -107,6 +108,9 @@ struct WaterClassical : PotentialLog {
     bool vwork = false;                // the virial's work buffers are wanted: the log has been on, or gamd_water_virial_eval called
     DevBuf vrows;                      // the virial log, slot for slot with rows
     DevBuf vpart, vljpart, vublk, vblk, veval_rows;     // one evaluation, and the eval call's row
+    int pme_order = 0, pme_n[3] = {0, 0, 0};            // gamd_water_pme: the spline order (0 = the plain sum) and the grid per box
+    DevBuf pme_gq, pme_gc;             // order != 0: per box and grid point, the integer spread and the complex transform (water_pme.hip)
+    DevBuf pme_tw, pme_mod;            // ... the twiddles and the three axes' moduli, uploaded by gamd_water_pme
 };
 
 // energy minimiser (gamd_minimize, minimize.hip): no observer — no clock, no entry in observer_list() — but a user of the
@@ -194,6 +198,8 @@ ObsBufs minimize_bufs(gamd_handle* h) {
 // force pass are as many as the pair slices, the blocks of the rho(k) pass the structure sampler's
 int water_kchunk(const gamd_handle* h, int n_k) { const int S = classical_slices(h); return std::max(1, (n_k + S - 1) / S); }
 
+size_t water_pme_blocks(const WaterClassical& wc) { return wc.pme_order ? (size_t)pme_blocks(wc.pme_n[0], wc.pme_n[1], wc.pme_n[2]) : 0; }
+
 ObsBufs water_bufs(gamd_handle* h) {
     WaterClassical& wc = h->obs->wc;
     const size_t nb = (size_t)h->n_boxes, n = (size_t)h->n, K = (size_t)wc.n_k;
@@ -202,7 +208,11 @@ ObsBufs water_bufs(gamd_handle* h) {
     t.insert(t.begin() + 6, {{&wc.kvec, sizeof(int) * 3 * K, false},                                         // behind blk; uploaded by water_klist_apply
                              {&wc.rho_partial, sizeof(double) * 2 * nb * (size_t)struct_rho_blocks(h) * K, false},
                              {&wc.sk, sizeof(double) * 3 * nb * K, false},
-                             {&wc.ublk, sizeof(double) * nb * ((K + 255) / 256), false}});
+                             {&wc.ublk, sizeof(double) * nb * std::max((K + 255) / 256, water_pme_blocks(wc)), false}});
+    // particle-mesh Ewald's own: nothing while the plain sum is in force
+    const size_t G = wc.pme_order ? (size_t)wc.pme_n[0] * (size_t)wc.pme_n[1] * (size_t)wc.pme_n[2] : 0;
+    t.push_back({&wc.pme_gq, sizeof(unsigned long long) * nb * G, false});
+    t.push_back({&wc.pme_gc, sizeof(double) * 2 * nb * G, false});
     // the M-site's own: nothing while the potential is 3-site
     const size_t m = wc.w_h != 0.0 ? 1 : 0;
     t.push_back({&wc.sites, m * sizeof(double) * 3 * n, false});
@@ -482,7 +492,19 @@ struct WaterPotential {
         const WaterClassical& wc = state(h);
         return W4Args{a, wc.w_h, 1.0 - 2.0 * wc.w_h, (classical_chunk(h) + 2) / 3, wc.sites.as<double>(), wc.ljpart.as<double>()};
     }
+    // particle-mesh Ewald in force (gamd_water_pme): `a` with one k slice and the convolution's blocks, the sites of the site model
+    static PmeArgs pme(const gamd_handle* h, const Args& a) {
+        const WaterClassical& wc = state(h);
+        PmeArgs p{a, wc.w_h != 0.0 ? wc.sites.as<double>() : nullptr, wc.pme_order, wc.pme_n[0], wc.pme_n[1], wc.pme_n[2],
+                  wc.pme_gq.as<unsigned long long>(), wc.pme_gc.as<double>(), wc.pme_tw.as<double>(), wc.pme_mod.as<double>()};
+        p.w.kslices = 1; p.w.kblocks = (int)water_pme_blocks(wc);
+        return p;
+    }
     static int launch(const gamd_handle* h, const Args& a, hipStream_t st) {
+        if (state(h).pme_order) {
+            const PmeArgs p = pme(h, a);
+            return state(h).w_h != 0.0 ? launch_w4_classical(msite(h, p.w), st, &p) : launch_water_classical(p.w, st, &p);
+        }
         return state(h).w_h != 0.0 ? launch_w4_classical(msite(h, a), st) : launch_water_classical(a, st);
     }
     // the virial's kernels behind launch() on the same argument block (water_virial.hip): the row of a.slot into `vrows`
@@ -505,6 +527,7 @@ struct WaterPotential {
         WaterClassical& wc = state(h);
         if (!species_dev) return fail(-22, "water classical potential: the charges need species (O = 1, H = 0, atoms ordered O,H,H)");
         if (int r = potential_check_box(h, wc, who, box)) return r;
+        if (wc.pme_order) return 0;                         // particle-mesh Ewald: no k-vector list, k_cut is not read
         int n2max = wc.n2max;
         std::vector<int> kv;
         if (int r = water_klist(wc.k_cut, box, h->n_boxes, &n2max, &kv)) return r;
@@ -512,6 +535,10 @@ struct WaterPotential {
     }
     // a force source as well (potential_drive): the forces alone, rounded to fp32, into the run's f
     static int drive(const gamd_handle* h, const Args& a, float* f_out, hipStream_t st) {
+        if (state(h).pme_order) {
+            const PmeArgs p = pme(h, a);
+            return state(h).w_h != 0.0 ? launch_w4_drive(msite(h, p.w), f_out, st, &p) : launch_water_drive(p.w, f_out, st, &p);
+        }
         return state(h).w_h != 0.0 ? launch_w4_drive(msite(h, a), f_out, st) : launch_water_drive(a, f_out, st);
     }
 };
@@ -1195,12 +1222,12 @@ int32_t gamd_water_configure(gamd_handle* h, const gamd_water_params* p) {
     int n2max = wc.n2max;
     std::vector<int> kv;
     const bool have_box = h->boxes_host.size() == 3 * (size_t)h->n_boxes;
-    if (have_box)
+    if (have_box && !wc.pme_order)                          // (particle-mesh Ewald is sticky and reads no list: k_cut is kept for order 0)
         if (int r = water_klist(p->k_cut, h->boxes_host.data(), h->n_boxes, &n2max, &kv)) return r;
     wc.q_h = p->q_h; wc.sigma = p->sigma_o; wc.epsilon = p->epsilon_o; wc.r_cut = p->r_cut; wc.r_switch = p->r_switch;
     wc.shift = p->shift ? 1 : 0; wc.alpha = p->alpha; wc.k_cut = p->k_cut; wc.coulomb = p->coulomb_const;
     wc.params_set = true;
-    if (have_box)
+    if (have_box && !wc.pme_order)
         if (int r = water_klist_apply(h, n2max, kv)) return r;
     return potential_configure<WaterPotential>(h, OBS_WATER, p->interval, p->max_samples, "gamd_water_configure");
 }
@@ -1222,6 +1249,49 @@ int32_t gamd_water_msite(gamd_handle* h, double w_h) {
         wc.w_h = before;
         return fail(-12, "gamd_water_msite: allocation failed");
     }
+    return 0;
+}
+
+int32_t gamd_water_pme(gamd_handle* h, const gamd_water_pme_params* p) {
+    if (!h) return fail(-22, "null handle");
+    if (!p) return fail(-22, "null argument");
+    if (h->cfg.kind != GAMD_KIND_WATER)
+        return fail(-22, "gamd_water_pme: a GAMD_KIND_LJ handle has no charges and no reciprocal sum (GAMD_KIND_WATER handles only)");
+    WaterClassical& wc = h->obs->wc;
+    if (!wc.params_set) return fail(-22, "gamd_water_pme needs the parameters of a gamd_water_configure call (interval 0 will do)");
+    if (h->pending.active) return fail(-22, "an MD run is still enqueued: call gamd_sync_status before gamd_water_pme");
+    if (p->order == 0) {                                    // the plain sum: the list of k_cut is built by the next run or eval
+        wc.pme_order = 0;
+        for (DevBuf* b : {&wc.pme_gq, &wc.pme_gc, &wc.pme_tw, &wc.pme_mod}) b->release();
+        return 0;
+    }
+    if (!gamd_pme_order_ok(p->order))
+        return fail(-22, "gamd_water_pme: order = %d is not 0 (off), 4 or 6 (odd orders are not offered: their interpolation modulus "
+                         "vanishes at m = n / 2)", (int)p->order);
+    const int n[3] = {p->nx, p->ny, p->nz};
+    for (int d = 0; d < 3; ++d)
+        if (!gamd_pme_length_ok(n[d]))
+            return fail(-22, "gamd_water_pme: grid length n%c = %d is not one of 8, 16, 32, 64, 128", "xyz"[d], n[d]);
+    if (wc.virial)
+        return fail(-22, "gamd_water_pme: the virial log is armed (gamd_water_virial) and there is no PME virial: switch the log off first");
+    wc.pme_order = p->order;
+    for (int d = 0; d < 3; ++d) wc.pme_n[d] = n[d];
+    DeviceGuard guard(h->dev);
+    InitStream init(h->init_stream);
+    std::vector<double> tw = gamd_pme_twiddles(), mod;
+    for (int d = 0; d < 3; ++d) {
+        const std::vector<double> m = gamd_pme_moduli(p->order, n[d]);
+        mod.insert(mod.end(), m.begin(), m.end());
+    }
+    // 24 bytes per box and grid point, and the tables
+    if (bufs_ensure_work(water_bufs(h)) || wc.pme_tw.ensure(sizeof(double) * tw.size(), true) ||
+        wc.pme_mod.ensure(sizeof(double) * mod.size(), true)) {
+        wc.pme_order = 0;                                   // the plain sum: the grids of a setting before may be gone
+        for (DevBuf* b : {&wc.pme_gq, &wc.pme_gc, &wc.pme_tw, &wc.pme_mod}) b->release();
+        return fail(-12, "gamd_water_pme: allocation of the %d x %d x %d grids of %d boxes failed", n[0], n[1], n[2], h->n_boxes);
+    }
+    HIP_TRY(init_upload(wc.pme_tw.p, tw.data(), sizeof(double) * tw.size()));
+    HIP_TRY(init_upload(wc.pme_mod.p, mod.data(), sizeof(double) * mod.size()));
     return 0;
 }
 
@@ -1249,6 +1319,9 @@ int32_t gamd_water_virial(gamd_handle* h, int32_t on) {
     if (!wc.params_set) return fail(-22, "gamd_water_virial needs the parameters of a gamd_water_configure call (interval 0 will do)");
     if (h->pending.active) return fail(-22, "an MD run is still enqueued: call gamd_sync_status before gamd_water_virial");
     if (!on) { wc.virial = false; return 0; }               // off: what was logged stays readable
+    if (wc.pme_order)
+        return fail(-22, "gamd_water_virial: particle-mesh Ewald is on (gamd_water_pme, order %d) and there is no PME virial: the log "
+                         "needs the plain sum (gamd_water_pme with order 0)", wc.pme_order);
     const bool before = wc.virial, work_before = wc.vwork;
     wc.virial = wc.vwork = true;
     DeviceGuard guard(h->dev);
@@ -1294,6 +1367,9 @@ int32_t gamd_water_virial_eval(gamd_handle* h, const float* pos_dev, const uint8
     if (h->cfg.kind != GAMD_KIND_WATER) return fail(-22, "gamd_water_virial_eval: a GAMD_KIND_LJ handle has no molecules (GAMD_KIND_WATER handles only)");
     WaterClassical& wc = h->obs->wc;
     if (h->pending.active) return fail(-22, "an MD run is still enqueued: call gamd_sync_status before gamd_water_virial_eval");
+    if (wc.pme_order)
+        return fail(-22, "gamd_water_virial_eval: particle-mesh Ewald is on (gamd_water_pme, order %d) and there is no PME virial: "
+                         "evaluate under the plain sum (gamd_water_pme with order 0)", wc.pme_order);
     wc.vwork = true;                                        // the work buffers are ensured with the potential's (potential_eval)
     std::vector<double> row;
     const size_t nv = WATER_VIR_ROW * (size_t)h->n_boxes;
@@ -1337,6 +1413,9 @@ int32_t gamd_water_minimize(gamd_handle* h, float* x_dev, const uint8_t* species
     if (wc.w_h != 0.0)
         return fail(-22, "gamd_water_minimize: the TIP4P M-site is set (gamd_water_msite, w_h = %.9g) and there is no 4-site rigid minimiser: "
                          "minimise with w_h = 0, set the weight, then take f from gamd_water_eval", wc.w_h);
+    if (wc.pme_order)
+        return fail(-22, "gamd_water_minimize: particle-mesh Ewald is on (gamd_water_pme, order %d) and there is no PME minimiser: "
+                         "minimise under the plain sum, switch PME on, then take f from gamd_water_eval", wc.pme_order);
     WMinArgs m{};
     m.rc = 0.5 * r_hh;
     const double t = std::sqrt(r_oh * r_oh - m.rc * m.rc);

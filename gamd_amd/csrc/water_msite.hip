@@ -229,18 +229,21 @@ __global__ void __launch_bounds__(256) k_w4_drive(W4Args b, float* __restrict__ 
     f_out[3 * i] = (float)F[0]; f_out[3 * i + 1] = (float)F[1]; f_out[3 * i + 2] = (float)F[2];
 }
 
-// what both launchers check, and the five launches they share: sites, pairs, rho, sk, recip; *gp = the rows' geometry
-int w4_launch_passes(const W4Args& b, PassGeom* gp, hipStream_t st) {
+// what both launchers check, and the launches they share: sites, pairs, lj, rho, sk, recip — or, with `pme` (gamd_water_pme),
+// launch_water_pme on the sites in place of the last three; *gp = the rows' geometry
+int w4_launch_passes(const W4Args& b, PassGeom* gp, hipStream_t st, const PmeArgs* pme) {
     const WaterArgs& a = b.w;
-    if (pass_geometry(a, 3, gp) || pass_k_geometry(a, gp->T, true)) return -1;
+    if (pass_geometry(a, 3, gp) || (!pme && pass_k_geometry(a, gp->T, true))) return -1;
     const int nb = gp->nb, npb = gp->npb;
     const long long T = gp->T;
-    if (!a.x || !a.species || !a.kvec || !a.part || !a.rho_partial || !a.sk || !a.ublk || !a.rpart || !a.f_cl || !a.devflags) return -1;
+    if (!a.x || !a.species || !a.part || !a.ublk || !a.rpart || !a.f_cl || !a.devflags) return -1;
+    if (!pme && (!a.kvec || !a.rho_partial || !a.sk)) return -1;
     if (!b.sites || !b.ljpart || !(b.w_h > 0.0) || !(b.w_h < 0.5) || b.mchunk < 1 || (long long)a.slices * b.mchunk < npb / 3) return -1;
     const long long Tm = (npb / 3 + GAMD_PASS_TILE - 1) / GAMD_PASS_TILE;
     hipLaunchKernelGGL(k_w4_sites, dim3((unsigned)T, nb), dim3(256), 0, st, b); GAMD_CHECK_LAUNCH();
     hipLaunchKernelGGL(k_w4_pairs, dim3((unsigned)(T * a.slices), nb), dim3(256), 0, st, b); GAMD_CHECK_LAUNCH();
     hipLaunchKernelGGL(k_w4_lj, dim3((unsigned)(Tm * a.slices), nb), dim3(256), 0, st, b); GAMD_CHECK_LAUNCH();
+    if (pme) return launch_water_pme(*pme, st);             // (its `sites` are b.sites: the launchers below see to it)
     hipLaunchKernelGGL(k_w4_rho, dim3(a.rho_blocks, (a.n_k + 63) / 64, nb), dim3(256), 0, st, b); GAMD_CHECK_LAUNCH();
     if (int r = launch_water_sk(a, st)) return r;
     hipLaunchKernelGGL(k_w4_recip, dim3((unsigned)(T * a.kslices), nb), dim3(256), 0, st, b); GAMD_CHECK_LAUNCH();
@@ -249,19 +252,19 @@ int w4_launch_passes(const W4Args& b, PassGeom* gp, hipStream_t st) {
 
 }  // namespace
 
-int launch_w4_classical(const W4Args& b, hipStream_t st) {
+int launch_w4_classical(const W4Args& b, hipStream_t st, const PmeArgs* pme) {
     const WaterArgs& a = b.w;
     PassGeom g;
-    if (a.blocks < 1 || a.blocks > 65535 || a.slot < 0 || !a.blk || !a.rows) return -1;
-    if (int r = w4_launch_passes(b, &g, st)) return r;
+    if (a.blocks < 1 || a.blocks > 65535 || a.slot < 0 || !a.blk || !a.rows || (pme && pme->sites != b.sites)) return -1;
+    if (int r = w4_launch_passes(b, &g, st, pme)) return r;
     hipLaunchKernelGGL(k_w4_atoms, dim3(a.blocks, g.nb), dim3(256), 0, st, b); GAMD_CHECK_LAUNCH();
     return launch_water_final(a, st);
 }
 
-int launch_w4_drive(const W4Args& b, float* f_out, hipStream_t st) {
+int launch_w4_drive(const W4Args& b, float* f_out, hipStream_t st, const PmeArgs* pme) {
     PassGeom g;
-    if (!f_out) return -1;
-    if (int r = w4_launch_passes(b, &g, st)) return r;
+    if (!f_out || (pme && pme->sites != b.sites)) return -1;
+    if (int r = w4_launch_passes(b, &g, st, pme)) return r;
     hipLaunchKernelGGL(k_w4_drive, dim3((unsigned)g.T, g.nb), dim3(256), 0, st, b, f_out); GAMD_CHECK_LAUNCH();
     return 0;
 }

@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import GamdClassicalParams, GamdMinimizeParams, GamdWaterParams, GamdReportParams, GamdStructParams, GamdTrajParams, GamdConfig, GamdMdParams, GamdNhcParams, TRAJ_FIELDS, check
+from ._lib import GamdClassicalParams, GamdMinimizeParams, GamdWaterParams, GamdWaterPmeParams, GamdReportParams, GamdStructParams, GamdTrajParams, GamdConfig, GamdMdParams, GamdNhcParams, TRAJ_FIELDS, check
 from .weights import ModelConfig, infer_config, validate_state_dict
 
 ArrayLike = Union[np.ndarray, torch.Tensor]
@@ -399,6 +399,31 @@ COULOMB_KJ_NM = 138.935456                   # 1 / (4 pi eps0) in kJ nm / (mol e
 # available to compare against.
 TIP3P = dict(q_h=0.417, sigma_o=3.15075, epsilon_o=0.635968, m_site=0.0)
 TIP4PEW = dict(q_h=0.52422, sigma_o=3.16435, epsilon_o=0.680946, m_site=0.106676721)
+
+
+PME_LENGTHS = (8, 16, 32, 64, 128)                          # the grid lengths gamd_water_pme takes
+
+
+def pme_grid(alpha: float, box, tol: float, order: int = 6):
+    """The smallest admissible grid (nx, ny, nz) for ``water_classical_configure(..., pme=...)``: per axis the smallest power of
+    two in {8, ..., 128} with n >= 2 alpha L / (3 tol^(1/5)), OpenMM's rule for its PME grid (``alpha`` in the reciprocal of the
+    length unit of ``box``, one edge or three).  The rule was derived for B-splines of order 5 and is used here as a STARTING
+    POINT, not a guarantee: ``order`` 6 is usually more accurate than it promises and 4 less; profiles/run_water_pme.md has
+    measured errors against the plain sum.  ``order`` is checked (4 or 6) and otherwise not used.  ValueError where an axis
+    would need more than 128 points."""
+    if int(order) not in (4, 6):
+        raise ValueError(f"order = {order!r} is not 4 or 6 (odd orders are not offered)")
+    if not (float(alpha) > 0.0 and 0.0 < float(tol) < 1.0):
+        raise ValueError(f"alpha = {alpha!r} must be positive and tol = {tol!r} in (0, 1)")
+    edges = np.broadcast_to(np.asarray(box, dtype=np.float64).reshape(-1), (3,))
+    out = []
+    for L in edges:
+        need = 2.0 * float(alpha) * float(L) / (3.0 * float(tol) ** 0.2)
+        fits = [n for n in PME_LENGTHS if n >= need]
+        if not fits:
+            raise ValueError(f"an edge of {L} needs {need:.1f} grid points at alpha = {alpha}, tol = {tol}: more than {PME_LENGTHS[-1]}")
+        out.append(fits[0])
+    return tuple(out)
 
 
 class RunWaterClassical(RunClassical):
@@ -1146,7 +1171,7 @@ class GamdForce:
                                   epsilon_o: float = 0.635968, r_cut: Optional[float] = None, r_switch: float = 0.0,
                                   shift: bool = False, ewald_tol: float = 1e-10, alpha: Optional[float] = None,
                                   k_cut: Optional[float] = None, coulomb_const: float = COULOMB_KJ_NM,
-                                  length_per_nm: float = 0.0, m_site: float = 0.0, virial: bool = False) -> None:
+                                  length_per_nm: float = 0.0, m_site: float = 0.0, virial: bool = False, pme=None, pme_order: int = 6) -> None:
         """While configured, every ``interval``-th completed step of md_run / md_run_nhc (counted across calls, by a counter
         of its own) evaluates the classical potential of 3-site water in double on the device — O-O Lennard-Jones plus
         point charges q_H and q_O = -2 q_H by a plain Ewald sum (real space inside ``r_cut``, same-molecule exclusion,
@@ -1180,7 +1205,17 @@ class GamdForce:
         ``.pressure``), by kernels of their own behind the observer's, which change nothing the observer, a force source or
         the trajectory computes.  Every call states it: the default switches the log off.
 
-        The sum is the limit OpenMM's PME approximates, not PME.  Not built: PME, a 4-site minimiser, the pressure tensor,
+        ``pme`` = n or (nx, ny, nz) sums the reciprocal part by smooth particle-mesh Ewald (Essmann et al. 1995) of B-spline
+        order ``pme_order`` (4 or 6) on a grid of that many points per box and axis, each one of 8, 16, 32, 64, 128
+        (``pme_grid`` proposes one): O(N p^3 + G log G) per sample instead of O(N K), in double with an integer spread, so the
+        bits repeat as the plain sum's do.  ``k_cut`` is then not read and the limit of 131 072 k-vectors does not apply;
+        ``alpha``, ``r_cut`` and every other term are unchanged.  The observer, ``water_classical_forces`` and the
+        ``"water_classical"`` force source follow it, with and without ``m_site``; ``virial=True``, ``water_classical_virial``
+        and ``water_minimize`` refuse it (minimise under the plain sum, configure again with ``pme``, take ``f`` from
+        ``water_classical_forces``).  Every call states it: the default None is the plain sum, bit for bit what it was.
+
+        The plain sum is the limit OpenMM's PME approximates.  Not built: the PME virial, the PME minimiser, odd orders,
+        grids that are no power of two, real-to-complex transforms, a 4-site minimiser, the pressure tensor,
         a barostat; the long-range dispersion correction is ``lj_dispersion_correction`` on the host (``pressure(...,
         dispersion=True)``).  No parity with OpenMM is claimed.  Check the parameters against your OpenMM system before
         comparing energies."""
@@ -1195,6 +1230,31 @@ class GamdForce:
             k_cut = 2.0 * alpha * root if k_cut is None else float(k_cut)
         p = GamdWaterParams(int(interval), int(max_samples), float(q_h), sigma_o, float(epsilon_o), r_cut, float(r_switch),
                             int(bool(shift)), 0, float(alpha), float(k_cut), float(coulomb_const))
+        off = GamdWaterPmeParams(0, 0, 0, 0)
+        if pme is None:
+            grid = None
+            if getattr(self, "_water_pme", None) is not None:       # the plain sum again, in front of its k-vector list
+                check(self._lib.gamd_water_pme(self._h, C.byref(off)), "gamd_water_pme")
+                self._water_pme = None
+        else:
+            grid = tuple(int(g) for g in ((pme,) * 3 if np.ndim(pme) == 0 else pme))
+            if len(grid) != 3 or any(g not in PME_LENGTHS for g in grid):
+                raise ValueError(f"pme = {pme!r}: one grid length or three, each one of {PME_LENGTHS}")
+            if int(pme_order) not in (4, 6):
+                raise ValueError(f"pme_order = {pme_order!r} is not 4 or 6 (odd orders are not offered)")
+            if virial:
+                raise ValueError("virial=True needs the plain sum: there is no PME virial (pme=None)")
+            if getattr(self, "_water_pme", None) is None:
+                # PME needs an accepted parameter block in front of it, and with PME on k_cut is not read: the block is first
+                # taken with a k_cut whose list cannot be refused (1.01 pi / r_cut: every edge is at least 2 r_cut, so the
+                # list holds the shortest vectors and little more), then again as the caller states it
+                first = GamdWaterParams(0, 0, float(q_h), sigma_o, float(epsilon_o), r_cut, float(r_switch), int(bool(shift)), 0,
+                                        float(alpha), min(float(k_cut), 1.01 * np.pi / r_cut), float(coulomb_const))
+                check(self._lib.gamd_water_configure(self._h, C.byref(first)), "gamd_water_configure")
+                check(self._lib.gamd_water_virial(self._h, 0), "gamd_water_virial")
+            on = GamdWaterPmeParams(int(pme_order), *grid)
+            check(self._lib.gamd_water_pme(self._h, C.byref(on)), "gamd_water_pme")
+            self._water_pme = (int(pme_order), grid)
         check(self._lib.gamd_water_configure(self._h, C.byref(p)), "gamd_water_configure")
         check(self._lib.gamd_water_msite(self._h, float(m_site)), "gamd_water_msite")
         check(self._lib.gamd_water_virial(self._h, int(bool(virial))), "gamd_water_virial")

@@ -532,7 +532,8 @@ int32_t gamd_classical_eval(gamd_handle* h, const float* pos_dev, const float* b
  * gamd_water_configure (interval 0 will do).
  * gamd_water_minimize (below) relaxes a start and leaves x and f as this source expects them.  With gamd_water_msite the
  * source drives the 4-site (TIP4P) form of the potential by seven launches; a start is then minimised with w_h = 0 (see there).
- * Not built: PME, the 4-site minimiser, a barostat.  The default parameters of gamd_water_configure remain UNVERIFIED
+ * Particle-mesh Ewald is gamd_water_pme (below).  Not built: the PME virial, the PME minimiser, odd orders, grids that are no power of two, real-to-complex transforms,
+ * the 4-site minimiser, a barostat.  The default parameters of gamd_water_configure remain UNVERIFIED
  * against OpenMM. */
 enum { GAMD_FORCE_NETWORK = 0, GAMD_FORCE_CLASSICAL = 1, GAMD_FORCE_WATER_CLASSICAL = 2 };
 int32_t gamd_md_force_source(gamd_handle* h, int32_t source);
@@ -630,11 +631,41 @@ int32_t gamd_water_eval(gamd_handle* h, const float* pos_dev, const uint8_t* spe
  * run, w_h not finite, negative or >= 0.5.  -12 when the extra work buffers cannot be allocated: they are ensured here or at
  * run entry, never inside a run.  Device memory added while w_h != 0: 24 B per atom (the sites) and 32 B per molecule and pair
  * slice (the oxygen's Lennard-Jones force and energy, apart from the site force).
- * Not built: PME, the 4-site minimiser (the molecular virial is gamd_water_virial below; the long-range dispersion correction
+ * Particle-mesh Ewald (gamd_water_pme, below) serves the M-site form as well.  Not built: the PME virial, the PME minimiser, odd orders, grids that are no power of two, real-to-complex transforms,
+ * the 4-site minimiser (the molecular virial is gamd_water_virial below; the long-range dispersion correction
  * is a host function of the Python package).  The TIP4P-Ew parameters the Python
  * package offers (q_H = 0.52422 e, sigma_O = 3.16435 Angstrom, epsilon_O = 0.680946 kJ/mol, w_h = 0.106676721) were written
  * down from memory and are UNVERIFIED against OpenMM's tip4pew.xml; no parity with OpenMM is claimed. */
 int32_t gamd_water_msite(gamd_handle* h, double w_h);
+
+/* Smooth particle-mesh Ewald (Essmann et al. 1995) for the reciprocal part of the water classical potential: an optional,
+ * sticky property of the handle, switched as the M-site is.  order = 4 or 6 (the B-spline order; even orders only: for an odd
+ * order the interpolation modulus vanishes at m = n / 2) and a grid of nx x ny x nz points per box, each length one of 8, 16,
+ * 32, 64, 128 (every box of the handle has a grid of its own, of the same dimensions).  order = 0 switches PME off: the plain
+ * sum of gamd_water_configure is back, served by its own kernels bit for bit.  The setting survives later gamd_water_configure
+ * and gamd_water_msite calls.
+ * While PME is on the observer's sample, gamd_water_eval and the GAMD_FORCE_WATER_CLASSICAL source replace their three
+ * reciprocal launches by ten (clear, spread, three line passes, convolution, three line passes, gather), in double, by
+ * hand-written kernels on the caller's stream: the charges in units of q_H are spread with the B-spline weights as 64-bit
+ * integers (quantum 2^-50 q_H, so the grid does not depend on the order of the additions, and the same bits come back run
+ * after run), transformed by a radix-2 FFT per axis, multiplied by exp(-pi^2 |m|^2 / alpha^2) / (|m|^2 B(m)) with m_d / L_d
+ * per component, transformed back and differentiated analytically at the atoms.  U_recip = (C / 2 pi V) q_H^2 sum_m G |Q^|^2
+ * stands in column 2 of the row.  k_cut is not read and the limit of 131 072 k-vectors does not apply; alpha, r_cut, the
+ * real-space, exclusion and self terms are unchanged.  The accuracy is set by the grid and the order, not by ewald_tol: with
+ * alpha = 0.63 / Angstrom (r_cut 6.8, ewald_tol 1e-8) and order 6 a spacing of 0.45 Angstrom leaves an rms force difference of
+ * a few 1e-5 of the rms force against the plain sum (profiles/run_water_pme.md).
+ * Not built: the PME virial and the PME minimiser — gamd_water_virial(h, 1), gamd_water_virial_eval and gamd_water_minimize
+ * return -22 while PME is on, and gamd_water_pme returns -22 while the virial log is armed (messages name PME).  Start recipe:
+ * minimise under the plain sum, switch PME on, take f from gamd_water_eval.  Nor odd orders, grids that are no power of two,
+ * real-to-complex transforms.
+ * -22, with a message naming the reason: a null handle or block, a GAMD_KIND_LJ handle, no accepted gamd_water_configure, a
+ * pending run, an order other than 0, 4, 6, a grid length outside {8, 16, 32, 64, 128}.  -12 when the grids cannot be
+ * allocated (24 B per box and grid point, plus the tables); the handle is then on the plain sum. */
+typedef struct gamd_water_pme_params {
+    int32_t order;      /* 0 = off, 4, 6 */
+    int32_t nx, ny, nz; /* grid points per axis and box */
+} gamd_water_pme_params;
+int32_t gamd_water_pme(gamd_handle* h, const gamd_water_pme_params* p);
 
 /* The molecular virial of the water classical potential, and with it the scalar pressure of a box of rigid molecules (with
  * rigid molecules the atomic virial is not the pressure: the constraint forces carry the rest).  Per box, all sums in double,
