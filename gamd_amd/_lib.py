@@ -130,6 +130,8 @@ SYMBOLS = {
     "gamd_water_configure": (_i32, [_vp, C.POINTER(GamdWaterParams)]),
     "gamd_water_msite": (_i32, [_vp, C.c_double]),
     "gamd_water_pme": (_i32, [_vp, C.POINTER(GamdWaterPmeParams)]),
+    "gamd_water_cells": (_i32, [_vp, _i32]),
+    "gamd_water_cells_read": (_i32, [_vp, _vp, _i32, C.POINTER(_i32), _vp, _i64, _vp, _i64]),
     "gamd_water_reset": (_i32, [_vp]),
     "gamd_water_read": (_i32, [_vp, _vp, _vp, _vp, _i64, C.POINTER(_i64), C.POINTER(_i64), _vp, _i64]),
     "gamd_water_eval": (_i32, [_vp, _vp, _vp, C.POINTER(C.c_float), C.c_float, _vp, _vp, _vp]),

@@ -663,8 +663,10 @@ struct WaterArgs {
 };
 // `pme` (gamd_water_pme; its w is `a` with kslices = 1 and kblocks = pme_blocks): launch_water_pme stands where the three
 // reciprocal launches are; null: the plain sum, launch for launch as it was
+// `cells` (gamd_water_cells; `a` arrives with slices = 1): launch_water_cells stands where the pair launch is; null: all pairs
 struct PmeArgs;
-int launch_water_classical(const WaterArgs& a, hipStream_t st, const PmeArgs* pme = nullptr);
+struct WCellBufs;
+int launch_water_classical(const WaterArgs& a, hipStream_t st, const PmeArgs* pme = nullptr, const WCellBufs* cells = nullptr);
 // k_water_rho, k_water_sk, k_water_recip alone, with launch_water_classical's checks for them: a.rpart (and a.sk, a.ublk) from a.x
 int launch_water_recip(const WaterArgs& a, hipStream_t st);
 // k_water_sk alone (it reads no positions): a.sk and a.ublk from a.rho_partial, for the water minimiser's own rho and force passes
@@ -702,7 +704,7 @@ inline int pass_k_geometry(const WaterArgs& a, long long T, bool chunked) {
 // pass of water_classical.hip (tiles, slices and arithmetic of k_water_pairs; forces only) into a.part, launch_water_recip, then
 // per atom the pair slices and the k slices added in order from 0, f_cl to a.f_cl and (float)f_cl to f_out ([n][3], the
 // caller's atom order).  a.f, a.blk, a.rows, a.steps, a.slot and a.g are not used.  Five launches, plain stores.
-int launch_water_drive(const WaterArgs& a, float* f_out, hipStream_t st, const PmeArgs* pme = nullptr);
+int launch_water_drive(const WaterArgs& a, float* f_out, hipStream_t st, const PmeArgs* pme = nullptr, const WCellBufs* cells = nullptr);
 
 // ---- the TIP4P M-site in the water classical potential (water_msite.hip) ------------------------------
 // The potential of WaterArgs with the negative charge on a virtual site M = O' + w_h (d_1 + d_2) of every molecule
@@ -719,9 +721,9 @@ struct W4Args {
     double* ljpart;            // [n_boxes][slices][n_per_box / 3][W4_LJ]
 };
 // k_w4_sites, k_w4_pairs, k_w4_lj, k_w4_rho, k_water_sk, k_w4_recip, k_w4_atoms, k_water_final: launch_water_classical's row and f_cl
-int launch_w4_classical(const W4Args& a, hipStream_t st, const PmeArgs* pme = nullptr);
+int launch_w4_classical(const W4Args& a, hipStream_t st, const PmeArgs* pme = nullptr, const WCellBufs* cells = nullptr);
 // ... the first six and k_w4_drive: launch_water_drive's f_cl and f_out (the energies of the pair pass are computed and not read)
-int launch_w4_drive(const W4Args& a, float* f_out, hipStream_t st, const PmeArgs* pme = nullptr);
+int launch_w4_drive(const W4Args& a, float* f_out, hipStream_t st, const PmeArgs* pme = nullptr, const WCellBufs* cells = nullptr);
 
 // ---- smooth particle-mesh Ewald for the water classical potential (water_pme.hip) -----------------------
 // A second producer of w.rpart and w.ublk (gamd_water_pme): instead of k_water_rho, k_water_sk and
@@ -744,6 +746,30 @@ struct PmeArgs {
 };
 inline int pme_blocks(int nx, int ny, int nz) { const long long g = (long long)nx * ny * nz / 256; return (int)(g < 128 ? g : 128); }
 int launch_water_pme(const PmeArgs& p, hipStream_t st);
+
+// ---- the real-space pairs of the water classical potential over a cell table (water_cells.hip) ------------
+// A second producer of the pair rows w.part (gamd_water_cells): instead of k_water_pairs, k_wsrc_pairs
+// or k_w4_pairs a table of the box's atoms ordered by (cell, atom index) is built from the positions — w.x, or `sites` for the
+// M-site form — and every atom walks the atoms of its cell's neighbour cells, gamd_water_walk's body on the same doubles.  The
+// rows go to w.part as ONE pair slice: `w` arrives with w.slices = 1 and w.chunk = n_per_box, and k_water_atoms, k_wsrc_atoms,
+// k_w4_atoms and k_w4_drive run on it as they are.  Six launches on `st`: clear, count, scan, fill, rank, pairs.
+// Every value read from memory and then used as an address — an atom's cell, a cell's start, a slot, a table entry's atom index —
+// passes through GAMD_CHK_RANGE.
+enum { GAMD_CHK_WCELL_CELL = 151, GAMD_CHK_WCELL_START = 152, GAMD_CHK_WCELL_SLOT = 153, GAMD_CHK_WCELL_ATOM = 154 };
+struct WCellAtom { double x, y, z; int idx, o; };   // a table entry: the position as the walk reads it, the atom inside its box, O != 0
+struct WCellBufs {
+    double r_cut;              // the cutoff the cells per axis are computed from (gamd_cells_per_axis), length unit
+    int cap;                   // cells per box the tables below have room for
+    int* sticky;               // host-mapped (checked build)
+    int* start;                // [n_boxes][cap + 1] the counts per cell, then (scan) the first slot of every cell and n_per_box behind the last
+    int* fill;                 // [n_boxes][cap] members placed so far (cleared with the counts at the head of every sample)
+    int* cell_of;              // [n] the atom's cell inside its box
+    int* members;              // [n] per box and cell the atoms of the cell, in the order the atomics gave
+    int* order;                // [n] per box the atoms in table order: by (cell, atom index)
+    WCellAtom* table;          // [n] the table-ordered copy
+};
+// nout = WATER_PART (the observer, gamd_water_eval) or 3 (the force source); lj: the O-O term in the walk (3-site), else `sites`
+int launch_water_cells(const WaterArgs& w, const WCellBufs& c, const double* sites, int nout, bool lj, hipStream_t st);
 
 // ---- molecular virial of the water classical potential (water_virial.hip) ------------------------------
 // The virial log of gamd_water_virial: launched BEHIND launch_water_classical / launch_w4_classical

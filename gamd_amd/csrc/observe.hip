@@ -9,6 +9,7 @@
 #include "gamd_host.h"
 #include "gamd_minimize_host.h"
 #include "gamd_pme_dev.h"
+#include "gamd_cells_dev.h"
 
 #include <algorithm>
 #include <array>
@@ -111,6 +112,12 @@ struct WaterClassical : PotentialLog {
     int pme_order = 0, pme_n[3] = {0, 0, 0};            // gamd_water_pme: the spline order (0 = the plain sum) and the grid per box
     DevBuf pme_gq, pme_gc;             // order != 0: per box and grid point, the integer spread and the complex transform (water_pme.hip)
     DevBuf pme_tw, pme_mod;            // ... the twiddles and the three axes' moduli, uploaded by gamd_water_pme
+    bool cells = false;                // gamd_water_cells: the real-space pairs walk a per-box cell table (water_cells.hip)
+    bool cells_sampled = false;        // ... and the table holds a sample's or an eval call's atoms
+    int cell_cap = 0;                  // cells per box the tables have room for (grows with the boxes the handle is given)
+    std::vector<float> cell_box;       // [n_boxes][3] the edges the last table was (or the next will be) built for
+    DevBuf cell_start, cell_fill;      // cells on: per box and cell
+    DevBuf cell_of, cell_members, cell_order, cell_table;   // ... per atom
 };
 
 // energy minimiser (gamd_minimize, minimize.hip): no observer — no clock, no entry in observer_list() — but a user of the
@@ -213,6 +220,12 @@ ObsBufs water_bufs(gamd_handle* h) {
     const size_t G = wc.pme_order ? (size_t)wc.pme_n[0] * (size_t)wc.pme_n[1] * (size_t)wc.pme_n[2] : 0;
     t.push_back({&wc.pme_gq, sizeof(unsigned long long) * nb * G, false});
     t.push_back({&wc.pme_gc, sizeof(double) * 2 * nb * G, false});
+    // the cell table's own: nothing while the pairs are walked all against all
+    const size_t c = wc.cells ? 1 : 0, cap = (size_t)wc.cell_cap;
+    t.push_back({&wc.cell_start, c * sizeof(int) * nb * (cap + 1), false});
+    t.push_back({&wc.cell_fill, c * sizeof(int) * nb * cap, false});
+    for (DevBuf* b : {&wc.cell_of, &wc.cell_members, &wc.cell_order}) t.push_back({b, c * sizeof(int) * n, false});
+    t.push_back({&wc.cell_table, c * sizeof(WCellAtom) * n, false});
     // the M-site's own: nothing while the potential is 3-site
     const size_t m = wc.w_h != 0.0 ? 1 : 0;
     t.push_back({&wc.sites, m * sizeof(double) * 3 * n, false});
@@ -419,6 +432,32 @@ int water_klist_apply(gamd_handle* h, int n2max, const std::vector<int>& kv) {
     return 0;
 }
 
+// the cell tables (gamd_water_cells) for the boxes `box` ([n_boxes][3], every edge at least 2 r_cut): room for the box with the
+// most cells, the edges kept for gamd_water_cells_read.  No run is pending.
+int water_cells_apply(gamd_handle* h, const float* box) {
+    WaterClassical& wc = h->obs->wc;
+    int cap = 1;
+    for (int b = 0; b < h->n_boxes; ++b) {
+        int cells = 1;
+        for (int d = 0; d < 3; ++d) cells *= gamd_cells_per_axis((double)box[3 * b + d], wc.r_cut);
+        cap = std::max(cap, cells);
+    }
+    wc.cell_box.assign(box, box + 3 * (size_t)h->n_boxes);
+    wc.cells_sampled = false;
+    if (cap > wc.cell_cap || !wc.cell_start.p || !wc.cell_table.p) {
+        DeviceGuard guard(h->dev);
+        InitStream init(h->init_stream);
+        const int before = wc.cell_cap;
+        wc.cell_cap = std::max(cap, before);
+        for (DevBuf* b : {&wc.cell_start, &wc.cell_fill}) b->release();
+        if (bufs_ensure_work(water_bufs(h))) {
+            wc.cell_cap = before;
+            return fail(-12, "water classical potential: allocation of the cell tables (%d cells per box, %d boxes) failed", cap, h->n_boxes);
+        }
+    }
+    return 0;
+}
+
 // every edge of every box the caller hands in
 int check_box_positive(const gamd_handle* h, const float* box) {
     for (int k = 0; k < 3 * h->n_boxes; ++k)
@@ -490,7 +529,7 @@ struct WaterPotential {
     // the site model in force (gamd_water_msite): w_h = 0 is the 3-site launcher as it was
     static W4Args msite(const gamd_handle* h, const Args& a) {
         const WaterClassical& wc = state(h);
-        return W4Args{a, wc.w_h, 1.0 - 2.0 * wc.w_h, (classical_chunk(h) + 2) / 3, wc.sites.as<double>(), wc.ljpart.as<double>()};
+        return W4Args{a, wc.w_h, 1.0 - 2.0 * wc.w_h, (a.chunk + 2) / 3, wc.sites.as<double>(), wc.ljpart.as<double>()};
     }
     // particle-mesh Ewald in force (gamd_water_pme): `a` with one k slice and the convolution's blocks, the sites of the site model
     static PmeArgs pme(const gamd_handle* h, const Args& a) {
@@ -500,12 +539,28 @@ struct WaterPotential {
         p.w.kslices = 1; p.w.kblocks = (int)water_pme_blocks(wc);
         return p;
     }
-    static int launch(const gamd_handle* h, const Args& a, hipStream_t st) {
-        if (state(h).pme_order) {
+    // the cell table in force (gamd_water_cells): the pair rows are ONE slice (k_w4_lj's too), the table's buffers
+    static Args one_slice(const gamd_handle* h, const Args& a) {
+        Args b = a;
+        if (state(h).cells) { b.slices = 1; b.chunk = h->n_per_box; }
+        return b;
+    }
+    static WCellBufs cell_bufs(const gamd_handle* h) {
+        const WaterClassical& wc = state(h);
+        return WCellBufs{wc.r_cut, wc.cell_cap, h->sticky_dev, wc.cell_start.as<int>(), wc.cell_fill.as<int>(), wc.cell_of.as<int>(),
+                         wc.cell_members.as<int>(), wc.cell_order.as<int>(), wc.cell_table.as<WCellAtom>()};
+    }
+    static int launch(const gamd_handle* h, const Args& a0, hipStream_t st) {
+        WaterClassical& wc = state(h);
+        const Args a = one_slice(h, a0);
+        const WCellBufs cb = cell_bufs(h);
+        const WCellBufs* c = wc.cells ? &cb : nullptr;
+        if (c) wc.cells_sampled = true;
+        if (wc.pme_order) {
             const PmeArgs p = pme(h, a);
-            return state(h).w_h != 0.0 ? launch_w4_classical(msite(h, p.w), st, &p) : launch_water_classical(p.w, st, &p);
+            return wc.w_h != 0.0 ? launch_w4_classical(msite(h, p.w), st, &p, c) : launch_water_classical(p.w, st, &p, c);
         }
-        return state(h).w_h != 0.0 ? launch_w4_classical(msite(h, a), st) : launch_water_classical(a, st);
+        return wc.w_h != 0.0 ? launch_w4_classical(msite(h, a), st, nullptr, c) : launch_water_classical(a, st, nullptr, c);
     }
     // the virial's kernels behind launch() on the same argument block (water_virial.hip): the row of a.slot into `vrows`
     static int virial(const gamd_handle* h, const Args& a, const float* v, double mass_o, double mass_h, double* vrows, hipStream_t st) {
@@ -527,6 +582,8 @@ struct WaterPotential {
         WaterClassical& wc = state(h);
         if (!species_dev) return fail(-22, "water classical potential: the charges need species (O = 1, H = 0, atoms ordered O,H,H)");
         if (int r = potential_check_box(h, wc, who, box)) return r;
+        if (wc.cells)                                       // the cell tables sized for these boxes (grown here when they need more)
+            if (int r = water_cells_apply(h, box)) return r;
         if (wc.pme_order) return 0;                         // particle-mesh Ewald: no k-vector list, k_cut is not read
         int n2max = wc.n2max;
         std::vector<int> kv;
@@ -534,12 +591,17 @@ struct WaterPotential {
         return water_klist_apply(h, n2max, kv);
     }
     // a force source as well (potential_drive): the forces alone, rounded to fp32, into the run's f
-    static int drive(const gamd_handle* h, const Args& a, float* f_out, hipStream_t st) {
-        if (state(h).pme_order) {
+    static int drive(const gamd_handle* h, const Args& a0, float* f_out, hipStream_t st) {
+        WaterClassical& wc = state(h);
+        const Args a = one_slice(h, a0);
+        const WCellBufs cb = cell_bufs(h);
+        const WCellBufs* c = wc.cells ? &cb : nullptr;
+        if (c) wc.cells_sampled = true;
+        if (wc.pme_order) {
             const PmeArgs p = pme(h, a);
-            return state(h).w_h != 0.0 ? launch_w4_drive(msite(h, p.w), f_out, st, &p) : launch_water_drive(p.w, f_out, st, &p);
+            return wc.w_h != 0.0 ? launch_w4_drive(msite(h, p.w), f_out, st, &p, c) : launch_water_drive(p.w, f_out, st, &p, c);
         }
-        return state(h).w_h != 0.0 ? launch_w4_drive(msite(h, a), f_out, st) : launch_water_drive(a, f_out, st);
+        return wc.w_h != 0.0 ? launch_w4_drive(msite(h, a), f_out, st, nullptr, c) : launch_water_drive(a, f_out, st, nullptr, c);
     }
 };
 
@@ -1295,6 +1357,64 @@ int32_t gamd_water_pme(gamd_handle* h, const gamd_water_pme_params* p) {
     return 0;
 }
 
+int32_t gamd_water_cells(gamd_handle* h, int32_t on) {
+    if (!h) return fail(-22, "null handle");
+    if (h->cfg.kind != GAMD_KIND_WATER)
+        return fail(-22, "gamd_water_cells: a GAMD_KIND_LJ handle has no water potential (GAMD_KIND_WATER handles only; there is no cell "
+                         "table for the Lennard-Jones classical potential)");
+    WaterClassical& wc = h->obs->wc;
+    if (!wc.params_set) return fail(-22, "gamd_water_cells needs the parameters of a gamd_water_configure call (interval 0 will do)");
+    if (h->pending.active) return fail(-22, "an MD run is still enqueued: call gamd_sync_status before gamd_water_cells");
+    if (on != 0 && on != 1) return fail(-22, "gamd_water_cells: on = %d is not 0 (all pairs) or 1 (the cell table)", (int)on);
+    auto drop = [&]() {
+        wc.cells = wc.cells_sampled = false;
+        wc.cell_cap = 0; wc.cell_box.clear();
+        for (DevBuf* b : {&wc.cell_start, &wc.cell_fill, &wc.cell_of, &wc.cell_members, &wc.cell_order, &wc.cell_table}) b->release();
+    };
+    if (!on) { drop(); return 0; }
+    if (wc.cells) return 0;                                 // on already: the table of the last sample stays readable
+    wc.cells = true;
+    DeviceGuard guard(h->dev);
+    InitStream init(h->init_stream);
+    // 44 bytes per atom here; the per-cell tables are sized by the boxes of the next run or eval call (water_cells_apply)
+    if (bufs_ensure_work(water_bufs(h))) {
+        drop();
+        return fail(-12, "gamd_water_cells: allocation of the cell tables of %d atoms failed", h->n);
+    }
+    return 0;
+}
+
+int32_t gamd_water_cells_read(gamd_handle* h, void* stream, int32_t box, int32_t* nc, int32_t* start, int64_t max_start, int32_t* order,
+                              int64_t max_order) {
+    if (!h) return fail(-22, "null handle");
+    if (h->cfg.kind != GAMD_KIND_WATER) return fail(-22, "gamd_water_cells_read: GAMD_KIND_WATER handles only");
+    const WaterClassical& wc = h->obs->wc;
+    if (!wc.cells) return fail(-22, "gamd_water_cells_read: the cell table is off (gamd_water_cells)");
+    if (!wc.cells_sampled || wc.cell_box.size() != 3 * (size_t)h->n_boxes)
+        return fail(-22, "gamd_water_cells_read: nothing has been sampled since the cell table was switched on or the boxes were given");
+    if (box < 0 || box >= h->n_boxes) return fail(-22, "gamd_water_cells_read: box = %d outside [0, %d)", (int)box, h->n_boxes);
+    if (!nc) return fail(-22, "null argument");
+    long long cells = 1;
+    for (int d = 0; d < 3; ++d) {
+        nc[d] = gamd_cells_per_axis((double)wc.cell_box[3 * (size_t)box + d], wc.r_cut);
+        cells *= nc[d];
+    }
+    if (cells > wc.cell_cap) return fail(-1, "gamd_water_cells_read: %lld cells, the tables hold %d", cells, wc.cell_cap);
+    if (start && max_start < cells + 1) return fail(-22, "start has room for %lld elements, the box has %lld cells + 1", (long long)max_start, cells);
+    if (order && max_order < h->n_per_box) return fail(-22, "order has room for %lld elements, a box has %d atoms", (long long)max_order, h->n_per_box);
+    DeviceGuard guard(h->dev);
+    hipStream_t st = (hipStream_t)stream;
+    if (start)
+        HIP_TRY(hipMemcpyAsync(start, wc.cell_start.as<int>() + (size_t)box * ((size_t)wc.cell_cap + 1), sizeof(int) * (size_t)(cells + 1),
+                               hipMemcpyDeviceToHost, st));
+    if (order)
+        HIP_TRY(hipMemcpyAsync(order, wc.cell_order.as<int>() + (size_t)box * (size_t)h->n_per_box, sizeof(int) * (size_t)h->n_per_box,
+                               hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (int t = check_traps(h)) return t;
+    return 0;
+}
+
 int32_t gamd_water_reset(gamd_handle* h) { return observer_reset(h, OBS_WATER, "gamd_water_reset"); }
 
 int32_t gamd_water_read(gamd_handle* h, void* stream, int64_t* steps, double* rows, int64_t max_rows, int64_t* n_rows,
@@ -1416,6 +1536,9 @@ int32_t gamd_water_minimize(gamd_handle* h, float* x_dev, const uint8_t* species
     if (wc.pme_order)
         return fail(-22, "gamd_water_minimize: particle-mesh Ewald is on (gamd_water_pme, order %d) and there is no PME minimiser: "
                          "minimise under the plain sum, switch PME on, then take f from gamd_water_eval", wc.pme_order);
+    if (wc.cells)
+        return fail(-22, "gamd_water_minimize: the cell table is on (gamd_water_cells) and the minimiser's f is the all-pairs force bit for "
+                         "bit: minimise with the cells off, switch them on, then take f from gamd_water_eval");
     WMinArgs m{};
     m.rc = 0.5 * r_hh;
     const double t = std::sqrt(r_oh * r_oh - m.rc * m.rc);

@@ -181,12 +181,16 @@ int launch_water_final(const WaterArgs& a, hipStream_t st) {
     return 0;
 }
 
-int launch_water_classical(const WaterArgs& a, hipStream_t st, const PmeArgs* pme) {
+int launch_water_classical(const WaterArgs& a, hipStream_t st, const PmeArgs* pme, const WCellBufs* cells) {
     PassGeom g;
     if (pass_geometry(a, 3, &g) || (!pme && pass_k_geometry(a, g.T, true)) || a.blocks < 1 || a.blocks > 65535 || a.slot < 0) return -1;
     if (!a.x || !a.species || !a.part || !a.ublk || !a.rpart || !a.f_cl || !a.blk || !a.rows || !a.devflags) return -1;
     if (!pme && (!a.kvec || !a.rho_partial || !a.sk)) return -1;
-    hipLaunchKernelGGL(k_water_pairs, dim3((unsigned)(g.T * a.slices), g.nb), dim3(256), 0, st, a); GAMD_CHECK_LAUNCH();
+    if (cells) {                                            // gamd_water_cells: the pair rows over the cell table, one slice
+        if (int r = launch_water_cells(a, *cells, nullptr, WATER_PART, true, st)) return r;
+    } else {
+        hipLaunchKernelGGL(k_water_pairs, dim3((unsigned)(g.T * a.slices), g.nb), dim3(256), 0, st, a); GAMD_CHECK_LAUNCH();
+    }
     if (int r = pme ? launch_water_pme(*pme, st) : launch_water_recip(a, st)) return r;        // (its checks are among those above)
     hipLaunchKernelGGL(k_water_atoms, dim3(a.blocks, g.nb), dim3(256), 0, st, a); GAMD_CHECK_LAUNCH();
     hipLaunchKernelGGL(k_water_final, dim3((g.nb + 63) / 64), dim3(64), 0, st, a); GAMD_CHECK_LAUNCH();

@@ -61,11 +61,15 @@ __global__ void __launch_bounds__(256) k_wsrc_atoms(WaterArgs a, float* __restri
 
 }  // namespace
 
-int launch_water_drive(const WaterArgs& a, float* f_out, hipStream_t st, const PmeArgs* pme) {
+int launch_water_drive(const WaterArgs& a, float* f_out, hipStream_t st, const PmeArgs* pme, const WCellBufs* cells) {
     PassGeom g;
     if (pass_geometry(a, 3, &g)) return -1;
     if (!a.x || !a.species || !a.part || !a.rpart || !a.f_cl || !a.devflags || !f_out) return -1;
-    hipLaunchKernelGGL(k_wsrc_pairs, dim3((unsigned)(g.T * a.slices), g.nb), dim3(256), 0, st, a); GAMD_CHECK_LAUNCH();
+    if (cells) {                                            // gamd_water_cells: the force rows over the cell table, one slice
+        if (int r = launch_water_cells(a, *cells, nullptr, 3, true, st)) return r;
+    } else {
+        hipLaunchKernelGGL(k_wsrc_pairs, dim3((unsigned)(g.T * a.slices), g.nb), dim3(256), 0, st, a); GAMD_CHECK_LAUNCH();
+    }
     if (int r = pme ? launch_water_pme(*pme, st) : launch_water_recip(a, st)) return r;
     hipLaunchKernelGGL(k_wsrc_atoms, dim3((unsigned)g.T, g.nb), dim3(256), 0, st, a, f_out); GAMD_CHECK_LAUNCH();
     return 0;

@@ -230,8 +230,9 @@ __global__ void __launch_bounds__(256) k_w4_drive(W4Args b, float* __restrict__ 
 }
 
 // what both launchers check, and the launches they share: sites, pairs, lj, rho, sk, recip — or, with `pme` (gamd_water_pme),
-// launch_water_pme on the sites in place of the last three; *gp = the rows' geometry
-int w4_launch_passes(const W4Args& b, PassGeom* gp, hipStream_t st, const PmeArgs* pme) {
+// launch_water_pme on the sites in place of the last three; with `cells` (gamd_water_cells, one pair slice) launch_water_cells on
+// the sites in place of k_w4_pairs, `nout` accumulators; *gp = the rows' geometry
+int w4_launch_passes(const W4Args& b, PassGeom* gp, hipStream_t st, const PmeArgs* pme, const WCellBufs* cells, int nout) {
     const WaterArgs& a = b.w;
     if (pass_geometry(a, 3, gp) || (!pme && pass_k_geometry(a, gp->T, true))) return -1;
     const int nb = gp->nb, npb = gp->npb;
@@ -241,7 +242,11 @@ int w4_launch_passes(const W4Args& b, PassGeom* gp, hipStream_t st, const PmeArg
     if (!b.sites || !b.ljpart || !(b.w_h > 0.0) || !(b.w_h < 0.5) || b.mchunk < 1 || (long long)a.slices * b.mchunk < npb / 3) return -1;
     const long long Tm = (npb / 3 + GAMD_PASS_TILE - 1) / GAMD_PASS_TILE;
     hipLaunchKernelGGL(k_w4_sites, dim3((unsigned)T, nb), dim3(256), 0, st, b); GAMD_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_w4_pairs, dim3((unsigned)(T * a.slices), nb), dim3(256), 0, st, b); GAMD_CHECK_LAUNCH();
+    if (cells) {
+        if (int r = launch_water_cells(a, *cells, b.sites, nout, false, st)) return r;
+    } else {
+        hipLaunchKernelGGL(k_w4_pairs, dim3((unsigned)(T * a.slices), nb), dim3(256), 0, st, b); GAMD_CHECK_LAUNCH();
+    }
     hipLaunchKernelGGL(k_w4_lj, dim3((unsigned)(Tm * a.slices), nb), dim3(256), 0, st, b); GAMD_CHECK_LAUNCH();
     if (pme) return launch_water_pme(*pme, st);             // (its `sites` are b.sites: the launchers below see to it)
     hipLaunchKernelGGL(k_w4_rho, dim3(a.rho_blocks, (a.n_k + 63) / 64, nb), dim3(256), 0, st, b); GAMD_CHECK_LAUNCH();
@@ -252,19 +257,19 @@ int w4_launch_passes(const W4Args& b, PassGeom* gp, hipStream_t st, const PmeArg
 
 }  // namespace
 
-int launch_w4_classical(const W4Args& b, hipStream_t st, const PmeArgs* pme) {
+int launch_w4_classical(const W4Args& b, hipStream_t st, const PmeArgs* pme, const WCellBufs* cells) {
     const WaterArgs& a = b.w;
     PassGeom g;
     if (a.blocks < 1 || a.blocks > 65535 || a.slot < 0 || !a.blk || !a.rows || (pme && pme->sites != b.sites)) return -1;
-    if (int r = w4_launch_passes(b, &g, st, pme)) return r;
+    if (int r = w4_launch_passes(b, &g, st, pme, cells, WATER_PART)) return r;
     hipLaunchKernelGGL(k_w4_atoms, dim3(a.blocks, g.nb), dim3(256), 0, st, b); GAMD_CHECK_LAUNCH();
     return launch_water_final(a, st);
 }
 
-int launch_w4_drive(const W4Args& b, float* f_out, hipStream_t st, const PmeArgs* pme) {
+int launch_w4_drive(const W4Args& b, float* f_out, hipStream_t st, const PmeArgs* pme, const WCellBufs* cells) {
     PassGeom g;
     if (!f_out || (pme && pme->sites != b.sites)) return -1;
-    if (int r = w4_launch_passes(b, &g, st, pme)) return r;
+    if (int r = w4_launch_passes(b, &g, st, pme, cells, 3)) return r;
     hipLaunchKernelGGL(k_w4_drive, dim3((unsigned)g.T, g.nb), dim3(256), 0, st, b, f_out); GAMD_CHECK_LAUNCH();
     return 0;
 }

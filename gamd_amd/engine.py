@@ -1171,7 +1171,8 @@ class GamdForce:
                                   epsilon_o: float = 0.635968, r_cut: Optional[float] = None, r_switch: float = 0.0,
                                   shift: bool = False, ewald_tol: float = 1e-10, alpha: Optional[float] = None,
                                   k_cut: Optional[float] = None, coulomb_const: float = COULOMB_KJ_NM,
-                                  length_per_nm: float = 0.0, m_site: float = 0.0, virial: bool = False, pme=None, pme_order: int = 6) -> None:
+                                  length_per_nm: float = 0.0, m_site: float = 0.0, virial: bool = False, pme=None, pme_order: int = 6,
+                                  cells: bool = False) -> None:
         """While configured, every ``interval``-th completed step of md_run / md_run_nhc (counted across calls, by a counter
         of its own) evaluates the classical potential of 3-site water in double on the device — O-O Lennard-Jones plus
         point charges q_H and q_O = -2 q_H by a plain Ewald sum (real space inside ``r_cut``, same-molecule exclusion,
@@ -1214,7 +1215,22 @@ class GamdForce:
         and ``water_minimize`` refuse it (minimise under the plain sum, configure again with ``pme``, take ``f`` from
         ``water_classical_forces``).  Every call states it: the default None is the plain sum, bit for bit what it was.
 
-        The plain sum is the limit OpenMM's PME approximates.  Not built: the PME virial, the PME minimiser, odd orders,
+        ``cells`` walks the real-space pairs over a per-box cell table instead of all against all: per sample the atoms are
+        ordered by (cell, atom index), cells of edge >= r_cut / 2, and every atom tests the atoms of the 5 x 5 x 5 cells around
+        its own (every cell of an axis that has fewer than five).  The pairs, the pair count and the charge sum are exactly the
+        all-pairs walk's, U_recip and U_self its bits; U_LJ, U_real + U_excl and the forces differ from it in the order of
+        the sums only, within 1e-12 of their sums of absolute terms.  The same bits come back run after run, and a driven
+        frame still carries ``fp32(water_classical_forces(x))``; the same atoms given in OTHER periodic images may change
+        cells at a face and with them the order of the sums (same bound, not the same bits).  The observer,
+        ``water_classical_forces`` and the ``"water_classical"`` force source follow it, with and without ``m_site`` and
+        ``pme``; the M-site form's O-O pass and the virial log's own walk stay all-pairs, and ``water_minimize`` refuses it
+        (minimise with ``cells=False``, configure again with ``cells=True``, take ``f`` from ``water_classical_forces``).
+        The table costs six launches per evaluation: it pays above a few thousand atoms (profiles/run_water_cells.md).  Every
+        call states it: the default False is the all-pairs walk, bit for bit what it was.  ``water_cells_table`` reads the
+        table of the last evaluation.
+
+        The plain sum is the limit OpenMM's PME approximates.  Not built: cells for the Lennard-Jones classical potential, for
+        the minimisers, for the virial walk and the M-site form's O-O pass, a table kept across steps with a skin; the PME virial, the PME minimiser, odd orders,
         grids that are no power of two, real-to-complex transforms, a 4-site minimiser, the pressure tensor,
         a barostat; the long-range dispersion correction is ``lj_dispersion_correction`` on the host (``pressure(...,
         dispersion=True)``).  No parity with OpenMM is claimed.  Check the parameters against your OpenMM system before
@@ -1258,10 +1274,26 @@ class GamdForce:
         check(self._lib.gamd_water_configure(self._h, C.byref(p)), "gamd_water_configure")
         check(self._lib.gamd_water_msite(self._h, float(m_site)), "gamd_water_msite")
         check(self._lib.gamd_water_virial(self._h, int(bool(virial))), "gamd_water_virial")
+        if cells or getattr(self, "_water_cells", False):           # (a handle that never had cells makes the calls it made)
+            check(self._lib.gamd_water_cells(self._h, int(bool(cells))), "gamd_water_cells")
+            self._water_cells = bool(cells)
         self._water_set = True
         self._water_virial = bool(virial)
         self._water_lj = dict(sigma=sigma_o, epsilon=float(epsilon_o), r_cut=r_cut, r_switch=float(r_switch), shift=bool(shift),
                               length_per_nm=float(length_per_nm))
+
+    def water_cells_table(self, box: int = 0):
+        """Diagnostic: the cell table of box ``box`` as the last sample, ``water_classical_forces`` call or driven step left it
+        (``cells=True``): (nc, start, order) — the cells per axis (3 ints), the first table slot of every cell with the atoms
+        per box behind the last (cell = (cx nc[1] + cy) nc[2] + cz), and the atoms' indices inside the box in table order,
+        that is by (cell, atom index).  Synchronises."""
+        nc = (C.c_int32 * 3)()
+        check(self._lib.gamd_water_cells_read(self._h, self._stream(), int(box), nc, None, 0, None, 0), "gamd_water_cells_read")
+        start = np.zeros(nc[0] * nc[1] * nc[2] + 1, dtype=np.int32)
+        order = np.zeros(self.n, dtype=np.int32)
+        check(self._lib.gamd_water_cells_read(self._h, self._stream(), int(box), nc, start.ctypes.data_as(C.c_void_p), start.size,
+                                              order.ctypes.data_as(C.c_void_p), order.size), "gamd_water_cells_read")
+        return np.array(list(nc), dtype=np.int64), start, order
 
     def water_classical_reset(self) -> None:
         """Step count and rows back to zero; parameters and configuration stay."""

@@ -667,6 +667,36 @@ typedef struct gamd_water_pme_params {
 } gamd_water_pme_params;
 int32_t gamd_water_pme(gamd_handle* h, const gamd_water_pme_params* p);
 
+/* The real-space pairs of the water classical potential over a cell table instead of all against all: an optional, sticky
+ * property of the handle, switched as the M-site and PME are.  on = 0 (the default): every entry point launches what it
+ * launched before this switch existed and gives the same bits.  on = 1: the observer's sample, gamd_water_eval and the
+ * GAMD_FORCE_WATER_CLASSICAL source, in the 3-site form and in the M-site form (on the charge sites), replace their pair launch
+ * by six (clear, count, scan, fill, rank, pairs) on the caller's stream.  Per sample and box the atoms are ordered by
+ * (cell, atom index) — cells of edge >= r_cut / 2, nc_d = min(floor(2 L_d / (r_cut (1 + 2^-20))), 64) per axis from the box's
+ * own edges — and every atom walks the 5 x 5 x 5 cells around its own (every cell of an axis with fewer than five), on the
+ * positions as they are given, with the all-pairs walk's operations: the set of pairs, the pair count and the charge sum are
+ * exactly the all-pairs path's, U_recip and U_self its bits; U_LJ, U_real + U_excl and the forces differ from it in the ORDER
+ * of the sums only and lie within the same 1e-12 of their sums of absolute terms of the float64 references.  The same bits come
+ * back run after run, from fresh handles, per box of a several-box handle, in chunked runs, and a driven frame still carries
+ * fp32(f_cl of gamd_water_eval on its positions).  NOT promised in bits: the same atoms given in other periodic images may
+ * fall into a neighbouring cell at a face, which changes the order of the sums (within the bound above).
+ * The table costs six launches: below a few thousand atoms all pairs are faster (profiles/run_water_cells.md).
+ * Not built, and served all-pairs while the switch is on: the O-O pass of the M-site form, the virial log's own pair walk
+ * (which reads the cells' f_cl), the Lennard-Jones classical potential; gamd_water_minimize returns -22 while the switch is on
+ * (its f is the all-pairs force bit for bit: minimise with the cells off, switch them on, take f from gamd_water_eval).  Nor a
+ * table kept across steps with a skin, nor non-orthorhombic boxes.
+ * -22, with a message naming the reason: a null handle, a GAMD_KIND_LJ handle, no accepted gamd_water_configure, a pending
+ * run, on not 0 or 1.  -12 when the tables cannot be allocated (44 B per atom, 8 B per box and cell); the switch is then off. */
+int32_t gamd_water_cells(gamd_handle* h, int32_t on);
+
+/* Diagnostic: the cell table of box `box` as the last sample, gamd_water_eval call or driven step left it, to the host.
+ * nc[3] = the cells per axis; start[nc[0] nc[1] nc[2] + 1] = the first table slot of every cell, cell = (cx nc[1] + cy) nc[2] +
+ * cz, and n_atoms per box behind the last; order[n_atoms per box] = the atoms (index inside the box) in table order.  start and
+ * order may be NULL.  Synchronises `stream`.  -22 if the switch is off, if nothing has been sampled since it was switched on or
+ * since the boxes were last given, or if a buffer is too short. */
+int32_t gamd_water_cells_read(gamd_handle* h, void* stream, int32_t box, int32_t* nc, int32_t* start, int64_t max_start,
+                              int32_t* order, int64_t max_order);
+
 /* The molecular virial of the water classical potential, and with it the scalar pressure of a box of rigid molecules (with
  * rigid molecules the atomic virial is not the pressure: the constraint forces carry the rest).  Per box, all sums in double,
  * every term in kJ/mol:
