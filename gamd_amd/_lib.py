@@ -125,6 +125,8 @@ SYMBOLS = {
     "gamd_classical_reset": (_i32, [_vp]),
     "gamd_classical_read": (_i32, [_vp, _vp, _vp, _vp, _i64, C.POINTER(_i64), C.POINTER(_i64), _vp, _i64]),
     "gamd_classical_eval": (_i32, [_vp, _vp, C.POINTER(C.c_float), C.c_float, _vp, _vp, _vp, _vp, _vp]),
+    "gamd_classical_cells": (_i32, [_vp, _i32]),
+    "gamd_classical_cells_read": (_i32, [_vp, _vp, _i32, C.POINTER(_i32), _vp, _i64, _vp, _i64]),
     "gamd_md_force_source": (_i32, [_vp, _i32]),
     "gamd_minimize": (_i32, [_vp, _vp, C.POINTER(C.c_float), C.c_float, _vp, _vp, C.POINTER(GamdMinimizeParams), _vp, _vp]),
     "gamd_water_configure": (_i32, [_vp, C.POINTER(GamdWaterParams)]),

@@ -605,14 +605,16 @@ struct ClassicalArgs {
     long long slot;            // row of this sample
     long long g;               // completed MD steps at this sample
 };
-int launch_classical(const ClassicalArgs& a, hipStream_t st);
+// `cells` (gamd_classical_cells; `a` arrives with slices = 1): launch_classical_cells stands where the pair launch is; null: all pairs
+struct WCellBufs;
+int launch_classical(const ClassicalArgs& a, hipStream_t st, const WCellBufs* cells = nullptr);
 
 // ---- classical force source (drive.hip) -------------------------------------------------------------
 // One force evaluation of a classical-source step of an enqueued MD run (gamd_md_force_source): the pair pass of classical.hip
 // (tiles, slices and arithmetic of k_classical_pairs; forces only) into a.part, then per atom the slice partials added in order
 // from 0, f_cl = F * len to a.f_cl and (float)f_cl to f_out ([n][3], the caller's atom order).  a.f, a.blk, a.rows, a.steps,
 // a.slot and a.g are not used.  Two launches, plain stores.
-int launch_classical_drive(const ClassicalArgs& a, float* f_out, hipStream_t st);
+int launch_classical_drive(const ClassicalArgs& a, float* f_out, hipStream_t st, const WCellBufs* cells = nullptr);
 
 // ---- water classical potential (water_classical.hip) ------------------------------------------------
 // One sample of an enqueued MD run (gamd_water_configure) or one gamd_water_eval call: 3-site water in the caller's order
@@ -771,6 +773,17 @@ struct WCellBufs {
 // nout = WATER_PART (the observer, gamd_water_eval) or 3 (the force source); lj: the O-O term in the walk (3-site), else `sites`
 int launch_water_cells(const WaterArgs& w, const WCellBufs& c, const double* sites, int nout, bool lj, hipStream_t st);
 
+// ---- the pairs of the Lennard-Jones classical potential over a cell table (classical_cells.hip) ------------
+// A second producer of the pair rows a.part (gamd_classical_cells): instead of k_classical_pairs,
+// k_drive_lj_pairs or k_min_pairs the table of WCellBufs (the entries' O flag is 0) is built from the positions — a.x, or `x64` for
+// the minimiser — and every atom walks the table's runs around its cell, gamd_lj_walk's body on the same doubles.  The rows go to
+// a.part as ONE pair slice: `a` arrives with a.slices = 1 and a.chunk = n_per_box, and k_classical_atoms, k_drive_lj_atoms and
+// k_min_atoms run on it as they are.  Six launches on `st`: clear, count, scan, fill, rank, pairs.  `stopped` (the minimiser's
+// gates, or null): a box with stopped[box] != 0 is left alone.  The range checks are water_cells.hip's, under codes of their own.
+enum { GAMD_CHK_LJCELL_CELL = 155, GAMD_CHK_LJCELL_START = 156, GAMD_CHK_LJCELL_SLOT = 157, GAMD_CHK_LJCELL_ATOM = 158 };
+// nout = CLASSICAL_PART (the observer, gamd_classical_eval), 3 (the force source) or 4 ({F, e_i}: an iteration of the minimiser)
+int launch_classical_cells(const ClassicalArgs& a, const WCellBufs& c, const double* x64, const int* stopped, int nout, hipStream_t st);
+
 // ---- molecular virial of the water classical potential (water_virial.hip) ------------------------------
 // The virial log of gamd_water_virial: launched BEHIND launch_water_classical / launch_w4_classical
 // of the same frame and argument block `w`, whose f_cl (the atoms' total classical forces) and sk ({Re S, Im S, A}) it reads;
@@ -825,7 +838,8 @@ struct MinArgs {
     FireArgs fire;
 };
 int launch_minimize_init(const MinArgs& m, const float* x, hipStream_t st);
-int launch_minimize_iter(const MinArgs& m, hipStream_t st);
+// `cells` (gamd_classical_cells; m.c arrives with slices = 1): the table from x64 and k_ljcell_min stand where k_min_pairs is
+int launch_minimize_iter(const MinArgs& m, hipStream_t st, const WCellBufs* cells = nullptr);
 // x_out = fp32(x64) wrapped (skipped for a box that failed at iteration 0); f_out = f_in for every box that did not fail
 int launch_minimize_store_x(const MinArgs& m, float* x_out, hipStream_t st);
 // (either minimiser's: n and bx are the handle's atoms and boxes)

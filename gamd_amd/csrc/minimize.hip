@@ -16,6 +16,9 @@
 //                   that stops keeps its positions.  Then v = c1 v + c2 F (or 0), v += dt F, dr = dt v, |dr| clamped per atom
 //                   to max_step, x64 += dr.
 //
+// With gamd_classical_cells on, launch_classical_cells (classical_cells.hip: the table rebuilt from x64, then k_ljcell_min) stands
+// where k_min_pairs is in every iteration, on ONE pair slice, and returns at once for a stopped box like the kernels here.
+//
 // F is in kJ/mol/nm and x, max_step in the handle's length unit: dt is a pseudo-time that absorbs the units (and the mass).
 // Scalar state {dt, alpha, n_pos} sits in two slots per box: iteration `it` reads slot it & 1 in every thread and thread 0 of
 // workgroup 0 writes slot (it + 1) & 1, so no thread reads what this launch writes.  `stopped[box]` is the gate: 0 while the box
@@ -205,10 +208,15 @@ int launch_minimize_init(const MinArgs& m, const float* x, hipStream_t st) {
     return 0;
 }
 
-int launch_minimize_iter(const MinArgs& m, hipStream_t st) {
+int launch_minimize_iter(const MinArgs& m, hipStream_t st, const WCellBufs* cells) {
     PassGeom g;
     if (min_check(m, &g)) return -1;
-    hipLaunchKernelGGL(k_min_pairs, dim3((unsigned)(g.T * m.c.slices), g.nb), dim3(256), 0, st, m); GAMD_CHECK_LAUNCH();
+    if (cells) {                                            // gamd_classical_cells: {F, u_i} over the cell table of x64, one slice
+        if (!m.c.devflags) return -1;
+        if (int r = launch_classical_cells(m.c, *cells, m.fire.x64, m.fire.stopped, 4, st)) return r;
+    } else {
+        hipLaunchKernelGGL(k_min_pairs, dim3((unsigned)(g.T * m.c.slices), g.nb), dim3(256), 0, st, m); GAMD_CHECK_LAUNCH();
+    }
     hipLaunchKernelGGL(k_min_atoms, dim3(m.c.blocks, g.nb), dim3(256), 0, st, m); GAMD_CHECK_LAUNCH();
     hipLaunchKernelGGL(k_min_update, dim3((unsigned)g.T, g.nb), dim3(256), 0, st, m); GAMD_CHECK_LAUNCH();
     return 0;

@@ -93,12 +93,26 @@ struct PotentialLog {
     DevBuf eval_rows, eval_box;        // the eval call: its row and its box edges
 };
 
+// the cell table of a potential's pair pass (gamd_water_cells, gamd_classical_cells): the switch, and per box the tables
+struct CellTables {
+    bool cells = false;                // the pairs walk a per-box cell table (water_cells.hip, classical_cells.hip)
+    bool cells_sampled = false;        // ... and the table holds the atoms of a sample, an eval call, a driven step or a minimiser's pass
+    int cell_cap = 0;                  // cells per box the tables have room for (grows with the boxes the handle is given)
+    std::vector<float> cell_box;       // [n_boxes][3] the edges the last enqueued table is built for (what the read call goes by)
+    double cell_rcut = 0.0;            // ... and its cutoff
+    std::vector<float> cell_box_next;  // [n_boxes][3] the edges the tables are sized for: those of the next evaluation (cells_apply)
+    // an evaluation is being enqueued under the cutoff r_cut: its table is the one a read call finds behind the stream
+    void enqueued(double r_cut) { cell_box = cell_box_next; cell_rcut = r_cut; cells_sampled = true; }
+    DevBuf cell_start, cell_fill;      // cells on: per box and cell
+    DevBuf cell_of, cell_members, cell_order, cell_table;   // ... per atom
+};
+
 // classical observer: Lennard-Jones and nothing else
-using Classical = PotentialLog;
+struct Classical : PotentialLog, CellTables {};
 
 // water classical observer: O-O Lennard-Jones plus the Ewald parameters, the k-vector list in force (built for the longest edge
 // of the boxes of the last configure, run or gamd_water_eval) and the work buffers that go by it
-struct WaterClassical : PotentialLog {
+struct WaterClassical : PotentialLog, CellTables {
     double q_h = 0.0, alpha = 0.0, k_cut = 0.0, coulomb = 0.0;
     int n2max = -1, n_k = 0;           // the list in force: every n with 0 < |n|^2 <= n2max (-1: none yet)
     DevBuf rpart;                      // one evaluation: per atom and k slice
@@ -112,12 +126,7 @@ struct WaterClassical : PotentialLog {
     int pme_order = 0, pme_n[3] = {0, 0, 0};            // gamd_water_pme: the spline order (0 = the plain sum) and the grid per box
     DevBuf pme_gq, pme_gc;             // order != 0: per box and grid point, the integer spread and the complex transform (water_pme.hip)
     DevBuf pme_tw, pme_mod;            // ... the twiddles and the three axes' moduli, uploaded by gamd_water_pme
-    bool cells = false;                // gamd_water_cells: the real-space pairs walk a per-box cell table (water_cells.hip)
-    bool cells_sampled = false;        // ... and the table holds a sample's or an eval call's atoms
-    int cell_cap = 0;                  // cells per box the tables have room for (grows with the boxes the handle is given)
-    std::vector<float> cell_box;       // [n_boxes][3] the edges the last table was (or the next will be) built for
-    DevBuf cell_start, cell_fill;      // cells on: per box and cell
-    DevBuf cell_of, cell_members, cell_order, cell_table;   // ... per atom
+    // (CellTables: gamd_water_cells)
 };
 
 // energy minimiser (gamd_minimize, minimize.hip): no observer — no clock, no entry in observer_list() — but a user of the
@@ -190,7 +199,20 @@ ObsBufs potential_bufs(gamd_handle* h, PotentialLog& pl, size_t row, size_t part
             {&pl.eval_rows, sizeof(double) * row * nb, false}, {&pl.eval_box, sizeof(float) * 3 * nb, false}};
 }
 
-ObsBufs classical_bufs(gamd_handle* h) { return potential_bufs(h, h->obs->cl, CLASSICAL_ROW, CLASSICAL_PART, CLASSICAL_ROW); }
+// the cell table's own: nothing while the pairs are walked all against all
+void cell_bufs_append(gamd_handle* h, CellTables& ct, ObsBufs& t) {
+    const size_t nb = (size_t)h->n_boxes, n = (size_t)h->n, c = ct.cells ? 1 : 0, cap = (size_t)ct.cell_cap;
+    t.push_back({&ct.cell_start, c * sizeof(int) * nb * (cap + 1), false});
+    t.push_back({&ct.cell_fill, c * sizeof(int) * nb * cap, false});
+    for (DevBuf* b : {&ct.cell_of, &ct.cell_members, &ct.cell_order}) t.push_back({b, c * sizeof(int) * n, false});
+    t.push_back({&ct.cell_table, c * sizeof(WCellAtom) * n, false});
+}
+
+ObsBufs classical_bufs(gamd_handle* h) {
+    ObsBufs t = potential_bufs(h, h->obs->cl, CLASSICAL_ROW, CLASSICAL_PART, CLASSICAL_ROW);
+    cell_bufs_append(h, h->obs->cl, t);
+    return t;
+}
 
 // energy minimiser: all of it work buffers (k_min_init writes every one in front of its first reader)
 ObsBufs minimize_bufs(gamd_handle* h) {
@@ -220,12 +242,7 @@ ObsBufs water_bufs(gamd_handle* h) {
     const size_t G = wc.pme_order ? (size_t)wc.pme_n[0] * (size_t)wc.pme_n[1] * (size_t)wc.pme_n[2] : 0;
     t.push_back({&wc.pme_gq, sizeof(unsigned long long) * nb * G, false});
     t.push_back({&wc.pme_gc, sizeof(double) * 2 * nb * G, false});
-    // the cell table's own: nothing while the pairs are walked all against all
-    const size_t c = wc.cells ? 1 : 0, cap = (size_t)wc.cell_cap;
-    t.push_back({&wc.cell_start, c * sizeof(int) * nb * (cap + 1), false});
-    t.push_back({&wc.cell_fill, c * sizeof(int) * nb * cap, false});
-    for (DevBuf* b : {&wc.cell_of, &wc.cell_members, &wc.cell_order}) t.push_back({b, c * sizeof(int) * n, false});
-    t.push_back({&wc.cell_table, c * sizeof(WCellAtom) * n, false});
+    cell_bufs_append(h, wc, t);
     // the M-site's own: nothing while the potential is 3-site
     const size_t m = wc.w_h != 0.0 ? 1 : 0;
     t.push_back({&wc.sites, m * sizeof(double) * 3 * n, false});
@@ -432,31 +449,38 @@ int water_klist_apply(gamd_handle* h, int n2max, const std::vector<int>& kv) {
     return 0;
 }
 
-// the cell tables (gamd_water_cells) for the boxes `box` ([n_boxes][3], every edge at least 2 r_cut): room for the box with the
-// most cells, the edges kept for gamd_water_cells_read.  No run is pending.
-int water_cells_apply(gamd_handle* h, const float* box) {
-    WaterClassical& wc = h->obs->wc;
+// the cell tables (gamd_water_cells, gamd_classical_cells) of the potential `wc` (buffer table `bufs`) for the boxes `box`
+// ([n_boxes][3], every edge at least 2 r_cut): room for the box with the most cells, the edges kept for the evaluations to come
+// (the read call goes by those of the last evaluation that was enqueued, CellTables::enqueued).  The
+// water potential's callers have no run pending; the Lennard-Jones potential's may (a run behind a run), and a table that
+// would have to grow under an enqueued run is refused.
+template <typename State>
+int cells_apply(gamd_handle* h, State& wc, ObsBufs (*bufs)(gamd_handle*), const char* who, const float* box) {
     int cap = 1;
     for (int b = 0; b < h->n_boxes; ++b) {
         int cells = 1;
         for (int d = 0; d < 3; ++d) cells *= gamd_cells_per_axis((double)box[3 * b + d], wc.r_cut);
         cap = std::max(cap, cells);
     }
-    wc.cell_box.assign(box, box + 3 * (size_t)h->n_boxes);
-    wc.cells_sampled = false;
-    if (cap > wc.cell_cap || !wc.cell_start.p || !wc.cell_table.p) {
+    const bool grow = cap > wc.cell_cap || !wc.cell_start.p || !wc.cell_table.p;
+    if (grow && h->pending.active)
+        return fail(-22, "an MD run is still enqueued: call gamd_sync_status before a run whose boxes need larger cell tables (%d cells per box)", cap);
+    wc.cell_box_next.assign(box, box + 3 * (size_t)h->n_boxes);
+    if (!h->pending.active) wc.cells_sampled = false;       // (behind an enqueued run its table stays the one to read)
+    if (grow) {
         DeviceGuard guard(h->dev);
         InitStream init(h->init_stream);
         const int before = wc.cell_cap;
         wc.cell_cap = std::max(cap, before);
         for (DevBuf* b : {&wc.cell_start, &wc.cell_fill}) b->release();
-        if (bufs_ensure_work(water_bufs(h))) {
+        if (bufs_ensure_work(bufs(h))) {
             wc.cell_cap = before;
-            return fail(-12, "water classical potential: allocation of the cell tables (%d cells per box, %d boxes) failed", cap, h->n_boxes);
+            return fail(-12, "%s potential: allocation of the cell tables (%d cells per box, %d boxes) failed", who, cap, h->n_boxes);
         }
     }
     return 0;
 }
+int water_cells_apply(gamd_handle* h, const float* box) { return cells_apply(h, h->obs->wc, water_bufs, "water classical", box); }
 
 // every edge of every box the caller hands in
 int check_box_positive(const gamd_handle* h, const float* box) {
@@ -489,14 +513,34 @@ struct LjPotential {
         Args a{};
         potential_args(h, state(h), len, a);
         a.eps24 = 24.0 * state(h).epsilon;
+        if (state(h).cells) { a.slices = 1; a.chunk = h->n_per_box; }      // gamd_classical_cells: the pair rows are ONE slice
         return a;
     }
     static void species(Args&, const uint8_t*) {}
-    static int launch(const gamd_handle*, const Args& a, hipStream_t st) { return launch_classical(a, st); }
+    // the cell table in force (gamd_classical_cells): its buffers, or null (b is the caller's room for them)
+    static const WCellBufs* cell_bufs(const gamd_handle* h, WCellBufs& b) {
+        Classical& cl = state(h);
+        if (!cl.cells) return nullptr;
+        b = WCellBufs{cl.r_cut, cl.cell_cap, h->sticky_dev, cl.cell_start.as<int>(), cl.cell_fill.as<int>(), cl.cell_of.as<int>(),
+                      cl.cell_members.as<int>(), cl.cell_order.as<int>(), cl.cell_table.as<WCellAtom>()};
+        cl.enqueued(cl.r_cut);
+        return &b;
+    }
+    static int launch(const gamd_handle* h, const Args& a, hipStream_t st) {
+        WCellBufs b;
+        return launch_classical(a, st, cell_bufs(h, b));
+    }
     static int sample_extra(const gamd_handle*, const Args&, const Particles&, hipStream_t) { return 0; }
-    static int check_box(gamd_handle* h, const float* box, const uint8_t*) { return potential_check_box(h, state(h), who, box); }
+    static int check_box(gamd_handle* h, const float* box, const uint8_t*) {
+        if (int r = potential_check_box(h, state(h), who, box)) return r;
+        // the cell tables sized for these boxes (grown here when they need more)
+        return state(h).cells ? cells_apply(h, state(h), classical_bufs, who, box) : 0;
+    }
     // a force source as well (potential_drive): the forces alone, rounded to fp32, into the run's f
-    static int drive(const gamd_handle*, const Args& a, float* f_out, hipStream_t st) { return launch_classical_drive(a, f_out, st); }
+    static int drive(const gamd_handle* h, const Args& a, float* f_out, hipStream_t st) {
+        WCellBufs b;
+        return launch_classical_drive(a, f_out, st, cell_bufs(h, b));
+    }
 };
 
 struct WaterPotential {
@@ -555,7 +599,7 @@ struct WaterPotential {
         const Args a = one_slice(h, a0);
         const WCellBufs cb = cell_bufs(h);
         const WCellBufs* c = wc.cells ? &cb : nullptr;
-        if (c) wc.cells_sampled = true;
+        if (c) wc.enqueued(wc.r_cut);
         if (wc.pme_order) {
             const PmeArgs p = pme(h, a);
             return wc.w_h != 0.0 ? launch_w4_classical(msite(h, p.w), st, &p, c) : launch_water_classical(p.w, st, &p, c);
@@ -596,7 +640,7 @@ struct WaterPotential {
         const Args a = one_slice(h, a0);
         const WCellBufs cb = cell_bufs(h);
         const WCellBufs* c = wc.cells ? &cb : nullptr;
-        if (c) wc.cells_sampled = true;
+        if (c) wc.enqueued(wc.r_cut);
         if (wc.pme_order) {
             const PmeArgs p = pme(h, a);
             return wc.w_h != 0.0 ? launch_w4_drive(msite(h, p.w), f_out, st, &p, c) : launch_water_drive(p.w, f_out, st, &p, c);
@@ -823,7 +867,10 @@ struct LjMinimizer {
     enum { FROZEN_CODE = -1, COPY_X64 = 1 };
     static P::Args& potential(Args& m) { return m.c; }
     static int init(const Args& m, const float* x, hipStream_t st) { return launch_minimize_init(m, x, st); }
-    static int iter(const Args& m, hipStream_t st) { return launch_minimize_iter(m, st); }
+    static int iter(const gamd_handle* h, const Args& m, hipStream_t st) {
+        WCellBufs b;
+        return launch_minimize_iter(m, st, P::cell_bufs(h, b));
+    }
     static int store_x(const Args& m, float* x, double*, hipStream_t st) { return launch_minimize_store_x(m, x, st); }
 };
 
@@ -834,7 +881,7 @@ struct WaterMinimizer {
     enum { FROZEN_CODE = -22, COPY_X64 = 0 };
     static P::Args& potential(Args& m) { return m.w; }
     static int init(const Args& m, const float* x, hipStream_t st) { return launch_wmin_init(m, x, st); }
-    static int iter(const Args& m, hipStream_t st) { return launch_wmin_iter(m, st); }
+    static int iter(const gamd_handle*, const Args& m, hipStream_t st) { return launch_wmin_iter(m, st); }
     static int store_x(const Args& m, float* x, double* x64_out, hipStream_t st) { return launch_wmin_store_x(m, x, x64_out, st); }
 };
 
@@ -879,14 +926,14 @@ int minimize_run(gamd_handle* h, typename M::Args m, float* x_dev, const uint8_t
     while (fi.it < q.max_iter && !all_stopped) {
         const long long chunk = std::min<long long>(q.check_every, q.max_iter - fi.it);
         for (long long k = 0; k < chunk; ++k, ++fi.it)
-            if ((r = M::iter(m, st))) return fail(-1, "%s launch failed (%d)", M::api, r);
+            if ((r = M::iter(h, m, st))) return fail(-1, "%s launch failed (%d)", M::api, r);
         HIP_TRY(hipMemcpyAsync(stopped.data(), mn.stopped.p, sizeof(int) * nb, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         all_stopped = std::all_of(stopped.begin(), stopped.end(), [](int s) { return s != 0; });
     }
     if (!all_stopped) {                                     // U and rms where max_iter left the boxes that still run
         fi.last = 1;
-        if ((r = M::iter(m, st))) return fail(-1, "%s launch failed (%d)", M::api, r);
+        if ((r = M::iter(h, m, st))) return fail(-1, "%s launch failed (%d)", M::api, r);
     }
     // x (and the water minimiser's x64), then the force source's own kernels on exactly that x
     if ((r = M::store_x(m, x_dev, x64_dev, st))) return fail(-1, "%s launch failed (%d)", M::api, r);
@@ -1244,6 +1291,72 @@ int32_t gamd_classical_eval(gamd_handle* h, const float* pos_dev, const float* b
     return 0;
 }
 
+namespace {
+// what the two read calls of a cell table share: the table of box `box` of the potential `ct` (cutoff r_cut) to the host
+int cells_read(gamd_handle* h, const CellTables& ct, const char* entry, const char* sw, void* stream, int32_t box, int32_t* nc,
+               int32_t* start, int64_t max_start, int32_t* order, int64_t max_order) {
+    if (!ct.cells) return fail(-22, "%s: the cell table is off (%s)", entry, sw);
+    if (!ct.cells_sampled || ct.cell_box.size() != 3 * (size_t)h->n_boxes)
+        return fail(-22, "%s: nothing has been sampled since the cell table was switched on or the boxes were given", entry);
+    if (box < 0 || box >= h->n_boxes) return fail(-22, "%s: box = %d outside [0, %d)", entry, (int)box, h->n_boxes);
+    if (!nc) return fail(-22, "null argument");
+    long long cells = 1;
+    for (int d = 0; d < 3; ++d) {
+        nc[d] = gamd_cells_per_axis((double)ct.cell_box[3 * (size_t)box + d], ct.cell_rcut);
+        cells *= nc[d];
+    }
+    if (cells > ct.cell_cap) return fail(-1, "%s: %lld cells, the tables hold %d", entry, cells, ct.cell_cap);
+    if (start && max_start < cells + 1) return fail(-22, "start has room for %lld elements, the box has %lld cells + 1", (long long)max_start, cells);
+    if (order && max_order < h->n_per_box) return fail(-22, "order has room for %lld elements, a box has %d atoms", (long long)max_order, h->n_per_box);
+    DeviceGuard guard(h->dev);
+    hipStream_t st = (hipStream_t)stream;
+    if (start)
+        HIP_TRY(hipMemcpyAsync(start, ct.cell_start.as<int>() + (size_t)box * ((size_t)ct.cell_cap + 1), sizeof(int) * (size_t)(cells + 1),
+                               hipMemcpyDeviceToHost, st));
+    if (order)
+        HIP_TRY(hipMemcpyAsync(order, ct.cell_order.as<int>() + (size_t)box * (size_t)h->n_per_box, sizeof(int) * (size_t)h->n_per_box,
+                               hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (int t = check_traps(h)) return t;
+    return 0;
+}
+}  // namespace
+
+int32_t gamd_classical_cells(gamd_handle* h, int32_t on) {
+    if (!h) return fail(-22, "null handle");
+    if (h->cfg.kind != GAMD_KIND_LJ)
+        return fail(-22, "gamd_classical_cells: a GAMD_KIND_WATER handle has no Lennard-Jones classical potential (GAMD_KIND_LJ handles "
+                         "only; gamd_water_cells switches the cell table of the water classical potential)");
+    Classical& cl = h->obs->cl;
+    if (!cl.params_set) return fail(-22, "gamd_classical_cells needs the parameters of a gamd_classical_configure call (interval 0 will do)");
+    if (h->pending.active) return fail(-22, "an MD run is still enqueued: call gamd_sync_status before gamd_classical_cells");
+    if (on != 0 && on != 1) return fail(-22, "gamd_classical_cells: on = %d is not 0 (all pairs) or 1 (the cell table)", (int)on);
+    auto drop = [&]() {
+        cl.cells = cl.cells_sampled = false;
+        cl.cell_cap = 0; cl.cell_box.clear(); cl.cell_box_next.clear();
+        for (DevBuf* b : {&cl.cell_start, &cl.cell_fill, &cl.cell_of, &cl.cell_members, &cl.cell_order, &cl.cell_table}) b->release();
+    };
+    if (!on) { drop(); return 0; }
+    if (cl.cells) return 0;                                 // on already: the table of the last evaluation stays readable
+    cl.cells = true;
+    DeviceGuard guard(h->dev);
+    InitStream init(h->init_stream);
+    // 44 bytes per atom here; the per-cell tables are sized by the boxes of the next run, eval or minimise call (cells_apply)
+    if (bufs_ensure_work(classical_bufs(h))) {
+        drop();
+        return fail(-12, "gamd_classical_cells: allocation of the cell tables of %d atoms failed", h->n);
+    }
+    return 0;
+}
+
+int32_t gamd_classical_cells_read(gamd_handle* h, void* stream, int32_t box, int32_t* nc, int32_t* start, int64_t max_start,
+                                  int32_t* order, int64_t max_order) {
+    if (!h) return fail(-22, "null handle");
+    if (h->cfg.kind != GAMD_KIND_LJ) return fail(-22, "gamd_classical_cells_read: GAMD_KIND_LJ handles only");
+    const Classical& cl = h->obs->cl;
+    return cells_read(h, cl, "gamd_classical_cells_read", "gamd_classical_cells", stream, box, nc, start, max_start, order, max_order);
+}
+
 int32_t gamd_minimize(gamd_handle* h, float* x_dev, const float* box, float length_per_nm, float* f_dev, double* x64_dev,
                       const gamd_minimize_params* params, double* rows_host, void* stream) {
     // the parameter block is checked first: these answers need no device
@@ -1360,15 +1473,15 @@ int32_t gamd_water_pme(gamd_handle* h, const gamd_water_pme_params* p) {
 int32_t gamd_water_cells(gamd_handle* h, int32_t on) {
     if (!h) return fail(-22, "null handle");
     if (h->cfg.kind != GAMD_KIND_WATER)
-        return fail(-22, "gamd_water_cells: a GAMD_KIND_LJ handle has no water potential (GAMD_KIND_WATER handles only; there is no cell "
-                         "table for the Lennard-Jones classical potential)");
+        return fail(-22, "gamd_water_cells: a GAMD_KIND_LJ handle has no water potential (GAMD_KIND_WATER handles only; "
+                         "gamd_classical_cells switches the cell table of the Lennard-Jones classical potential)");
     WaterClassical& wc = h->obs->wc;
     if (!wc.params_set) return fail(-22, "gamd_water_cells needs the parameters of a gamd_water_configure call (interval 0 will do)");
     if (h->pending.active) return fail(-22, "an MD run is still enqueued: call gamd_sync_status before gamd_water_cells");
     if (on != 0 && on != 1) return fail(-22, "gamd_water_cells: on = %d is not 0 (all pairs) or 1 (the cell table)", (int)on);
     auto drop = [&]() {
         wc.cells = wc.cells_sampled = false;
-        wc.cell_cap = 0; wc.cell_box.clear();
+        wc.cell_cap = 0; wc.cell_box.clear(); wc.cell_box_next.clear();
         for (DevBuf* b : {&wc.cell_start, &wc.cell_fill, &wc.cell_of, &wc.cell_members, &wc.cell_order, &wc.cell_table}) b->release();
     };
     if (!on) { drop(); return 0; }
@@ -1389,30 +1502,7 @@ int32_t gamd_water_cells_read(gamd_handle* h, void* stream, int32_t box, int32_t
     if (!h) return fail(-22, "null handle");
     if (h->cfg.kind != GAMD_KIND_WATER) return fail(-22, "gamd_water_cells_read: GAMD_KIND_WATER handles only");
     const WaterClassical& wc = h->obs->wc;
-    if (!wc.cells) return fail(-22, "gamd_water_cells_read: the cell table is off (gamd_water_cells)");
-    if (!wc.cells_sampled || wc.cell_box.size() != 3 * (size_t)h->n_boxes)
-        return fail(-22, "gamd_water_cells_read: nothing has been sampled since the cell table was switched on or the boxes were given");
-    if (box < 0 || box >= h->n_boxes) return fail(-22, "gamd_water_cells_read: box = %d outside [0, %d)", (int)box, h->n_boxes);
-    if (!nc) return fail(-22, "null argument");
-    long long cells = 1;
-    for (int d = 0; d < 3; ++d) {
-        nc[d] = gamd_cells_per_axis((double)wc.cell_box[3 * (size_t)box + d], wc.r_cut);
-        cells *= nc[d];
-    }
-    if (cells > wc.cell_cap) return fail(-1, "gamd_water_cells_read: %lld cells, the tables hold %d", cells, wc.cell_cap);
-    if (start && max_start < cells + 1) return fail(-22, "start has room for %lld elements, the box has %lld cells + 1", (long long)max_start, cells);
-    if (order && max_order < h->n_per_box) return fail(-22, "order has room for %lld elements, a box has %d atoms", (long long)max_order, h->n_per_box);
-    DeviceGuard guard(h->dev);
-    hipStream_t st = (hipStream_t)stream;
-    if (start)
-        HIP_TRY(hipMemcpyAsync(start, wc.cell_start.as<int>() + (size_t)box * ((size_t)wc.cell_cap + 1), sizeof(int) * (size_t)(cells + 1),
-                               hipMemcpyDeviceToHost, st));
-    if (order)
-        HIP_TRY(hipMemcpyAsync(order, wc.cell_order.as<int>() + (size_t)box * (size_t)h->n_per_box, sizeof(int) * (size_t)h->n_per_box,
-                               hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (int t = check_traps(h)) return t;
-    return 0;
+    return cells_read(h, wc, "gamd_water_cells_read", "gamd_water_cells", stream, box, nc, start, max_start, order, max_order);
 }
 
 int32_t gamd_water_reset(gamd_handle* h) { return observer_reset(h, OBS_WATER, "gamd_water_reset"); }

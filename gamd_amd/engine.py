@@ -1071,7 +1071,8 @@ class GamdForce:
 
     # -- classical observer (the LJ potential energy, virial and force error on sampled frames; classical force labels) ---
     def classical_configure(self, interval: int, max_samples: int = 0, sigma: float = 3.4, epsilon: float = 0.238 * KJ_PER_KCAL,
-                            r_cut: Optional[float] = None, r_switch: Optional[float] = None, shift: bool = True) -> None:
+                            r_cut: Optional[float] = None, r_switch: Optional[float] = None, shift: bool = True,
+                            cells: bool = False) -> None:
         """While configured, every ``interval``-th completed step of md_run / md_run_nhc (counted across calls, by a counter
         of its own) evaluates the switched, shifted Lennard-Jones potential on all pairs of every box in double on the
         device and logs the potential energy, the virial, the pair count and the error sums of the run's (network) forces
@@ -1083,14 +1084,33 @@ class GamdForce:
         3.4 Angstrom, epsilon = 0.238 kcal/mol, cutoff 3 sigma, switch width 3.4 Angstrom, shifted) are meant to be those of
         openmmtools' ``LennardJonesFluid(shift=True)`` behind the reference's data generator, but they were written down from
         memory and are UNVERIFIED: neither OpenMM nor openmmtools was available to compare against, and no long-range
-        dispersion correction is applied.  Check them against your OpenMM system before comparing energies."""
+        dispersion correction is applied.  Check them against your OpenMM system before comparing energies.
+
+        ``cells`` walks the pairs over a per-box cell table instead of all against all: per evaluation the atoms are ordered
+        by (cell, atom index), cells of edge >= r_cut / 2, and every atom tests the atoms of the 5 x 5 x 5 cells around its
+        own (every cell of an axis that has fewer than five).  The pairs and the pair count are exactly the all-pairs walk's;
+        the energy, the virial and the forces differ from it in the order of the sums only, within 1e-12 of their sums of
+        absolute terms.  The same bits come back run after run, a driven frame still carries
+        ``classical_forces(x)[0].float()`` and so does ``minimize``'s ``f``; the same atoms given in OTHER periodic images may
+        change cells at a face and with them the order of the sums (same bound, not the same bits).  The observer,
+        ``classical_forces``, the ``"classical"`` force source and ``minimize`` follow it.  The table costs six launches per
+        evaluation; where it pays: profiles/run_classical_cells.md.  Every call states it: the default False is the all-pairs
+        walk, bit for bit what it was.  ``classical_cells_table`` reads the table of the last evaluation."""
         r_cut = 3.0 * float(sigma) if r_cut is None else float(r_cut)
         r_switch = r_cut - float(sigma) if r_switch is None else float(r_switch)
         p = GamdClassicalParams(int(interval), int(max_samples), float(sigma), float(epsilon), r_cut, r_switch, int(bool(shift)), 0)
         check(self._lib.gamd_classical_configure(self._h, C.byref(p)), "gamd_classical_configure")
+        if cells or getattr(self, "_classical_cells", False):       # (a handle that never had cells makes the calls it made)
+            check(self._lib.gamd_classical_cells(self._h, int(bool(cells))), "gamd_classical_cells")
+            self._classical_cells = bool(cells)
         self._classical_set = True
         self._classical_lj = dict(sigma=float(sigma), epsilon=float(epsilon), r_cut=r_cut, r_switch=r_switch, shift=bool(shift),
                                   length_per_nm=0.0)
+
+    def classical_cells_table(self, box: int = 0):
+        """Diagnostic: the cell table of box ``box`` as the last sample, ``classical_forces`` call, driven step or ``minimize``
+        call left it (``cells=True``): (nc, start, order) as ``water_cells_table`` returns them.  Synchronises."""
+        return self._cells_table("gamd_classical_cells_read", box)
 
     def classical_reset(self) -> None:
         """Step count and rows back to zero; parameters and configuration stay."""
@@ -1229,8 +1249,7 @@ class GamdForce:
         call states it: the default False is the all-pairs walk, bit for bit what it was.  ``water_cells_table`` reads the
         table of the last evaluation.
 
-        The plain sum is the limit OpenMM's PME approximates.  Not built: cells for the Lennard-Jones classical potential, for
-        the minimisers, for the virial walk and the M-site form's O-O pass, a table kept across steps with a skin; the PME virial, the PME minimiser, odd orders,
+        The plain sum is the limit OpenMM's PME approximates.  Not built: cells for the water minimiser, for the virial walk and the M-site form's O-O pass, a table kept across steps with a skin; the PME virial, the PME minimiser, odd orders,
         grids that are no power of two, real-to-complex transforms, a 4-site minimiser, the pressure tensor,
         a barostat; the long-range dispersion correction is ``lj_dispersion_correction`` on the host (``pressure(...,
         dispersion=True)``).  No parity with OpenMM is claimed.  Check the parameters against your OpenMM system before
@@ -1287,12 +1306,17 @@ class GamdForce:
         (``cells=True``): (nc, start, order) — the cells per axis (3 ints), the first table slot of every cell with the atoms
         per box behind the last (cell = (cx nc[1] + cy) nc[2] + cz), and the atoms' indices inside the box in table order,
         that is by (cell, atom index).  Synchronises."""
+        return self._cells_table("gamd_water_cells_read", box)
+
+    def _cells_table(self, entry: str, box: int):
+        """(nc, start, order) of box ``box`` through the read call ``entry`` of a potential's cell table."""
+        rd = getattr(self._lib, entry)
         nc = (C.c_int32 * 3)()
-        check(self._lib.gamd_water_cells_read(self._h, self._stream(), int(box), nc, None, 0, None, 0), "gamd_water_cells_read")
+        check(rd(self._h, self._stream(), int(box), nc, None, 0, None, 0), entry)
         start = np.zeros(nc[0] * nc[1] * nc[2] + 1, dtype=np.int32)
         order = np.zeros(self.n, dtype=np.int32)
-        check(self._lib.gamd_water_cells_read(self._h, self._stream(), int(box), nc, start.ctypes.data_as(C.c_void_p), start.size,
-                                              order.ctypes.data_as(C.c_void_p), order.size), "gamd_water_cells_read")
+        check(rd(self._h, self._stream(), int(box), nc, start.ctypes.data_as(C.c_void_p), start.size,
+                 order.ctypes.data_as(C.c_void_p), order.size), entry)
         return np.array(list(nc), dtype=np.int64), start, order
 
     def water_classical_reset(self) -> None:

@@ -497,6 +497,31 @@ int32_t gamd_classical_read(gamd_handle* h, void* stream, int64_t* steps, double
 int32_t gamd_classical_eval(gamd_handle* h, const float* pos_dev, const float* box, float length_per_nm, double* f_out_dev,
                             double* energy, double* virial, double* pairs, void* stream);
 
+/* The pairs of the Lennard-Jones classical potential over a cell table instead of all against all: an optional, sticky property
+ * of the handle, switched as gamd_water_cells is.  on = 0 (the default): every entry point launches what it launched before
+ * this switch existed and gives the same bits.  on = 1: the observer's sample, gamd_classical_eval, the GAMD_FORCE_CLASSICAL
+ * source and gamd_minimize (every iteration, from its double positions, and its final force) replace their pair launch by six
+ * (clear, count, scan, fill, rank, pairs) on the caller's stream.  Per evaluation and box the atoms are ordered by
+ * (cell, atom index) — cells of edge >= r_cut / 2, nc_d = min(floor(2 L_d / (r_cut (1 + 2^-20))), 64) per axis from the box's
+ * own edges — and every atom walks the table's runs under the 5 x 5 (x, y) columns around its cell (every cell of an axis with
+ * fewer than five), on the positions as they are given, with the all-pairs walk's operations: the set of pairs and the pair
+ * count are exactly the all-pairs path's; E, W and the forces differ from it in the ORDER of the sums only and lie within the
+ * same 1e-12 of their sums of absolute terms of the float64 reference.  The same bits come back run after run, from fresh
+ * handles, per box of a several-box handle, in chunked runs, across a neighbour-buffer overflow; a driven frame still carries
+ * fp32(f_cl of gamd_classical_eval on its positions) and gamd_minimize's f is that at its x.  NOT promised in bits: the same
+ * atoms given in other periodic images may fall into a neighbouring cell at a face, which changes the order of the sums (within
+ * the bound above).  Whether the table pays at a size: profiles/run_classical_cells.md.  Not built: a table kept across steps
+ * with a skin, non-orthorhombic boxes.
+ * -22, with a message naming the reason: a null handle, a GAMD_KIND_WATER handle (gamd_water_cells is that potential's), no
+ * accepted gamd_classical_configure, a pending run, on not 0 or 1; from a run that follows a pending run when its boxes need
+ * larger tables.  -12 when the tables cannot be allocated (44 B per atom, 8 B per box and cell); the switch is then off. */
+int32_t gamd_classical_cells(gamd_handle* h, int32_t on);
+
+/* Diagnostic: the cell table of box `box` as the last sample, gamd_classical_eval call, driven step or gamd_minimize call left
+ * it, to the host; arguments, meaning and refusals are gamd_water_cells_read's (below). */
+int32_t gamd_classical_cells_read(gamd_handle* h, void* stream, int32_t box, int32_t* nc, int32_t* start, int64_t max_start,
+                                  int32_t* order, int64_t max_order);
+
 /* Force source of an enqueued run: the classical run next to the GNN run — the reference's LJ data generator is a
  * Nose-Hoover-chain run under the classical force (dataset/generate_lj_data.py:74-107), and lj.ipynb cells 5-6 plot the
  * GNN-driven logs against its log.  Sticky per handle, GAMD_FORCE_NETWORK by default.  It decides where the forces of
@@ -682,7 +707,7 @@ int32_t gamd_water_pme(gamd_handle* h, const gamd_water_pme_params* p);
  * fall into a neighbouring cell at a face, which changes the order of the sums (within the bound above).
  * The table costs six launches: below a few thousand atoms all pairs are faster (profiles/run_water_cells.md).
  * Not built, and served all-pairs while the switch is on: the O-O pass of the M-site form, the virial log's own pair walk
- * (which reads the cells' f_cl), the Lennard-Jones classical potential; gamd_water_minimize returns -22 while the switch is on
+ * (which reads the cells' f_cl); gamd_water_minimize returns -22 while the switch is on
  * (its f is the all-pairs force bit for bit: minimise with the cells off, switch them on, take f from gamd_water_eval).  Nor a
  * table kept across steps with a skin, nor non-orthorhombic boxes.
  * -22, with a message naming the reason: a null handle, a GAMD_KIND_LJ handle, no accepted gamd_water_configure, a pending
