@@ -14,8 +14,8 @@
 //                       (fixed assignment), then the fixed tree of k_report_ke (shuffle 32 .. 1, (w0 + w1) + (w2 + w3)).
 //   k_classical_final   one thread per box adds the block rows in order and writes the row the HOST chose: E = sum e_i / 2,
 //                       W = sum w_i / 2, pairs = sum pairs_i / 2 (halving is exact), the five sums, the atoms left out.
-// With gamd_classical_cells on, launch_classical_cells (classical_cells.hip: a per-box cell table and a pair pass over it, the same
-// pairs in another order of the sums) stands where k_classical_pairs is, on ONE pair slice; the two kernels behind it are these.
+// With gamd_classical_cells on, launch_classical_cells (classical_cells.hip: cell_table.hip's per-box table and a pair pass over it, the
+// same pairs in another order of the sums) stands where k_classical_pairs is, on ONE pair slice; the two kernels behind it are these.
 // The arithmetic of a pair term is spelled out in DESIGN.md section 4.9 (tests/classical_ref.py mirrors it).  d_ij = -d_ji bit
 // for bit (rint is odd), so u_ij = u_ji and F_ij = -F_ji bit for bit.  Fixed atom-to-thread assignment, fixed slices and
 // blocks per handle, no floating-point atomics, contraction off: the same bits run after run.  Every kernel returns while
@@ -91,7 +91,7 @@ __global__ void k_classical_final(ClassicalArgs a) {
 
 }  // namespace
 
-int launch_classical(const ClassicalArgs& a, hipStream_t st, const WCellBufs* cells) {
+int launch_classical(const ClassicalArgs& a, hipStream_t st, const CellTabBufs* cells) {
     PassGeom g;
     if (pass_geometry(a, 1, &g) || a.blocks < 1 || a.blocks > 65535 || a.slot < 0) return -1;
     if (!a.x || !a.part || !a.f_cl || !a.blk || !a.rows || !a.devflags) return -1;

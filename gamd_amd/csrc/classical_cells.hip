@@ -5,12 +5,9 @@
 // they are given, never wrapped: a pair's d, minimum image and r^2 come from the same operations on the same two doubles as in
 // gamd_lj_walk (gamd_passes_dev.h), so the set of pairs and the pair count are the all-pairs walk's by construction.
 // Per box nx x ny x nz cells (gamd_cells_dev.h: cells per axis, cell of a coordinate, neighbour lists), cell = (cx ny + cy) nz + cz.
+// The table — the box's atoms ordered by (cell, atom index), entries {x, y, z, atom index} and an O flag of 0 — is
+// cell_table.hip's, built by launch_cell_table in front of the pair pass of every evaluation.
 //
-//   k_ljcell_clear, k_ljcell_count, k_ljcell_scan, k_ljcell_fill, k_ljcell_rank
-//                   the table, by the five steps of water_cells.hip (which see): integer counts, an exclusive scan, an unordered
-//                   fill, rank-by-counting into a table ordered by (cell, atom index) whose entries are {x, y, z, atom index}.
-//                   The counts and the fill cursors are the only buffers updated in place and are cleared at the head of EVERY
-//                   evaluation: a sample that runs twice writes the same bits twice.
 //   k_ljcell_pairs  the pair pass with every accumulator {Fx, Fy, Fz, e_i, w_i, pairs_i} (the observer, gamd_classical_eval)
 //   k_ljcell_force  ... the force accumulators only (the force source, the minimiser's final force)
 //   k_ljcell_min    ... {Fx, Fy, Fz, e_i} (an iteration of the minimiser, whose table was built from x64)
@@ -30,16 +27,15 @@
 //                   minimiser's f.
 // No floating-point atomics; fixed slot-to-lane and column-to-lane assignment; contraction off: the same bits run after run.
 // Every kernel returns while DEVFLAG_FROZEN is set, and for a box the minimiser has stopped.  Checked build: an atom's cell, a
-// cell's start, a slot and a table entry's atom index pass through GAMD_CHK_RANGE before they are used as addresses.  A box
-// whose cells exceed the tables' room (the host sizes them from the same boxes by the same expression; cannot happen) is left
-// alone by every kernel.
+// cell's start and a table entry's atom index pass through GAMD_CHK_RANGE before they are used as addresses.  A box whose cells
+// exceed the tables' room (the host sizes them from the same boxes by the same function; cannot happen) is left alone by every
+// kernel.
 #include "gamd_common.h"
 #include "gamd_internal.h"
 
 #pragma clang fp contract(off)
 
 #include "gamd_passes_dev.h"
-#include "gamd_cells_dev.h"
 
 namespace {
 
@@ -51,21 +47,9 @@ constexpr int LJCELL_BATCH = 4;                                 // table entries
 
 struct LjCellArgs {
     ClassicalArgs a;
-    WCellBufs c;
-    const double* x64;         // [n][3] the minimiser's positions, or null: the fp32 positions a.x
+    CellTabBufs c;
     const int* stopped;        // [n_boxes] the minimiser's gates, or null
 };
-
-struct LjCellGeom { int nx, ny, nz, cells; bool ok; };
-__device__ __forceinline__ LjCellGeom ljcell_geom(const LjCellArgs& k, int box) {
-    LjCellGeom g;
-    g.nx = gamd_cells_per_axis(gamd_box_edge(k.a, box, 0), k.c.r_cut);
-    g.ny = gamd_cells_per_axis(gamd_box_edge(k.a, box, 1), k.c.r_cut);
-    g.nz = gamd_cells_per_axis(gamd_box_edge(k.a, box, 2), k.c.r_cut);
-    g.cells = (g.nx * g.ny) * g.nz;                         // <= 64^3
-    g.ok = g.cells <= k.c.cap;
-    return g;
-}
 
 // a frame that will be evaluated again, or a box whose positions stay
 __device__ __forceinline__ bool ljcell_gated(const LjCellArgs& k, int box) {
@@ -73,106 +57,8 @@ __device__ __forceinline__ bool ljcell_gated(const LjCellArgs& k, int box) {
     return k.stopped && k.stopped[box] != 0;
 }
 
-// atom i (all boxes) as the walk reads it
-__device__ __forceinline__ void ljcell_load(const LjCellArgs& k, size_t i, double& px, double& py, double& pz) {
-    if (k.x64) GamdPosF64{k.x64}.load(i, px, py, pz);
-    else GamdPosF32{k.a.x}.load(i, px, py, pz);
-}
-
-__global__ void __launch_bounds__(256) k_ljcell_clear(LjCellArgs k) {
-    const int box = blockIdx.y;
-    if (ljcell_gated(k, box)) return;
-    const LjCellGeom g = ljcell_geom(k, box);
-    if (!g.ok) return;
-    const int c = blockIdx.x * 256 + threadIdx.x;
-    if (c <= g.cells) k.c.start[(size_t)box * ((size_t)k.c.cap + 1) + (size_t)c] = 0;
-    if (c < g.cells) k.c.fill[(size_t)box * (size_t)k.c.cap + (size_t)c] = 0;
-}
-
-__global__ void __launch_bounds__(256) k_ljcell_count(LjCellArgs k) {
-    const ClassicalArgs& a = k.a;
-    const int box = blockIdx.y, npb = gamd_npb(a);
-    if (ljcell_gated(k, box)) return;
-    const LjCellGeom g = ljcell_geom(k, box);
-    const int il = blockIdx.x * 256 + threadIdx.x;          // one thread per atom
-    if (!g.ok || il >= npb) return;
-    const size_t i = (size_t)box * (size_t)npb + (size_t)il;
-    double px, py, pz;
-    ljcell_load(k, i, px, py, pz);
-    const int cx = gamd_cells_index(px, gamd_box_edge(a, box, 0), g.nx), cy = gamd_cells_index(py, gamd_box_edge(a, box, 1), g.ny),
-              cz = gamd_cells_index(pz, gamd_box_edge(a, box, 2), g.nz);
-    const int c = (cx * g.ny + cy) * g.nz + cz;             // in [0, cells): every factor is in its range for every bit pattern
-    k.c.cell_of[i] = c;
-    atomicAdd(k.c.start + (size_t)box * ((size_t)k.c.cap + 1) + (size_t)c, 1);
-}
-
-__global__ void __launch_bounds__(256) k_ljcell_scan(LjCellArgs k) {
-    __shared__ int sums[256];
-    const int box = blockIdx.x, tid = threadIdx.x;
-    if (ljcell_gated(k, box)) return;                       // (uniform)
-    const LjCellGeom g = ljcell_geom(k, box);
-    if (!g.ok) return;                                      // (uniform)
-    int* start = k.c.start + (size_t)box * ((size_t)k.c.cap + 1);
-    const int run = (g.cells + 255) / 256;
-    const int c0 = tid * run < g.cells ? tid * run : g.cells, c1 = c0 + run < g.cells ? c0 + run : g.cells;
-    int s = 0;
-    for (int c = c0; c < c1; ++c) s += start[c];
-    sums[tid] = s;
-    __syncthreads();
-    for (int d = 1; d < 256; d <<= 1) {                     // inclusive scan of the 256 sums
-        const int v = tid >= d ? sums[tid - d] : 0;
-        __syncthreads();
-        sums[tid] += v;
-        __syncthreads();
-    }
-    int at = sums[tid] - s;                                 // the atoms in front of this thread's run
-    for (int c = c0; c < c1; ++c) {
-        const int m = start[c];
-        start[c] = at;
-        at += m;
-    }
-    if (tid == 255) start[g.cells] = sums[255];
-}
-
-__global__ void __launch_bounds__(256) k_ljcell_fill(LjCellArgs k) {
-    const ClassicalArgs& a = k.a;
-    const int box = blockIdx.y, npb = gamd_npb(a);
-    if (ljcell_gated(k, box)) return;
-    const LjCellGeom g = ljcell_geom(k, box);
-    const int il = blockIdx.x * 256 + threadIdx.x;          // one thread per atom
-    if (!g.ok || il >= npb) return;
-    const size_t a0 = (size_t)box * (size_t)npb;
-    const int c = GAMD_CHK_RANGE(k.c.sticky, k.c.cell_of[a0 + (size_t)il], 0, g.cells - 1, GAMD_CHK_LJCELL_CELL);
-    const int s0 = GAMD_CHK_RANGE(k.c.sticky, k.c.start[(size_t)box * ((size_t)k.c.cap + 1) + (size_t)c], 0, npb, GAMD_CHK_LJCELL_START);
-    const int m = atomicAdd(k.c.fill + (size_t)box * (size_t)k.c.cap + (size_t)c, 1);
-    const int slot = GAMD_CHK_RANGE(k.c.sticky, s0 + m, 0, npb - 1, GAMD_CHK_LJCELL_SLOT);
-    k.c.members[a0 + (size_t)slot] = il;
-}
-
-__global__ void __launch_bounds__(256) k_ljcell_rank(LjCellArgs k) {
-    const ClassicalArgs& a = k.a;
-    const int box = blockIdx.y, npb = gamd_npb(a);
-    if (ljcell_gated(k, box)) return;
-    const LjCellGeom g = ljcell_geom(k, box);
-    const int il = blockIdx.x * 256 + threadIdx.x;          // one thread per atom
-    if (!g.ok || il >= npb) return;
-    const size_t a0 = (size_t)box * (size_t)npb;
-    const int* start = k.c.start + (size_t)box * ((size_t)k.c.cap + 1);
-    const int c = GAMD_CHK_RANGE(k.c.sticky, k.c.cell_of[a0 + (size_t)il], 0, g.cells - 1, GAMD_CHK_LJCELL_CELL);
-    const int s0 = GAMD_CHK_RANGE(k.c.sticky, start[c], 0, npb, GAMD_CHK_LJCELL_START);
-    const int s1 = GAMD_CHK_RANGE(k.c.sticky, start[c + 1], 0, npb, GAMD_CHK_LJCELL_START);
-    int rank = 0;
-    for (int s = s0; s < s1; ++s) rank += k.c.members[a0 + (size_t)s] < il ? 1 : 0;
-    const int slot = GAMD_CHK_RANGE(k.c.sticky, s0 + rank, 0, npb - 1, GAMD_CHK_LJCELL_SLOT);
-    k.c.order[a0 + (size_t)slot] = il;
-    WCellAtom t;
-    ljcell_load(k, a0 + (size_t)il, t.x, t.y, t.z);
-    t.idx = il; t.o = 0;
-    k.c.table[a0 + (size_t)slot] = t;
-}
-
 // a table entry in one 32-byte load: {x, y, z} and, in the low half of the fourth double, the atom inside its box
-static_assert(sizeof(WCellAtom) == sizeof(double4) && offsetof(WCellAtom, idx) == 3 * sizeof(double), "a table entry is read as a double4");
+static_assert(sizeof(CellTabAtom) == sizeof(double4) && offsetof(CellTabAtom, idx) == 3 * sizeof(double), "a table entry is read as a double4");
 __device__ __forceinline__ int ljcell_idx(const double4& t) { return (int)(unsigned)(unsigned long long)__double_as_longlong(t.w); }
 
 template <int NOUT>
@@ -182,7 +68,7 @@ __device__ __forceinline__ void ljcell_walk(const LjCellArgs& k) {
     const int l = threadIdx.x & (LJCELL_LANES - 1);
     const int box = blockIdx.y, npb = gamd_npb(a);
     const size_t a0 = (size_t)box * (size_t)npb;            // the caller's order is box-major
-    const LjCellGeom g = ljcell_geom(k, box);
+    const CellTabGeom g = gamd_celltab_geom(k.a, k.c, box);
     if (!g.ok) return;                                      // (uniform)
     const int sl = blockIdx.x * LJCELL_SLOTS + (int)(threadIdx.x / LJCELL_LANES);
     const bool vi = sl < npb;
@@ -282,21 +168,14 @@ __global__ void __launch_bounds__(256) k_ljcell_min(LjCellArgs k) {
 
 }  // namespace
 
-int launch_classical_cells(const ClassicalArgs& a, const WCellBufs& c, const double* x64, const int* stopped, int nout, hipStream_t st) {
+int launch_classical_cells(const ClassicalArgs& a, const CellTabBufs& c, const double* x64, const int* stopped, int nout, hipStream_t st) {
     PassGeom g;
     if (pass_rows(a, 1, &g) || a.slices != 1 || (nout != 3 && nout != 4 && nout != CLASSICAL_PART)) return -1;
     if ((!a.x && !x64) || !a.part || !a.devflags) return -1;
-    if (c.cap < 1 || c.cap > GAMD_CELLS_MAX * GAMD_CELLS_MAX * GAMD_CELLS_MAX || !(c.r_cut > 0.0)) return -1;
-    if (!c.start || !c.fill || !c.cell_of || !c.members || !c.order || !c.table) return -1;
     if (((long long)g.npb + LJCELL_SLOTS - 1) / LJCELL_SLOTS > 0x7fffffll) return -1;
-    const LjCellArgs k{a, c, x64, stopped};
-    const dim3 atoms((unsigned)g.T, g.nb), b256(256);
-    hipLaunchKernelGGL(k_ljcell_clear, dim3((unsigned)((c.cap + 1 + 255) / 256), g.nb), b256, 0, st, k); GAMD_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_ljcell_count, atoms, b256, 0, st, k); GAMD_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_ljcell_scan, dim3(g.nb), b256, 0, st, k); GAMD_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_ljcell_fill, atoms, b256, 0, st, k); GAMD_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_ljcell_rank, atoms, b256, 0, st, k); GAMD_CHECK_LAUNCH();
-    const dim3 pg((unsigned)((g.npb + LJCELL_SLOTS - 1) / LJCELL_SLOTS), g.nb);
+    if (int r = launch_cell_table(cell_tab_args(a, c, stopped, x64, nullptr, GAMD_CHK_LJCELL_CELL), st)) return r;
+    const LjCellArgs k{a, c, stopped};
+    const dim3 pg((unsigned)((g.npb + LJCELL_SLOTS - 1) / LJCELL_SLOTS), g.nb), b256(256);
     if (nout == 3) hipLaunchKernelGGL(k_ljcell_force, pg, b256, 0, st, k);
     else if (nout == 4) hipLaunchKernelGGL(k_ljcell_min, pg, b256, 0, st, k);
     else hipLaunchKernelGGL(k_ljcell_pairs, pg, b256, 0, st, k);

@@ -8,8 +8,8 @@
 //                       partial row (the row keeps its CLASSICAL_PART stride; e_i, w_i, pairs_i are not written).
 //   k_drive_lj_atoms    one thread per atom: the slices' partials added in order from 0, f_cl = F * len in double to f_cl, and
 //                       (float)f_cl (round to nearest) to the run's force buffer.
-// With gamd_classical_cells on, launch_classical_cells (classical_cells.hip, k_ljcell_force) stands where k_drive_lj_pairs is, on ONE
-// pair slice: the force terms and their order are those of the observer's cell pass, so the contract below holds there too.
+// With gamd_classical_cells on, launch_classical_cells (cell_table.hip's table, then k_ljcell_force of classical_cells.hip) stands where
+// k_drive_lj_pairs is, on ONE pair slice: the force terms and their order are those of the observer's cell pass, so the contract below holds there too.
 // No energy sums, no error sums, no final kernel.  The force bits are those of k_classical_pairs / k_classical_atoms on the same
 // positions: f == fp32(f_cl of gamd_classical_eval) bit for bit.  `part` and `f_cl` are shared with the observer on one stream;
 // a step that is driven and sampled evaluates twice and writes the same bits twice.  Fixed assignment, no floating-point
@@ -49,7 +49,7 @@ __global__ void __launch_bounds__(256) k_drive_lj_atoms(ClassicalArgs a, float* 
 
 }  // namespace
 
-int launch_classical_drive(const ClassicalArgs& a, float* f_out, hipStream_t st, const WCellBufs* cells) {
+int launch_classical_drive(const ClassicalArgs& a, float* f_out, hipStream_t st, const CellTabBufs* cells) {
     PassGeom g;
     if (pass_geometry(a, 1, &g)) return -1;
     if (!a.x || !a.part || !a.f_cl || !a.devflags || !f_out) return -1;

@@ -1,7 +1,8 @@
-// gamd_cells_dev.h — what the cell-table kernels of the water classical potential (water_cells.hip)
-// share with the host and with a plain C++ compiler: the cells per axis of a box, the cell of a coordinate, and the neighbour
-// cells of a cell along one axis.  No ROCm header is needed to include it: a stand-alone host program
-// (tools/cells_host_check.cpp) calls every function here under the address and undefined-behaviour sanitizers.
+// gamd_cells_dev.h — what the cell-table kernels of the classical potentials (the builder cell_table.hip and the walks
+// water_cells.hip and classical_cells.hip) share with the host and with a plain C++ compiler: the cells
+// per axis and per box, the cell of a coordinate, and the neighbour cells of a cell along one axis.  No ROCm header is needed to
+// include it: a stand-alone host program (tools/cells_host_check.cpp) calls every function here under the address and
+// undefined-behaviour sanitizers.
 //
 // Reach.  R = 2: a cell's edge is at least r_cut / 2, and a pair inside the cutoff lies at most two cells apart along every
 // axis.  The 5^3 = 125 cells of that size cover 15.6 r_cut^3 against the sphere's 4.2 r_cut^3; R = 1 (27 cells of edge r_cut)
@@ -45,6 +46,12 @@ GAMD_CELLS_HD int gamd_cells_per_axis(double L, double r_cut) {
     const double v = floor((2.0 * L) / (r_cut * GAMD_CELLS_MARGIN));
     if (!(v >= 1.0)) return 1;                              // a ratio below 1, or not a number
     return v < (double)GAMD_CELLS_MAX ? (int)v : GAMD_CELLS_MAX;
+}
+
+// cells of a box with the edges Lx, Ly, Lz: nc = the three axes' gamd_cells_per_axis, returned their product, in [1, 64^3]
+GAMD_CELLS_HD int gamd_cells_count(double Lx, double Ly, double Lz, double r_cut, int nc[3]) {
+    nc[0] = gamd_cells_per_axis(Lx, r_cut); nc[1] = gamd_cells_per_axis(Ly, r_cut); nc[2] = gamd_cells_per_axis(Lz, r_cut);
+    return (nc[0] * nc[1]) * nc[2];
 }
 
 // cell in [0, nc) of coordinate x along an axis of edge L (see "Cell of a coordinate")

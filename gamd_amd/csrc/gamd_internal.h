@@ -574,6 +574,45 @@ struct StructArgs {
 int launch_struct_pairs(const StructArgs& a, hipStream_t st);
 int launch_struct_sk(const StructArgs& a, hipStream_t st);
 
+// ---- the cell table under the classical potentials' pair passes (cell_table.hip) ---------------------------------------
+// Per box a table of the atoms ordered by (cell, atom index), rebuilt at the head of every evaluation from the positions as they
+// are given (gamd_cells_dev.h: the cells of a box, the cell of a coordinate).  One builder, five
+// launches on `st`: clear, count, scan, fill, rank; the walks over the table are the potentials' own (water_cells.hip,
+// classical_cells.hip).  Every kernel returns while DEVFLAG_FROZEN is set and for a box with stopped[box] != 0.
+// Every value read from memory and then used as an address — an atom's cell, a cell's start, a slot — passes through
+// GAMD_CHK_RANGE under the caller's codes chk, chk + 1, chk + 2 (a table entry's atom index: the walks', chk + 3).
+struct CellTabAtom { double x, y, z; int idx, o; };   // a table entry: the position as the walk reads it, the atom inside its box, O != 0
+struct CellTabBufs {
+    double r_cut;              // the cutoff the cells per axis are computed from (gamd_cells_per_axis), length unit
+    int cap;                   // cells per box the tables below have room for
+    int* sticky;               // host-mapped (checked build)
+    int* start;                // [n_boxes][cap + 1] the counts per cell, then (scan) the first slot of every cell and n_per_box behind the last
+    int* fill;                 // [n_boxes][cap] members placed so far (cleared with the counts at the head of every sample)
+    int* cell_of;              // [n] the atom's cell inside its box
+    int* members;              // [n] per box and cell the atoms of the cell, in the order the atomics gave
+    int* order;                // [n] per box the atoms in table order: by (cell, atom index)
+    CellTabAtom* table;        // [n] the table-ordered copy
+};
+struct CellTabArgs {
+    int n;                     // atoms of all boxes
+    BoxRef bx;
+    float box[3];              // n_boxes <= 1 and box_edges == null
+    const float* box_edges;    // device [n_boxes][3], or null: box / bx.boxes of the run
+    const int* devflags;
+    const int* stopped;        // [n_boxes] a minimiser's gates, or null: no per-box gate
+    const float* x;            // [n][3] positions, length unit, any periodic image
+    const double* x64;         // [n][3] a minimiser's positions or the M-site pass's charge sites, or null: x widened
+    const uint8_t* species;    // [n] O != 0, or null: every entry's O flag is 0
+    int chk;                   // the caller's first range-check code
+    CellTabBufs c;
+};
+// the builder's block from a potential's (ClassicalArgs, WaterArgs: its atoms, boxes, flags and fp32 positions)
+template <typename Args>
+inline CellTabArgs cell_tab_args(const Args& a, const CellTabBufs& c, const int* stopped, const double* x64, const uint8_t* species, int chk) {
+    return CellTabArgs{a.n, a.bx, {a.box[0], a.box[1], a.box[2]}, a.box_edges, a.devflags, stopped, a.x, x64, species, chk, c};
+}
+int launch_cell_table(const CellTabArgs& k, hipStream_t st);
+
 // ---- classical potential (classical.hip) ----------------------------------------------------------
 // One sample of an enqueued MD run (gamd_classical_configure) or one gamd_classical_eval call: the switched, shifted
 // Lennard-Jones potential of include/gamd_hip.h on every pair of every box in double, from the caller's fp32 positions in the
@@ -606,15 +645,14 @@ struct ClassicalArgs {
     long long g;               // completed MD steps at this sample
 };
 // `cells` (gamd_classical_cells; `a` arrives with slices = 1): launch_classical_cells stands where the pair launch is; null: all pairs
-struct WCellBufs;
-int launch_classical(const ClassicalArgs& a, hipStream_t st, const WCellBufs* cells = nullptr);
+int launch_classical(const ClassicalArgs& a, hipStream_t st, const CellTabBufs* cells = nullptr);
 
 // ---- classical force source (drive.hip) -------------------------------------------------------------
 // One force evaluation of a classical-source step of an enqueued MD run (gamd_md_force_source): the pair pass of classical.hip
 // (tiles, slices and arithmetic of k_classical_pairs; forces only) into a.part, then per atom the slice partials added in order
 // from 0, f_cl = F * len to a.f_cl and (float)f_cl to f_out ([n][3], the caller's atom order).  a.f, a.blk, a.rows, a.steps,
 // a.slot and a.g are not used.  Two launches, plain stores.
-int launch_classical_drive(const ClassicalArgs& a, float* f_out, hipStream_t st, const WCellBufs* cells = nullptr);
+int launch_classical_drive(const ClassicalArgs& a, float* f_out, hipStream_t st, const CellTabBufs* cells = nullptr);
 
 // ---- water classical potential (water_classical.hip) ------------------------------------------------
 // One sample of an enqueued MD run (gamd_water_configure) or one gamd_water_eval call: 3-site water in the caller's order
@@ -667,8 +705,7 @@ struct WaterArgs {
 // reciprocal launches are; null: the plain sum, launch for launch as it was
 // `cells` (gamd_water_cells; `a` arrives with slices = 1): launch_water_cells stands where the pair launch is; null: all pairs
 struct PmeArgs;
-struct WCellBufs;
-int launch_water_classical(const WaterArgs& a, hipStream_t st, const PmeArgs* pme = nullptr, const WCellBufs* cells = nullptr);
+int launch_water_classical(const WaterArgs& a, hipStream_t st, const PmeArgs* pme = nullptr, const CellTabBufs* cells = nullptr);
 // k_water_rho, k_water_sk, k_water_recip alone, with launch_water_classical's checks for them: a.rpart (and a.sk, a.ublk) from a.x
 int launch_water_recip(const WaterArgs& a, hipStream_t st);
 // k_water_sk alone (it reads no positions): a.sk and a.ublk from a.rho_partial, for the water minimiser's own rho and force passes
@@ -706,7 +743,7 @@ inline int pass_k_geometry(const WaterArgs& a, long long T, bool chunked) {
 // pass of water_classical.hip (tiles, slices and arithmetic of k_water_pairs; forces only) into a.part, launch_water_recip, then
 // per atom the pair slices and the k slices added in order from 0, f_cl to a.f_cl and (float)f_cl to f_out ([n][3], the
 // caller's atom order).  a.f, a.blk, a.rows, a.steps, a.slot and a.g are not used.  Five launches, plain stores.
-int launch_water_drive(const WaterArgs& a, float* f_out, hipStream_t st, const PmeArgs* pme = nullptr, const WCellBufs* cells = nullptr);
+int launch_water_drive(const WaterArgs& a, float* f_out, hipStream_t st, const PmeArgs* pme = nullptr, const CellTabBufs* cells = nullptr);
 
 // ---- the TIP4P M-site in the water classical potential (water_msite.hip) ------------------------------
 // The potential of WaterArgs with the negative charge on a virtual site M = O' + w_h (d_1 + d_2) of every molecule
@@ -723,9 +760,9 @@ struct W4Args {
     double* ljpart;            // [n_boxes][slices][n_per_box / 3][W4_LJ]
 };
 // k_w4_sites, k_w4_pairs, k_w4_lj, k_w4_rho, k_water_sk, k_w4_recip, k_w4_atoms, k_water_final: launch_water_classical's row and f_cl
-int launch_w4_classical(const W4Args& a, hipStream_t st, const PmeArgs* pme = nullptr, const WCellBufs* cells = nullptr);
+int launch_w4_classical(const W4Args& a, hipStream_t st, const PmeArgs* pme = nullptr, const CellTabBufs* cells = nullptr);
 // ... the first six and k_w4_drive: launch_water_drive's f_cl and f_out (the energies of the pair pass are computed and not read)
-int launch_w4_drive(const W4Args& a, float* f_out, hipStream_t st, const PmeArgs* pme = nullptr, const WCellBufs* cells = nullptr);
+int launch_w4_drive(const W4Args& a, float* f_out, hipStream_t st, const PmeArgs* pme = nullptr, const CellTabBufs* cells = nullptr);
 
 // ---- smooth particle-mesh Ewald for the water classical potential (water_pme.hip) -----------------------
 // A second producer of w.rpart and w.ublk (gamd_water_pme): instead of k_water_rho, k_water_sk and
@@ -751,38 +788,25 @@ int launch_water_pme(const PmeArgs& p, hipStream_t st);
 
 // ---- the real-space pairs of the water classical potential over a cell table (water_cells.hip) ------------
 // A second producer of the pair rows w.part (gamd_water_cells): instead of k_water_pairs, k_wsrc_pairs
-// or k_w4_pairs a table of the box's atoms ordered by (cell, atom index) is built from the positions — w.x, or `sites` for the
-// M-site form — and every atom walks the atoms of its cell's neighbour cells, gamd_water_walk's body on the same doubles.  The
-// rows go to w.part as ONE pair slice: `w` arrives with w.slices = 1 and w.chunk = n_per_box, and k_water_atoms, k_wsrc_atoms,
-// k_w4_atoms and k_w4_drive run on it as they are.  Six launches on `st`: clear, count, scan, fill, rank, pairs.
-// Every value read from memory and then used as an address — an atom's cell, a cell's start, a slot, a table entry's atom index —
-// passes through GAMD_CHK_RANGE.
+// or k_w4_pairs the table of CellTabBufs is built from the positions — w.x, or `sites` for the M-site form — with the O flags of
+// w.species (launch_cell_table), and every atom walks the atoms of its cell's neighbour cells, gamd_water_walk's body on the same
+// doubles.  The rows go to w.part as ONE pair slice: `w` arrives with w.slices = 1 and w.chunk = n_per_box, and k_water_atoms,
+// k_wsrc_atoms, k_w4_atoms and k_w4_drive run on it as they are.  Six launches on `st`: the table's five, pairs.
+// The first three codes are the builder's chk, chk + 1, chk + 2; the walk checks what it reads under the same ones and _ATOM.
 enum { GAMD_CHK_WCELL_CELL = 151, GAMD_CHK_WCELL_START = 152, GAMD_CHK_WCELL_SLOT = 153, GAMD_CHK_WCELL_ATOM = 154 };
-struct WCellAtom { double x, y, z; int idx, o; };   // a table entry: the position as the walk reads it, the atom inside its box, O != 0
-struct WCellBufs {
-    double r_cut;              // the cutoff the cells per axis are computed from (gamd_cells_per_axis), length unit
-    int cap;                   // cells per box the tables below have room for
-    int* sticky;               // host-mapped (checked build)
-    int* start;                // [n_boxes][cap + 1] the counts per cell, then (scan) the first slot of every cell and n_per_box behind the last
-    int* fill;                 // [n_boxes][cap] members placed so far (cleared with the counts at the head of every sample)
-    int* cell_of;              // [n] the atom's cell inside its box
-    int* members;              // [n] per box and cell the atoms of the cell, in the order the atomics gave
-    int* order;                // [n] per box the atoms in table order: by (cell, atom index)
-    WCellAtom* table;          // [n] the table-ordered copy
-};
 // nout = WATER_PART (the observer, gamd_water_eval) or 3 (the force source); lj: the O-O term in the walk (3-site), else `sites`
-int launch_water_cells(const WaterArgs& w, const WCellBufs& c, const double* sites, int nout, bool lj, hipStream_t st);
+int launch_water_cells(const WaterArgs& w, const CellTabBufs& c, const double* sites, int nout, bool lj, hipStream_t st);
 
 // ---- the pairs of the Lennard-Jones classical potential over a cell table (classical_cells.hip) ------------
 // A second producer of the pair rows a.part (gamd_classical_cells): instead of k_classical_pairs,
-// k_drive_lj_pairs or k_min_pairs the table of WCellBufs (the entries' O flag is 0) is built from the positions — a.x, or `x64` for
-// the minimiser — and every atom walks the table's runs around its cell, gamd_lj_walk's body on the same doubles.  The rows go to
-// a.part as ONE pair slice: `a` arrives with a.slices = 1 and a.chunk = n_per_box, and k_classical_atoms, k_drive_lj_atoms and
-// k_min_atoms run on it as they are.  Six launches on `st`: clear, count, scan, fill, rank, pairs.  `stopped` (the minimiser's
-// gates, or null): a box with stopped[box] != 0 is left alone.  The range checks are water_cells.hip's, under codes of their own.
+// k_drive_lj_pairs or k_min_pairs the table of CellTabBufs (no species: the entries' O flag is 0) is built from the positions —
+// a.x, or `x64` for the minimiser — and every atom walks the table's runs around its cell, gamd_lj_walk's body on the same
+// doubles.  The rows go to a.part as ONE pair slice: `a` arrives with a.slices = 1 and a.chunk = n_per_box, and k_classical_atoms,
+// k_drive_lj_atoms and k_min_atoms run on it as they are.  Six launches on `st`: the table's five, pairs.  `stopped` (the
+// minimiser's gates, or null): a box with stopped[box] != 0 is left alone.  The codes: as the water walk's, of their own.
 enum { GAMD_CHK_LJCELL_CELL = 155, GAMD_CHK_LJCELL_START = 156, GAMD_CHK_LJCELL_SLOT = 157, GAMD_CHK_LJCELL_ATOM = 158 };
 // nout = CLASSICAL_PART (the observer, gamd_classical_eval), 3 (the force source) or 4 ({F, e_i}: an iteration of the minimiser)
-int launch_classical_cells(const ClassicalArgs& a, const WCellBufs& c, const double* x64, const int* stopped, int nout, hipStream_t st);
+int launch_classical_cells(const ClassicalArgs& a, const CellTabBufs& c, const double* x64, const int* stopped, int nout, hipStream_t st);
 
 // ---- molecular virial of the water classical potential (water_virial.hip) ------------------------------
 // The virial log of gamd_water_virial: launched BEHIND launch_water_classical / launch_w4_classical
@@ -838,8 +862,8 @@ struct MinArgs {
     FireArgs fire;
 };
 int launch_minimize_init(const MinArgs& m, const float* x, hipStream_t st);
-// `cells` (gamd_classical_cells; m.c arrives with slices = 1): the table from x64 and k_ljcell_min stand where k_min_pairs is
-int launch_minimize_iter(const MinArgs& m, hipStream_t st, const WCellBufs* cells = nullptr);
+// `cells` (gamd_classical_cells; m.c arrives with slices = 1): launch_classical_cells (the table from x64, k_ljcell_min) stands where k_min_pairs is
+int launch_minimize_iter(const MinArgs& m, hipStream_t st, const CellTabBufs* cells = nullptr);
 // x_out = fp32(x64) wrapped (skipped for a box that failed at iteration 0); f_out = f_in for every box that did not fail
 int launch_minimize_store_x(const MinArgs& m, float* x_out, hipStream_t st);
 // (either minimiser's: n and bx are the handle's atoms and boxes)

@@ -12,6 +12,7 @@
 #include "gamd_common.h"
 #include "gamd_internal.h"
 #include "gamd_potential_dev.h"
+#include "gamd_cells_dev.h"
 
 #pragma clang fp contract(off)
 
@@ -35,6 +36,18 @@ struct GamdPosF64 {                                         // double positions:
 
 template <typename Args>
 __device__ __forceinline__ int gamd_npb(const Args& a) { return a.bx.n_boxes > 1 ? a.bx.n_per_box : a.n; }
+
+// ---- the cell table's geometry of a box (cell_table.hip builds the table, water_cells.hip and classical_cells.hip walk it) ----
+struct CellTabGeom { int nx, ny, nz, cells; bool ok; };     // ok: the tables have room for the box's cells
+template <typename Args>
+__device__ __forceinline__ CellTabGeom gamd_celltab_geom(const Args& a, const CellTabBufs& c, int box) {
+    int nc[3];
+    CellTabGeom g;
+    g.cells = gamd_cells_count(gamd_box_edge(a, box, 0), gamd_box_edge(a, box, 1), gamd_box_edge(a, box, 2), c.r_cut, nc);   // <= 64^3
+    g.nx = nc[0]; g.ny = nc[1]; g.nz = nc[2];
+    g.ok = g.cells <= c.cap;
+    return g;
+}
 
 // ---- the Lennard-Jones tile walk ------------------------------------------------------------------------------------
 // grid (T * slices, boxes), T = 256-atom row tiles per box: workgroup (I, s) keeps atom t of tile I in the registers of thread t

@@ -16,8 +16,8 @@
 //                   that stops keeps its positions.  Then v = c1 v + c2 F (or 0), v += dt F, dr = dt v, |dr| clamped per atom
 //                   to max_step, x64 += dr.
 //
-// With gamd_classical_cells on, launch_classical_cells (classical_cells.hip: the table rebuilt from x64, then k_ljcell_min) stands
-// where k_min_pairs is in every iteration, on ONE pair slice, and returns at once for a stopped box like the kernels here.
+// With gamd_classical_cells on, launch_classical_cells (cell_table.hip's table rebuilt from x64, then k_ljcell_min of classical_cells.hip)
+// stands where k_min_pairs is in every iteration, on ONE pair slice, and returns at once for a stopped box like the kernels here.
 //
 // F is in kJ/mol/nm and x, max_step in the handle's length unit: dt is a pseudo-time that absorbs the units (and the mass).
 // Scalar state {dt, alpha, n_pos} sits in two slots per box: iteration `it` reads slot it & 1 in every thread and thread 0 of
@@ -208,7 +208,7 @@ int launch_minimize_init(const MinArgs& m, const float* x, hipStream_t st) {
     return 0;
 }
 
-int launch_minimize_iter(const MinArgs& m, hipStream_t st, const WCellBufs* cells) {
+int launch_minimize_iter(const MinArgs& m, hipStream_t st, const CellTabBufs* cells) {
     PassGeom g;
     if (min_check(m, &g)) return -1;
     if (cells) {                                            // gamd_classical_cells: {F, u_i} over the cell table of x64, one slice

@@ -95,7 +95,7 @@ struct PotentialLog {
 
 // the cell table of a potential's pair pass (gamd_water_cells, gamd_classical_cells): the switch, and per box the tables
 struct CellTables {
-    bool cells = false;                // the pairs walk a per-box cell table (water_cells.hip, classical_cells.hip)
+    bool cells = false;                // the pairs walk cell_table.hip's per-box table (water_cells.hip, classical_cells.hip)
     bool cells_sampled = false;        // ... and the table holds the atoms of a sample, an eval call, a driven step or a minimiser's pass
     int cell_cap = 0;                  // cells per box the tables have room for (grows with the boxes the handle is given)
     std::vector<float> cell_box;       // [n_boxes][3] the edges the last enqueued table is built for (what the read call goes by)
@@ -105,6 +105,24 @@ struct CellTables {
     void enqueued(double r_cut) { cell_box = cell_box_next; cell_rcut = r_cut; cells_sampled = true; }
     DevBuf cell_start, cell_fill;      // cells on: per box and cell
     DevBuf cell_of, cell_members, cell_order, cell_table;   // ... per atom
+    // the switch off: no table, no room
+    void drop() {
+        cells = cells_sampled = false;
+        cell_cap = 0; cell_box.clear(); cell_box_next.clear();
+        for (DevBuf* b : {&cell_start, &cell_fill, &cell_of, &cell_members, &cell_order, &cell_table}) b->release();
+    }
+    // the table in force for an evaluation that is being enqueued under r_cut: its buffers, or null while the switch is off (b is
+    // the caller's room for them)
+    const CellTabBufs* bufs(double r_cut, int* sticky, CellTabBufs& b) {
+        if (!cells) return nullptr;
+        b = CellTabBufs{r_cut, cell_cap, sticky, cell_start.as<int>(), cell_fill.as<int>(), cell_of.as<int>(), cell_members.as<int>(),
+                        cell_order.as<int>(), cell_table.as<CellTabAtom>()};
+        enqueued(r_cut);
+        return &b;
+    }
+    // ... whose pair rows are ONE slice
+    template <typename Args>
+    void one_slice(Args& a, int n_per_box) const { if (cells) { a.slices = 1; a.chunk = n_per_box; } }
 };
 
 // classical observer: Lennard-Jones and nothing else
@@ -205,7 +223,7 @@ void cell_bufs_append(gamd_handle* h, CellTables& ct, ObsBufs& t) {
     t.push_back({&ct.cell_start, c * sizeof(int) * nb * (cap + 1), false});
     t.push_back({&ct.cell_fill, c * sizeof(int) * nb * cap, false});
     for (DevBuf* b : {&ct.cell_of, &ct.cell_members, &ct.cell_order}) t.push_back({b, c * sizeof(int) * n, false});
-    t.push_back({&ct.cell_table, c * sizeof(WCellAtom) * n, false});
+    t.push_back({&ct.cell_table, c * sizeof(CellTabAtom) * n, false});
 }
 
 ObsBufs classical_bufs(gamd_handle* h) {
@@ -458,9 +476,8 @@ template <typename State>
 int cells_apply(gamd_handle* h, State& wc, ObsBufs (*bufs)(gamd_handle*), const char* who, const float* box) {
     int cap = 1;
     for (int b = 0; b < h->n_boxes; ++b) {
-        int cells = 1;
-        for (int d = 0; d < 3; ++d) cells *= gamd_cells_per_axis((double)box[3 * b + d], wc.r_cut);
-        cap = std::max(cap, cells);
+        int nc[3];
+        cap = std::max(cap, gamd_cells_count((double)box[3 * b], (double)box[3 * b + 1], (double)box[3 * b + 2], wc.r_cut, nc));
     }
     const bool grow = cap > wc.cell_cap || !wc.cell_start.p || !wc.cell_table.p;
     if (grow && h->pending.active)
@@ -480,6 +497,26 @@ int cells_apply(gamd_handle* h, State& wc, ObsBufs (*bufs)(gamd_handle*), const 
     }
     return 0;
 }
+// the two switches of the cell table, gamd_classical_cells and gamd_water_cells (`entry`; `conf`: the configure call the
+// parameters come from): off drops the tables, on allocates what goes by the atoms — 44 bytes per atom; the per-cell tables are
+// sized by the boxes of the next run, eval or minimise call (cells_apply)
+template <typename State>
+int cells_switch(gamd_handle* h, State& pl, ObsBufs (*bufs)(gamd_handle*), const char* entry, const char* conf, int32_t on) {
+    if (!pl.params_set) return fail(-22, "%s needs the parameters of a %s call (interval 0 will do)", entry, conf);
+    if (h->pending.active) return fail(-22, "an MD run is still enqueued: call gamd_sync_status before %s", entry);
+    if (on != 0 && on != 1) return fail(-22, "%s: on = %d is not 0 (all pairs) or 1 (the cell table)", entry, (int)on);
+    if (!on) { pl.drop(); return 0; }
+    if (pl.cells) return 0;                                 // on already: the table of the last evaluation stays readable
+    pl.cells = true;
+    DeviceGuard guard(h->dev);
+    InitStream init(h->init_stream);
+    if (bufs_ensure_work(bufs(h))) {
+        pl.drop();
+        return fail(-12, "%s: allocation of the cell tables of %d atoms failed", entry, h->n);
+    }
+    return 0;
+}
+
 int water_cells_apply(gamd_handle* h, const float* box) { return cells_apply(h, h->obs->wc, water_bufs, "water classical", box); }
 
 // every edge of every box the caller hands in
@@ -513,21 +550,14 @@ struct LjPotential {
         Args a{};
         potential_args(h, state(h), len, a);
         a.eps24 = 24.0 * state(h).epsilon;
-        if (state(h).cells) { a.slices = 1; a.chunk = h->n_per_box; }      // gamd_classical_cells: the pair rows are ONE slice
+        state(h).one_slice(a, h->n_per_box);                // gamd_classical_cells
         return a;
     }
     static void species(Args&, const uint8_t*) {}
-    // the cell table in force (gamd_classical_cells): its buffers, or null (b is the caller's room for them)
-    static const WCellBufs* cell_bufs(const gamd_handle* h, WCellBufs& b) {
-        Classical& cl = state(h);
-        if (!cl.cells) return nullptr;
-        b = WCellBufs{cl.r_cut, cl.cell_cap, h->sticky_dev, cl.cell_start.as<int>(), cl.cell_fill.as<int>(), cl.cell_of.as<int>(),
-                      cl.cell_members.as<int>(), cl.cell_order.as<int>(), cl.cell_table.as<WCellAtom>()};
-        cl.enqueued(cl.r_cut);
-        return &b;
-    }
+    // the cell table in force (gamd_classical_cells), or null
+    static const CellTabBufs* cell_bufs(const gamd_handle* h, CellTabBufs& b) { return state(h).bufs(state(h).r_cut, h->sticky_dev, b); }
     static int launch(const gamd_handle* h, const Args& a, hipStream_t st) {
-        WCellBufs b;
+        CellTabBufs b;
         return launch_classical(a, st, cell_bufs(h, b));
     }
     static int sample_extra(const gamd_handle*, const Args&, const Particles&, hipStream_t) { return 0; }
@@ -538,7 +568,7 @@ struct LjPotential {
     }
     // a force source as well (potential_drive): the forces alone, rounded to fp32, into the run's f
     static int drive(const gamd_handle* h, const Args& a, float* f_out, hipStream_t st) {
-        WCellBufs b;
+        CellTabBufs b;
         return launch_classical_drive(a, f_out, st, cell_bufs(h, b));
     }
 };
@@ -583,23 +613,12 @@ struct WaterPotential {
         p.w.kslices = 1; p.w.kblocks = (int)water_pme_blocks(wc);
         return p;
     }
-    // the cell table in force (gamd_water_cells): the pair rows are ONE slice (k_w4_lj's too), the table's buffers
-    static Args one_slice(const gamd_handle* h, const Args& a) {
-        Args b = a;
-        if (state(h).cells) { b.slices = 1; b.chunk = h->n_per_box; }
-        return b;
-    }
-    static WCellBufs cell_bufs(const gamd_handle* h) {
-        const WaterClassical& wc = state(h);
-        return WCellBufs{wc.r_cut, wc.cell_cap, h->sticky_dev, wc.cell_start.as<int>(), wc.cell_fill.as<int>(), wc.cell_of.as<int>(),
-                         wc.cell_members.as<int>(), wc.cell_order.as<int>(), wc.cell_table.as<WCellAtom>()};
-    }
-    static int launch(const gamd_handle* h, const Args& a0, hipStream_t st) {
+    // (the cell table in force, gamd_water_cells: the pair rows are one slice, k_w4_lj's too)
+    static int launch(const gamd_handle* h, Args a, hipStream_t st) {
         WaterClassical& wc = state(h);
-        const Args a = one_slice(h, a0);
-        const WCellBufs cb = cell_bufs(h);
-        const WCellBufs* c = wc.cells ? &cb : nullptr;
-        if (c) wc.enqueued(wc.r_cut);
+        wc.one_slice(a, h->n_per_box);
+        CellTabBufs cb;
+        const CellTabBufs* c = wc.bufs(wc.r_cut, h->sticky_dev, cb);
         if (wc.pme_order) {
             const PmeArgs p = pme(h, a);
             return wc.w_h != 0.0 ? launch_w4_classical(msite(h, p.w), st, &p, c) : launch_water_classical(p.w, st, &p, c);
@@ -635,12 +654,11 @@ struct WaterPotential {
         return water_klist_apply(h, n2max, kv);
     }
     // a force source as well (potential_drive): the forces alone, rounded to fp32, into the run's f
-    static int drive(const gamd_handle* h, const Args& a0, float* f_out, hipStream_t st) {
+    static int drive(const gamd_handle* h, Args a, float* f_out, hipStream_t st) {
         WaterClassical& wc = state(h);
-        const Args a = one_slice(h, a0);
-        const WCellBufs cb = cell_bufs(h);
-        const WCellBufs* c = wc.cells ? &cb : nullptr;
-        if (c) wc.enqueued(wc.r_cut);
+        wc.one_slice(a, h->n_per_box);
+        CellTabBufs cb;
+        const CellTabBufs* c = wc.bufs(wc.r_cut, h->sticky_dev, cb);
         if (wc.pme_order) {
             const PmeArgs p = pme(h, a);
             return wc.w_h != 0.0 ? launch_w4_drive(msite(h, p.w), f_out, st, &p, c) : launch_water_drive(p.w, f_out, st, &p, c);
@@ -868,7 +886,7 @@ struct LjMinimizer {
     static P::Args& potential(Args& m) { return m.c; }
     static int init(const Args& m, const float* x, hipStream_t st) { return launch_minimize_init(m, x, st); }
     static int iter(const gamd_handle* h, const Args& m, hipStream_t st) {
-        WCellBufs b;
+        CellTabBufs b;
         return launch_minimize_iter(m, st, P::cell_bufs(h, b));
     }
     static int store_x(const Args& m, float* x, double*, hipStream_t st) { return launch_minimize_store_x(m, x, st); }
@@ -1300,11 +1318,8 @@ int cells_read(gamd_handle* h, const CellTables& ct, const char* entry, const ch
         return fail(-22, "%s: nothing has been sampled since the cell table was switched on or the boxes were given", entry);
     if (box < 0 || box >= h->n_boxes) return fail(-22, "%s: box = %d outside [0, %d)", entry, (int)box, h->n_boxes);
     if (!nc) return fail(-22, "null argument");
-    long long cells = 1;
-    for (int d = 0; d < 3; ++d) {
-        nc[d] = gamd_cells_per_axis((double)ct.cell_box[3 * (size_t)box + d], ct.cell_rcut);
-        cells *= nc[d];
-    }
+    const float* L = ct.cell_box.data() + 3 * (size_t)box;
+    const long long cells = gamd_cells_count((double)L[0], (double)L[1], (double)L[2], ct.cell_rcut, nc);
     if (cells > ct.cell_cap) return fail(-1, "%s: %lld cells, the tables hold %d", entry, cells, ct.cell_cap);
     if (start && max_start < cells + 1) return fail(-22, "start has room for %lld elements, the box has %lld cells + 1", (long long)max_start, cells);
     if (order && max_order < h->n_per_box) return fail(-22, "order has room for %lld elements, a box has %d atoms", (long long)max_order, h->n_per_box);
@@ -1327,26 +1342,7 @@ int32_t gamd_classical_cells(gamd_handle* h, int32_t on) {
     if (h->cfg.kind != GAMD_KIND_LJ)
         return fail(-22, "gamd_classical_cells: a GAMD_KIND_WATER handle has no Lennard-Jones classical potential (GAMD_KIND_LJ handles "
                          "only; gamd_water_cells switches the cell table of the water classical potential)");
-    Classical& cl = h->obs->cl;
-    if (!cl.params_set) return fail(-22, "gamd_classical_cells needs the parameters of a gamd_classical_configure call (interval 0 will do)");
-    if (h->pending.active) return fail(-22, "an MD run is still enqueued: call gamd_sync_status before gamd_classical_cells");
-    if (on != 0 && on != 1) return fail(-22, "gamd_classical_cells: on = %d is not 0 (all pairs) or 1 (the cell table)", (int)on);
-    auto drop = [&]() {
-        cl.cells = cl.cells_sampled = false;
-        cl.cell_cap = 0; cl.cell_box.clear(); cl.cell_box_next.clear();
-        for (DevBuf* b : {&cl.cell_start, &cl.cell_fill, &cl.cell_of, &cl.cell_members, &cl.cell_order, &cl.cell_table}) b->release();
-    };
-    if (!on) { drop(); return 0; }
-    if (cl.cells) return 0;                                 // on already: the table of the last evaluation stays readable
-    cl.cells = true;
-    DeviceGuard guard(h->dev);
-    InitStream init(h->init_stream);
-    // 44 bytes per atom here; the per-cell tables are sized by the boxes of the next run, eval or minimise call (cells_apply)
-    if (bufs_ensure_work(classical_bufs(h))) {
-        drop();
-        return fail(-12, "gamd_classical_cells: allocation of the cell tables of %d atoms failed", h->n);
-    }
-    return 0;
+    return cells_switch(h, h->obs->cl, classical_bufs, "gamd_classical_cells", "gamd_classical_configure", on);
 }
 
 int32_t gamd_classical_cells_read(gamd_handle* h, void* stream, int32_t box, int32_t* nc, int32_t* start, int64_t max_start,
@@ -1475,26 +1471,7 @@ int32_t gamd_water_cells(gamd_handle* h, int32_t on) {
     if (h->cfg.kind != GAMD_KIND_WATER)
         return fail(-22, "gamd_water_cells: a GAMD_KIND_LJ handle has no water potential (GAMD_KIND_WATER handles only; "
                          "gamd_classical_cells switches the cell table of the Lennard-Jones classical potential)");
-    WaterClassical& wc = h->obs->wc;
-    if (!wc.params_set) return fail(-22, "gamd_water_cells needs the parameters of a gamd_water_configure call (interval 0 will do)");
-    if (h->pending.active) return fail(-22, "an MD run is still enqueued: call gamd_sync_status before gamd_water_cells");
-    if (on != 0 && on != 1) return fail(-22, "gamd_water_cells: on = %d is not 0 (all pairs) or 1 (the cell table)", (int)on);
-    auto drop = [&]() {
-        wc.cells = wc.cells_sampled = false;
-        wc.cell_cap = 0; wc.cell_box.clear(); wc.cell_box_next.clear();
-        for (DevBuf* b : {&wc.cell_start, &wc.cell_fill, &wc.cell_of, &wc.cell_members, &wc.cell_order, &wc.cell_table}) b->release();
-    };
-    if (!on) { drop(); return 0; }
-    if (wc.cells) return 0;                                 // on already: the table of the last sample stays readable
-    wc.cells = true;
-    DeviceGuard guard(h->dev);
-    InitStream init(h->init_stream);
-    // 44 bytes per atom here; the per-cell tables are sized by the boxes of the next run or eval call (water_cells_apply)
-    if (bufs_ensure_work(water_bufs(h))) {
-        drop();
-        return fail(-12, "gamd_water_cells: allocation of the cell tables of %d atoms failed", h->n);
-    }
-    return 0;
+    return cells_switch(h, h->obs->wc, water_bufs, "gamd_water_cells", "gamd_water_configure", on);
 }
 
 int32_t gamd_water_cells_read(gamd_handle* h, void* stream, int32_t box, int32_t* nc, int32_t* start, int64_t max_start, int32_t* order,

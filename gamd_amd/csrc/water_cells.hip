@@ -5,17 +5,9 @@
 // left (M-site), never wrapped: a pair's d, minimum image and r^2 come from the same operations on the same two doubles as in
 // gamd_water_walk (gamd_passes_dev.h), so the set of pairs and the pair count are the all-pairs walk's by construction.
 // Per box nx x ny x nz cells (gamd_cells_dev.h: cells per axis, cell of a coordinate, neighbour lists), cell = (cx ny + cy) nz + cz.
+// The table — the box's atoms ordered by (cell, atom index), entries {position, atom, O flag} — is cell_table.hip's, built by
+// launch_cell_table in front of the pair pass of every evaluation.
 //
-//   k_wcell_clear   one thread per cell: the counts and the fill cursors to zero.  They are the only buffers updated in place, so
-//                   they are cleared at the head of EVERY sample: a sample that runs twice writes the same bits twice.
-//   k_wcell_count   one thread per atom: its cell to cell_of, one integer atomicAdd on the cell's count.
-//   k_wcell_scan    one workgroup per box: the exclusive scan of the counts in place — thread t sums its run of ceil(cells / 256)
-//                   cells, the 256 sums are scanned in LDS, the thread writes its run's prefixes; start[cells] = the atoms.
-//   k_wcell_fill    one thread per atom: slot start[cell] + atomicAdd(fill[cell], 1) of `members` takes the atom.  Which atom of a
-//                   cell gets which slot depends on the arrival order; what the cell's run of slots holds as a SET does not.
-//   k_wcell_rank    one thread per atom: its rank is the number of members of its cell with a lower atom index (a count over the
-//                   cell's run: O(occupancy) whatever the positions are, no sort), its slot start[cell] + rank; `order` and the
-//                   table entry {position, atom, O flag} of that slot.  The table is ordered by (cell, atom index): reproducible.
 //   k_wcell_pairs   the pair pass, 3-site, every accumulator (the observer, gamd_water_eval)       384 threads: six waves share
 //   k_wcell_force   ... the force accumulators only (the force source)                             64 consecutive table slots,
 //   k_wcell_pairs4  the pair pass on the charge sites, Lennard-Jones term off (k_w4_lj's)          lane l of every wave owns slot
@@ -31,16 +23,15 @@
 //                   (((((m + p_0) + p_1) + p_2) + p_3) + p_4), and stores the atom's row of `part`.  Both variants add the same
 //                   terms in the same order: a driven frame's force is fp32(f_cl of gamd_water_eval) bit for bit.
 // No floating-point atomics; fixed slot-to-lane and cell-to-wave assignment; contraction off: the same bits run after run.  Every
-// kernel returns while DEVFLAG_FROZEN is set.  Checked build: an atom's cell, a cell's start, a slot and a table entry's atom
-// index pass through GAMD_CHK_RANGE before they are used as addresses.  A box whose cells exceed the tables' room (the host sizes
-// them from the same boxes by the same expression; cannot happen) is left alone by every kernel.
+// kernel returns while DEVFLAG_FROZEN is set.  Checked build: an atom's cell, a cell's start and a table entry's atom index pass
+// through GAMD_CHK_RANGE before they are used as addresses.  A box whose cells exceed the tables' room (the host sizes them from
+// the same boxes by the same function; cannot happen) is left alone by every kernel.
 #include "gamd_common.h"
 #include "gamd_internal.h"
 
 #pragma clang fp contract(off)
 
 #include "gamd_passes_dev.h"
-#include "gamd_cells_dev.h"
 
 namespace {
 
@@ -50,117 +41,14 @@ constexpr int WCELL_WAVES = 1 + WCELL_ENTRIES;              // its waves: the mo
 
 struct WCellArgs {
     WaterArgs w;
-    WCellBufs c;
+    CellTabBufs c;
     const double* sites;       // [n][3] the charge sites k_w4_sites left, or null: the fp32 positions w.x
 };
-
-struct WCellGeom { int nx, ny, nz, cells; bool ok; };
-__device__ __forceinline__ WCellGeom wcell_geom(const WCellArgs& k, int box) {
-    WCellGeom g;
-    g.nx = gamd_cells_per_axis(gamd_box_edge(k.w, box, 0), k.c.r_cut);
-    g.ny = gamd_cells_per_axis(gamd_box_edge(k.w, box, 1), k.c.r_cut);
-    g.nz = gamd_cells_per_axis(gamd_box_edge(k.w, box, 2), k.c.r_cut);
-    g.cells = (g.nx * g.ny) * g.nz;                         // <= 64^3
-    g.ok = g.cells <= k.c.cap;
-    return g;
-}
 
 // atom i (all boxes) as the walk reads it
 __device__ __forceinline__ void wcell_load(const WCellArgs& k, size_t i, double& px, double& py, double& pz) {
     if (k.sites) GamdPosF64{k.sites}.load(i, px, py, pz);
     else GamdPosF32{k.w.x}.load(i, px, py, pz);
-}
-
-__global__ void __launch_bounds__(256) k_wcell_clear(WCellArgs k) {
-    if (k.w.devflags[DEVFLAG_FROZEN]) return;
-    const int box = blockIdx.y;
-    const WCellGeom g = wcell_geom(k, box);
-    if (!g.ok) return;
-    const int c = blockIdx.x * 256 + threadIdx.x;
-    if (c <= g.cells) k.c.start[(size_t)box * ((size_t)k.c.cap + 1) + (size_t)c] = 0;
-    if (c < g.cells) k.c.fill[(size_t)box * (size_t)k.c.cap + (size_t)c] = 0;
-}
-
-__global__ void __launch_bounds__(256) k_wcell_count(WCellArgs k) {
-    const WaterArgs& a = k.w;
-    if (a.devflags[DEVFLAG_FROZEN]) return;
-    const int box = blockIdx.y, npb = gamd_npb(a);
-    const WCellGeom g = wcell_geom(k, box);
-    const int il = blockIdx.x * 256 + threadIdx.x;          // one thread per atom
-    if (!g.ok || il >= npb) return;
-    const size_t i = (size_t)box * (size_t)npb + (size_t)il;
-    double px, py, pz;
-    wcell_load(k, i, px, py, pz);
-    const int cx = gamd_cells_index(px, gamd_box_edge(a, box, 0), g.nx), cy = gamd_cells_index(py, gamd_box_edge(a, box, 1), g.ny),
-              cz = gamd_cells_index(pz, gamd_box_edge(a, box, 2), g.nz);
-    const int c = (cx * g.ny + cy) * g.nz + cz;             // in [0, cells): every factor is in its range for every bit pattern
-    k.c.cell_of[i] = c;
-    atomicAdd(k.c.start + (size_t)box * ((size_t)k.c.cap + 1) + (size_t)c, 1);
-}
-
-__global__ void __launch_bounds__(256) k_wcell_scan(WCellArgs k) {
-    if (k.w.devflags[DEVFLAG_FROZEN]) return;
-    __shared__ int sums[256];
-    const int box = blockIdx.x, tid = threadIdx.x;
-    const WCellGeom g = wcell_geom(k, box);
-    if (!g.ok) return;                                      // (uniform)
-    int* start = k.c.start + (size_t)box * ((size_t)k.c.cap + 1);
-    const int run = (g.cells + 255) / 256;
-    const int c0 = tid * run < g.cells ? tid * run : g.cells, c1 = c0 + run < g.cells ? c0 + run : g.cells;
-    int s = 0;
-    for (int c = c0; c < c1; ++c) s += start[c];
-    sums[tid] = s;
-    __syncthreads();
-    for (int d = 1; d < 256; d <<= 1) {                     // inclusive scan of the 256 sums
-        const int v = tid >= d ? sums[tid - d] : 0;
-        __syncthreads();
-        sums[tid] += v;
-        __syncthreads();
-    }
-    int at = sums[tid] - s;                                 // the atoms in front of this thread's run
-    for (int c = c0; c < c1; ++c) {
-        const int m = start[c];
-        start[c] = at;
-        at += m;
-    }
-    if (tid == 255) start[g.cells] = sums[255];
-}
-
-__global__ void __launch_bounds__(256) k_wcell_fill(WCellArgs k) {
-    const WaterArgs& a = k.w;
-    if (a.devflags[DEVFLAG_FROZEN]) return;
-    const int box = blockIdx.y, npb = gamd_npb(a);
-    const WCellGeom g = wcell_geom(k, box);
-    const int il = blockIdx.x * 256 + threadIdx.x;          // one thread per atom
-    if (!g.ok || il >= npb) return;
-    const size_t a0 = (size_t)box * (size_t)npb;
-    const int c = GAMD_CHK_RANGE(k.c.sticky, k.c.cell_of[a0 + (size_t)il], 0, g.cells - 1, GAMD_CHK_WCELL_CELL);
-    const int s0 = GAMD_CHK_RANGE(k.c.sticky, k.c.start[(size_t)box * ((size_t)k.c.cap + 1) + (size_t)c], 0, npb, GAMD_CHK_WCELL_START);
-    const int m = atomicAdd(k.c.fill + (size_t)box * (size_t)k.c.cap + (size_t)c, 1);
-    const int slot = GAMD_CHK_RANGE(k.c.sticky, s0 + m, 0, npb - 1, GAMD_CHK_WCELL_SLOT);
-    k.c.members[a0 + (size_t)slot] = il;
-}
-
-__global__ void __launch_bounds__(256) k_wcell_rank(WCellArgs k) {
-    const WaterArgs& a = k.w;
-    if (a.devflags[DEVFLAG_FROZEN]) return;
-    const int box = blockIdx.y, npb = gamd_npb(a);
-    const WCellGeom g = wcell_geom(k, box);
-    const int il = blockIdx.x * 256 + threadIdx.x;          // one thread per atom
-    if (!g.ok || il >= npb) return;
-    const size_t a0 = (size_t)box * (size_t)npb;
-    const int* start = k.c.start + (size_t)box * ((size_t)k.c.cap + 1);
-    const int c = GAMD_CHK_RANGE(k.c.sticky, k.c.cell_of[a0 + (size_t)il], 0, g.cells - 1, GAMD_CHK_WCELL_CELL);
-    const int s0 = GAMD_CHK_RANGE(k.c.sticky, start[c], 0, npb, GAMD_CHK_WCELL_START);
-    const int s1 = GAMD_CHK_RANGE(k.c.sticky, start[c + 1], 0, npb, GAMD_CHK_WCELL_START);
-    int rank = 0;
-    for (int s = s0; s < s1; ++s) rank += k.c.members[a0 + (size_t)s] < il ? 1 : 0;
-    const int slot = GAMD_CHK_RANGE(k.c.sticky, s0 + rank, 0, npb - 1, GAMD_CHK_WCELL_SLOT);
-    k.c.order[a0 + (size_t)slot] = il;
-    WCellAtom t;
-    wcell_load(k, a0 + (size_t)il, t.x, t.y, t.z);
-    t.idx = il; t.o = a.species[a0 + (size_t)il] != 0 ? 1 : 0;
-    k.c.table[a0 + (size_t)slot] = t;
 }
 
 // one term of gamd_water_walk's body (gamd_passes_dev.h), statement for statement: the pair's d is (dx, dy, dz) before the
@@ -208,7 +96,7 @@ __device__ __forceinline__ void wcell_walk(const WCellArgs& k) {
     const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);     // (the wave: uniform)
     const int box = blockIdx.y, npb = gamd_npb(a);
     const size_t a0 = (size_t)box * (size_t)npb;            // the caller's order is box-major
-    const WCellGeom g = wcell_geom(k, box);
+    const CellTabGeom g = gamd_celltab_geom(k.w, k.c, box);
     if (!g.ok) return;                                      // (uniform)
     const bool vi = blockIdx.x * WCELL_SLOTS + lane < npb;
     // a lane behind the last slot walks the last slot's atom again and stores nothing: no branch on vi around the walk, whose
@@ -218,7 +106,7 @@ __device__ __forceinline__ void wcell_walk(const WCellArgs& k) {
     const int span_x = gamd_cells_span(g.nx);
     int span_y = gamd_cells_span(g.ny), span_z = gamd_cells_span(g.nz), ny = g.ny, nz = g.nz;
     const int* start = k.c.start + (size_t)box * ((size_t)k.c.cap + 1);
-    const WCellAtom* table = k.c.table + a0;
+    const CellTabAtom* table = k.c.table + a0;
     // the table's and the output rows' addresses and the inner loops' geometry are held in vector registers from here on: left
     // to the compiler they stay in scalar registers across the walk, which the potential's constants and those of erf and erfc
     // fill already (eight scalar spills otherwise)
@@ -226,7 +114,7 @@ __device__ __forceinline__ void wcell_walk(const WCellArgs& k) {
     asm volatile("" : "+v"(start), "+v"(table), "+v"(span_y), "+v"(span_z), "+v"(ny), "+v"(nz), "+v"(rows));
     const double q_h = a.q_h, q_o = -(q_h + q_h);           // -2 q_h, exact
     double fx = 0.0, fy = 0.0, fz = 0.0, elj = 0.0, ec = 0.0, cnt = 0.0;
-    const WCellAtom me = table[slot];
+    const CellTabAtom me = table[slot];
     const int il = GAMD_CHK_RANGE(k.c.sticky, me.idx, 0, npb - 1, GAMD_CHK_WCELL_ATOM);
     const double xi = me.x, yi = me.y, zi = me.z;
     const bool oi = me.o != 0;
@@ -253,7 +141,7 @@ __device__ __forceinline__ void wcell_walk(const WCellArgs& k) {
                 const int s0 = GAMD_CHK_RANGE(k.c.sticky, start[c2], 0, npb, GAMD_CHK_WCELL_START);
                 const int s1 = GAMD_CHK_RANGE(k.c.sticky, start[c2 + 1], 0, npb, GAMD_CHK_WCELL_START);
                 for (int s = s0; s < s1; ++s) {
-                    const WCellAtom t = table[s];
+                    const CellTabAtom t = table[s];
                     if (t.idx / 3 == mi) continue;          // the atom itself and its molecule: wave 0's
                     wcell_term<NOUT, LJ, false>(a, Lx, Ly, Lz, xi - t.x, yi - t.y, zi - t.z, qi, q_h, q_o, oi, t.o != 0, fx, fy, fz, elj,
                                                 ec, cnt);
@@ -296,19 +184,12 @@ __global__ void __launch_bounds__(WCELL_SLOTS * WCELL_WAVES) k_wcell_force4(WCel
 
 }  // namespace
 
-int launch_water_cells(const WaterArgs& w, const WCellBufs& c, const double* sites, int nout, bool lj, hipStream_t st) {
+int launch_water_cells(const WaterArgs& w, const CellTabBufs& c, const double* sites, int nout, bool lj, hipStream_t st) {
     PassGeom g;
     if (pass_rows(w, 3, &g) || w.slices != 1 || (nout != 3 && nout != WATER_PART) || lj == (sites != nullptr)) return -1;
     if (!w.x || !w.species || !w.part || !w.devflags) return -1;
-    if (c.cap < 1 || c.cap > GAMD_CELLS_MAX * GAMD_CELLS_MAX * GAMD_CELLS_MAX || !(c.r_cut > 0.0)) return -1;
-    if (!c.start || !c.fill || !c.cell_of || !c.members || !c.order || !c.table) return -1;
+    if (int r = launch_cell_table(cell_tab_args(w, c, nullptr, sites, w.species, GAMD_CHK_WCELL_CELL), st)) return r;
     const WCellArgs k{w, c, sites};
-    const dim3 atoms((unsigned)g.T, g.nb), b256(256);
-    hipLaunchKernelGGL(k_wcell_clear, dim3((unsigned)((c.cap + 1 + 255) / 256), g.nb), b256, 0, st, k); GAMD_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_wcell_count, atoms, b256, 0, st, k); GAMD_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_wcell_scan, dim3(g.nb), b256, 0, st, k); GAMD_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_wcell_fill, atoms, b256, 0, st, k); GAMD_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_wcell_rank, atoms, b256, 0, st, k); GAMD_CHECK_LAUNCH();
     const dim3 pg((unsigned)((g.npb + WCELL_SLOTS - 1) / WCELL_SLOTS), g.nb), pb(WCELL_SLOTS * WCELL_WAVES);
     if (lj) {
         if (nout == 3) hipLaunchKernelGGL(k_wcell_force, pg, pb, 0, st, k); else hipLaunchKernelGGL(k_wcell_pairs, pg, pb, 0, st, k);

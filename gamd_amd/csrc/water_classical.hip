@@ -181,7 +181,7 @@ int launch_water_final(const WaterArgs& a, hipStream_t st) {
     return 0;
 }
 
-int launch_water_classical(const WaterArgs& a, hipStream_t st, const PmeArgs* pme, const WCellBufs* cells) {
+int launch_water_classical(const WaterArgs& a, hipStream_t st, const PmeArgs* pme, const CellTabBufs* cells) {
     PassGeom g;
     if (pass_geometry(a, 3, &g) || (!pme && pass_k_geometry(a, g.T, true)) || a.blocks < 1 || a.blocks > 65535 || a.slot < 0) return -1;
     if (!a.x || !a.species || !a.part || !a.ublk || !a.rpart || !a.f_cl || !a.blk || !a.rows || !a.devflags) return -1;

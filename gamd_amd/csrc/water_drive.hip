@@ -61,7 +61,7 @@ __global__ void __launch_bounds__(256) k_wsrc_atoms(WaterArgs a, float* __restri
 
 }  // namespace
 
-int launch_water_drive(const WaterArgs& a, float* f_out, hipStream_t st, const PmeArgs* pme, const WCellBufs* cells) {
+int launch_water_drive(const WaterArgs& a, float* f_out, hipStream_t st, const PmeArgs* pme, const CellTabBufs* cells) {
     PassGeom g;
     if (pass_geometry(a, 3, &g)) return -1;
     if (!a.x || !a.species || !a.part || !a.rpart || !a.f_cl || !a.devflags || !f_out) return -1;

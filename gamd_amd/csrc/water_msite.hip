@@ -232,7 +232,7 @@ __global__ void __launch_bounds__(256) k_w4_drive(W4Args b, float* __restrict__ 
 // what both launchers check, and the launches they share: sites, pairs, lj, rho, sk, recip — or, with `pme` (gamd_water_pme),
 // launch_water_pme on the sites in place of the last three; with `cells` (gamd_water_cells, one pair slice) launch_water_cells on
 // the sites in place of k_w4_pairs, `nout` accumulators; *gp = the rows' geometry
-int w4_launch_passes(const W4Args& b, PassGeom* gp, hipStream_t st, const PmeArgs* pme, const WCellBufs* cells, int nout) {
+int w4_launch_passes(const W4Args& b, PassGeom* gp, hipStream_t st, const PmeArgs* pme, const CellTabBufs* cells, int nout) {
     const WaterArgs& a = b.w;
     if (pass_geometry(a, 3, gp) || (!pme && pass_k_geometry(a, gp->T, true))) return -1;
     const int nb = gp->nb, npb = gp->npb;
@@ -257,7 +257,7 @@ int w4_launch_passes(const W4Args& b, PassGeom* gp, hipStream_t st, const PmeArg
 
 }  // namespace
 
-int launch_w4_classical(const W4Args& b, hipStream_t st, const PmeArgs* pme, const WCellBufs* cells) {
+int launch_w4_classical(const W4Args& b, hipStream_t st, const PmeArgs* pme, const CellTabBufs* cells) {
     const WaterArgs& a = b.w;
     PassGeom g;
     if (a.blocks < 1 || a.blocks > 65535 || a.slot < 0 || !a.blk || !a.rows || (pme && pme->sites != b.sites)) return -1;
@@ -266,7 +266,7 @@ int launch_w4_classical(const W4Args& b, hipStream_t st, const PmeArgs* pme, con
     return launch_water_final(a, st);
 }
 
-int launch_w4_drive(const W4Args& b, float* f_out, hipStream_t st, const PmeArgs* pme, const WCellBufs* cells) {
+int launch_w4_drive(const W4Args& b, float* f_out, hipStream_t st, const PmeArgs* pme, const CellTabBufs* cells) {
     PassGeom g;
     if (!f_out || (pme && pme->sites != b.sites)) return -1;
     if (int r = w4_launch_passes(b, &g, st, pme, cells, 3)) return r;

@@ -1,5 +1,5 @@
-"""The cell table of the Lennard-Jones classical potential (gamd_classical_cells, gamd_amd/csrc/classical_cells.hip) as far as it
-can be seen without a GPU.
+"""The cell table of the Lennard-Jones classical potential (gamd_classical_cells, gamd_amd/csrc/cell_table.hip and
+classical_cells.hip) as far as it can be seen without a GPU.
 
 On every shape of tests/classical_cells_cases.py (the shapes tests/test_gpu_classical_cells.py runs):
   * the case is well posed: the cells per axis it is meant to have, 2 r_cut <= the shortest edge, no pair within 1e-12 r_cut of
@@ -10,7 +10,7 @@ On every shape of tests/classical_cells_cases.py (the shapes tests/test_gpu_clas
     two when the z window wraps, the whole z line below five cells — and the columns' runs, concatenated in column order, are
     the slots of neighbour_cells in ITS order, x outermost and z innermost; the eight lanes' columns partition them.
 
-gamd_cells_dev.h is unchanged and gains no function: tools/cells_host_check.cpp (tests/test_water_cells_host.py) covers it."""
+gamd_cells_dev.h is covered by tools/cells_host_check.cpp (tests/test_water_cells_host.py)."""
 import os
 
 import numpy as np

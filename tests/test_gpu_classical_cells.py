@@ -14,6 +14,8 @@ What is asserted
 * Bit equality: a second call, a fresh handle, each box of a two-box handle against that box alone.
 * Off is untouched: a handle toggled on and off again gives the bits of a handle that never had cells.
 * The refusals name their reason and leave the handle usable.
+* One builder, one table (gamd_amd/csrc/cell_table.hip): an LJ handle and a water handle given the same positions hold equal
+  tables, both the numpy restatement's.
 
 The shapes are those of tests/classical_cells_cases.py; tests/test_classical_cells_host.py checks on the CPU that each is well
 posed (no pair within 1e-12 r_cut of the cutoff, 2 r_cut <= the shortest edge) and has the cells per axis it is meant to have."""
@@ -201,3 +203,53 @@ def test_refusals_name_their_reason_and_leave_the_handle_usable():
     _eval(eng, xs, box)
     assert _assert_table(eng, xs, box, 6.0) == (9, 8, 10)
     eng.close()
+
+
+# ---- 4: one builder, one table -----------------------------------------------------------------------------------------
+def _shared_positions(box, seed):
+    """192 fp32 positions in the box `box`: a third moved by -3 .. +3 box edges, and 40 coordinates put ON faces of the cells of
+    both cutoffs below (the fp32 edge times i / nc, rounded to fp32), zero and the edge itself among them"""
+    rng = np.random.default_rng(seed)
+    b = box.astype(np.float64)
+    x = rng.uniform(0.0, 1.0, (192, 3)) * b[None, :]
+    x[::3] += rng.integers(-3, 4, size=(64, 3)) * b[None, :]
+    for k, i in enumerate(rng.choice(192, 40, replace=False)):
+        d, rc = k % 3, (6.8, 3.0)[(k // 3) % 2]
+        nc = int(cf.ncells(box, rc)[d])
+        x[i, d] = b[d] * ((k // 6) % (nc + 1)) / nc + (b[d] if k >= 30 else 0.0)
+    return x.astype(np.float32)
+
+
+@pytest.mark.parametrize("n_boxes", [1, 2])
+def test_the_lj_and_the_water_handle_build_the_same_table_from_the_same_positions_and_it_is_numpy_s(n_boxes):
+    """cell_table.hip serves both potentials: an LJ handle of 192 atoms and a water handle of 64 molecules, given the same 192
+    fp32 positions per box, hold equal tables, both the numpy restatement's, with no allowance.  r_cut = 6.8: (4, 5, 6) cells, one
+    axis below five, the scan walks one cell per thread; r_cut = 3.0: (10, 11, 14) = 1540 cells, every axis wraps, seven cells per
+    thread, most of them empty.  The second box of the two-box handles has other edges (and other cells per axis).  Only the
+    tables are judged: the positions are no molecules, and the water handle's reciprocal sum is cut short (k_cut) because
+    nothing of it is read."""
+    from test_gpu_water_classical import _engine as _water_engine
+    import water_classical_ref as wr
+    boxes = np.array([[15.1, 17.5, 21.2], [16.4, 13.7, 19.3]], dtype=np.float32)[:n_boxes]
+    want = {6.8: [(4, 5, 6), (4, 4, 5)], 3.0: [(10, 11, 14), (10, 9, 12)]}
+    x = np.concatenate([_shared_positions(boxes[b], 21 + b) for b in range(n_boxes)])
+    hb = boxes if n_boxes > 1 else boxes[0]
+    lj = _engine(192, hb[0] if n_boxes > 1 else hb, n_boxes=n_boxes, cutoff=6.5)
+    wat, species = _water_engine(64, hb[0] if n_boxes > 1 else hb, n_boxes=n_boxes)
+    for r_cut in (6.8, 3.0):
+        assert (2.0 * r_cut <= boxes).all()
+        lj.classical_configure(0, cells=True, r_cut=r_cut, r_switch=0.8 * r_cut)
+        lj.classical_forces(x, box=hb)
+        wat.water_classical_configure(0, cells=True, **wr.Water(r_cut=r_cut, k_cut=2.0).kwargs())
+        wat.water_classical_forces(x, species, box=hb)
+        for b in range(n_boxes):
+            xb = x[192 * b:192 * (b + 1)]
+            ref = cf.table(xb.astype(np.float64), boxes[b], r_cut)
+            tl, tw = lj.classical_cells_table(b), wat.water_cells_table(b)
+            assert tuple(int(v) for v in ref[0]) == want[r_cut][b]
+            for name, r, a, w in zip(("nc", "start", "order"), ref, tl, tw):
+                assert np.array_equal(a, w) and np.array_equal(a, r), (r_cut, b, name)
+            print(f"r_cut {r_cut} box {b}: nc {want[r_cut][b]}, {int((np.diff(ref[1]) == 0).sum())} of {len(ref[1]) - 1} cells empty, "
+                  f"occupancy up to {int(np.diff(ref[1]).max())}")
+    lj.close()
+    wat.close()

@@ -1,5 +1,5 @@
-"""The cell table of the water classical potential (gamd_water_cells, gamd_amd/csrc/gamd_cells_dev.h, water_cells.hip) as far as
-it can be seen without a GPU.
+"""The cell table of the water classical potential (gamd_water_cells, gamd_amd/csrc/gamd_cells_dev.h, cell_table.hip,
+water_cells.hip) as far as it can be seen without a GPU.
 
 The numpy restatement (tests/water_cells_ref.py) on the shapes of tests/test_gpu_water_cells.py (CASES below: the configurations
 of tests/test_water_pme_host.py, atoms in several periodic images):
@@ -11,8 +11,9 @@ of tests/test_water_pme_host.py, atoms in several periodic images):
 
 gamd_cells_dev.h is called by a stand-alone program (tools/cells_host_check.cpp) built with the host compiler and the address and
 undefined-behaviour sanitizers: NaN, +-inf, +-1e30, +-0, exact multiples of L and their neighbours, negative values that round
-to s = 1, every face of every nc from 3 to 64, cells per axis for edges and cutoffs that are not numbers, every neighbour list,
-and 2 10^5 random pairs just inside the cutoff.  No Python code runs under a sanitizer."""
+to s = 1, every face of every nc from 3 to 64, cells per axis for edges and cutoffs that are not numbers, the cells per box of
+every triple of those edges (the product of the axes' counts, 64^3 at the most), every neighbour list, and 2 10^5 random pairs
+just inside the cutoff.  No Python code runs under a sanitizer."""
 import os
 import subprocess
 
@@ -124,6 +125,7 @@ def test_index_cells_per_axis_neighbours_and_reach_hold_for_every_input(check_ou
     assert "FAIL" not in check_out, check_out[-2000:]
     assert lines["index"].split()[0] == "ok" and int(lines["index"].split()[1]) > 2000000
     assert lines["axis"] == "ok 135"
+    assert lines["count"] == f"ok {9 * 15 ** 3}"
     assert lines["neighbour"] == f"ok {sum((5 if n >= 5 else n) * n for n in range(1, 65))}"
     assert lines["reach"].split()[0] == "ok" and int(lines["reach"].split()[1]) > 150000
 

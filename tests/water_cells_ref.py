@@ -1,4 +1,4 @@
-"""The cell table of the water classical potential (gamd_water_cells, gamd_amd/csrc/gamd_cells_dev.h and water_cells.hip) restated
+"""The cell table of the water classical potential (gamd_water_cells, gamd_amd/csrc/gamd_cells_dev.h and cell_table.hip) restated
 in numpy: the header's operations in the header's order, in float64, so that every function agrees with the device bit for bit.
 
   ncells(box, r_cut)           cells per axis: min(floor(2 L / (r_cut (1 + 2^-20))), 64), at least 1, from the box's fp32 edges widened

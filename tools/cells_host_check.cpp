@@ -1,4 +1,4 @@
-// cells_host_check.cpp — gamd_amd/csrc/gamd_cells_dev.h without a GPU and without ROCm: the cells per axis of a box, the cell of a
+// cells_host_check.cpp — gamd_amd/csrc/gamd_cells_dev.h without a GPU and without ROCm: the cells per axis and per box, the cell of a
 // coordinate and the neighbour cells of a cell, called from a plain main() that tests/test_water_cells_host.py builds with the
 // address and undefined-behaviour sanitizers.  Prints one line per property ("name ok count"); the first violation is printed as
 // "name FAIL ..." and the exit status is 1.
@@ -91,6 +91,25 @@ int main() {
         std::printf("axis FAIL the documented shapes\n"); g_fail = 1;
     }
     std::printf("axis %s %ld\n", g_fail ? "FAIL" : "ok", n_axis);
+
+    // ---- cells per box: the product of the three axes' counts over every triple of the edges above, never more than 64^3 ----------
+    long n_count = 0;
+    for (double rc : {3.0, 4.2, 4.5, 6.8, 9.5, 12.0, 0.1, 1e-300, 1e300}) {
+        const double Ls[] = {2.0 * rc, std::nextafter(2.0 * rc, inf), 13.66, 14.2, 15.1, 20.0, 53.0, 110.0, 1e6, 1e300, 0.0, -1.0, nan, inf, -inf};
+        for (double Lx : Ls)
+            for (double Ly : Ls)
+                for (double Lz : Ls) {
+                    int nc[3] = {-1, -1, -1};
+                    const int cells = gamd_cells_count(Lx, Ly, Lz, rc, nc);
+                    const int px = gamd_cells_per_axis(Lx, rc), py = gamd_cells_per_axis(Ly, rc), pz = gamd_cells_per_axis(Lz, rc);
+                    if (nc[0] != px || nc[1] != py || nc[2] != pz || (long long)cells != (long long)px * py * pz || cells < 1 ||
+                        cells > GAMD_CELLS_MAX * GAMD_CELLS_MAX * GAMD_CELLS_MAX) {
+                        std::printf("count FAIL L=%a %a %a rc=%a: %d cells, nc %d %d %d\n", Lx, Ly, Lz, rc, cells, nc[0], nc[1], nc[2]); g_fail = 1;
+                    }
+                    ++n_count;
+                }
+    }
+    std::printf("count %s %ld\n", g_fail ? "FAIL" : "ok", n_count);
 
     // ---- neighbour cells: in range, no cell twice, every cell within two (wrapped) is there, the order is the documented one ----
     long n_nb = 0;

@@ -24,9 +24,11 @@ each of the others and drops rows.
   i  gamd_minimize: 258 atoms (the lj258_seed0 snapshot), and a two-box handle (the snapshot and the lattice, different edges):
      40 iterations towards a tolerance they do not reach, with check_every = 1 and 16
   j  gamd_water_minimize: 86 molecules in a box with three different edges, the same 40 iterations and check_every
-Between them every kernel of classical.hip, drive.hip, minimize.hip, water_classical.hip, water_drive.hip, water_msite.hip and
-water_minimize.hip writes into the dump: a partial tile, a molecule across a tile edge, more than one slice, two boxes, and a
-k-vector list longer than one box needs.
+  fc, gc, hc, i2c  f, g, h and i's two-box handle with the pairs over the cell table (cells=True); gp: gc with particle-mesh Ewald
+     (16^3, order 6).  Each also dumps the cell table (nc, start, order) of every box as the last evaluation left it
+Between them every kernel of classical.hip, drive.hip, minimize.hip, water_classical.hip, water_drive.hip, water_msite.hip,
+water_minimize.hip, cell_table.hip, water_cells.hip and classical_cells.hip writes into the dump: a partial tile, a molecule across
+a tile edge, more than one slice, two boxes, and a k-vector list longer than one box needs.
 Written per case: final x, v, f and every attribute of report_read(), traj_read(), structure_read() and
 classical_read(forces=True) / water_classical_read(forces=True); for a, e and h what the call outside the run returned; for i
 and j x, f, x64 and the rows of every call, and the observer's f_cl behind the last.
@@ -61,15 +63,28 @@ def _water_kw(box, unit=1.0):
                 k_cut=8.0 * 4.0 / r_cut / unit)
 
 
-def _collect(out, name, eng, x, v, f, extra=None, observers=("report", "traj", "structure"), outside=None):
+def _fields(obj):
+    """what a read call returned from the device (the parameters it repeats, a dict, are the host's own)"""
+    return {k: val for k, val in vars(obj).items() if val is not None and not isinstance(val, dict)}
+
+
+def _tables(eng):
+    """the cell table of every box as the last evaluation left it"""
+    read = eng.classical_cells_table if eng.cfg.kind == "lj" else eng.water_cells_table
+    return {f"cells.box{b}.{k}": val for b in range(eng.n_boxes) for k, val in zip(("nc", "start", "order"), read(b))}
+
+
+def _collect(out, name, eng, x, v, f, extra=None, observers=("report", "traj", "structure"), outside=None, cells=False):
     water = eng.cfg.kind != "lj"
     got = {"x": x.cpu().numpy(), "v": v.cpu().numpy(), "f": f.cpu().numpy(), **(extra or {})}
     reads = [(who, getattr(eng, who + "_read")()) for who in observers]
     reads.append(("water_classical", eng.water_classical_read(forces=True)) if water else ("classical", eng.classical_read(forces=True)))
     for who, obj in reads:
-        got.update({f"{who}.{k}": val for k, val in vars(obj).items() if val is not None})
+        got.update({f"{who}.{k}": val for k, val in _fields(obj).items()})
     if outside:                                          # behind the reads: the call leaves its forces where forces=True reads them
         got.update(outside(eng))
+    if cells:
+        got.update(_tables(eng))
     out.update({f"{name}/{k}": np.asarray(val) for k, val in got.items()})
     eng.close()
 
@@ -115,7 +130,7 @@ def _water_outside(x, species, boxes, **kw):
         length, unit = _bohr()
         eng.water_classical_configure(0, **_water_kw(boxes, unit), **kw)
         fo, rd = eng.water_classical_forces((x.double() * unit).float(), species, box=boxes * unit, length_per_nm=length)
-        return {"eval.forces": fo.cpu().numpy(), **{f"eval.{k}": val for k, val in vars(rd).items() if val is not None}}
+        return {"eval.forces": fo.cpu().numpy(), **{f"eval.{k}": val for k, val in _fields(rd).items()}}
     return call
 
 
@@ -130,31 +145,32 @@ def _water_two_boxes(out):
 DRIVEN = 12
 
 
-def _lj_source(out):
-    """case f"""
+def _lj_source(out, name, cells=False):
+    """cases f and fc"""
     from test_gpu_classical_drive import _Lj258
     case = _Lj258()
     eng, x, v, f = case.make()
-    eng.classical_configure(5, max_samples=3)            # the defaults: shifted, switched over the last sigma
+    eng.classical_configure(5, max_samples=3, cells=cells)      # the defaults: shifted, switched over the last sigma
     eng.md_force_source("classical")
     f = eng.classical_forces(x)[0].float().contiguous()
     eng.traj_configure(1, max_frames=DRIVEN, fields=("x", "v", "f"))
     case.run(eng, x, v, f, DRIVEN)
-    _collect(out, "f", eng, x, v, f, observers=("traj",))
+    _collect(out, name, eng, x, v, f, observers=("traj",), cells=cells)
 
 
 def _water_source(out, name, **kw):
-    """cases g and h"""
+    """cases g and h, gc, hc and gp"""
     case, eng, x, v, f, boxes, species = _two_water_boxes()
     eng.water_classical_configure(3, max_samples=3, **_water_kw(boxes), **kw)
     eng.md_force_source("water_classical")
     f = eng.water_classical_forces(x, species, box=boxes)[0].float().contiguous()
     eng.traj_configure(1, max_frames=DRIVEN, fields=("x", "v", "f"))
     eng.md_run(x, v, f, DRIVEN, gamma_per_ps=25.0, seed=11, box=boxes, **{**case.md, "species": species})
-    _collect(out, name, eng, x, v, f, observers=("traj",), outside=_water_outside(x, species, boxes, **kw) if kw else None)
+    _collect(out, name, eng, x, v, f, observers=("traj",), outside=_water_outside(x, species, boxes, **kw) if kw else None,
+             cells=kw.get("cells", False))
 
 
-def _minimise_calls(out, name, eng, call, read):
+def _minimise_calls(out, name, eng, call, read, cells=False):
     """40 iterations towards a tolerance they do not reach, looked at after every one and after every 16"""
     for every in (1, 16):
         res, x = call(tolerance=1e-300, max_iter=40, check_every=every)
@@ -163,22 +179,27 @@ def _minimise_calls(out, name, eng, call, read):
         out[f"{name}/every{every}.rows"] = np.asarray(res.rows)
         out[f"{name}/every{every}.status"] = np.asarray(res.status)
     out[f"{name}/f_cl"] = np.asarray(read(forces=True).forces)
+    if cells:
+        out.update({f"{name}/{k}": np.asarray(val) for k, val in _tables(eng).items()})
     eng.close()
 
 
 def _minimisers(out):
-    """cases i and j"""
+    """cases i, i2c and j"""
     from test_gpu_classical_drive import _seeded_engine
     from test_gpu_minimize import _golden_start, _lattice_start
     from test_gpu_water_minimize import EDGES, _start, _water_engine
     (xa, ba), (xb, bb) = _golden_start(), _lattice_start()
-    for name, x0, box, nb in (("i1", xa, None, 1), ("i2", np.concatenate([xa, xb]), np.array([[ba] * 3, [bb] * 3], dtype=np.float32), 2)):
+    two = np.concatenate([xa, xb]), np.array([[ba] * 3, [bb] * 3], dtype=np.float32), 2
+    for name, x0, box, nb in (("i1", xa, None, 1), ("i2",) + two, ("i2c",) + two):
         eng = _seeded_engine(258, float(ba), n_boxes=nb)
+        if name == "i2c":
+            eng.classical_configure(0, cells=True)
 
         def call(x0=x0, box=box, eng=eng, **kw):
             x = torch.from_numpy(np.ascontiguousarray(x0, dtype=np.float32)).cuda()
             return eng.minimize(x, box=box, return_x64=True, **kw), x
-        _minimise_calls(out, name, eng, call, eng.classical_read)
+        _minimise_calls(out, name, eng, call, eng.classical_read, cells=name == "i2c")
     x0, box, species = _start(86, edges=EDGES)
     eng = _water_engine(86, box, 0.48 * float(np.min(box)))
 
@@ -208,9 +229,13 @@ def dump(path):
     _collect(out, "d", eng, x, v, f, {"resumed": eng.sync_status()})
     assert out["d/resumed"] == 1, "case d was meant to outgrow its edge buffer"
     _water_two_boxes(out)
-    _lj_source(out)
+    _lj_source(out, "f")
+    _lj_source(out, "fc", cells=True)
     _water_source(out, "g")
     _water_source(out, "h", m_site=0.1)
+    _water_source(out, "gc", cells=True)
+    _water_source(out, "hc", m_site=0.1, cells=True)
+    _water_source(out, "gp", cells=True, pme=(16, 16, 16))
     _minimisers(out)
     np.savez(path, **out)
     print(f"{path}: {len(out)} entries from {os.environ.get('GAMD_LIB', 'the default library')}")
