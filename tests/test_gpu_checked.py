@@ -50,6 +50,7 @@ REPRESENTATIVE = [
     "tests/test_gpu_hidden256.py::test_reference_goldens_stage_by_stage",
     "tests/test_gpu_lifecycle.py::test_fresh_handles_on_side_streams_match_the_default_stream",
     "tests/test_gpu_lifecycle.py::test_candidate_rebuild_by_sliced_workgroups_sorts_like_the_exact_build",
+    "tests/test_gpu_md_noise.py::test_one_step_noise_is_the_restatement[batch-3x258-skin]",
 ]
 
 

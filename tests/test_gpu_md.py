@@ -135,8 +135,11 @@ def _bond_errors(x, v, pairs, lengths):
 def test_rigid_water_langevin_matches_shake_rattle_oracle():
     """The water drivers integrate rigid molecules (OpenMM constraints at hack_integrator.py:145-164,178).
     Device: SETTLE + analytic velocity constraint, one molecule per thread; oracle: SHAKE/RATTLE iterated to
-    convergence in f64 (the constrained update is unique).  The device noise of each step is recovered from an
-    unconstrained run with the same (seed, step) so the stochastic step is compared too."""
+    convergence in f64 (the constrained update is unique).  The oracle draws each step's noise from the numpy restatement of
+    the generator (tests/md_noise_ref.py), nothing from the device, so a wrong generator does not cancel out of the comparison.
+    The device's own noise, recovered from an unconstrained run with the same (seed, step), is held to the restatement as well,
+    at the bound of tests/test_gpu_md_noise.py."""
+    import md_noise_ref as nr
     from gamd_amd import workloads as wl
     eng, sd, pos, box, species, bonds, mass, pairs, lengths, v0 = _water_setup()
     n = pos.shape[0]
@@ -150,8 +153,11 @@ def test_rigid_water_langevin_matches_shake_rattle_oracle():
         x = torch.from_numpy(pos).float().cuda()
         v = torch.zeros(n, 3, device="cuda")
         f = torch.zeros(n, 3, device="cuda")
-        eng.md_run(x, v, f, 1, first_step=step, **kw)                  # v = bs*xi + (dt/2)(10/m) f_new
-        return (v.cpu().double().numpy() - 0.5 * dt * 10.0 / mass * f.cpu().double().numpy()) / bs
+        eng.md_run(x, v, f, 1, first_step=step, **kw)                  # v = fl(fl(bs*xi) + kick*f_new), kick = (dt/2)(10/m)
+        # the kick's product in fp32 as d_baoab_second_dof forms it, so that what is left is the rounding of the stored v
+        kick = np.float32(0.5) * np.float32(dt) * np.float32(10.0) * (np.float32(1.0) / mass.astype(np.float32))
+        dv = (kick * f.cpu().numpy()).astype(np.float64)
+        return (v.cpu().double().numpy() - dv) / nr.noise_scale_f32(mass.reshape(-1), dt, gamma, T).reshape(-1, 1)
 
     x = torch.from_numpy(pos).float().cuda()
     v = torch.from_numpy(v0).float().cuda()
@@ -161,7 +167,11 @@ def test_rigid_water_langevin_matches_shake_rattle_oracle():
     eng.md_run(x, v, f, steps, rigid_water=True, r_oh=wl.TIP3P_R_OH, r_hh=wl.TIP3P_R_HH, **kw)
     for s in range(steps):
         vr = orc.remove_cm_motion(vr, mass)                           # the WaterBox System's CMMotionRemover (:142); default on
-        xr, vr = orc.baoab_first_half_rigid(xr, vr, fr, 1.0 / mass, dt, a, bs, device_noise(s), pairs, lengths)
+        xi_ref = nr.box_noise(seed, s, n)
+        xi_err = float(np.abs(device_noise(s) - xi_ref).max())
+        print(f"rigid water, step {s}: max |xi_dev - xi_ref| {xi_err:.3e}")
+        assert xi_err <= 5e-6
+        xr, vr = orc.baoab_first_half_rigid(xr, vr, fr, 1.0 / mass, dt, a, bs, xi_ref, pairs, lengths)
         fr = _oracle_water_forces(sd, xr, box, species, bonds)
         vr = orc.baoab_second_half_rigid(xr, vr, fr, 1.0 / mass, dt, pairs)
     xd, vd = x.cpu().double().numpy(), v.cpu().double().numpy()
