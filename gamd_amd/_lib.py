@@ -76,8 +76,15 @@ class GamdMinimizeParams(C.Structure):
                 ("f_alpha", C.c_double), ("max_step", C.c_double), ("n_min", C.c_int32), ("reserved", C.c_int32)]
 
 
+class GamdLbfgsParams(C.Structure):
+    _fields_ = [("tolerance", C.c_double), ("max_iter", C.c_int64), ("check_every", C.c_int64), ("max_step", C.c_double),
+                ("c1", C.c_double), ("curv", C.c_double), ("m", C.c_int32), ("max_ls", C.c_int32), ("reserved", C.c_int64)]
+
+
 MINIMIZE_ROW = 8                                            # GAMD_MINIMIZE_ROW: doubles per box of gamd_minimize's rows
 MINIMIZE_STATE = ("converged", "max_iter", "failed")        # GAMD_MIN_*: a row's state and the call's return value
+LBFGS_ROW = 10                                              # GAMD_LBFGS_ROW: doubles per box of gamd_minimize_lbfgs's rows
+LBFGS_STATE = ("converged", "max_iter", "failed", "line_search")   # GAMD_LBFGS_*: a row's state and the call's return value
 CLASSICAL_ROW = 9                                           # GAMD_CLASSICAL_ROW: doubles per box and row of gamd_classical_read
 WATER_ROW = 12                                              # GAMD_WATER_ROW: doubles per box and row of gamd_water_read
 WATER_VIRIAL_ROW = 6                                        # GAMD_WATER_VIRIAL_ROW: doubles per box and row of gamd_water_virial_read
@@ -129,6 +136,7 @@ SYMBOLS = {
     "gamd_classical_cells_read": (_i32, [_vp, _vp, _i32, C.POINTER(_i32), _vp, _i64, _vp, _i64]),
     "gamd_md_force_source": (_i32, [_vp, _i32]),
     "gamd_minimize": (_i32, [_vp, _vp, C.POINTER(C.c_float), C.c_float, _vp, _vp, C.POINTER(GamdMinimizeParams), _vp, _vp]),
+    "gamd_minimize_lbfgs": (_i32, [_vp, _vp, C.POINTER(C.c_float), C.c_float, _vp, _vp, C.POINTER(GamdLbfgsParams), _vp, _vp]),
     "gamd_water_configure": (_i32, [_vp, C.POINTER(GamdWaterParams)]),
     "gamd_water_msite": (_i32, [_vp, C.c_double]),
     "gamd_water_pme": (_i32, [_vp, C.POINTER(GamdWaterPmeParams)]),

@@ -869,6 +869,49 @@ int launch_minimize_store_x(const MinArgs& m, float* x_out, hipStream_t st);
 // (either minimiser's: n and bx are the handle's atoms and boxes)
 int launch_minimize_store_f(const FireArgs& m, int n, const BoxRef& bx, const float* f_in, float* f_out, hipStream_t st);
 
+// ---- L-BFGS energy minimiser (lbfgs.hip) --------------------------------------------------------------
+// Limited-memory BFGS with a backtracking line search under the Lennard-Jones potential of classical.hip, per box, all state in
+// double (tests/lbfgs_ref.py is the recipe).  `c` as for MinArgs.  One evaluation is three launches
+// whatever m is (pairs on the trial positions, dots, decide/update); with gamd_classical_cells the table's five come on top.
+// Pass `it` (0: the start, then one per evaluation) reads state slot it & 1 and the gates gates[it & 1], and writes the other of
+// each: no thread reads what its launch writes, and a box that stops in a pass still finishes that pass in every thread.
+// The ring's slot numbers live in the state: they pass through GAMD_CHK_RANGE before they address the ring.
+enum { LBFGS_M = 8,            // ring slots the scalar state has room for: m <= LBFGS_M
+       LBFGS_SC = 16,          // per box and slot, scalars: t, rejections, pairs held, next ring slot, U, F.F, max |F_i|, accepted, skipped, resets
+       LBFGS_SY = LBFGS_SC,                             // [M][M] s_i . y_j by ring slot
+       LBFGS_YY = LBFGS_SY + LBFGS_M * LBFGS_M,         // [M][M] y_i . y_j
+       LBFGS_FS = LBFGS_YY + LBFGS_M * LBFGS_M,         // [M] F . s_i
+       LBFGS_FY = LBFGS_FS + LBFGS_M,                   // [M] F . y_i
+       LBFGS_SLOT = LBFGS_FY + LBFGS_M,
+       LBFGS_ACC = 9 + 3 * LBFGS_M,                     // per box and block: sum u_i, Ft.Ft, F.s, s.s, s.y, y.y, s.Ft, y.Ft, [M] s.y_k, [M] Ft.s_k, [M] Ft.y_k, max |Ft_i|
+       LBFGS_ROW = 10 };       // per box: state, evaluations, accepted steps, U and rms at the start, U, rms and max |F_i| at the end, pushes skipped, resets
+enum { LBFGS_CONVERGED = 0, LBFGS_MAX_ITER = 1, LBFGS_FAILED = 2, LBFGS_LINE_SEARCH = 3 };
+enum { GAMD_CHK_LBFGS_COUNT = 161, GAMD_CHK_LBFGS_SLOT = 162 };
+struct LbfgsArgs {
+    ClassicalArgs c;
+    double* x;                 // [n][3] the accepted positions, length unit, unwrapped
+    double* xt;                // [n][3] the trial positions
+    double* f;                 // [n][3] kJ/mol/nm at x
+    double* ft;                // [n][3] kJ/mol/nm at xt
+    double* d;                 // [n][3] the direction of the running line search
+    double* ring;              // [2 m][n][3]: s of slot 0 .. m - 1, then y of slot 0 .. m - 1
+    double* blk;               // [n_boxes][blocks][LBFGS_ACC]
+    double* state;             // [n_boxes][2][LBFGS_SLOT]
+    int* gates;                // [2][n_boxes] 0: running, else 1 + LBFGS_*
+    double* rows;              // [n_boxes][LBFGS_ROW]
+    int* sticky;               // host-mapped (checked build)
+    double tol;                // kJ/mol/nm
+    double max_step, c1, curv;
+    int m, max_ls;
+    long long max_iter;
+    long long it;              // evaluations enqueued in front of this pass's
+};
+int launch_lbfgs_init(const LbfgsArgs& l, const float* x, hipStream_t st);
+// `cells` as for launch_minimize_iter
+int launch_lbfgs_eval(const LbfgsArgs& l, hipStream_t st, const CellTabBufs* cells = nullptr);
+// x_out = fp32(x) wrapped, for every box that did not fail; `gates`: the set the last pass wrote
+int launch_lbfgs_store_x(const LbfgsArgs& l, const int* gates, float* x_out, hipStream_t st);
+
 // ---- water energy minimiser (water_minimize.hip) ------------------------------------------------------
 // Rigid-molecule FIRE under the 3-site water potential of water_classical.hip, per box, all state in double (DESIGN.md section
 // 4.13).  `w` carries the potential's constants, the geometry of the pair and reciprocal passes and the observer's work buffers

@@ -8,6 +8,7 @@
 // sample, one read call and one eval call (potential_*).
 #include "gamd_host.h"
 #include "gamd_minimize_host.h"
+#include "gamd_lbfgs_host.h"
 #include "gamd_pme_dev.h"
 #include "gamd_cells_dev.h"
 
@@ -155,9 +156,17 @@ struct Minimizer {
     DevBuf state, stopped, rows;
 };
 
+// L-BFGS energy minimiser (gamd_minimize_lbfgs, lbfgs.hip): as Minimizer, with buffers of its own — gamd_minimize's stay as they are
+struct Lbfgs {
+    DevBuf x, xt, f, ft, d;            // [n][3] doubles
+    DevBuf ring;                       // [2 m][n][3] doubles, for the largest m a call has asked for
+    DevBuf f32;                        // [n][3] floats: the force source's output in front of the per-box store
+    DevBuf blk, state, gates, rows;
+};
+
 }  // namespace
 
-struct Observers { Reporter rep; Recorder rec; StructSampler ss; Classical cl; WaterClassical wc; Minimizer mn; };
+struct Observers { Reporter rep; Recorder rec; StructSampler ss; Classical cl; WaterClassical wc; Minimizer mn; Lbfgs lb; };
 
 namespace {
 
@@ -239,6 +248,17 @@ ObsBufs minimize_bufs(gamd_handle* h) {
     return {{&mn.x64, sizeof(double) * n3, false}, {&mn.v64, sizeof(double) * n3, false}, {&mn.f64, sizeof(double) * n3, false},
             {&mn.f32, sizeof(float) * n3, false}, {&mn.state, sizeof(double) * 2 * MIN_STATE * nb, false},
             {&mn.stopped, sizeof(int) * nb, false}, {&mn.rows, sizeof(double) * MIN_ROW * nb, false}};
+}
+
+// L-BFGS energy minimiser: all of it work buffers (k_lbfgs_init writes what a pass reads in front of its first write)
+ObsBufs lbfgs_bufs(gamd_handle* h, int m) {
+    Lbfgs& lb = h->obs->lb;
+    const size_t nb = (size_t)h->n_boxes, n3 = 3 * (size_t)h->n;
+    return {{&lb.x, sizeof(double) * n3, false}, {&lb.xt, sizeof(double) * n3, false}, {&lb.f, sizeof(double) * n3, false},
+            {&lb.ft, sizeof(double) * n3, false}, {&lb.d, sizeof(double) * n3, false}, {&lb.ring, sizeof(double) * n3 * 2 * (size_t)m, false},
+            {&lb.f32, sizeof(float) * n3, false}, {&lb.blk, sizeof(double) * LBFGS_ACC * nb * (size_t)classical_blocks(h), false},
+            {&lb.state, sizeof(double) * 2 * LBFGS_SLOT * nb, false}, {&lb.gates, sizeof(int) * 2 * nb, false},
+            {&lb.rows, sizeof(double) * LBFGS_ROW * nb, false}};
 }
 
 // water classical observer: the pair pass has the classical observer's tiles, slices and blocks; the k slices of the reciprocal
@@ -970,6 +990,72 @@ int minimize_run(gamd_handle* h, typename M::Args m, float* x_dev, const uint8_t
     return worst;
 }
 
+// gamd_minimize_lbfgs behind the checks that need no device: minimize_run's order of things — the boxes, every allocation, the look
+// at the frozen flag, init, the evaluations in chunks of check_every with a look at the gates behind each (pass max_iter stops
+// every box that still runs), x, the force source's own kernels on exactly that x, f, the rows.
+int lbfgs_run(gamd_handle* h, float* x_dev, const float* box, double len, float* f_dev, double* x64_dev, const gamd_lbfgs_params& q,
+              double* rows_host, void* stream) {
+    using P = LjPotential;
+    static constexpr const char* api = "gamd_minimize_lbfgs";
+    if (!x_dev || !f_dev || !box) return fail(-22, "null argument");
+    if (int r = check_box_positive(h, box)) return r;
+    if (int r = P::check_box(h, box, nullptr)) return r;
+    PotentialLog& pl = P::state(h);
+    DeviceGuard guard(h->dev);
+    hipStream_t st = (hipStream_t)stream;
+    InitStream init(st);
+    // every allocation in front of the first enqueue
+    if (bufs_ensure_work(P::bufs(h)) || bufs_ensure_work(lbfgs_bufs(h, q.m))) return fail(-12, "%s: allocation failed", api);
+    const size_t nb = (size_t)h->n_boxes, n3 = 3 * (size_t)h->n;
+    std::vector<int> gates(nb, 0);
+    std::vector<double> rows(LBFGS_ROW * nb, 0.0);
+    HIP_TRY(init_upload(pl.eval_box.p, box, sizeof(float) * 3 * nb));
+    // the force source's kernels return at once on a frozen handle: f would be what the last call left
+    int frozen = 0;
+    HIP_TRY(hipMemcpyAsync(&frozen, h->devflags.as<int>() + DEVFLAG_FROZEN, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (frozen) return fail(-1, "%s: the handle is frozen by a neighbour-buffer overflow (call gamd_sync_status)", api);
+    Lbfgs& lb = h->obs->lb;
+    LbfgsArgs l{};
+    l.c = P::args(h, len);
+    l.c.box_edges = pl.eval_box.as<float>();
+    l.x = lb.x.as<double>(); l.xt = lb.xt.as<double>(); l.f = lb.f.as<double>(); l.ft = lb.ft.as<double>(); l.d = lb.d.as<double>();
+    l.ring = lb.ring.as<double>(); l.blk = lb.blk.as<double>(); l.state = lb.state.as<double>(); l.gates = lb.gates.as<int>();
+    l.rows = lb.rows.as<double>(); l.sticky = h->sticky_dev;
+    l.tol = q.tolerance; l.max_step = q.max_step; l.c1 = q.c1; l.curv = q.curv; l.m = q.m; l.max_ls = q.max_ls; l.max_iter = q.max_iter;
+    int r;
+    if ((r = launch_lbfgs_init(l, x_dev, st))) return fail(-1, "%s launch failed (%d)", api, r);
+    CellTabBufs cb;
+    const CellTabBufs* cells = P::cell_bufs(h, cb);
+    bool all_stopped = false;
+    while (l.it <= q.max_iter && !all_stopped) {            // pass 0 is the start's, pass k evaluation k
+        const long long chunk = std::min<long long>(q.check_every, q.max_iter + 1 - l.it);
+        for (long long k = 0; k < chunk; ++k, ++l.it)
+            if ((r = launch_lbfgs_eval(l, st, cells))) return fail(-1, "%s launch failed (%d)", api, r);
+        HIP_TRY(hipMemcpyAsync(gates.data(), lb.gates.as<int>() + (size_t)(l.it & 1) * nb, sizeof(int) * nb, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        all_stopped = std::all_of(gates.begin(), gates.end(), [](int s) { return s != 0; });
+    }
+    const int* gates_dev = lb.gates.as<int>() + (size_t)(l.it & 1) * nb;    // the set the last pass wrote
+    // x, then the force source's own kernels on exactly that x
+    if ((r = launch_lbfgs_store_x(l, gates_dev, x_dev, st))) return fail(-1, "%s launch failed (%d)", api, r);
+    ClassicalArgs drive = l.c;
+    drive.x = x_dev;
+    if ((r = P::drive(h, drive, lb.f32.as<float>(), st))) return fail(-1, "%s launch failed (%d)", api, r);
+    pl.evaluated = true;
+    FireArgs gate{};                                        // launch_minimize_store_f reads the gates alone: 1 + GAMD_MIN_FAILED is 1 + GAMD_LBFGS_FAILED
+    gate.stopped = const_cast<int*>(gates_dev);
+    if ((r = launch_minimize_store_f(gate, l.c.n, l.c.bx, lb.f32.as<float>(), f_dev, st))) return fail(-1, "%s launch failed (%d)", api, r);
+    if (x64_dev) HIP_TRY(hipMemcpyAsync(x64_dev, lb.x.p, sizeof(double) * n3, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemcpyAsync(rows.data(), lb.rows.p, sizeof(double) * rows.size(), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (int t = check_traps(h)) return t;
+    if (rows_host) std::memcpy(rows_host, rows.data(), sizeof(double) * rows.size());
+    int worst = 0;
+    for (size_t b = 0; b < nb; ++b) worst = std::max(worst, (int)rows[LBFGS_ROW * b]);
+    return worst;
+}
+
 // one of each +-n with 0 < |n|^2 <= n2max (the one whose first non-zero component is positive), sorted by (|n|^2, nx, ny, nz)
 std::vector<int> struct_kvectors(int n2max) {
     int m = 0;
@@ -998,6 +1084,7 @@ void observers_free(gamd_handle* h) {
     for (const Observer& ob : observer_list(h))
         for (const ObsBuf& b : ob.bufs(h)) b.buf->release();
     for (const ObsBuf& b : minimize_bufs(h)) b.buf->release();
+    for (const ObsBuf& b : lbfgs_bufs(h, 0)) b.buf->release();
     delete h->obs; h->obs = nullptr;
 }
 
@@ -1096,6 +1183,12 @@ static_assert(sizeof(gamd_minimize_params) == 88 && offsetof(gamd_minimize_param
               "gamd_minimize_params layout is part of the C ABI (gamd_amd/_lib.py mirrors it)");
 static_assert(GAMD_MINIMIZE_ROW == MIN_ROW && GAMD_MIN_CONVERGED == MIN_CONVERGED && GAMD_MIN_MAX_ITER == MIN_MAX_ITER && GAMD_MIN_FAILED == MIN_FAILED,
               "the row and the states of gamd_minimize are the kernels'");
+static_assert(sizeof(gamd_lbfgs_params) == 64 && offsetof(gamd_lbfgs_params, max_iter) == 8 && offsetof(gamd_lbfgs_params, max_step) == 24 &&
+              offsetof(gamd_lbfgs_params, m) == 48 && offsetof(gamd_lbfgs_params, max_ls) == 52 && offsetof(gamd_lbfgs_params, reserved) == 56,
+              "gamd_lbfgs_params layout is part of the C ABI (gamd_amd/_lib.py mirrors it)");
+static_assert(GAMD_LBFGS_ROW == LBFGS_ROW && GAMD_LBFGS_CONVERGED == LBFGS_CONVERGED && GAMD_LBFGS_MAX_ITER == LBFGS_MAX_ITER &&
+              GAMD_LBFGS_FAILED == LBFGS_FAILED && GAMD_LBFGS_LINE_SEARCH == LBFGS_LINE_SEARCH && LBFGS_FAILED == MIN_FAILED,
+              "the row and the states of gamd_minimize_lbfgs are the kernels'; a failed box's gate is gamd_minimize's");
 
 extern "C" {
 
@@ -1367,6 +1460,21 @@ int32_t gamd_minimize(gamd_handle* h, float* x_dev, const float* box, float leng
     if (h->pending.active) return fail(-22, "an MD run is still enqueued: call gamd_sync_status before gamd_minimize");
     return minimize_run<LjMinimizer>(h, MinArgs{}, x_dev, nullptr, box, length_per_nm > 0.f ? (double)length_per_nm : 10.0, f_dev, x64_dev, q,
                                      rows_host, stream);
+}
+
+int32_t gamd_minimize_lbfgs(gamd_handle* h, float* x_dev, const float* box, float length_per_nm, float* f_dev, double* x64_dev,
+                            const gamd_lbfgs_params* params, double* rows_host, void* stream) {
+    // the parameter block is checked first: these answers need no device
+    gamd_lbfgs_params q;
+    if (int r = lbfgs_fill_params(params, &q, g_err, sizeof(g_err))) return r;
+    if (!h) return fail(-22, "null handle");
+    if (h->cfg.kind != GAMD_KIND_LJ)
+        return fail(-22, "gamd_minimize_lbfgs: a GAMD_KIND_WATER handle has no classical potential to minimise (the Lennard-Jones "
+                         "potential has no electrostatics; GAMD_KIND_LJ handles only)");
+    Classical& cl = LjPotential::state(h);
+    if (!cl.params_set) return fail(-22, "gamd_minimize_lbfgs needs the parameters of a gamd_classical_configure call (interval 0 will do)");
+    if (h->pending.active) return fail(-22, "an MD run is still enqueued: call gamd_sync_status before gamd_minimize_lbfgs");
+    return lbfgs_run(h, x_dev, box, length_per_nm > 0.f ? (double)length_per_nm : 10.0, f_dev, x64_dev, q, rows_host, stream);
 }
 
 int32_t gamd_water_configure(gamd_handle* h, const gamd_water_params* p) {

@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import GamdClassicalParams, GamdMinimizeParams, GamdWaterParams, GamdWaterPmeParams, GamdReportParams, GamdStructParams, GamdTrajParams, GamdConfig, GamdMdParams, GamdNhcParams, TRAJ_FIELDS, check
+from ._lib import GamdClassicalParams, GamdLbfgsParams, GamdMinimizeParams, GamdWaterParams, GamdWaterPmeParams, GamdReportParams, GamdStructParams, GamdTrajParams, GamdConfig, GamdMdParams, GamdNhcParams, TRAJ_FIELDS, check
 from .weights import ModelConfig, infer_config, validate_state_dict
 
 ArrayLike = Union[np.ndarray, torch.Tensor]
@@ -501,6 +501,36 @@ class MinimizeResult:
 
     def __repr__(self):
         return f"MinimizeResult(state={self.state}, iterations={self.iterations.tolist()}, energy={self.energy.tolist()}, rms={self.rms.tolist()})"
+
+
+class LbfgsResult:
+    """What ``GamdForce.minimize_lbfgs`` did.  ``status``: the call's return value (0 every box converged, 1 a box stopped at
+    max_iter, 2 a box failed: not finite, 3 a box stopped in the line search; the largest wins).  Per box, float64 [B] unless
+    noted: ``state`` (list of "converged" | "max_iter" | "failed" | "line_search"), ``evaluations`` (int64: pair evaluations
+    behind the start's), ``accepted`` (int64: steps taken), ``energy_start`` / ``rms_start`` and ``energy`` / ``rms`` (kJ/mol,
+    kJ/mol/nm: root mean square of the 3N force components, OpenMM's tolerance), ``fmax`` (largest per-atom |F_i| at the end),
+    ``skipped`` (int64: accepted steps whose pair the curvature test kept out of the history), ``resets`` (int64: line
+    searches that failed and emptied the history).  ``x`` / ``f``: the tensors the call wrote; ``x64``: the unrounded,
+    unwrapped double positions or None.  ``rows`` is the library's table [B, 10]."""
+
+    def __init__(self, status: int, rows, x=None, f=None, x64=None):
+        self.status = int(status)
+        self.rows = np.asarray(rows, dtype=np.float64)
+        self.state = [_lib.LBFGS_STATE[int(s)] for s in self.rows[:, 0]]
+        self.evaluations = self.rows[:, 1].astype(np.int64)
+        self.accepted = self.rows[:, 2].astype(np.int64)
+        self.energy_start, self.rms_start = self.rows[:, 3], self.rows[:, 4]
+        self.energy, self.rms, self.fmax = self.rows[:, 5], self.rows[:, 6], self.rows[:, 7]
+        self.skipped, self.resets = self.rows[:, 8].astype(np.int64), self.rows[:, 9].astype(np.int64)
+        self.x, self.f, self.x64 = x, f, x64
+
+    @property
+    def converged(self) -> bool:
+        return self.status == 0
+
+    def __repr__(self):
+        return (f"LbfgsResult(state={self.state}, evaluations={self.evaluations.tolist()}, energy={self.energy.tolist()}, "
+                f"rms={self.rms.tolist()})")
 
 
 class GamdForce:
@@ -1185,6 +1215,31 @@ class GamdForce:
                                            C.c_void_p(f.data_ptr()), C.c_void_p(x64.data_ptr()) if return_x64 else None,
                                            C.byref(p), rows.ctypes.data_as(C.c_void_p), self._stream()), "gamd_minimize")
         return MinimizeResult(st, rows, x, f, x64)
+
+    def minimize_lbfgs(self, x: torch.Tensor, f: Optional[torch.Tensor] = None, tolerance: float = 10.0, max_iter: int = 0, box=None,
+                       length_per_nm: float = 0.0, return_x64: bool = False, check_every: int = 0, m: int = 0, c1: float = 0.0,
+                       curv: float = 0.0, max_ls: int = 0, max_step: float = 0.0) -> "LbfgsResult":
+        """``minimize`` with L-BFGS in place of FIRE: the same task, arguments and results (``x`` changed in place, ``f`` the
+        classical forces at exactly that ``x``, ``classical_forces(x)[0].float()`` bit for bit; a failed box keeps its ``x``
+        and ``f``), for the tolerances at which FIRE's iteration count is what costs (the rollout drivers'
+        ``minimizeEnergy(1e-6)``).  A history of ``m`` pairs (1 .. 8, 0 = 6) shapes the direction, a backtracking line search
+        (sufficient decrease ``c1``, 0 = 1e-4; ``max_ls`` halvings, 0 = 20) sizes the step, no atom moves further than
+        ``max_step`` (0 = 0.1, the engine's length unit) in one trial, a pair enters the history when s.y > ``curv`` |s||y|
+        (0 = 1e-10), and ``max_iter`` (0 = 10 000) bounds the pair evaluations.  OpenMM's minimiser is L-BFGS too, but the line
+        search and the stopping rule here are this library's own: no parity with OpenMM is claimed.  tests/lbfgs_ref.py is the
+        recipe in float64.  LJ models only; 2 r_cut must not exceed a box edge.  Synchronises."""
+        if not getattr(self, "_classical_set", False):
+            self.classical_configure(0)
+        if f is None:
+            f = torch.zeros_like(x)
+        self._md_state(x, f)
+        x64 = torch.empty((self.n_total, 3), dtype=torch.float64, device=self.device) if return_x64 else None
+        p = GamdLbfgsParams(float(tolerance), int(max_iter), int(check_every), float(max_step), float(c1), float(curv), int(m), int(max_ls), 0)
+        rows = np.zeros((self.n_boxes, _lib.LBFGS_ROW), dtype=np.float64)
+        st = check(self._lib.gamd_minimize_lbfgs(self._h, C.c_void_p(x.data_ptr()), self._box_arg(box), float(length_per_nm),
+                                                 C.c_void_p(f.data_ptr()), C.c_void_p(x64.data_ptr()) if return_x64 else None,
+                                                 C.byref(p), rows.ctypes.data_as(C.c_void_p), self._stream()), "gamd_minimize_lbfgs")
+        return LbfgsResult(st, rows, x, f, x64)
 
     # -- water classical observer (3-site water: O-O Lennard-Jones plus an Ewald sum, on sampled frames; force labels) ------
     def water_classical_configure(self, interval: int, max_samples: int = 0, q_h: float = 0.417, sigma_o: Optional[float] = None,

@@ -819,6 +819,63 @@ enum { GAMD_MIN_CONVERGED = 0, GAMD_MIN_MAX_ITER = 1, GAMD_MIN_FAILED = 2 };
 int32_t gamd_minimize(gamd_handle* h, float* x_dev, const float* box, float length_per_nm, float* f_dev, double* x64_dev,
                       const gamd_minimize_params* params, double* rows_host, void* stream);
 
+/* L-BFGS energy minimiser: gamd_minimize's task, arguments and tail with a quasi-Newton algorithm, for the tolerances and sizes
+ * at which FIRE's iteration count is what costs (the rollout drivers' minimizeEnergy(1e-6)).  OpenMM's minimizeEnergy is L-BFGS
+ * too, but NO parity with its implementation is claimed: the line search and the stopping rule below are this library's own.
+ * What is matched is the meaning of the tolerance: the root mean square of all 3N force components of a box, in kJ/mol/nm.
+ * gamd_minimize, its parameter block, its states and its bits are untouched by this entry.
+ * Per box, in double: x is the fp32 input widened, F in kJ/mol/nm (through length_per_nm) and U in kJ/mol are the pair term of
+ * gamd_classical_configure as gamd_minimize evaluates it; x and max_step are in the handle's length unit (the quasi-Newton
+ * scaling absorbs the units, as FIRE's dt does).  The history is a ring of at most m pairs (s, y).
+ *   1. U and F at the start.  U or F.F not finite: the box stops as GAMD_LBFGS_FAILED and keeps the x it was given.
+ *      rms = sqrt(F.F / 3N) <= tolerance: it stops as GAMD_LBFGS_CONVERGED with 0 evaluations.
+ *   2. The direction d.  Empty history: d = F max_step / max_i |F_i| (the largest per-atom norm).  Otherwise d = H F by the
+ *      two-loop recursion over the ring with H0 = s.y / y.y of the newest pair.  The trial factor t = 1.
+ *   3. The trial displacement s_i = t d_i per atom, scaled to length max_step where it is longer; x_t = x + s, and s is from
+ *      here on the difference x_t - x as the doubles give it.
+ *   4. U_t and F_t at x_t: one evaluation, counted whatever follows.
+ *   5. The trial is accepted iff F.s > 0, U_t is finite and U_t <= U - c1 F.s.  Rejected: t = t / 2 and step 3 again; after
+ *      max_ls rejections in a row, or at once when F.s <= 0, the search has failed: with a non-empty history the history is
+ *      emptied (a reset), d is step 2's steepest direction, t = 1 and step 3 follows; with an empty one the box stops as
+ *      GAMD_LBFGS_LINE_SEARCH at x.
+ *   6. Accepted: y = F - F_t; the pair (s, y) enters the ring, displacing the oldest of m, iff s.y > curv sqrt(s.s y.y) (else
+ *      the push is skipped); x = x_t, F = F_t, U = U_t.  rms <= tolerance: GAMD_LBFGS_CONVERGED.  Else, max_iter evaluations
+ *      used up: GAMD_LBFGS_MAX_ITER.  Else step 2.
+ *   7. A box that uses up max_iter on a rejected trial stops as GAMD_LBFGS_MAX_ITER at the last accepted x.
+ * One evaluation is three launches whatever m is (six more with gamd_classical_cells): the pair pass on x_t, one pass for every
+ * inner product, one pass that decides and updates; the recursion runs on the inner products of the ring's vectors alone.
+ * Everything is in double with fixed summation orders, no floating-point atomics and no contraction: the same bits run after
+ * run, whatever check_every is, and every box of a handle gets the bits it gets alone.  The host enqueues check_every
+ * evaluations at a time and looks at the boxes' states only between such chunks; a box that stopped is skipped on the device.
+ * Nothing is allocated between the first and the last enqueue.  tests/lbfgs_ref.py is this recipe in float64 on the host.
+ * On return (the stream is synchronised) x_dev, f_dev and x64_dev are as gamd_minimize leaves them: the accepted double positions
+ * rounded to fp32 and wrapped; the classical force source's force at exactly those fp32 positions; the unrounded positions.
+ * Nothing is written for a box that failed.
+ *   rows_host    double [n_boxes][GAMD_LBFGS_ROW] HOST or NULL: state (GAMD_LBFGS_*), evaluations (behind the start's), accepted
+ *                steps, U and rms at the start, U, rms and the largest per-atom |F_i| at the end, pushes the curvature test
+ *                skipped, history resets.
+ * Returns 0: every box converged; 1: a box stopped at max_iter; 2: a box failed (not finite); 3: a box stopped in the line
+ * search — the largest wins.  -22, with a message naming the reason, before anything is enqueued: what gamd_minimize refuses
+ * (null params / x_dev / f_dev / box, tolerance, negative counts, max_step, a null or GAMD_KIND_WATER handle, no accepted
+ * gamd_classical_configure, a pending run, a box edge that is not positive or below 2 * r_cut), m outside [1, 8], c1 outside
+ * (0, 1), a negative curv or max_ls, a non-zero reserved.  -12 when an allocation fails; -1 on a frozen handle.
+ * Device memory besides the classical observer's work buffers: 24 (2 m + 5) + 12 B per atom, the ring sized for the m in force. */
+typedef struct gamd_lbfgs_params {
+    double tolerance;        /* kJ/mol/nm, > 0 and finite */
+    int64_t max_iter;        /* evaluations behind the start's at most; 0 = 10000 */
+    int64_t check_every;     /* evaluations enqueued between two looks at the boxes' states; 0 = 64 */
+    double max_step;         /* length unit of the handle; 0 = 0.1 */
+    double c1;               /* sufficient decrease, in (0, 1); 0 = 1e-4 */
+    double curv;             /* curvature test of a push, > 0; 0 = 1e-10 */
+    int32_t m;               /* pairs in the ring, 1 .. 8; 0 = 6 */
+    int32_t max_ls;          /* rejections in a row that fail a line search; 0 = 20 */
+    int64_t reserved;        /* 0 */
+} gamd_lbfgs_params;
+enum { GAMD_LBFGS_ROW = 10 };
+enum { GAMD_LBFGS_CONVERGED = 0, GAMD_LBFGS_MAX_ITER = 1, GAMD_LBFGS_FAILED = 2, GAMD_LBFGS_LINE_SEARCH = 3 };
+int32_t gamd_minimize_lbfgs(gamd_handle* h, float* x_dev, const float* box, float length_per_nm, float* f_dev, double* x64_dev,
+                            const gamd_lbfgs_params* params, double* rows_host, void* stream);
+
 /* Energy minimiser for rigid 3-site water: every water driver of the reference relaxes its start in front of the first step
  * (minimizeEnergy, dataset/generate_tip3p_data.py:85).  gamd_water_minimize is gamd_minimize for a GAMD_KIND_WATER handle under
  * the potential of the last gamd_water_configure (interval 0 will do), ON THE DEVICE, and leaves x and f as a
