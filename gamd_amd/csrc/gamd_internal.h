@@ -932,3 +932,43 @@ int launch_wmin_iter(const WMinArgs& m, hipStream_t st);
 // x_io = fp32(x64) with molecules whole and the oxygen in [0, L) (skipped for a box that failed at iteration 0); x64_out (may be
 // null) = x64, or the input widened for such a box
 int launch_wmin_store_x(const WMinArgs& m, float* x_io, double* x64_out, hipStream_t st);
+// the four force launches of an iteration alone (k_wmin_pairs, k_wmin_rho, k_water_sk, k_wmin_recip) on m.fire.x64 under the gate
+// m.fire.stopped, into m.w.part, m.w.rpart, m.w.sk and m.w.ublk: nothing else of m.fire is read (water_lbfgs.hip hands over its
+// trial positions and the gate set of its pass)
+int launch_wmin_force(const WMinArgs& m, hipStream_t st);
+
+// ---- water L-BFGS energy minimiser (water_lbfgs.hip) ---------------------------------------------------
+// Limited-memory BFGS with a backtracking line search on RIGID 3-site molecules under the water potential, per box, all state
+// in double (tests/water_lbfgs_ref.py is the recipe).  `w`, ra, rb, rc as for WMinArgs; the L-BFGS
+// members, the state slots (LBFGS_SLOT), the gates, the rows (LBFGS_ROW) and the states are LbfgsArgs'.  One evaluation is six
+// launches whatever m is: launch_wmin_force on xt under the gates of the pass, k_wlb_mols, k_wlb_update.  Pass `it`, the two
+// gate sets and the two state slots as for LbfgsArgs.
+enum { WLB_ULJ = 0, WLB_UC = 1, WLB_Z2 = 2, WLB_FTFT = 3, WLB_FS = 4, WLB_SS = 5, WLB_SY = 6, WLB_YY = 7, WLB_SFT = 8, WLB_YFT = 9,
+       WLB_SYK = 10, WLB_FTSK = WLB_SYK + LBFGS_M, WLB_FTYK = WLB_FTSK + LBFGS_M, WLB_MAX = WLB_FTYK + LBFGS_M,
+       WLB_ACC = WLB_MAX + 1 };  // per box and block: sum u_LJ, sum u_coul, sum z^2, Ft.Ft, F.s, s.s, s.y, y.y, s.Ft, y.Ft, [M] s.y_k, [M] Ft.s_k, [M] Ft.y_k, max |Ft_i|
+enum { GAMD_CHK_WLBFGS_COUNT = 163, GAMD_CHK_WLBFGS_SLOT = 164 };
+struct WLbfgsArgs {
+    WaterArgs w;
+    double ra, rb, rc;         // the unit-weight canonical triangle, as WMinArgs
+    double* x;                 // [n][3] the accepted positions, length unit, unwrapped, every molecule rigid
+    double* xt;                // [n][3] the trial positions, rigid
+    double* f;                 // [n][3] kJ/mol/nm at x, projected at x
+    double* ft;                // [n][3] kJ/mol/nm at xt, projected at xt
+    double* d;                 // [n][3] the direction of the running line search
+    double* ring;              // [2 m][n][3]: s of slot 0 .. m - 1, then y of slot 0 .. m - 1
+    double* blk;               // [n_boxes][blocks][WLB_ACC]
+    double* state;             // [n_boxes][2][LBFGS_SLOT]
+    int* gates;                // [2][n_boxes] 0: running, else 1 + LBFGS_*
+    double* rows;              // [n_boxes][LBFGS_ROW]
+    int* sticky;               // host-mapped (checked build)
+    double tol;                // kJ/mol/nm
+    double max_step, c1, curv;
+    int m, max_ls;
+    long long max_iter;
+    long long it;              // evaluations enqueued in front of this pass's
+};
+int launch_wlbfgs_init(const WLbfgsArgs& l, const float* x, hipStream_t st);
+int launch_wlbfgs_eval(const WLbfgsArgs& l, hipStream_t st);
+// x_io = fp32(x) by k_wmin_store_x's wrap and x64_out (may be null) = x, for every box that did not fail (such a box keeps x_io,
+// and x64_out is x_io widened); `gates`: the set the last pass wrote
+int launch_wlbfgs_store_x(const WLbfgsArgs& l, const int* gates, float* x_io, double* x64_out, hipStream_t st);

@@ -1,14 +1,15 @@
-// gamd_lbfgs_host.h — the parameter block of gamd_minimize_lbfgs as the host takes it: the checks that need neither a handle nor
-// a device, and the defaults a zero selects.  Plain C++ (no HIP header), after gamd_minimize_host.h.
+// gamd_lbfgs_host.h — the parameter block of gamd_minimize_lbfgs and gamd_water_minimize_lbfgs as the host takes it: the checks
+// that need neither a handle nor a device, and the defaults a zero selects.  Plain C++ (no HIP header), after gamd_minimize_host.h.
 #pragma once
 #include "../../include/gamd_hip.h"
 
 #include <cmath>
 #include <cstdio>
 
-// p as given -> *out with every zero replaced by its default.  0, or -22 with the reason in err (out is then left as it was).
-inline int lbfgs_fill_params(const gamd_lbfgs_params* p, gamd_lbfgs_params* out, char* err, size_t err_len) {
-    auto refuse = [&](const char* what, double v) { std::snprintf(err, err_len, "gamd_minimize_lbfgs: %s (%g)", what, v); return -22; };
+// p as given -> *out with every zero replaced by its default.  0, or -22 with the reason in err (out is then left as it was);
+// `api` is the entry the message names.
+inline int lbfgs_fill_params(const gamd_lbfgs_params* p, gamd_lbfgs_params* out, char* err, size_t err_len, const char* api = "gamd_minimize_lbfgs") {
+    auto refuse = [&](const char* what, double v) { std::snprintf(err, err_len, "%s: %s (%g)", api, what, v); return -22; };
     if (!p) { std::snprintf(err, err_len, "null argument"); return -22; }
     if (!(p->tolerance > 0.0) || !std::isfinite(p->tolerance)) return refuse("tolerance is not positive and finite", p->tolerance);
     if (p->max_iter < 0) return refuse("max_iter is negative", (double)p->max_iter);

@@ -79,4 +79,22 @@ __device__ __forceinline__ void project(const D3 (&x)[3], D3 (&u)[3]) {
     u[2] = u[2] - ((g1 * r1) + (g2 * r2));
 }
 
+// component d of molecule `mol` as the minimisers return it: x_io = fp32(x64 - s), s the lattice vector (edge L, an fp32 value)
+// that brings the oxygen into [0, L); x64_out (may be null) = x64
+__device__ __forceinline__ void store_wrapped(const double* x64, size_t mol, int d, double L, float* x_io, double* x64_out) {
+    const float Lf = (float)L;                              // exact: the edge is an fp32 value
+    const double xo = x64[9 * mol + d];
+    double s = L * floor(xo / L);
+    if (xo - s < 0.0) s = s - L;                            // the quotient rounded up to an integer
+    if ((float)(xo - s) >= Lf) s = s + L;                   // the oxygen rounds up to L: it goes to 0 with its hydrogens
+    float o = (float)(xo - s);
+    if (o < 0.f) o = 0.f;
+    x_io[9 * mol + d] = o;
+    x_io[9 * mol + 3 + d] = (float)(x64[9 * mol + 3 + d] - s);
+    x_io[9 * mol + 6 + d] = (float)(x64[9 * mol + 6 + d] - s);
+    if (x64_out) {
+        x64_out[9 * mol + d] = xo; x64_out[9 * mol + 3 + d] = x64[9 * mol + 3 + d]; x64_out[9 * mol + 6 + d] = x64[9 * mol + 6 + d];
+    }
+}
+
 }  // namespace gamd_wmin

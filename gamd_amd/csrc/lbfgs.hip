@@ -20,7 +20,8 @@
 //                   runs on SCALARS only: the inner products s_i.y_j, y_i.y_j, F.s_i, F.y_i of the ring, kept per box in the
 //                   state and brought up to date from the new dots (y = F - Ft: y.v = F.v - Ft.v), give the coefficients of
 //                   d = cf F + sum cs_j s_j + sum cy_j y_j, and every thread forms its atom's d from the ring.  Then the
-//                   next trial: s = t d, |s_i| clamped to max_step, xt = x + s.
+//                   next trial: s = t d, |s_i| clamped to max_step, xt = x + s.  The decision, the ring's products and the
+//                   recursion are gamd_lbfgs_dev.h's, shared with k_wlb_update (water_lbfgs.hip).
 //
 // With gamd_classical_cells on, launch_classical_cells (cell_table.hip's table rebuilt from xt, then k_ljcell_min of
 // classical_cells.hip) stands where k_lbfgs_pairs is, on ONE pair slice.
@@ -39,6 +40,7 @@
 #pragma clang fp contract(off)
 
 #include "gamd_passes_dev.h"
+#include "gamd_lbfgs_dev.h"
 
 namespace {
 
@@ -216,60 +218,29 @@ __global__ void __launch_bounds__(256) k_lbfgs_update(LbfgsArgs l) {
     const double* cur = l.state + ((size_t)box * 2 + (size_t)(l.it & 1)) * LBFGS_SLOT;
     double* nxt = l.state + ((size_t)box * 2 + (size_t)((l.it + 1) & 1)) * LBFGS_SLOT;
     double* row = l.rows + (size_t)box * LBFGS_ROW;
-    double t = cur[0], ls = cur[1];
+    gamd_lbfgs::Scalars sc = gamd_lbfgs::load_scalars(cur);
     const int cnt = GAMD_CHK_RANGE(l.sticky, (int)cur[2], 0, l.m, GAMD_CHK_LBFGS_COUNT);
     const int head = GAMD_CHK_RANGE(l.sticky, (int)cur[3], 0, l.m - 1, GAMD_CHK_LBFGS_SLOT);   // the slot a push writes
-    double U = cur[4], FF = cur[5], fm = cur[6], n_acc = cur[7], n_skip = cur[8], n_reset = cur[9];
     const double Ut = 0.5 * sacc[LB_US];                    // every pair sits in two rows
-    const double ftft = sacc[LB_FTFT], fs = sacc[LB_FS], ss = sacc[LB_SS], sy = sacc[LB_SY], yy = sacc[LB_YY];
+    const double ftft = sacc[LB_FTFT], sy = sacc[LB_SY], yy = sacc[LB_YY];
     const double rms_t = sqrt(ftft / (3.0 * (double)npb));
     const bool start = l.it == 0;
 
     // ---- the decision, by every thread from the same bits ----
-    int stop = 0;
-    bool accept, push = false, reset = false;
-    if (start) {
-        if (writer) { row[3] = Ut; row[4] = rms_t; }
-        accept = true;
-        if (!isfinite(Ut) || !isfinite(ftft)) { stop = 1 + LBFGS_FAILED; U = Ut; FF = ftft; fm = sacc[LB_MAX]; }
-    } else {
-        accept = fs > 0.0 && isfinite(Ut) && Ut <= U - l.c1 * fs;
-    }
-    if (!stop) {
-        if (accept) {
-            if (!start) {
-                push = sy > l.curv * sqrt(ss * yy);
-                n_acc += 1.0;
-                if (!push) n_skip += 1.0;
-            }
-            U = Ut; FF = ftft; fm = sacc[LB_MAX];
-            if (rms_t <= l.tol) stop = 1 + LBFGS_CONVERGED;
-            else if (l.it == l.max_iter) stop = 1 + LBFGS_MAX_ITER;
-            t = 1.0; ls = 0.0;
-        } else if (l.it == l.max_iter) {
-            stop = 1 + LBFGS_MAX_ITER;
-        } else {
-            ls += 1.0;
-            if (ls >= (double)l.max_ls || !(fs > 0.0)) {    // the search has failed
-                if (cnt > 0) { reset = true; n_reset += 1.0; t = 1.0; ls = 0.0; }
-                else stop = 1 + LBFGS_LINE_SEARCH;
-            } else {
-                t = t / 2.0;
-            }
-        }
-    }
+    if (start && writer) { row[3] = Ut; row[4] = rms_t; }
+    const gamd_lbfgs::Decision dc = gamd_lbfgs::decide(l, start, cnt, Ut, ftft, sacc[LB_MAX], rms_t, sacc[LB_FS], sacc[LB_SS], sy, yy, sc);
 
     // ---- the accepted point: the ring's new pair, x = xt, F = Ft (a box that stops here still takes it) ----
     const int il = blockIdx.x * GAMD_PASS_TILE + tid;
     const bool vi = il < npb;
     const size_t i = (size_t)box * (size_t)npb + (size_t)(vi ? il : 0);
     double x[3] = {0.0, 0.0, 0.0}, f[3] = {0.0, 0.0, 0.0};
-    if (vi && stop != 1 + LBFGS_FAILED) {
+    if (vi && dc.stop != 1 + LBFGS_FAILED) {
         lb_load(l.x, i, x); lb_load(l.f, i, f);
-        if (accept) {
+        if (dc.accept) {
             double xt[3], ft[3];
             lb_load(l.xt, i, xt); lb_load(l.ft, i, ft);
-            if (push) {
+            if (dc.push) {
                 const double s[3] = {xt[0] - x[0], xt[1] - x[1], xt[2] - x[2]};
                 const double y[3] = {f[0] - ft[0], f[1] - ft[1], f[2] - ft[2]};
                 lb_store(lb_ring(l, 0, head), i, s); lb_store(lb_ring(l, 1, head), i, y);
@@ -279,106 +250,49 @@ __global__ void __launch_bounds__(256) k_lbfgs_update(LbfgsArgs l) {
             lb_store(l.x, i, x); lb_store(l.f, i, f);
         }
     }
-    if (stop) {
+    if (dc.stop) {
         if (writer) {
-            row[0] = (double)(stop - 1); row[1] = (double)l.it; row[2] = n_acc; row[5] = U; row[6] = sqrt(FF / (3.0 * (double)npb));
-            row[7] = fm; row[8] = n_skip; row[9] = n_reset;
-            gates_out[box] = stop;
+            row[0] = (double)(dc.stop - 1); row[1] = (double)l.it; row[2] = sc.n_acc; row[5] = sc.U; row[6] = sqrt(sc.FF / (3.0 * (double)npb));
+            row[7] = sc.fm; row[8] = sc.n_skip; row[9] = sc.n_reset;
+            gates_out[box] = dc.stop;
         }
         return;
     }
 
     // ---- the state of the next pass: the scalars, and the ring's products with the new pair in slot `head` ----
-    const int cnt2 = reset ? 0 : (push ? (cnt + 1 < l.m ? cnt + 1 : l.m) : cnt);
-    const int head2 = reset ? 0 : (push ? (head + 1 == l.m ? 0 : head + 1) : head);
-    const int oldest = cnt2 < l.m ? 0 : head2;              // pair j of the ring, oldest first, sits in slot oldest + j (mod m)
-    auto n_sy = [&](int p, int q) -> double {               // s_p . y_q
-        if (push && p == head) return q == head ? sy : sacc[LB_SYK + q];
-        if (push && q == head) return cur[LBFGS_FS + p] - sacc[LB_FTSK + p];       // s_p . (F - Ft)
-        return cur[LBFGS_SY + p * LBFGS_M + q];
-    };
-    auto n_yy = [&](int p, int q) -> double {
-        if (push && p == head) return q == head ? yy : cur[LBFGS_FY + q] - sacc[LB_FTYK + q];
-        if (push && q == head) return cur[LBFGS_FY + p] - sacc[LB_FTYK + p];
-        return cur[LBFGS_YY + p * LBFGS_M + q];
-    };
-    auto n_fs = [&](int p) -> double { return !accept ? cur[LBFGS_FS + p] : (push && p == head ? sacc[LB_SFT] : sacc[LB_FTSK + p]); };
-    auto n_fy = [&](int p) -> double { return !accept ? cur[LBFGS_FY + p] : (push && p == head ? sacc[LB_YFT] : sacc[LB_FTYK + p]); };
-    auto slot_of = [&](int j) -> int { const int p = oldest + j; return p >= l.m ? p - l.m : p; };
-    if (tid < LBFGS_M * LBFGS_M) {
-        const int p = tid / LBFGS_M, q = tid % LBFGS_M;
-        if (blockIdx.x == 0) { nxt[LBFGS_SY + tid] = n_sy(p, q); nxt[LBFGS_YY + tid] = n_yy(p, q); }
-        const bool in = p < cnt2 && q < cnt2;               // here p, q count from the oldest pair
-        g_sy[tid] = in ? n_sy(slot_of(p), slot_of(q)) : 0.0;
-        g_yy[tid] = in ? n_yy(slot_of(p), slot_of(q)) : 0.0;
-    }
-    if (tid < LBFGS_M) {
-        if (blockIdx.x == 0) { nxt[LBFGS_FS + tid] = n_fs(tid); nxt[LBFGS_FY + tid] = n_fy(tid); }
-        g_fs[tid] = tid < cnt2 ? n_fs(slot_of(tid)) : 0.0;
-        g_fy[tid] = tid < cnt2 ? n_fy(slot_of(tid)) : 0.0;
-    }
+    const gamd_lbfgs::Ring rg = gamd_lbfgs::ring_next(l.m, cnt, head, dc, cur, nxt, blockIdx.x == 0, tid, sy, yy, sacc[LB_SFT], sacc[LB_YFT],
+                                                     sacc + LB_SYK, sacc + LB_FTSK, sacc + LB_FTYK, g_sy, g_yy, g_fs, g_fy);
     if (writer) {
-        nxt[0] = t; nxt[1] = ls; nxt[2] = (double)cnt2; nxt[3] = (double)head2; nxt[4] = U; nxt[5] = FF; nxt[6] = fm;
-        nxt[7] = n_acc; nxt[8] = n_skip; nxt[9] = n_reset;
+        nxt[0] = sc.t; nxt[1] = sc.ls; nxt[2] = (double)rg.cnt; nxt[3] = (double)rg.head; nxt[4] = sc.U; nxt[5] = sc.FF; nxt[6] = sc.fm;
+        nxt[7] = sc.n_acc; nxt[8] = sc.n_skip; nxt[9] = sc.n_reset;
         gates_out[box] = 0;
     }
     __syncthreads();
 
     // ---- the direction: kept through a line search, new behind an accepted step or an emptied ring ----
     double d[3] = {0.0, 0.0, 0.0};
-    if (accept || reset) {
-        if (cnt2 == 0) {                                    // steepest descent, the longest per-atom step max_step
-            const double sc = l.max_step / fm;
-            if (vi) { d[0] = f[0] * sc; d[1] = f[1] * sc; d[2] = f[2] * sc; }
+    if (dc.accept || dc.reset) {
+        if (rg.cnt == 0) {                                  // steepest descent, the longest per-atom step max_step
+            const double sd = l.max_step / sc.fm;
+            if (vi) { d[0] = f[0] * sd; d[1] = f[1] * sd; d[2] = f[2] * sd; }
         } else {                                            // the two-loop recursion on the coefficients of d
-            double cy[LBFGS_M], cs[LBFGS_M], al[LBFGS_M];
-#pragma unroll
-            for (int j = 0; j < LBFGS_M; ++j) { cy[j] = 0.0; cs[j] = 0.0; al[j] = 0.0; }
-#pragma unroll
-            for (int p = LBFGS_M - 1; p >= 0; --p) {
-                if (p < cnt2) {
-                    double sq = g_fs[p];
-#pragma unroll
-                    for (int j = 0; j < LBFGS_M; ++j)
-                        if (j < cnt2) sq = sq + cy[j] * g_sy[p * LBFGS_M + j];
-                    al[p] = sq / g_sy[p * LBFGS_M + p];
-                    cy[p] = cy[p] - al[p];
-                }
-            }
-            const int nw = cnt2 - 1;                        // the newest pair
-            const double h0 = g_sy[nw * LBFGS_M + nw] / g_yy[nw * LBFGS_M + nw];
-            const double cf = h0;
-#pragma unroll
-            for (int j = 0; j < LBFGS_M; ++j) cy[j] = h0 * cy[j];
-#pragma unroll
-            for (int p = 0; p < LBFGS_M; ++p) {
-                if (p < cnt2) {
-                    double yr = cf * g_fy[p];
-#pragma unroll
-                    for (int j = 0; j < LBFGS_M; ++j)
-                        if (j < cnt2) yr = yr + cy[j] * g_yy[p * LBFGS_M + j];
-#pragma unroll
-                    for (int j = 0; j < LBFGS_M; ++j)
-                        if (j < cnt2) yr = yr + cs[j] * g_sy[j * LBFGS_M + p];
-                    const double beta = yr / g_sy[p * LBFGS_M + p];
-                    cs[p] = cs[p] + (al[p] - beta);
-                }
-            }
+            double cf, cs[LBFGS_M], cy[LBFGS_M];
+            gamd_lbfgs::coefficients(rg.cnt, g_sy, g_yy, g_fs, g_fy, cf, cs, cy);
             if (vi) {
                 d[0] = cf * f[0]; d[1] = cf * f[1]; d[2] = cf * f[2];
 #pragma unroll
                 for (int j = 0; j < LBFGS_M; ++j) {
-                    if (j < cnt2) {
+                    if (j < rg.cnt) {
                         double v[3];
-                        lb_load(lb_ring(l, 0, slot_of(j)), i, v);
+                        lb_load(lb_ring(l, 0, rg.slot_of(j)), i, v);
                         d[0] = d[0] + cs[j] * v[0]; d[1] = d[1] + cs[j] * v[1]; d[2] = d[2] + cs[j] * v[2];
                     }
                 }
 #pragma unroll
                 for (int j = 0; j < LBFGS_M; ++j) {
-                    if (j < cnt2) {
+                    if (j < rg.cnt) {
                         double v[3];
-                        lb_load(lb_ring(l, 1, slot_of(j)), i, v);
+                        lb_load(lb_ring(l, 1, rg.slot_of(j)), i, v);
                         d[0] = d[0] + cy[j] * v[0]; d[1] = d[1] + cy[j] * v[1]; d[2] = d[2] + cy[j] * v[2];
                     }
                 }
@@ -391,7 +305,7 @@ __global__ void __launch_bounds__(256) k_lbfgs_update(LbfgsArgs l) {
     if (!vi) return;
 
     // ---- the next trial ----
-    double s[3] = {t * d[0], t * d[1], t * d[2]};
+    double s[3] = {sc.t * d[0], sc.t * d[1], sc.t * d[2]};
     const double nrm = sqrt((s[0] * s[0] + s[1] * s[1]) + s[2] * s[2]);
     if (nrm > l.max_step) {
         const double sc = l.max_step / nrm;

@@ -156,7 +156,8 @@ struct Minimizer {
     DevBuf state, stopped, rows;
 };
 
-// L-BFGS energy minimiser (gamd_minimize_lbfgs, lbfgs.hip): as Minimizer, with buffers of its own — gamd_minimize's stay as they are
+// L-BFGS energy minimisers (gamd_minimize_lbfgs, lbfgs.hip; gamd_water_minimize_lbfgs, water_lbfgs.hip): as Minimizer, with buffers
+// of their own — gamd_minimize's and gamd_water_minimize's stay as they are
 struct Lbfgs {
     DevBuf x, xt, f, ft, d;            // [n][3] doubles
     DevBuf ring;                       // [2 m][n][3] doubles, for the largest m a call has asked for
@@ -250,13 +251,14 @@ ObsBufs minimize_bufs(gamd_handle* h) {
             {&mn.stopped, sizeof(int) * nb, false}, {&mn.rows, sizeof(double) * MIN_ROW * nb, false}};
 }
 
-// L-BFGS energy minimiser: all of it work buffers (k_lbfgs_init writes what a pass reads in front of its first write)
-ObsBufs lbfgs_bufs(gamd_handle* h, int m) {
+// L-BFGS energy minimisers: all of it work buffers (k_lbfgs_init / k_wlb_init write what a pass reads in front of its first write);
+// acc: the columns of the minimiser's block row (a handle is of one kind, so only one of the two ever sizes the buffers)
+ObsBufs lbfgs_bufs(gamd_handle* h, int m, int acc) {
     Lbfgs& lb = h->obs->lb;
     const size_t nb = (size_t)h->n_boxes, n3 = 3 * (size_t)h->n;
     return {{&lb.x, sizeof(double) * n3, false}, {&lb.xt, sizeof(double) * n3, false}, {&lb.f, sizeof(double) * n3, false},
             {&lb.ft, sizeof(double) * n3, false}, {&lb.d, sizeof(double) * n3, false}, {&lb.ring, sizeof(double) * n3 * 2 * (size_t)m, false},
-            {&lb.f32, sizeof(float) * n3, false}, {&lb.blk, sizeof(double) * LBFGS_ACC * nb * (size_t)classical_blocks(h), false},
+            {&lb.f32, sizeof(float) * n3, false}, {&lb.blk, sizeof(double) * (size_t)acc * nb * (size_t)classical_blocks(h), false},
             {&lb.state, sizeof(double) * 2 * LBFGS_SLOT * nb, false}, {&lb.gates, sizeof(int) * 2 * nb, false},
             {&lb.rows, sizeof(double) * LBFGS_ROW * nb, false}};
 }
@@ -990,22 +992,55 @@ int minimize_run(gamd_handle* h, typename M::Args m, float* x_dev, const uint8_t
     return worst;
 }
 
-// gamd_minimize_lbfgs behind the checks that need no device: minimize_run's order of things — the boxes, every allocation, the look
-// at the frozen flag, init, the evaluations in chunks of check_every with a look at the gates behind each (pass max_iter stops
-// every box that still runs), x, the force source's own kernels on exactly that x, f, the rows.
-int lbfgs_run(gamd_handle* h, float* x_dev, const float* box, double len, float* f_dev, double* x64_dev, const gamd_lbfgs_params& q,
-              double* rows_host, void* stream) {
+// What an L-BFGS minimiser supplies besides the potential it builds on, as LjMinimizer and WaterMinimizer do for FIRE: its name,
+// its argument block (the potential's, the L-BFGS members — the same names in both — and what is its own, which its entry point
+// fills), the columns of its block row, its launchers, the code a frozen handle is refused with, and whether the caller's x64 is
+// a copy behind the run (LJ) or written by its store-x kernel (water).
+struct LjLbfgs {
     using P = LjPotential;
+    using Args = LbfgsArgs;
     static constexpr const char* api = "gamd_minimize_lbfgs";
+    enum { FROZEN_CODE = -1, COPY_X64 = 1, ACC = LBFGS_ACC };
+    static P::Args& potential(Args& l) { return l.c; }
+    static int init(const Args& l, const float* x, hipStream_t st) { return launch_lbfgs_init(l, x, st); }
+    static int eval(const gamd_handle* h, const Args& l, hipStream_t st) {
+        CellTabBufs b;
+        return launch_lbfgs_eval(l, st, P::cell_bufs(h, b));
+    }
+    static int store_x(const Args& l, const int* gates, float* x, double*, hipStream_t st) { return launch_lbfgs_store_x(l, gates, x, st); }
+};
+
+struct WaterLbfgs {
+    using P = WaterPotential;
+    using Args = WLbfgsArgs;
+    static constexpr const char* api = "gamd_water_minimize_lbfgs";
+    enum { FROZEN_CODE = -22, COPY_X64 = 0, ACC = WLB_ACC };
+    static P::Args& potential(Args& l) { return l.w; }
+    static int init(const Args& l, const float* x, hipStream_t st) { return launch_wlbfgs_init(l, x, st); }
+    static int eval(const gamd_handle*, const Args& l, hipStream_t st) { return launch_wlbfgs_eval(l, st); }
+    static int store_x(const Args& l, const int* gates, float* x, double* x64_out, hipStream_t st) {
+        return launch_wlbfgs_store_x(l, gates, x, x64_out, st);
+    }
+};
+
+// An L-BFGS entry behind the checks that need no device: minimize_run's order of things — the boxes, every allocation, the look
+// at the frozen flag, init, the evaluations in chunks of check_every with a look at the gates behind each (pass max_iter stops
+// every box that still runs), x (and the water minimiser's x64), the force source's own kernels on exactly that x, f, the rows.
+// `l` arrives with what is the minimiser's own filled in.
+template <typename M>
+int lbfgs_run(gamd_handle* h, typename M::Args l, float* x_dev, const uint8_t* species_dev, const float* box, double len, float* f_dev,
+              double* x64_dev, const gamd_lbfgs_params& q, double* rows_host, void* stream) {
+    using P = typename M::P;
+    static constexpr const char* api = M::api;
     if (!x_dev || !f_dev || !box) return fail(-22, "null argument");
     if (int r = check_box_positive(h, box)) return r;
-    if (int r = P::check_box(h, box, nullptr)) return r;
+    if (int r = P::check_box(h, box, species_dev)) return r;
     PotentialLog& pl = P::state(h);
     DeviceGuard guard(h->dev);
     hipStream_t st = (hipStream_t)stream;
     InitStream init(st);
     // every allocation in front of the first enqueue
-    if (bufs_ensure_work(P::bufs(h)) || bufs_ensure_work(lbfgs_bufs(h, q.m))) return fail(-12, "%s: allocation failed", api);
+    if (bufs_ensure_work(P::bufs(h)) || bufs_ensure_work(lbfgs_bufs(h, q.m, M::ACC))) return fail(-12, "%s: allocation failed", api);
     const size_t nb = (size_t)h->n_boxes, n3 = 3 * (size_t)h->n;
     std::vector<int> gates(nb, 0);
     std::vector<double> rows(LBFGS_ROW * nb, 0.0);
@@ -1014,39 +1049,38 @@ int lbfgs_run(gamd_handle* h, float* x_dev, const float* box, double len, float*
     int frozen = 0;
     HIP_TRY(hipMemcpyAsync(&frozen, h->devflags.as<int>() + DEVFLAG_FROZEN, sizeof(int), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    if (frozen) return fail(-1, "%s: the handle is frozen by a neighbour-buffer overflow (call gamd_sync_status)", api);
+    if (frozen) return fail(M::FROZEN_CODE, "%s: the handle is frozen by a neighbour-buffer overflow (call gamd_sync_status)", api);
     Lbfgs& lb = h->obs->lb;
-    LbfgsArgs l{};
-    l.c = P::args(h, len);
-    l.c.box_edges = pl.eval_box.as<float>();
+    typename P::Args& a = M::potential(l);
+    a = P::args(h, len);
+    a.box_edges = pl.eval_box.template as<float>();
+    P::species(a, species_dev);
     l.x = lb.x.as<double>(); l.xt = lb.xt.as<double>(); l.f = lb.f.as<double>(); l.ft = lb.ft.as<double>(); l.d = lb.d.as<double>();
     l.ring = lb.ring.as<double>(); l.blk = lb.blk.as<double>(); l.state = lb.state.as<double>(); l.gates = lb.gates.as<int>();
     l.rows = lb.rows.as<double>(); l.sticky = h->sticky_dev;
     l.tol = q.tolerance; l.max_step = q.max_step; l.c1 = q.c1; l.curv = q.curv; l.m = q.m; l.max_ls = q.max_ls; l.max_iter = q.max_iter;
     int r;
-    if ((r = launch_lbfgs_init(l, x_dev, st))) return fail(-1, "%s launch failed (%d)", api, r);
-    CellTabBufs cb;
-    const CellTabBufs* cells = P::cell_bufs(h, cb);
+    if ((r = M::init(l, x_dev, st))) return fail(-1, "%s launch failed (%d)", api, r);
     bool all_stopped = false;
     while (l.it <= q.max_iter && !all_stopped) {            // pass 0 is the start's, pass k evaluation k
         const long long chunk = std::min<long long>(q.check_every, q.max_iter + 1 - l.it);
         for (long long k = 0; k < chunk; ++k, ++l.it)
-            if ((r = launch_lbfgs_eval(l, st, cells))) return fail(-1, "%s launch failed (%d)", api, r);
+            if ((r = M::eval(h, l, st))) return fail(-1, "%s launch failed (%d)", api, r);
         HIP_TRY(hipMemcpyAsync(gates.data(), lb.gates.as<int>() + (size_t)(l.it & 1) * nb, sizeof(int) * nb, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         all_stopped = std::all_of(gates.begin(), gates.end(), [](int s) { return s != 0; });
     }
     const int* gates_dev = lb.gates.as<int>() + (size_t)(l.it & 1) * nb;    // the set the last pass wrote
-    // x, then the force source's own kernels on exactly that x
-    if ((r = launch_lbfgs_store_x(l, gates_dev, x_dev, st))) return fail(-1, "%s launch failed (%d)", api, r);
-    ClassicalArgs drive = l.c;
+    // x (and the water minimiser's x64), then the force source's own kernels on exactly that x
+    if ((r = M::store_x(l, gates_dev, x_dev, x64_dev, st))) return fail(-1, "%s launch failed (%d)", api, r);
+    typename P::Args drive = a;
     drive.x = x_dev;
     if ((r = P::drive(h, drive, lb.f32.as<float>(), st))) return fail(-1, "%s launch failed (%d)", api, r);
     pl.evaluated = true;
     FireArgs gate{};                                        // launch_minimize_store_f reads the gates alone: 1 + GAMD_MIN_FAILED is 1 + GAMD_LBFGS_FAILED
     gate.stopped = const_cast<int*>(gates_dev);
-    if ((r = launch_minimize_store_f(gate, l.c.n, l.c.bx, lb.f32.as<float>(), f_dev, st))) return fail(-1, "%s launch failed (%d)", api, r);
-    if (x64_dev) HIP_TRY(hipMemcpyAsync(x64_dev, lb.x.p, sizeof(double) * n3, hipMemcpyDeviceToDevice, st));
+    if ((r = launch_minimize_store_f(gate, a.n, a.bx, lb.f32.as<float>(), f_dev, st))) return fail(-1, "%s launch failed (%d)", api, r);
+    if (M::COPY_X64 && x64_dev) HIP_TRY(hipMemcpyAsync(x64_dev, lb.x.p, sizeof(double) * n3, hipMemcpyDeviceToDevice, st));
     HIP_TRY(hipMemcpyAsync(rows.data(), lb.rows.p, sizeof(double) * rows.size(), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     if (int t = check_traps(h)) return t;
@@ -1054,6 +1088,38 @@ int lbfgs_run(gamd_handle* h, float* x_dev, const float* box, double len, float*
     int worst = 0;
     for (size_t b = 0; b < nb; ++b) worst = std::max(worst, (int)rows[LBFGS_ROW * b]);
     return worst;
+}
+
+// What the two water minimisers refuse behind their parameter blocks and in front of the device, under the name of the entry:
+// the geometry (0 = TIP3P, scaled by the unit), the handle's kind, the molecules, the potential's parameters, a pending run and
+// the three forms of the potential that have no minimiser.  On 0 the unit-weight canonical triangle of SETTLE is in ra, rb, rc.
+int water_minimize_checks(const char* api, gamd_handle* h, double len, double r_oh, double r_hh, double* ra, double* rb, double* rc) {
+    if (!(r_oh >= 0.0) || !(r_hh >= 0.0) || !std::isfinite(r_oh) || !std::isfinite(r_hh))
+        return fail(-22, "%s: r_oh = %g, r_hh = %g: a length is not positive", api, r_oh, r_hh);
+    if (r_oh == 0.0) r_oh = 0.9572 * (len / 10.0);          // TIP3P, as the md parameter blocks document it
+    if (r_hh == 0.0) r_hh = (2.0 * 0.9572 * std::sin(0.5 * 104.52 * (3.141592653589793 / 180.0))) * (len / 10.0);    // 1.5139 A
+    if (!(r_hh < 2.0 * r_oh)) return fail(-22, "%s: r_hh = %g is not below 2 r_oh = %g: no such triangle", api, r_hh, 2.0 * r_oh);
+    if (!h) return fail(-22, "null handle");
+    if (h->cfg.kind != GAMD_KIND_WATER)
+        return fail(-22, "%s: a GAMD_KIND_LJ handle has no molecules and no charges (GAMD_KIND_WATER handles only; "
+                         "gamd_minimize relaxes Lennard-Jones boxes)", api);
+    if (h->n_per_box % 3) return fail(-22, "%s: n_atoms = %d per box is not a multiple of 3 (atoms ordered O,H,H)", api, h->n_per_box);
+    WaterClassical& wc = WaterPotential::state(h);
+    if (!wc.params_set) return fail(-22, "%s needs the parameters of a gamd_water_configure call (interval 0 will do)", api);
+    if (h->pending.active) return fail(-22, "an MD run is still enqueued: call gamd_sync_status before %s", api);
+    if (wc.w_h != 0.0)
+        return fail(-22, "%s: the TIP4P M-site is set (gamd_water_msite, w_h = %.9g) and there is no 4-site rigid minimiser: "
+                         "minimise with w_h = 0, set the weight, then take f from gamd_water_eval", api, wc.w_h);
+    if (wc.pme_order)
+        return fail(-22, "%s: particle-mesh Ewald is on (gamd_water_pme, order %d) and there is no PME minimiser: "
+                         "minimise under the plain sum, switch PME on, then take f from gamd_water_eval", api, wc.pme_order);
+    if (wc.cells)
+        return fail(-22, "%s: the cell table is on (gamd_water_cells) and the minimiser's f is the all-pairs force bit for "
+                         "bit: minimise with the cells off, switch them on, then take f from gamd_water_eval", api);
+    *rc = 0.5 * r_hh;
+    const double t = std::sqrt(r_oh * r_oh - *rc * *rc);
+    *ra = (2.0 * t) / 3.0; *rb = t / 3.0;
+    return 0;
 }
 
 // one of each +-n with 0 < |n|^2 <= n2max (the one whose first non-zero component is positive), sorted by (|n|^2, nx, ny, nz)
@@ -1084,7 +1150,7 @@ void observers_free(gamd_handle* h) {
     for (const Observer& ob : observer_list(h))
         for (const ObsBuf& b : ob.bufs(h)) b.buf->release();
     for (const ObsBuf& b : minimize_bufs(h)) b.buf->release();
-    for (const ObsBuf& b : lbfgs_bufs(h, 0)) b.buf->release();
+    for (const ObsBuf& b : lbfgs_bufs(h, 0, 0)) b.buf->release();
     delete h->obs; h->obs = nullptr;
 }
 
@@ -1474,7 +1540,7 @@ int32_t gamd_minimize_lbfgs(gamd_handle* h, float* x_dev, const float* box, floa
     Classical& cl = LjPotential::state(h);
     if (!cl.params_set) return fail(-22, "gamd_minimize_lbfgs needs the parameters of a gamd_classical_configure call (interval 0 will do)");
     if (h->pending.active) return fail(-22, "an MD run is still enqueued: call gamd_sync_status before gamd_minimize_lbfgs");
-    return lbfgs_run(h, x_dev, box, length_per_nm > 0.f ? (double)length_per_nm : 10.0, f_dev, x64_dev, q, rows_host, stream);
+    return lbfgs_run<LjLbfgs>(h, LbfgsArgs{}, x_dev, nullptr, box, length_per_nm > 0.f ? (double)length_per_nm : 10.0, f_dev, x64_dev, q, rows_host, stream);
 }
 
 int32_t gamd_water_configure(gamd_handle* h, const gamd_water_params* p) {
@@ -1692,33 +1758,21 @@ int32_t gamd_water_minimize(gamd_handle* h, float* x_dev, const uint8_t* species
     gamd_minimize_params q;
     if (int r = minimize_fill_params(params, &q, g_err, sizeof(g_err))) return r;
     const double len = length_per_nm > 0.f ? (double)length_per_nm : 10.0;
-    if (!(r_oh >= 0.0) || !(r_hh >= 0.0) || !std::isfinite(r_oh) || !std::isfinite(r_hh))
-        return fail(-22, "gamd_water_minimize: r_oh = %g, r_hh = %g: a length is not positive", r_oh, r_hh);
-    if (r_oh == 0.0) r_oh = 0.9572 * (len / 10.0);          // TIP3P, as the md parameter blocks document it
-    if (r_hh == 0.0) r_hh = (2.0 * 0.9572 * std::sin(0.5 * 104.52 * (3.141592653589793 / 180.0))) * (len / 10.0);    // 1.5139 A
-    if (!(r_hh < 2.0 * r_oh)) return fail(-22, "gamd_water_minimize: r_hh = %g is not below 2 r_oh = %g: no such triangle", r_hh, 2.0 * r_oh);
-    if (!h) return fail(-22, "null handle");
-    if (h->cfg.kind != GAMD_KIND_WATER)
-        return fail(-22, "gamd_water_minimize: a GAMD_KIND_LJ handle has no molecules and no charges (GAMD_KIND_WATER handles only; "
-                         "gamd_minimize relaxes Lennard-Jones boxes)");
-    if (h->n_per_box % 3) return fail(-22, "gamd_water_minimize: n_atoms = %d per box is not a multiple of 3 (atoms ordered O,H,H)", h->n_per_box);
-    WaterClassical& wc = WaterPotential::state(h);
-    if (!wc.params_set) return fail(-22, "gamd_water_minimize needs the parameters of a gamd_water_configure call (interval 0 will do)");
-    if (h->pending.active) return fail(-22, "an MD run is still enqueued: call gamd_sync_status before gamd_water_minimize");
-    if (wc.w_h != 0.0)
-        return fail(-22, "gamd_water_minimize: the TIP4P M-site is set (gamd_water_msite, w_h = %.9g) and there is no 4-site rigid minimiser: "
-                         "minimise with w_h = 0, set the weight, then take f from gamd_water_eval", wc.w_h);
-    if (wc.pme_order)
-        return fail(-22, "gamd_water_minimize: particle-mesh Ewald is on (gamd_water_pme, order %d) and there is no PME minimiser: "
-                         "minimise under the plain sum, switch PME on, then take f from gamd_water_eval", wc.pme_order);
-    if (wc.cells)
-        return fail(-22, "gamd_water_minimize: the cell table is on (gamd_water_cells) and the minimiser's f is the all-pairs force bit for "
-                         "bit: minimise with the cells off, switch them on, then take f from gamd_water_eval");
     WMinArgs m{};
-    m.rc = 0.5 * r_hh;
-    const double t = std::sqrt(r_oh * r_oh - m.rc * m.rc);
-    m.ra = (2.0 * t) / 3.0; m.rb = t / 3.0;
+    if (int r = water_minimize_checks("gamd_water_minimize", h, len, r_oh, r_hh, &m.ra, &m.rb, &m.rc)) return r;
     return minimize_run<WaterMinimizer>(h, m, x_dev, species_dev, box, len, f_dev, x64_dev, q, rows_host, stream);
+}
+
+int32_t gamd_water_minimize_lbfgs(gamd_handle* h, float* x_dev, const uint8_t* species_dev, const float* box, float length_per_nm,
+                                  double r_oh, double r_hh, float* f_dev, double* x64_dev, const gamd_lbfgs_params* params,
+                                  double* rows_host, void* stream) {
+    // the parameter block is checked first: these answers need no device
+    gamd_lbfgs_params q;
+    if (int r = lbfgs_fill_params(params, &q, g_err, sizeof(g_err), "gamd_water_minimize_lbfgs")) return r;
+    const double len = length_per_nm > 0.f ? (double)length_per_nm : 10.0;
+    WLbfgsArgs l{};
+    if (int r = water_minimize_checks("gamd_water_minimize_lbfgs", h, len, r_oh, r_hh, &l.ra, &l.rb, &l.rc)) return r;
+    return lbfgs_run<WaterLbfgs>(h, l, x_dev, species_dev, box, len, f_dev, x64_dev, q, rows_host, stream);
 }
 
 }  // extern "C"

@@ -26,6 +26,8 @@
 //                   FIRE's mixing on F_c, v += dt F_c, dr = dt v, ONE factor per molecule so that the largest |dr| of its
 //                   three atoms is at most max_step, and x64 <- SETTLE(reference x64, new x64 + dr).
 //
+// launch_wmin_force enqueues the first four alone, on the positions and under the gate of the argument block it is handed: the
+// water L-BFGS minimiser (water_lbfgs.hip) evaluates its trial positions through it.
 // Scalar state, the two slots per box, the `stopped` gate and the rows are minimize.hip's.  Fixed assignment, no floating-point
 // atomics, contraction off, plain stores: the same bits run after run, and a box gets the bits it gets alone.
 // (No kernel uses a value it read from memory as an address: the checked build has nothing to range-check here.)
@@ -305,33 +307,36 @@ __global__ void __launch_bounds__(256) k_wmin_store_x(WMinArgs m, float* __restr
         return;
     }
 #pragma unroll
-    for (int d = 0; d < 3; ++d) {
-        const double L = gamd_box_edge(a, box, d);
-        const float Lf = (float)L;                          // exact: the edge is an fp32 value
-        const double xo = m.fire.x64[9 * mol + d];
-        double s = L * floor(xo / L);
-        if (xo - s < 0.0) s = s - L;                        // the quotient rounded up to an integer
-        if ((float)(xo - s) >= Lf) s = s + L;               // the oxygen rounds up to L: it goes to 0 with its hydrogens
-        float o = (float)(xo - s);
-        if (o < 0.f) o = 0.f;
-        x_io[9 * mol + d] = o;
-        x_io[9 * mol + 3 + d] = (float)(m.fire.x64[9 * mol + 3 + d] - s);
-        x_io[9 * mol + 6 + d] = (float)(m.fire.x64[9 * mol + 6 + d] - s);
-        if (x64_out) {
-            x64_out[9 * mol + d] = xo; x64_out[9 * mol + 3 + d] = m.fire.x64[9 * mol + 3 + d]; x64_out[9 * mol + 6 + d] = m.fire.x64[9 * mol + 6 + d];
-        }
-    }
+    for (int d = 0; d < 3; ++d) store_wrapped(m.fire.x64, mol, d, gamd_box_edge(a, box, d), x_io, x64_out);
 }
 
-// what every launcher checks: the geometry covers a row and the grids stay inside their limits, every buffer is there
-int wmin_check(const WMinArgs& m, PassGeom* g, long long* mol_tiles) {
+// what the force launches need: the geometry covers a row and the grids stay inside their limits, the potential's buffers, the
+// positions and the gate are there
+int wmin_force_check(const WMinArgs& m, PassGeom* g) {
     const WaterArgs& a = m.w;
-    const FireArgs& fi = m.fire;
     if (pass_geometry(a, 3, g) || pass_k_geometry(a, g->T, false) || a.blocks < 1 || a.blocks > 65535) return -1;
     if (!a.species || !a.kvec || !a.part || !a.rho_partial || !a.sk || !a.ublk || !a.rpart || !a.blk || !a.box_edges || !a.devflags) return -1;
+    if (!m.fire.x64 || !m.fire.stopped) return -1;
+    return 0;
+}
+
+// what every launcher of the minimiser checks: that, and every buffer of FIRE's
+int wmin_check(const WMinArgs& m, PassGeom* g, long long* mol_tiles) {
+    const FireArgs& fi = m.fire;
+    if (wmin_force_check(m, g)) return -1;
     if (!fi.x64 || !fi.v64 || !fi.f64 || !fi.state || !fi.stopped || !fi.rows || fi.it < 0) return -1;
     if (!(m.ra > 0.0) || !(m.rb > 0.0) || !(m.rc > 0.0)) return -1;
     *mol_tiles = (g->npb / 3 + GAMD_PASS_TILE - 1) / GAMD_PASS_TILE;
+    return 0;
+}
+
+// pairs; rho, sk, recip
+int wmin_force(const WMinArgs& m, const PassGeom& g, hipStream_t st) {
+    const WaterArgs& a = m.w;
+    hipLaunchKernelGGL(k_wmin_pairs, dim3((unsigned)(g.T * a.slices), g.nb), dim3(256), 0, st, m); GAMD_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_wmin_rho, dim3(a.rho_blocks, (a.n_k + 63) / 64, g.nb), dim3(256), 0, st, m); GAMD_CHECK_LAUNCH();
+    if (int r = launch_water_sk(a, st)) return r;
+    hipLaunchKernelGGL(k_wmin_recip, dim3((unsigned)(g.T * a.kslices), g.nb), dim3(256), 0, st, m); GAMD_CHECK_LAUNCH();
     return 0;
 }
 
@@ -348,13 +353,16 @@ int launch_wmin_iter(const WMinArgs& m, hipStream_t st) {
     PassGeom g; long long M;
     if (wmin_check(m, &g, &M)) return -1;
     const WaterArgs& a = m.w;
-    hipLaunchKernelGGL(k_wmin_pairs, dim3((unsigned)(g.T * a.slices), g.nb), dim3(256), 0, st, m); GAMD_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_wmin_rho, dim3(a.rho_blocks, (a.n_k + 63) / 64, g.nb), dim3(256), 0, st, m); GAMD_CHECK_LAUNCH();
-    if (int r = launch_water_sk(a, st)) return r;
-    hipLaunchKernelGGL(k_wmin_recip, dim3((unsigned)(g.T * a.kslices), g.nb), dim3(256), 0, st, m); GAMD_CHECK_LAUNCH();
+    if (int r = wmin_force(m, g, st)) return r;
     hipLaunchKernelGGL(k_wmin_mols, dim3(a.blocks, g.nb), dim3(256), 0, st, m); GAMD_CHECK_LAUNCH();
     hipLaunchKernelGGL(k_wmin_update, dim3((unsigned)M, g.nb), dim3(256), 0, st, m); GAMD_CHECK_LAUNCH();
     return 0;
+}
+
+int launch_wmin_force(const WMinArgs& m, hipStream_t st) {
+    PassGeom g;
+    if (wmin_force_check(m, &g)) return -1;
+    return wmin_force(m, g, st);
 }
 
 int launch_wmin_store_x(const WMinArgs& m, float* x_io, double* x64_out, hipStream_t st) {

@@ -1482,14 +1482,7 @@ class GamdForce:
         if f is None:
             f = torch.zeros_like(x)
         self._md_state(x, f)
-        flags = None
-        if species is not None:
-            s = torch.as_tensor(species).reshape(-1).to(device=self.device)
-            if s.numel() == self.n and self.n_boxes > 1:
-                s = s.repeat(self.n_boxes)
-            if s.numel() != self.n_total:
-                raise ValueError("species must have one entry per atom")
-            flags = (s != 0).to(torch.uint8).contiguous()
+        flags = self._water_flags(species)
         unit = float(np.float32(length_per_nm)) / 10.0 if length_per_nm else 1.0     # the fp32 value the library holds
         from . import workloads as wl
         r_oh = float(r_oh) if r_oh else wl.TIP3P_R_OH * unit
@@ -1504,6 +1497,55 @@ class GamdForce:
                                                  C.c_void_p(x64.data_ptr()) if return_x64 else None, C.byref(p),
                                                  rows.ctypes.data_as(C.c_void_p), self._stream()), "gamd_water_minimize")
         return MinimizeResult(st, rows, x, f, x64)
+
+    def _water_flags(self, species):
+        if species is None:
+            return None
+        s = torch.as_tensor(species).reshape(-1).to(device=self.device)
+        if s.numel() == self.n and self.n_boxes > 1:
+            s = s.repeat(self.n_boxes)
+        if s.numel() != self.n_total:
+            raise ValueError("species must have one entry per atom")
+        return (s != 0).to(torch.uint8).contiguous()
+
+    def water_minimize_lbfgs(self, x: torch.Tensor, species, f: Optional[torch.Tensor] = None, tolerance: float = 10.0, max_iter: int = 0,
+                             box=None, length_per_nm: float = 0.0, r_oh: float = 0.0, r_hh: float = 0.0, return_x64: bool = False,
+                             check_every: int = 0, m: int = 0, c1: float = 0.0, curv: float = 0.0, max_ls: int = 0,
+                             max_step: float = 0.0) -> "LbfgsResult":
+        """``water_minimize`` with L-BFGS in place of FIRE: the same task, arguments and results (``x`` changed in place:
+        molecules whole, every oxygen in [0, L); ``f`` the classical forces at exactly that ``x``,
+        ``water_classical_forces(x, species)[0].float()`` bit for bit; ``result.x64`` exactly rigid; a failed box keeps its
+        ``x`` and ``f``), with the algorithm, constants and result of ``minimize_lbfgs``: a history of ``m`` pairs, a
+        backtracking line search on sufficient decrease (``c1``, ``max_ls``), one clamp factor per molecule so that no atom's
+        trial displacement exceeds ``max_step`` in front of SETTLE, ``max_iter`` evaluations at most.  The iterate stays on
+        the manifold of rigid molecules: the force is projected onto the tangent space of the bond constraints (unit
+        weights), SETTLE carries every trial back, and the history is used without vector transport.  ``rms`` and ``fmax``
+        are of the projected force.  tests/water_lbfgs_ref.py is the recipe in float64; no parity with OpenMM is claimed.
+
+        The DEFAULT Lennard-Jones term of ``water_classical_configure`` is cut at ``r_cut`` without a switch or a shift, so U
+        jumps (about 0.03 kJ/mol at r_cut = 6.5 Angstrom) when an O-O pair crosses the cutoff, and the sufficient-decrease
+        test cannot pass such a jump once the steps gain less than that: on the default potential the call stops as
+        "line_search" somewhere below a tolerance of about 1.  For tolerances below about 1 configure the potential with
+        ``r_switch`` > 0 or ``shift=True``.  Water models only, 3-site, plain Ewald sum, all pairs: with ``m_site``, ``pme``
+        or ``cells`` in force it raises (-22, naming the reason) before anything is enqueued.  Synchronises."""
+        if not getattr(self, "_water_set", False):
+            self.water_classical_configure(0, length_per_nm=length_per_nm)
+        if f is None:
+            f = torch.zeros_like(x)
+        self._md_state(x, f)
+        flags = self._water_flags(species)
+        unit = float(np.float32(length_per_nm)) / 10.0 if length_per_nm else 1.0     # the fp32 value the library holds
+        from . import workloads as wl
+        r_oh = float(r_oh) if r_oh else wl.TIP3P_R_OH * unit
+        r_hh = float(r_hh) if r_hh else wl.TIP3P_R_HH * unit
+        x64 = torch.empty((self.n_total, 3), dtype=torch.float64, device=self.device) if return_x64 else None
+        p = GamdLbfgsParams(float(tolerance), int(max_iter), int(check_every), float(max_step), float(c1), float(curv), int(m), int(max_ls), 0)
+        rows = np.zeros((self.n_boxes, _lib.LBFGS_ROW), dtype=np.float64)
+        st = check(self._lib.gamd_water_minimize_lbfgs(self._h, C.c_void_p(x.data_ptr()), C.c_void_p(flags.data_ptr()) if flags is not None else None,
+                                                       self._box_arg(box), float(length_per_nm), r_oh, r_hh, C.c_void_p(f.data_ptr()),
+                                                       C.c_void_p(x64.data_ptr()) if return_x64 else None, C.byref(p),
+                                                       rows.ctypes.data_as(C.c_void_p), self._stream()), "gamd_water_minimize_lbfgs")
+        return LbfgsResult(st, rows, x, f, x64)
 
     def sync_status(self) -> int:
         """0, or 1 when an enqueued MD run overflowed a neighbour buffer, froze on the device and was resumed."""

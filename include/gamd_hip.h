@@ -924,6 +924,59 @@ int32_t gamd_water_minimize(gamd_handle* h, float* x_dev, const uint8_t* species
                             double r_oh, double r_hh, float* f_dev, double* x64_dev, const gamd_minimize_params* params,
                             double* rows_host, void* stream);
 
+/* L-BFGS energy minimiser for rigid 3-site water: gamd_water_minimize's task, arguments, return tail and f contract with
+ * gamd_minimize_lbfgs's algorithm, parameter block, states and result row, for the tolerances at which FIRE's iteration count is
+ * what costs (one water evaluation is six launches with the pair walk and the Ewald sum).  OpenMM's minimizeEnergy is L-BFGS
+ * too, with the constraints as restraints: NO parity with it is claimed, what is shared is the meaning of the tolerance — the
+ * root mean square over 3N of the components of the PROJECTED force, in kJ/mol/nm.  gamd_water_minimize, gamd_minimize_lbfgs,
+ * their parameter blocks, states and bits are untouched by this entry.
+ * Per box, in double.  Atoms O,H,H, molecule = index / 3, r_oh, r_hh and the UNIT weights of all constraint arithmetic as for
+ * gamd_water_minimize; the iterate lives on the manifold of rigid molecules, SETTLE is the retraction onto it.
+ *   0. x = the fp32 input widened, then every molecule put on the exact geometry by SETTLE with reference = new = the input.
+ *   1. U and the raw force at x exactly as step 1 of gamd_water_minimize gives them; F is the raw force projected onto the
+ *      tangent space of the three bond constraints at x (gamd_water_minimize's F_c), rms = sqrt(F.F / 3N).  U or F.F not
+ *      finite: the box stops as GAMD_LBFGS_FAILED and keeps the x it was given.  rms <= tolerance: GAMD_LBFGS_CONVERGED with
+ *      0 evaluations.
+ *   2. The direction d.  Empty history: d = F max_step / max_i |F_i| (the largest per-atom norm).  Otherwise d = H F by the
+ *      two-loop recursion over the ring with H0 = s.y / y.y of the newest pair.  The trial factor t = 1.
+ *   3. The trial: s = t d; per MOLECULE one factor max_step / max_k |s_k| where the largest |s_k| of its three atoms exceeds
+ *      max_step (gamd_water_minimize's clamp); x_t = SETTLE(reference x, new x + s).  From here on s is x_t - x as the doubles
+ *      give it: it includes SETTLE's second-order correction, so a per-atom |s| may exceed max_step by that correction.  A
+ *      molecule SETTLE cannot place makes x_t, and with it U_t and F.s, not finite: the trial is rejected, and F.s counts as
+ *      not positive in step 5.
+ *   4. U_t and F_t at x_t, F_t projected at x_t: one evaluation, counted whatever follows.
+ *   5. The trial is accepted iff F.s > 0, U_t is finite and U_t <= U - c1 F.s.  F is tangent at x, so F.s is the directional
+ *      derivative along the retraction to first order.  Rejected: t / 2, max_ls, the reset and the GAMD_LBFGS_LINE_SEARCH stop
+ *      exactly as step 5 of gamd_minimize_lbfgs.
+ *   6. Accepted: y = F - F_t, each projected at its own point; the push test, x = x_t, F = F_t, U = U_t, the stop tests and
+ *      GAMD_LBFGS_MAX_ITER exactly as steps 6 and 7 of gamd_minimize_lbfgs.  The ring's vectors are used AS STORED: there is
+ *      no vector transport of s and y to the tangent space of the new point.  d is then not exactly tangent at x; SETTLE
+ *      removes the normal part of the step, and the sufficient-decrease test guards descent.
+ * The DEFAULT Lennard-Jones term of gamd_water_configure is truncated at r_cut without a switch or a shift: U jumps by about
+ * 0.03 kJ/mol when an O-O pair crosses r_cut = 6.5 A, and a sufficient-decrease test cannot pass such a jump once the steps
+ * gain less than that.  On the default potential the search therefore stops as GAMD_LBFGS_LINE_SEARCH somewhere below a
+ * tolerance of about 1 (FIRE never looks at U and does not notice): TOLERANCES BELOW ABOUT 1 NEED r_switch > 0 OR shift = 1.
+ * One evaluation is six launches whatever m is: the four force launches of gamd_water_minimize on x_t, one per-molecule pass
+ * that projects F_t and forms every inner product, one pass that decides, runs the recursion on the inner products alone and
+ * forms the next trial with SETTLE.  Everything is in double with fixed summation orders, no floating-point atomics and no
+ * contraction: the same bits run after run, whatever check_every is, and every box of a handle gets the bits it gets alone.  A
+ * box that stopped is skipped on the device; nothing is allocated between the first and the last enqueue.
+ * tests/water_lbfgs_ref.py is this recipe in float64 on the host.
+ * On return (the stream is synchronised) x_dev (molecules whole, the oxygen in [0, L) by gamd_water_minimize's wrap), f_dev (bit
+ * for bit the fp32 rounding of gamd_water_eval's forces on x_dev, by the water force source's own kernels) and x64_dev (exactly
+ * rigid; the input widened for a failed box) are as gamd_water_minimize leaves them.  Nothing is written for a box that failed.
+ *   rows_host    double [n_boxes][GAMD_LBFGS_ROW] HOST or NULL: gamd_minimize_lbfgs's row; the forces in it are F_c, and fmax is
+ *                the largest per-atom |F_c,i|.
+ * Returns 0 / 1 / 2 / 3 as gamd_minimize_lbfgs, the largest wins.  -22, with a message naming the reason, before anything is
+ * enqueued: what gamd_minimize_lbfgs refuses in the parameter block, and everything gamd_water_minimize refuses — a set M-site
+ * (gamd_water_msite), particle-mesh Ewald on (gamd_water_pme) and the cell table on (gamd_water_cells) among them, which have
+ * no minimiser here either — a frozen handle included.  -12 when an allocation fails.
+ * Device memory besides the water classical observer's work buffers: 24 (2 m + 5) + 12 B per atom, the ring sized for the
+ * largest m a call has asked for (x, x_t, F, F_t, d and the ring in double, the fp32 force). */
+int32_t gamd_water_minimize_lbfgs(gamd_handle* h, float* x_dev, const uint8_t* species_dev, const float* box, float length_per_nm,
+                                  double r_oh, double r_hh, float* f_dev, double* x64_dev, const gamd_lbfgs_params* params,
+                                  double* rows_host, void* stream);
+
 /* Event-timed replay of one force evaluation: per-kernel milliseconds of the last gamd_profile call.
  * names: newline-separated kernel labels; ms: one float per label.  For bench.py's roofline block. */
 int32_t gamd_profile(gamd_handle* h, const float* pos_dev, const uint8_t* species_dev, const float* box,

@@ -4,7 +4,7 @@ classical force that logs PE / KE / total energy every 50 steps and writes data_
 such a run costs.
 
     python tools/water_ground_truth.py [--workloads w774 c3] [--steps 200] [--interval 50] [--frames 4] [--dt-fs 2.0]
-                                       [--energy-ps 1.0] [--ewald-tol 1e-8] [--minimize-tolerance 10] [--relax-steps 0] [--seed 0]
+                                       [--energy-ps 1.0] [--ewald-tol 1e-8] [--minimize-tolerance 10] [--lbfgs] [--relax-steps 0] [--seed 0]
                                        [--m-site W] [--out DIR]
 
 For a seeded box of rigid 3-site water (w774: 258 molecules = 774 atoms, the generator's 2 nm box; c3: 1 390 molecules = 4 170
@@ -22,7 +22,9 @@ atoms) on one handle in skin mode, as bench.py runs the water workloads, each wo
 The start is the workload's lattice box (wl.water_box: whole rigid molecules on a cubic lattice, random orientations).  Left
 alone, the lattice releases about 20 kJ/mol per molecule and heats a 300 K start past 1 000 K within 0.4 ps; so, as the
 generator's minimizeEnergy (:85) does, step 0 minimises it on the device first: GamdForce.water_minimize to
---minimize-tolerance kJ/mol/nm (rigid-molecule FIRE, not OpenMM's L-BFGS; 0: not minimised).  The earlier stand-in stays
+--minimize-tolerance kJ/mol/nm (rigid-molecule FIRE, not OpenMM's L-BFGS; 0: not minimised), or with --lbfgs
+GamdForce.water_minimize_lbfgs (this library's own L-BFGS on rigid molecules; "iterations" are then its evaluations, and
+tolerances below about 1 need a switched or shifted Lennard-Jones term).  The earlier stand-in stays
 available: --relax-steps steps of a strongly damped water-classical Langevin run at 300 K (--relax-dt-fs, --relax-gamma;
 0 steps, the default: none), behind the minimiser when both are on.  Everything below starts from the end of step 0.  The
 potential is the plain Ewald sum of
@@ -126,10 +128,13 @@ def _one(args, w, out_dir):
     # 0. the generator's minimizeEnergy: the lattice minimised on the device ...
     if args.minimize_tolerance > 0:
         x = x0.clone()
-        m = eng.water_minimize(x, species, tolerance=args.minimize_tolerance, r_oh=md["r_oh"], r_hh=md["r_hh"])
-        res["minimize"] = dict(tolerance=args.minimize_tolerance, state=m.state[0], iterations=int(m.iterations[0]), u0=float(m.energy_start[0]),
-                               u=float(m.energy[0]), rms0=float(m.rms_start[0]), rms=float(m.rms[0]))
-        print(f"{w}: lattice minimised to tolerance {args.minimize_tolerance:g} kJ/mol/nm: {m.state[0]} after {int(m.iterations[0])} iterations, "
+        minimise = eng.water_minimize_lbfgs if args.lbfgs else eng.water_minimize
+        m = minimise(x, species, tolerance=args.minimize_tolerance, r_oh=md["r_oh"], r_hh=md["r_hh"])
+        count = int(m.evaluations[0] if args.lbfgs else m.iterations[0])
+        res["minimize"] = dict(tolerance=args.minimize_tolerance, algorithm="lbfgs" if args.lbfgs else "fire", state=m.state[0], iterations=count,
+                               u0=float(m.energy_start[0]), u=float(m.energy[0]), rms0=float(m.rms_start[0]), rms=float(m.rms[0]))
+        print(f"{w}: lattice minimised to tolerance {args.minimize_tolerance:g} kJ/mol/nm: {m.state[0]} after {count} "
+              f"{'evaluations of L-BFGS' if args.lbfgs else 'iterations'}, "
               f"PE {res['minimize']['u0']:.3f} -> {res['minimize']['u']:.3f} kJ/mol, projected rms {res['minimize']['rms0']:.3f} -> {res['minimize']['rms']:.3f}")
         if m.status == 2:
             raise SystemExit(f"{w}: the minimiser failed (the start is not finite)")
@@ -201,6 +206,7 @@ def main():
     ap.add_argument("--ewald-tol", type=float, default=1e-8)
     ap.add_argument("--minimize-tolerance", type=float, default=10.0,
                     help="step 0: GamdForce.water_minimize to this tolerance in kJ/mol/nm (0: the start is not minimised)")
+    ap.add_argument("--lbfgs", action="store_true", help="step 0 with GamdForce.water_minimize_lbfgs in place of water_minimize (FIRE)")
     ap.add_argument("--relax-steps", type=int, default=0,
                     help="water-classical Langevin steps at 300 K in front of everything else, behind the minimiser (0: none)")
     ap.add_argument("--relax-dt-fs", type=float, default=1.0)
@@ -219,7 +225,7 @@ def main():
     for w in args.workloads:                                                # a fresh process per workload; this one opens no GPU
         cmd = [sys.executable, os.path.abspath(__file__), "--only", w, "--out", out_dir] + \
               [a for k in ("steps", "interval", "frames", "dt_fs", "energy_ps", "ewald_tol", "minimize_tolerance", "relax_steps", "relax_dt_fs", "relax_gamma", "m_site", "seed")
-               for a in ("--" + k.replace("_", "-"), str(getattr(args, k)))]
+               for a in ("--" + k.replace("_", "-"), str(getattr(args, k)))] + (["--lbfgs"] if args.lbfgs else [])
         p = subprocess.run(cmd, capture_output=True, text=True)
         sys.stdout.write(p.stdout.split("RESULT ", 1)[0])
         if p.returncode != 0 or "RESULT " not in p.stdout:
