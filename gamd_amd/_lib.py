@@ -152,6 +152,7 @@ SYMBOLS = {
                                    C.POINTER(GamdMinimizeParams), _vp, _vp]),
     "gamd_water_minimize_lbfgs": (_i32, [_vp, _vp, _vp, C.POINTER(C.c_float), C.c_float, C.c_double, C.c_double, _vp, _vp,
                                          C.POINTER(GamdLbfgsParams), _vp, _vp]),
+    "gamd_water_minimize_potential": (_i32, [_vp, _i32]),
     "gamd_profile": (_i32, [_vp, _vp, _vp, C.POINTER(C.c_float), _vp, _vp, C.c_char_p, C.c_size_t,
                             C.POINTER(C.c_float), _i32, C.POINTER(_i32)]),
     "gamd_timing_enable": (_i32, [_vp, _i32]),

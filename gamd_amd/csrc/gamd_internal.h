@@ -794,7 +794,8 @@ int launch_water_pme(const PmeArgs& p, hipStream_t st);
 // k_wsrc_atoms, k_w4_atoms and k_w4_drive run on it as they are.  Six launches on `st`: the table's five, pairs.
 // The first three codes are the builder's chk, chk + 1, chk + 2; the walk checks what it reads under the same ones and _ATOM.
 enum { GAMD_CHK_WCELL_CELL = 151, GAMD_CHK_WCELL_START = 152, GAMD_CHK_WCELL_SLOT = 153, GAMD_CHK_WCELL_ATOM = 154 };
-// nout = WATER_PART (the observer, gamd_water_eval) or 3 (the force source); lj: the O-O term in the walk (3-site), else `sites`
+// nout = WATER_PART (the observer, gamd_water_eval) or 3 (the force source); lj: the O-O term in the walk (3-site: w.x, or
+// `sites` = a minimiser's double positions), else the M-site form on `sites`
 int launch_water_cells(const WaterArgs& w, const CellTabBufs& c, const double* sites, int nout, bool lj, hipStream_t st);
 
 // ---- the pairs of the Lennard-Jones classical potential over a cell table (classical_cells.hip) ------------
@@ -972,3 +973,44 @@ int launch_wlbfgs_eval(const WLbfgsArgs& l, hipStream_t st);
 // x_io = fp32(x) by k_wmin_store_x's wrap and x64_out (may be null) = x, for every box that did not fail (such a box keeps x_io,
 // and x64_out is x_io widened); `gates`: the set the last pass wrote
 int launch_wlbfgs_store_x(const WLbfgsArgs& l, const int* gates, float* x_io, double* x64_out, hipStream_t st);
+
+// ---- the water minimisers under the configured potential (water_relax.hip) -----------------------------
+// gamd_water_minimize_potential: an iteration of gamd_water_minimize or an evaluation of
+// gamd_water_minimize_lbfgs whose force stage follows the three switches of the potential as WaterPotential::drive does, on the
+// minimiser's DOUBLE positions.  The argument blocks arrive as the routed potential leaves them: w.slices = 1 and
+// w.chunk = n_per_box under the cell table, w.kslices = 1 and w.kblocks = pme_blocks under particle-mesh Ewald.
+//   3-site   pairs: k_wmin_pairs, or launch_water_cells on x64 with the O-O term in the walk;
+//            reciprocal: k_wmin_rho, k_water_sk, k_wmin_recip (the strided k walk), or launch_water_pme on x64
+//   M-site   k_wrx_sites; pairs: k_w4_pairs, or launch_water_cells on the sites; k_wrx_lj;
+//            reciprocal: k_w4_rho, k_water_sk, k_w4_recip (the kchunk walk), or launch_water_pme on the sites
+// then k_wrx_mols and k_wmin_update, or k_wrx_lbmols and k_wlb_update.  The k_wrx_ and k_wmin_ / k_wlb_ kernels skip a stopped
+// box; the reused observer kernels know DEVFLAG_FROZEN alone and evaluate it again into work buffers nobody reads for it.
+// (No k_wrx_ kernel uses a value it read from memory as an address but k_wrx_lbmols' ring count, which passes through
+// GAMD_CHK_RANGE under GAMD_CHK_WLBFGS_COUNT as in k_wlb_mols.)
+struct WRxRoute {
+    double w_h;                // the M-site's hydrogen weight, 0 = 3-site
+    int mchunk;                // w_h != 0: molecules per slice of the Lennard-Jones pass, as W4Args
+    double* sites;             // w_h != 0: [n][3] the charge sites k_wrx_sites writes
+    double* ljpart;            // w_h != 0: [n_boxes][slices][n_per_box / 3][W4_LJ]
+    const PmeArgs* pme;        // particle-mesh Ewald in force (its w and sites are set here), or null: the plain sum
+    const CellTabBufs* cells;  // the cell table in force, or null: all pairs
+};
+// what the three kinds of k_wrx_ kernels take
+struct WRxSiteArgs { W4Args b; const double* x64; const int* stopped; };       // k_wrx_sites, k_wrx_lj: positions and gates of the pass
+struct WRxMinArgs { WMinArgs m; double w_h, w_o; const double* ljpart; };      // k_wrx_mols
+struct WRxLbArgs { WLbfgsArgs l; double w_h, w_o; const double* ljpart; };     // k_wrx_lbmols
+int launch_wrx_iter(const WMinArgs& m, const WRxRoute& r, hipStream_t st);
+int launch_wrx_eval(const WLbfgsArgs& l, const WRxRoute& r, hipStream_t st);
+// pieces of the existing files the route is put together from, each with its launcher's own checks: k_wmin_pairs alone; k_wmin_rho,
+// k_water_sk, k_wmin_recip alone; k_wmin_update / k_wlb_update alone; k_w4_pairs alone; k_w4_rho, k_water_sk, k_w4_recip alone.
+// `routed` (also on the init and store-x launchers below): the block is a routed one, whose k side is not the plain sum's.
+int launch_wmin_pairs(const WMinArgs& m, hipStream_t st);
+int launch_wmin_recip(const WMinArgs& m, hipStream_t st);
+int launch_wmin_update(const WMinArgs& m, hipStream_t st);
+int launch_wlbfgs_update(const WLbfgsArgs& l, hipStream_t st);
+int launch_w4_pairs(const W4Args& b, hipStream_t st);
+int launch_w4_recip(const W4Args& b, hipStream_t st);
+int launch_wmin_init_routed(const WMinArgs& m, const float* x, hipStream_t st);
+int launch_wmin_store_x_routed(const WMinArgs& m, float* x_io, double* x64_out, hipStream_t st);
+int launch_wlbfgs_init_routed(const WLbfgsArgs& l, const float* x, hipStream_t st);
+int launch_wlbfgs_store_x_routed(const WLbfgsArgs& l, const int* gates, float* x_io, double* x64_out, hipStream_t st);

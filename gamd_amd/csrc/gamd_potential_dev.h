@@ -79,10 +79,13 @@ __device__ __forceinline__ double water_frac(double x, double L) { return (x - L
 // the TIP4P virtual site of one molecule (water_msite.hip; OpenMM's ThreeParticleAverageSite with weights 1 - 2 w, w, w):
 // M = O' + w (d_1 + d_2), d_k = H_k - O per component as d - L rint(d / L), from the fp32 positions widened, and O' = O wrapped
 // into [0, L) by water_wrap.  The hydrogens may be in any image; where x + k L is exact in fp32, d_k and O' — and so M — are the
-// same doubles for every image of every atom.  The one place M is computed: every 4-site kernel reads its result.
+// same doubles for every image of every atom.  The one place M is computed: every 4-site kernel reads its result.  T = float:
+// the fp32 atoms widened (k_w4_sites); T = double: a minimiser's positions as they are (k_wrx_sites, water_relax.hip) — the
+// same statements, the widening is then the identity.
 __device__ __forceinline__ double water_wrap(double x, double L) { return x - L * floor(x / L); }
 
-__device__ __forceinline__ void water_msite(const float* o, const float* h1, const float* h2, double Lx, double Ly, double Lz, double w,
+template <typename T>
+__device__ __forceinline__ void water_msite(const T* o, const T* h1, const T* h2, double Lx, double Ly, double Lz, double w,
                                             double& mx, double& my, double& mz) {
     const double ox = (double)o[0], oy = (double)o[1], oz = (double)o[2];
     double ax = (double)h1[0] - ox, ay = (double)h1[1] - oy, az = (double)h1[2] - oz;

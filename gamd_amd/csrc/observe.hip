@@ -146,6 +146,7 @@ struct WaterClassical : PotentialLog, CellTables {
     DevBuf pme_gq, pme_gc;             // order != 0: per box and grid point, the integer spread and the complex transform (water_pme.hip)
     DevBuf pme_tw, pme_mod;            // ... the twiddles and the three axes' moduli, uploaded by gamd_water_pme
     // (CellTables: gamd_water_cells)
+    bool min_configured = false;       // gamd_water_minimize_potential: the minimisers follow the three switches above (water_relax.hip)
 };
 
 // energy minimiser (gamd_minimize, minimize.hip): no observer — no clock, no entry in observer_list() — but a user of the
@@ -906,12 +907,34 @@ struct LjMinimizer {
     static constexpr const char* api = "gamd_minimize";
     enum { FROZEN_CODE = -1, COPY_X64 = 1 };
     static P::Args& potential(Args& m) { return m.c; }
-    static int init(const Args& m, const float* x, hipStream_t st) { return launch_minimize_init(m, x, st); }
+    static void route_args(const gamd_handle*, P::Args&) {}
+    static int init(const gamd_handle*, const Args& m, const float* x, hipStream_t st) { return launch_minimize_init(m, x, st); }
     static int iter(const gamd_handle* h, const Args& m, hipStream_t st) {
         CellTabBufs b;
         return launch_minimize_iter(m, st, P::cell_bufs(h, b));
     }
-    static int store_x(const Args& m, float* x, double*, hipStream_t st) { return launch_minimize_store_x(m, x, st); }
+    static int store_x(const gamd_handle*, const Args& m, float* x, double*, hipStream_t st) { return launch_minimize_store_x(m, x, st); }
+};
+
+// gamd_water_minimize_potential: what the two water minimisers share while the switch is on — the potential's block as the
+// route leaves it (WaterPotential::launch's one pair slice under the cell table, WaterPotential::pme's one k slice and the
+// convolution's blocks under particle-mesh Ewald), and the route of a pass (p, cb: the caller's room)
+struct WaterRelax {
+    static bool on(const gamd_handle* h) { return WaterPotential::state(h).min_configured; }
+    static void route_args(const gamd_handle* h, WaterArgs& a) {
+        const WaterClassical& wc = WaterPotential::state(h);
+        if (!wc.min_configured) return;
+        wc.one_slice(a, h->n_per_box);
+        if (wc.pme_order) { a.kslices = 1; a.kblocks = (int)water_pme_blocks(wc); }
+    }
+    static WRxRoute route(const gamd_handle* h, const WaterArgs& a, PmeArgs& p, CellTabBufs& cb) {
+        WaterClassical& wc = WaterPotential::state(h);
+        const bool m = wc.w_h != 0.0;
+        WRxRoute r{wc.w_h, m ? (a.chunk + 2) / 3 : 0, m ? wc.sites.as<double>() : nullptr, m ? wc.ljpart.as<double>() : nullptr, nullptr,
+                   wc.bufs(wc.r_cut, h->sticky_dev, cb)};
+        if (wc.pme_order) { p = WaterPotential::pme(h, a); r.pme = &p; }
+        return r;
+    }
 };
 
 struct WaterMinimizer {
@@ -920,9 +943,19 @@ struct WaterMinimizer {
     static constexpr const char* api = "gamd_water_minimize";
     enum { FROZEN_CODE = -22, COPY_X64 = 0 };
     static P::Args& potential(Args& m) { return m.w; }
-    static int init(const Args& m, const float* x, hipStream_t st) { return launch_wmin_init(m, x, st); }
-    static int iter(const gamd_handle*, const Args& m, hipStream_t st) { return launch_wmin_iter(m, st); }
-    static int store_x(const Args& m, float* x, double* x64_out, hipStream_t st) { return launch_wmin_store_x(m, x, x64_out, st); }
+    static void route_args(const gamd_handle* h, P::Args& a) { WaterRelax::route_args(h, a); }
+    static int init(const gamd_handle* h, const Args& m, const float* x, hipStream_t st) {
+        return WaterRelax::on(h) ? launch_wmin_init_routed(m, x, st) : launch_wmin_init(m, x, st);
+    }
+    // the switch on: the route of the configured potential (water_relax.hip); off: the six launches as they were
+    static int iter(const gamd_handle* h, const Args& m, hipStream_t st) {
+        if (!WaterRelax::on(h)) return launch_wmin_iter(m, st);
+        PmeArgs p; CellTabBufs cb;
+        return launch_wrx_iter(m, WaterRelax::route(h, m.w, p, cb), st);
+    }
+    static int store_x(const gamd_handle* h, const Args& m, float* x, double* x64_out, hipStream_t st) {
+        return WaterRelax::on(h) ? launch_wmin_store_x_routed(m, x, x64_out, st) : launch_wmin_store_x(m, x, x64_out, st);
+    }
 };
 
 // The minimiser's run behind the checks that are its entry point's own: the boxes, every allocation, the look at the frozen
@@ -955,13 +988,15 @@ int minimize_run(gamd_handle* h, typename M::Args m, float* x_dev, const uint8_t
     a = P::args(h, len);
     a.box_edges = pl.eval_box.template as<float>();
     P::species(a, species_dev);
+    const typename P::Args plain = a;                       // the force source's block behind the run
+    M::route_args(h, a);
     FireArgs& fi = m.fire;
     fi.x64 = mn.x64.as<double>(); fi.v64 = mn.v64.as<double>(); fi.f64 = mn.f64.as<double>();
     fi.state = mn.state.as<double>(); fi.stopped = mn.stopped.as<int>(); fi.rows = mn.rows.as<double>();
     fi.tol = q.tolerance; fi.dt_start = q.dt_start; fi.dt_max = q.dt_max; fi.f_inc = q.f_inc; fi.f_dec = q.f_dec;
     fi.alpha_start = q.alpha_start; fi.f_alpha = q.f_alpha; fi.max_step = q.max_step; fi.n_min = q.n_min;
     int r;
-    if ((r = M::init(m, x_dev, st))) return fail(-1, "%s launch failed (%d)", M::api, r);
+    if ((r = M::init(h, m, x_dev, st))) return fail(-1, "%s launch failed (%d)", M::api, r);
     bool all_stopped = false;
     while (fi.it < q.max_iter && !all_stopped) {
         const long long chunk = std::min<long long>(q.check_every, q.max_iter - fi.it);
@@ -976,8 +1011,8 @@ int minimize_run(gamd_handle* h, typename M::Args m, float* x_dev, const uint8_t
         if ((r = M::iter(h, m, st))) return fail(-1, "%s launch failed (%d)", M::api, r);
     }
     // x (and the water minimiser's x64), then the force source's own kernels on exactly that x
-    if ((r = M::store_x(m, x_dev, x64_dev, st))) return fail(-1, "%s launch failed (%d)", M::api, r);
-    typename P::Args drive = a;
+    if ((r = M::store_x(h, m, x_dev, x64_dev, st))) return fail(-1, "%s launch failed (%d)", M::api, r);
+    typename P::Args drive = plain;
     drive.x = x_dev;
     if ((r = P::drive(h, drive, mn.f32.as<float>(), st))) return fail(-1, "%s launch failed (%d)", M::api, r);
     pl.evaluated = true;
@@ -1002,12 +1037,15 @@ struct LjLbfgs {
     static constexpr const char* api = "gamd_minimize_lbfgs";
     enum { FROZEN_CODE = -1, COPY_X64 = 1, ACC = LBFGS_ACC };
     static P::Args& potential(Args& l) { return l.c; }
-    static int init(const Args& l, const float* x, hipStream_t st) { return launch_lbfgs_init(l, x, st); }
+    static void route_args(const gamd_handle*, P::Args&) {}
+    static int init(const gamd_handle*, const Args& l, const float* x, hipStream_t st) { return launch_lbfgs_init(l, x, st); }
     static int eval(const gamd_handle* h, const Args& l, hipStream_t st) {
         CellTabBufs b;
         return launch_lbfgs_eval(l, st, P::cell_bufs(h, b));
     }
-    static int store_x(const Args& l, const int* gates, float* x, double*, hipStream_t st) { return launch_lbfgs_store_x(l, gates, x, st); }
+    static int store_x(const gamd_handle*, const Args& l, const int* gates, float* x, double*, hipStream_t st) {
+        return launch_lbfgs_store_x(l, gates, x, st);
+    }
 };
 
 struct WaterLbfgs {
@@ -1016,10 +1054,18 @@ struct WaterLbfgs {
     static constexpr const char* api = "gamd_water_minimize_lbfgs";
     enum { FROZEN_CODE = -22, COPY_X64 = 0, ACC = WLB_ACC };
     static P::Args& potential(Args& l) { return l.w; }
-    static int init(const Args& l, const float* x, hipStream_t st) { return launch_wlbfgs_init(l, x, st); }
-    static int eval(const gamd_handle*, const Args& l, hipStream_t st) { return launch_wlbfgs_eval(l, st); }
-    static int store_x(const Args& l, const int* gates, float* x, double* x64_out, hipStream_t st) {
-        return launch_wlbfgs_store_x(l, gates, x, x64_out, st);
+    static void route_args(const gamd_handle* h, P::Args& a) { WaterRelax::route_args(h, a); }
+    static int init(const gamd_handle* h, const Args& l, const float* x, hipStream_t st) {
+        return WaterRelax::on(h) ? launch_wlbfgs_init_routed(l, x, st) : launch_wlbfgs_init(l, x, st);
+    }
+    // the switch on: the route of the configured potential on the trial positions (water_relax.hip); off: the six launches as they were
+    static int eval(const gamd_handle* h, const Args& l, hipStream_t st) {
+        if (!WaterRelax::on(h)) return launch_wlbfgs_eval(l, st);
+        PmeArgs p; CellTabBufs cb;
+        return launch_wrx_eval(l, WaterRelax::route(h, l.w, p, cb), st);
+    }
+    static int store_x(const gamd_handle* h, const Args& l, const int* gates, float* x, double* x64_out, hipStream_t st) {
+        return WaterRelax::on(h) ? launch_wlbfgs_store_x_routed(l, gates, x, x64_out, st) : launch_wlbfgs_store_x(l, gates, x, x64_out, st);
     }
 };
 
@@ -1055,12 +1101,14 @@ int lbfgs_run(gamd_handle* h, typename M::Args l, float* x_dev, const uint8_t* s
     a = P::args(h, len);
     a.box_edges = pl.eval_box.template as<float>();
     P::species(a, species_dev);
+    const typename P::Args plain = a;                       // the force source's block behind the run
+    M::route_args(h, a);
     l.x = lb.x.as<double>(); l.xt = lb.xt.as<double>(); l.f = lb.f.as<double>(); l.ft = lb.ft.as<double>(); l.d = lb.d.as<double>();
     l.ring = lb.ring.as<double>(); l.blk = lb.blk.as<double>(); l.state = lb.state.as<double>(); l.gates = lb.gates.as<int>();
     l.rows = lb.rows.as<double>(); l.sticky = h->sticky_dev;
     l.tol = q.tolerance; l.max_step = q.max_step; l.c1 = q.c1; l.curv = q.curv; l.m = q.m; l.max_ls = q.max_ls; l.max_iter = q.max_iter;
     int r;
-    if ((r = M::init(l, x_dev, st))) return fail(-1, "%s launch failed (%d)", api, r);
+    if ((r = M::init(h, l, x_dev, st))) return fail(-1, "%s launch failed (%d)", api, r);
     bool all_stopped = false;
     while (l.it <= q.max_iter && !all_stopped) {            // pass 0 is the start's, pass k evaluation k
         const long long chunk = std::min<long long>(q.check_every, q.max_iter + 1 - l.it);
@@ -1072,8 +1120,8 @@ int lbfgs_run(gamd_handle* h, typename M::Args l, float* x_dev, const uint8_t* s
     }
     const int* gates_dev = lb.gates.as<int>() + (size_t)(l.it & 1) * nb;    // the set the last pass wrote
     // x (and the water minimiser's x64), then the force source's own kernels on exactly that x
-    if ((r = M::store_x(l, gates_dev, x_dev, x64_dev, st))) return fail(-1, "%s launch failed (%d)", api, r);
-    typename P::Args drive = a;
+    if ((r = M::store_x(h, l, gates_dev, x_dev, x64_dev, st))) return fail(-1, "%s launch failed (%d)", api, r);
+    typename P::Args drive = plain;
     drive.x = x_dev;
     if ((r = P::drive(h, drive, lb.f32.as<float>(), st))) return fail(-1, "%s launch failed (%d)", api, r);
     pl.evaluated = true;
@@ -1092,7 +1140,8 @@ int lbfgs_run(gamd_handle* h, typename M::Args l, float* x_dev, const uint8_t* s
 
 // What the two water minimisers refuse behind their parameter blocks and in front of the device, under the name of the entry:
 // the geometry (0 = TIP3P, scaled by the unit), the handle's kind, the molecules, the potential's parameters, a pending run and
-// the three forms of the potential that have no minimiser.  On 0 the unit-weight canonical triangle of SETTLE is in ra, rb, rc.
+// the three forms of the potential the minimisers follow only while gamd_water_minimize_potential is on.  On 0 the unit-weight
+// canonical triangle of SETTLE is in ra, rb, rc.
 int water_minimize_checks(const char* api, gamd_handle* h, double len, double r_oh, double r_hh, double* ra, double* rb, double* rc) {
     if (!(r_oh >= 0.0) || !(r_hh >= 0.0) || !std::isfinite(r_oh) || !std::isfinite(r_hh))
         return fail(-22, "%s: r_oh = %g, r_hh = %g: a length is not positive", api, r_oh, r_hh);
@@ -1107,15 +1156,20 @@ int water_minimize_checks(const char* api, gamd_handle* h, double len, double r_
     WaterClassical& wc = WaterPotential::state(h);
     if (!wc.params_set) return fail(-22, "%s needs the parameters of a gamd_water_configure call (interval 0 will do)", api);
     if (h->pending.active) return fail(-22, "an MD run is still enqueued: call gamd_sync_status before %s", api);
-    if (wc.w_h != 0.0)
-        return fail(-22, "%s: the TIP4P M-site is set (gamd_water_msite, w_h = %.9g) and there is no 4-site rigid minimiser: "
-                         "minimise with w_h = 0, set the weight, then take f from gamd_water_eval", api, wc.w_h);
-    if (wc.pme_order)
-        return fail(-22, "%s: particle-mesh Ewald is on (gamd_water_pme, order %d) and there is no PME minimiser: "
-                         "minimise under the plain sum, switch PME on, then take f from gamd_water_eval", api, wc.pme_order);
-    if (wc.cells)
-        return fail(-22, "%s: the cell table is on (gamd_water_cells) and the minimiser's f is the all-pairs force bit for "
-                         "bit: minimise with the cells off, switch them on, then take f from gamd_water_eval", api);
+    if (!wc.min_configured) {                               // gamd_water_minimize_potential is off: the oldest form alone
+        if (wc.w_h != 0.0)
+            return fail(-22, "%s: the TIP4P M-site is set (gamd_water_msite, w_h = %.9g) and there is no 4-site rigid minimiser "
+                             "while gamd_water_minimize_potential is off: switch it on, or minimise with w_h = 0, set the weight, "
+                             "then take f from gamd_water_eval", api, wc.w_h);
+        if (wc.pme_order)
+            return fail(-22, "%s: particle-mesh Ewald is on (gamd_water_pme, order %d) and there is no PME minimiser while "
+                             "gamd_water_minimize_potential is off: switch it on, or minimise under the plain sum, switch PME on, "
+                             "then take f from gamd_water_eval", api, wc.pme_order);
+        if (wc.cells)
+            return fail(-22, "%s: the cell table is on (gamd_water_cells) and the minimiser's f is the all-pairs force bit for "
+                             "bit while gamd_water_minimize_potential is off: switch it on, or minimise with the cells off, "
+                             "switch them on, then take f from gamd_water_eval", api);
+    }
     *rc = 0.5 * r_hh;
     const double t = std::sqrt(r_oh * r_oh - *rc * *rc);
     *ra = (2.0 * t) / 3.0; *rb = t / 3.0;
@@ -1646,6 +1700,22 @@ int32_t gamd_water_cells(gamd_handle* h, int32_t on) {
         return fail(-22, "gamd_water_cells: a GAMD_KIND_LJ handle has no water potential (GAMD_KIND_WATER handles only; "
                          "gamd_classical_cells switches the cell table of the Lennard-Jones classical potential)");
     return cells_switch(h, h->obs->wc, water_bufs, "gamd_water_cells", "gamd_water_configure", on);
+}
+
+int32_t gamd_water_minimize_potential(gamd_handle* h, int32_t on) {
+    if (!h) return fail(-22, "null handle");
+    if (h->cfg.kind != GAMD_KIND_WATER)
+        return fail(-22, "gamd_water_minimize_potential: a GAMD_KIND_LJ handle has no water potential (GAMD_KIND_WATER handles "
+                         "only; gamd_minimize follows gamd_classical_cells by itself)");
+    WaterClassical& wc = h->obs->wc;
+    if (!wc.params_set)
+        return fail(-22, "gamd_water_minimize_potential needs the parameters of a gamd_water_configure call (interval 0 will do)");
+    if (h->pending.active) return fail(-22, "an MD run is still enqueued: call gamd_sync_status before gamd_water_minimize_potential");
+    if (on != 0 && on != 1)
+        return fail(-22, "gamd_water_minimize_potential: on = %d is not 0 (3-site, plain sum, all pairs only) or 1 (the potential as "
+                         "configured)", (int)on);
+    wc.min_configured = on == 1;
+    return 0;
 }
 
 int32_t gamd_water_cells_read(gamd_handle* h, void* stream, int32_t box, int32_t* nc, int32_t* start, int64_t max_start, int32_t* order,

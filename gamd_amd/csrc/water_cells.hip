@@ -2,7 +2,8 @@
 // 4.10.4): a second producer of the pair rows `part`.  The kernels behind them (k_water_atoms, k_wsrc_atoms, k_w4_atoms,
 // k_w4_drive, k_water_final), the reciprocal kernels (plain or particle-mesh), the M-site prepass and k_w4_lj are launched as they
 // are, on an argument block with ONE pair slice.  Positions are the fp32 atoms widened (3-site) or the charge sites k_w4_sites
-// left (M-site), never wrapped: a pair's d, minimum image and r^2 come from the same operations on the same two doubles as in
+// left (M-site) — or, from the water minimisers under the configured potential (water_relax.hip), their double positions
+// (3-site, the O-O term in the walk) or the sites k_wrx_sites left — never wrapped: a pair's d, minimum image and r^2 come from the same operations on the same two doubles as in
 // gamd_water_walk (gamd_passes_dev.h), so the set of pairs and the pair count are the all-pairs walk's by construction.
 // Per box nx x ny x nz cells (gamd_cells_dev.h: cells per axis, cell of a coordinate, neighbour lists), cell = (cx ny + cy) nz + cz.
 // The table — the box's atoms ordered by (cell, atom index), entries {position, atom, O flag} — is cell_table.hip's, built by
@@ -186,8 +187,9 @@ __global__ void __launch_bounds__(WCELL_SLOTS * WCELL_WAVES) k_wcell_force4(WCel
 
 int launch_water_cells(const WaterArgs& w, const CellTabBufs& c, const double* sites, int nout, bool lj, hipStream_t st) {
     PassGeom g;
-    if (pass_rows(w, 3, &g) || w.slices != 1 || (nout != 3 && nout != WATER_PART) || lj == (sites != nullptr)) return -1;
-    if (!w.x || !w.species || !w.part || !w.devflags) return -1;
+    // (lj with sites: the 3-site walk on a minimiser's double positions, water_relax.hip; the M-site form has no other positions)
+    if (pass_rows(w, 3, &g) || w.slices != 1 || (nout != 3 && nout != WATER_PART) || (!lj && !sites)) return -1;
+    if (!(sites || w.x) || !w.species || !w.part || !w.devflags) return -1;
     if (int r = launch_cell_table(cell_tab_args(w, c, nullptr, sites, w.species, GAMD_CHK_WCELL_CELL), st)) return r;
     const WCellArgs k{w, c, sites};
     const dim3 pg((unsigned)((g.npb + WCELL_SLOTS - 1) / WCELL_SLOTS), g.nb), pb(WCELL_SLOTS * WCELL_WAVES);

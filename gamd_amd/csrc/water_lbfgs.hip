@@ -322,10 +322,13 @@ __global__ void __launch_bounds__(256) k_wlb_store_x(WLbfgsArgs l, const int* __
 }
 
 // what every launcher checks: the force launches' checks on the trial positions, and every buffer of the minimiser's own
-int wlbfgs_check(const WLbfgsArgs& l, WMinArgs* force, PassGeom* g, long long* mol_tiles) {
+// (`routed`: a block of gamd_water_minimize_potential, water_relax.hip — the k side is the route's and its launchers' to check)
+int wlbfgs_check(const WLbfgsArgs& l, WMinArgs* force, PassGeom* g, long long* mol_tiles, bool routed = false) {
     const WaterArgs& a = l.w;
-    if (pass_geometry(a, 3, g) || pass_k_geometry(a, g->T, false) || a.blocks < 1 || a.blocks > 65535) return -1;
-    if (!a.species || !a.kvec || !a.part || !a.rho_partial || !a.sk || !a.ublk || !a.rpart || !a.box_edges || !a.devflags) return -1;
+    if (pass_geometry(a, 3, g) || a.blocks < 1 || a.blocks > 65535) return -1;
+    if (routed ? a.kblocks < 1 : pass_k_geometry(a, g->T, false)) return -1;
+    if (!routed && (!a.kvec || !a.rho_partial || !a.sk)) return -1;
+    if (!a.species || !a.part || !a.ublk || !a.rpart || !a.box_edges || !a.devflags) return -1;
     if (!l.x || !l.xt || !l.f || !l.ft || !l.d || !l.ring || !l.blk || !l.state || !l.gates || !l.rows) return -1;
     if (l.m < 1 || l.m > LBFGS_M || l.max_ls < 1 || l.it < 0 || l.max_iter < 0) return -1;
     if (!(l.ra > 0.0) || !(l.rb > 0.0) || !(l.rc > 0.0)) return -1;
@@ -359,6 +362,29 @@ int launch_wlbfgs_eval(const WLbfgsArgs& l, hipStream_t st) {
 int launch_wlbfgs_store_x(const WLbfgsArgs& l, const int* gates, float* x_io, double* x64_out, hipStream_t st) {
     PassGeom g; long long M; WMinArgs force;
     if (wlbfgs_check(l, &force, &g, &M) || !gates || !x_io) return -1;
+    hipLaunchKernelGGL(k_wlb_store_x, dim3((unsigned)M, g.nb), dim3(256), 0, st, l, gates, x_io, x64_out); GAMD_CHECK_LAUNCH();
+    return 0;
+}
+
+// ---- the pieces water_relax.hip puts its routes together from (gamd_water_minimize_potential) ----------------------------
+// k_wlb_update alone, behind a molecule pass that wrote k_wlb_mols' columns
+int launch_wlbfgs_update(const WLbfgsArgs& l, hipStream_t st) {
+    PassGeom g; long long M; WMinArgs force;
+    if (wlbfgs_check(l, &force, &g, &M, true)) return -1;
+    hipLaunchKernelGGL(k_wlb_update, dim3((unsigned)M, g.nb), dim3(256), 0, st, l); GAMD_CHECK_LAUNCH();
+    return 0;
+}
+
+int launch_wlbfgs_init_routed(const WLbfgsArgs& l, const float* x, hipStream_t st) {
+    PassGeom g; long long M; WMinArgs force;
+    if (wlbfgs_check(l, &force, &g, &M, true) || !x) return -1;
+    hipLaunchKernelGGL(k_wlb_init, dim3((unsigned)M, g.nb), dim3(256), 0, st, l, x); GAMD_CHECK_LAUNCH();
+    return 0;
+}
+
+int launch_wlbfgs_store_x_routed(const WLbfgsArgs& l, const int* gates, float* x_io, double* x64_out, hipStream_t st) {
+    PassGeom g; long long M; WMinArgs force;
+    if (wlbfgs_check(l, &force, &g, &M, true) || !gates || !x_io) return -1;
     hipLaunchKernelGGL(k_wlb_store_x, dim3((unsigned)M, g.nb), dim3(256), 0, st, l, gates, x_io, x64_out); GAMD_CHECK_LAUNCH();
     return 0;
 }

@@ -320,24 +320,45 @@ int wmin_force_check(const WMinArgs& m, PassGeom* g) {
     return 0;
 }
 
+// ... of a ROUTED block (gamd_water_minimize_potential, water_relax.hip): the k side is the route's and its launchers' to check
+int wmin_routed_check(const WMinArgs& m, PassGeom* g) {
+    const WaterArgs& a = m.w;
+    if (pass_geometry(a, 3, g) || a.kblocks < 1 || a.blocks < 1 || a.blocks > 65535) return -1;
+    if (!a.species || !a.part || !a.ublk || !a.rpart || !a.blk || !a.box_edges || !a.devflags) return -1;
+    if (!m.fire.x64 || !m.fire.stopped) return -1;
+    return 0;
+}
+
 // what every launcher of the minimiser checks: that, and every buffer of FIRE's
-int wmin_check(const WMinArgs& m, PassGeom* g, long long* mol_tiles) {
+int wmin_check(const WMinArgs& m, PassGeom* g, long long* mol_tiles, bool routed = false) {
     const FireArgs& fi = m.fire;
-    if (wmin_force_check(m, g)) return -1;
+    if (routed ? wmin_routed_check(m, g) : wmin_force_check(m, g)) return -1;
     if (!fi.x64 || !fi.v64 || !fi.f64 || !fi.state || !fi.stopped || !fi.rows || fi.it < 0) return -1;
     if (!(m.ra > 0.0) || !(m.rb > 0.0) || !(m.rc > 0.0)) return -1;
     *mol_tiles = (g->npb / 3 + GAMD_PASS_TILE - 1) / GAMD_PASS_TILE;
     return 0;
 }
 
-// pairs; rho, sk, recip
-int wmin_force(const WMinArgs& m, const PassGeom& g, hipStream_t st) {
+// pairs
+int wmin_pairs(const WMinArgs& m, const PassGeom& g, hipStream_t st) {
     const WaterArgs& a = m.w;
     hipLaunchKernelGGL(k_wmin_pairs, dim3((unsigned)(g.T * a.slices), g.nb), dim3(256), 0, st, m); GAMD_CHECK_LAUNCH();
+    return 0;
+}
+
+// rho, sk, recip
+int wmin_recip(const WMinArgs& m, const PassGeom& g, hipStream_t st) {
+    const WaterArgs& a = m.w;
     hipLaunchKernelGGL(k_wmin_rho, dim3(a.rho_blocks, (a.n_k + 63) / 64, g.nb), dim3(256), 0, st, m); GAMD_CHECK_LAUNCH();
     if (int r = launch_water_sk(a, st)) return r;
     hipLaunchKernelGGL(k_wmin_recip, dim3((unsigned)(g.T * a.kslices), g.nb), dim3(256), 0, st, m); GAMD_CHECK_LAUNCH();
     return 0;
+}
+
+// pairs; rho, sk, recip
+int wmin_force(const WMinArgs& m, const PassGeom& g, hipStream_t st) {
+    if (int r = wmin_pairs(m, g, st)) return r;
+    return wmin_recip(m, g, st);
 }
 
 }  // namespace
@@ -368,6 +389,43 @@ int launch_wmin_force(const WMinArgs& m, hipStream_t st) {
 int launch_wmin_store_x(const WMinArgs& m, float* x_io, double* x64_out, hipStream_t st) {
     PassGeom g; long long M;
     if (wmin_check(m, &g, &M) || !x_io) return -1;
+    hipLaunchKernelGGL(k_wmin_store_x, dim3((unsigned)M, g.nb), dim3(256), 0, st, m, x_io, x64_out); GAMD_CHECK_LAUNCH();
+    return 0;
+}
+
+// ---- the pieces water_relax.hip puts its routes together from (gamd_water_minimize_potential) ----------------------------
+// k_wmin_pairs alone: the pair side of the force launches' checks
+int launch_wmin_pairs(const WMinArgs& m, hipStream_t st) {
+    PassGeom g;
+    if (wmin_routed_check(m, &g)) return -1;
+    return wmin_pairs(m, g, st);
+}
+
+// k_wmin_rho, k_water_sk, k_wmin_recip alone: every check of the force launches (the strided k walk's geometry among them)
+int launch_wmin_recip(const WMinArgs& m, hipStream_t st) {
+    PassGeom g;
+    if (wmin_force_check(m, &g)) return -1;
+    return wmin_recip(m, g, st);
+}
+
+// k_wmin_update alone, behind a molecule pass that wrote k_wmin_mols' columns
+int launch_wmin_update(const WMinArgs& m, hipStream_t st) {
+    PassGeom g; long long M;
+    if (wmin_check(m, &g, &M, true)) return -1;
+    hipLaunchKernelGGL(k_wmin_update, dim3((unsigned)M, g.nb), dim3(256), 0, st, m); GAMD_CHECK_LAUNCH();
+    return 0;
+}
+
+int launch_wmin_init_routed(const WMinArgs& m, const float* x, hipStream_t st) {
+    PassGeom g; long long M;
+    if (wmin_check(m, &g, &M, true) || !x) return -1;
+    hipLaunchKernelGGL(k_wmin_init, dim3((unsigned)M, g.nb), dim3(256), 0, st, m, x); GAMD_CHECK_LAUNCH();
+    return 0;
+}
+
+int launch_wmin_store_x_routed(const WMinArgs& m, float* x_io, double* x64_out, hipStream_t st) {
+    PassGeom g; long long M;
+    if (wmin_check(m, &g, &M, true) || !x_io) return -1;
     hipLaunchKernelGGL(k_wmin_store_x, dim3((unsigned)M, g.nb), dim3(256), 0, st, m, x_io, x64_out); GAMD_CHECK_LAUNCH();
     return 0;
 }

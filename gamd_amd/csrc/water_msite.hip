@@ -273,3 +273,25 @@ int launch_w4_drive(const W4Args& b, float* f_out, hipStream_t st, const PmeArgs
     hipLaunchKernelGGL(k_w4_drive, dim3((unsigned)g.T, g.nb), dim3(256), 0, st, b, f_out); GAMD_CHECK_LAUNCH();
     return 0;
 }
+
+// ---- the pieces water_relax.hip puts its routes together from (gamd_water_minimize_potential): the sites are its k_wrx_sites' --
+// k_w4_pairs alone
+int launch_w4_pairs(const W4Args& b, hipStream_t st) {
+    const WaterArgs& a = b.w;
+    PassGeom g;
+    if (pass_geometry(a, 3, &g) || !a.species || !a.part || !a.devflags || !b.sites) return -1;
+    hipLaunchKernelGGL(k_w4_pairs, dim3((unsigned)(g.T * a.slices), g.nb), dim3(256), 0, st, b); GAMD_CHECK_LAUNCH();
+    return 0;
+}
+
+// k_w4_rho, k_water_sk, k_w4_recip alone: the kchunk walk's geometry
+int launch_w4_recip(const W4Args& b, hipStream_t st) {
+    const WaterArgs& a = b.w;
+    PassGeom g;
+    if (pass_rows(a, 3, &g) || pass_k_geometry(a, g.T, true)) return -1;
+    if (!a.species || !a.kvec || !a.rho_partial || !a.sk || !a.ublk || !a.rpart || !a.devflags || !b.sites) return -1;
+    hipLaunchKernelGGL(k_w4_rho, dim3(a.rho_blocks, (a.n_k + 63) / 64, g.nb), dim3(256), 0, st, b); GAMD_CHECK_LAUNCH();
+    if (int r = launch_water_sk(a, st)) return r;
+    hipLaunchKernelGGL(k_w4_recip, dim3((unsigned)(g.T * a.kslices), g.nb), dim3(256), 0, st, b); GAMD_CHECK_LAUNCH();
+    return 0;
+}

@@ -1247,7 +1247,7 @@ class GamdForce:
                                   shift: bool = False, ewald_tol: float = 1e-10, alpha: Optional[float] = None,
                                   k_cut: Optional[float] = None, coulomb_const: float = COULOMB_KJ_NM,
                                   length_per_nm: float = 0.0, m_site: float = 0.0, virial: bool = False, pme=None, pme_order: int = 6,
-                                  cells: bool = False) -> None:
+                                  cells: bool = False, minimize_configured: bool = False) -> None:
         """While configured, every ``interval``-th completed step of md_run / md_run_nhc (counted across calls, by a counter
         of its own) evaluates the classical potential of 3-site water in double on the device — O-O Lennard-Jones plus
         point charges q_H and q_O = -2 q_H by a plain Ewald sum (real space inside ``r_cut``, same-molecule exclusion,
@@ -1271,7 +1271,8 @@ class GamdForce:
         are then taken on M, H, H, the Lennard-Jones term stays on O with a cutoff test of its own, and M's force goes back
         to the atoms with the same weights, the exact gradient with respect to O, H, H.  Handles, integrators and SETTLE
         still see three atoms.  The observer, ``water_classical_forces`` and the ``"water_classical"`` force source all
-        follow it; ``water_minimize`` refuses it.  Every call states the whole potential: the default 0 is 3-site water,
+        follow it; ``water_minimize`` and ``water_minimize_lbfgs`` follow it with ``minimize_configured=True`` and refuse it
+        otherwise.  Every call states the whole potential: the default 0 is 3-site water,
         bit for bit what it was.  ``water_classical_configure(0, **TIP4PEW)`` (module constant: q_H = 0.52422 e, sigma_O =
         3.16435 Angstrom, epsilon_O = 0.680946 kJ/mol, w = 0.106676721) is meant to be OpenMM's ``tip4pew.xml``; these values
         too were written down from memory and are UNVERIFIED.  ``sigma_o`` given explicitly is in the engine's length unit.
@@ -1286,9 +1287,9 @@ class GamdForce:
         (``pme_grid`` proposes one): O(N p^3 + G log G) per sample instead of O(N K), in double with an integer spread, so the
         bits repeat as the plain sum's do.  ``k_cut`` is then not read and the limit of 131 072 k-vectors does not apply;
         ``alpha``, ``r_cut`` and every other term are unchanged.  The observer, ``water_classical_forces`` and the
-        ``"water_classical"`` force source follow it, with and without ``m_site``; ``virial=True``, ``water_classical_virial``
-        and ``water_minimize`` refuse it (minimise under the plain sum, configure again with ``pme``, take ``f`` from
-        ``water_classical_forces``).  Every call states it: the default None is the plain sum, bit for bit what it was.
+        ``"water_classical"`` force source follow it, with and without ``m_site``; ``virial=True`` and
+        ``water_classical_virial`` refuse it, and so do the minimisers unless ``minimize_configured=True`` (without it:
+        minimise under the plain sum, configure again with ``pme``, take ``f`` from ``water_classical_forces``).  Every call states it: the default None is the plain sum, bit for bit what it was.
 
         ``cells`` walks the real-space pairs over a per-box cell table instead of all against all: per sample the atoms are
         ordered by (cell, atom index), cells of edge >= r_cut / 2, and every atom tests the atoms of the 5 x 5 x 5 cells around
@@ -1298,14 +1299,20 @@ class GamdForce:
         frame still carries ``fp32(water_classical_forces(x))``; the same atoms given in OTHER periodic images may change
         cells at a face and with them the order of the sums (same bound, not the same bits).  The observer,
         ``water_classical_forces`` and the ``"water_classical"`` force source follow it, with and without ``m_site`` and
-        ``pme``; the M-site form's O-O pass and the virial log's own walk stay all-pairs, and ``water_minimize`` refuses it
-        (minimise with ``cells=False``, configure again with ``cells=True``, take ``f`` from ``water_classical_forces``).
+        ``pme``; the M-site form's O-O pass and the virial log's own walk stay all-pairs, and the minimisers refuse it unless
+        ``minimize_configured=True`` (without it: minimise with ``cells=False``, configure again with ``cells=True``, take
+        ``f`` from ``water_classical_forces``).
         The table costs six launches per evaluation: it pays above a few thousand atoms (profiles/run_water_cells.md).  Every
         call states it: the default False is the all-pairs walk, bit for bit what it was.  ``water_cells_table`` reads the
         table of the last evaluation.
 
-        The plain sum is the limit OpenMM's PME approximates.  Not built: cells for the water minimiser, for the virial walk and the M-site form's O-O pass, a table kept across steps with a skin; the PME virial, the PME minimiser, odd orders,
-        grids that are no power of two, real-to-complex transforms, a 4-site minimiser, the pressure tensor,
+        ``minimize_configured`` makes ``water_minimize`` and ``water_minimize_lbfgs`` minimise under the potential as this call
+        states it — ``m_site``, ``pme`` (both orders, every grid) and ``cells`` in any combination, none of them included —
+        instead of refusing the three.  With none of them set the minimisers' results are bit for bit what they are without
+        it.  Every call states it: the default False is the minimisers as they were (3-site, plain sum, all pairs only).
+
+        The plain sum is the limit OpenMM's PME approximates.  Not built: cells for the virial walk and the M-site form's O-O pass, a table kept across steps with a skin; the PME virial, odd orders,
+        grids that are no power of two, real-to-complex transforms, the pressure tensor,
         a barostat; the long-range dispersion correction is ``lj_dispersion_correction`` on the host (``pressure(...,
         dispersion=True)``).  No parity with OpenMM is claimed.  Check the parameters against your OpenMM system before
         comparing energies."""
@@ -1351,6 +1358,9 @@ class GamdForce:
         if cells or getattr(self, "_water_cells", False):           # (a handle that never had cells makes the calls it made)
             check(self._lib.gamd_water_cells(self._h, int(bool(cells))), "gamd_water_cells")
             self._water_cells = bool(cells)
+        if minimize_configured or getattr(self, "_water_min_configured", False):    # (likewise)
+            check(self._lib.gamd_water_minimize_potential(self._h, int(bool(minimize_configured))), "gamd_water_minimize_potential")
+            self._water_min_configured = bool(minimize_configured)
         self._water_set = True
         self._water_virial = bool(virial)
         self._water_lj = dict(sigma=sigma_o, epsilon=float(epsilon_o), r_cut=r_cut, r_switch=float(r_switch), shift=bool(shift),
@@ -1471,9 +1481,14 @@ class GamdForce:
         unrounded, unwrapped, exactly rigid double positions (``result.x64``).  Water models only; 2 r_cut must not exceed a
         box edge.  Synchronises.
 
-        The minimiser is 3-site: with ``m_site`` != 0 in force it raises (the library answers -22 and names the M-site)
-        before anything is enqueued.  A 4-site start: minimise with ``m_site=0``, configure again with the weight, and pass
-        ``water_classical_forces(x, species)[0].float()`` as ``f`` on entry of the run."""
+        Without ``water_classical_configure(..., minimize_configured=True)`` the minimiser is 3-site, plain sum, all pairs:
+        with ``m_site`` != 0, ``pme`` or ``cells`` in force it raises (the library answers -22 and names the form and the
+        switch) before anything is enqueued.  With it, the call minimises under the potential as configured, whatever
+        combination of the three is set: the same arguments, states and rows; ``f`` is still
+        ``water_classical_forces(x, species)[0].float()`` bit for bit, now under that configuration; ``tolerance`` bounds the
+        rms of the projected force on the three real atoms, M's force having been spread onto them with the weights
+        1 - 2 w, w, w; U in the result is the configured potential's.  With none of the three set the results are the
+        switch-off results bit for bit."""
         unknown = set(fire) - {"dt_start", "dt_max", "n_min", "f_inc", "f_dec", "alpha_start", "f_alpha", "max_step"}
         if unknown:
             raise TypeError(f"water_minimize() got unexpected FIRE constants {sorted(unknown)}")
@@ -1526,8 +1541,12 @@ class GamdForce:
         jumps (about 0.03 kJ/mol at r_cut = 6.5 Angstrom) when an O-O pair crosses the cutoff, and the sufficient-decrease
         test cannot pass such a jump once the steps gain less than that: on the default potential the call stops as
         "line_search" somewhere below a tolerance of about 1.  For tolerances below about 1 configure the potential with
-        ``r_switch`` > 0 or ``shift=True``.  Water models only, 3-site, plain Ewald sum, all pairs: with ``m_site``, ``pme``
-        or ``cells`` in force it raises (-22, naming the reason) before anything is enqueued.  Synchronises."""
+        ``r_switch`` > 0 or ``shift=True``.  Water models only.  Without
+        ``water_classical_configure(..., minimize_configured=True)``: 3-site, plain Ewald sum, all pairs — with ``m_site``,
+        ``pme`` or ``cells`` in force it raises (-22, naming the reason and the switch) before anything is enqueued.  With it:
+        the potential as configured, under ``water_minimize``'s contract for that case (``f`` under the configuration in
+        force, the projected force of the three real atoms after M's force has been spread); the trial positions go through
+        the same route as the iterate's.  Synchronises."""
         if not getattr(self, "_water_set", False):
             self.water_classical_configure(0, length_per_nm=length_per_nm)
         if f is None:

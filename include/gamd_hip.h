@@ -556,9 +556,10 @@ int32_t gamd_classical_cells_read(gamd_handle* h, void* stream, int32_t box, int
  * -22 from gamd_md_force_source besides the above: GAMD_FORCE_WATER_CLASSICAL on a GAMD_KIND_LJ handle, or before an accepted
  * gamd_water_configure (interval 0 will do).
  * gamd_water_minimize (below) relaxes a start and leaves x and f as this source expects them.  With gamd_water_msite the
- * source drives the 4-site (TIP4P) form of the potential by seven launches; a start is then minimised with w_h = 0 (see there).
- * Particle-mesh Ewald is gamd_water_pme (below).  Not built: the PME virial, the PME minimiser, odd orders, grids that are no power of two, real-to-complex transforms,
- * the 4-site minimiser, a barostat.  The default parameters of gamd_water_configure remain UNVERIFIED
+ * source drives the 4-site (TIP4P) form of the potential by seven launches; a start is then minimised under that form with
+ * gamd_water_minimize_potential on (below), or with w_h = 0 (see there).
+ * Particle-mesh Ewald is gamd_water_pme (below).  Not built: the PME virial, odd orders, grids that are no power of two, real-to-complex transforms,
+ * a barostat.  The default parameters of gamd_water_configure remain UNVERIFIED
  * against OpenMM. */
 enum { GAMD_FORCE_NETWORK = 0, GAMD_FORCE_CLASSICAL = 1, GAMD_FORCE_WATER_CLASSICAL = 2 };
 int32_t gamd_md_force_source(gamd_handle* h, int32_t source);
@@ -649,15 +650,16 @@ int32_t gamd_water_eval(gamd_handle* h, const float* pos_dev, const uint8_t* spe
  * With w_h != 0 the observer is eight launches (a site prepass, the Coulomb pair pass, the O-O Lennard-Jones pass, charge
  * density, S(k), per-atom k sums, the per-atom pass, the final row) and the force source seven behind the neighbour stage (its
  * pair passes are the observer's: energies are computed and not read); f is bit for bit the fp32 rounding of gamd_water_eval's forces, and must hold that on entry.
- * gamd_water_minimize with w_h != 0 returns -22 (the message names the M-site) before anything is enqueued: there is no 4-site
- * rigid minimiser.  Start recipe: gamd_water_minimize with w_h = 0, gamd_water_msite(h, w_h), gamd_water_eval on the minimised
- * x, its forces rounded to fp32 as f on entry of the run.
+ * gamd_water_minimize with w_h != 0 minimises under the 4-site form while gamd_water_minimize_potential is on (below); while it
+ * is off (the default) it returns -22 (the message names the M-site and the switch) before anything is enqueued.  Start recipe
+ * without the switch: gamd_water_minimize with w_h = 0, gamd_water_msite(h, w_h), gamd_water_eval on the minimised x, its forces
+ * rounded to fp32 as f on entry of the run.
  * -22, with a message naming the reason: a null handle, a GAMD_KIND_LJ handle, no accepted gamd_water_configure, a pending
  * run, w_h not finite, negative or >= 0.5.  -12 when the extra work buffers cannot be allocated: they are ensured here or at
  * run entry, never inside a run.  Device memory added while w_h != 0: 24 B per atom (the sites) and 32 B per molecule and pair
  * slice (the oxygen's Lennard-Jones force and energy, apart from the site force).
- * Particle-mesh Ewald (gamd_water_pme, below) serves the M-site form as well.  Not built: the PME virial, the PME minimiser, odd orders, grids that are no power of two, real-to-complex transforms,
- * the 4-site minimiser (the molecular virial is gamd_water_virial below; the long-range dispersion correction
+ * Particle-mesh Ewald (gamd_water_pme, below) serves the M-site form as well.  Not built: the PME virial, odd orders, grids that are no power of two, real-to-complex transforms
+ * (the molecular virial is gamd_water_virial below; the long-range dispersion correction
  * is a host function of the Python package).  The TIP4P-Ew parameters the Python
  * package offers (q_H = 0.52422 e, sigma_O = 3.16435 Angstrom, epsilon_O = 0.680946 kJ/mol, w_h = 0.106676721) were written
  * down from memory and are UNVERIFIED against OpenMM's tip4pew.xml; no parity with OpenMM is claimed. */
@@ -679,9 +681,10 @@ int32_t gamd_water_msite(gamd_handle* h, double w_h);
  * real-space, exclusion and self terms are unchanged.  The accuracy is set by the grid and the order, not by ewald_tol: with
  * alpha = 0.63 / Angstrom (r_cut 6.8, ewald_tol 1e-8) and order 6 a spacing of 0.45 Angstrom leaves an rms force difference of
  * a few 1e-5 of the rms force against the plain sum (profiles/run_water_pme.md).
- * Not built: the PME virial and the PME minimiser — gamd_water_virial(h, 1), gamd_water_virial_eval and gamd_water_minimize
- * return -22 while PME is on, and gamd_water_pme returns -22 while the virial log is armed (messages name PME).  Start recipe:
- * minimise under the plain sum, switch PME on, take f from gamd_water_eval.  Nor odd orders, grids that are no power of two,
+ * Not built: the PME virial — gamd_water_virial(h, 1) and gamd_water_virial_eval return -22 while PME is on, and gamd_water_pme
+ * returns -22 while the virial log is armed (messages name PME).  The minimisers follow PME while gamd_water_minimize_potential
+ * is on (below) and return -22 while it is off; start recipe without the switch: minimise under the plain sum, switch PME on,
+ * take f from gamd_water_eval.  Nor odd orders, grids that are no power of two,
  * real-to-complex transforms.
  * -22, with a message naming the reason: a null handle or block, a GAMD_KIND_LJ handle, no accepted gamd_water_configure, a
  * pending run, an order other than 0, 4, 6, a grid length outside {8, 16, 32, 64, 128}.  -12 when the grids cannot be
@@ -707,7 +710,8 @@ int32_t gamd_water_pme(gamd_handle* h, const gamd_water_pme_params* p);
  * fall into a neighbouring cell at a face, which changes the order of the sums (within the bound above).
  * The table costs six launches: below a few thousand atoms all pairs are faster (profiles/run_water_cells.md).
  * Not built, and served all-pairs while the switch is on: the O-O pass of the M-site form, the virial log's own pair walk
- * (which reads the cells' f_cl); gamd_water_minimize returns -22 while the switch is on
+ * (which reads the cells' f_cl).  The minimisers walk the table while gamd_water_minimize_potential is on (below); while it is
+ * off gamd_water_minimize returns -22 while this switch is on
  * (its f is the all-pairs force bit for bit: minimise with the cells off, switch them on, take f from gamd_water_eval).  Nor a
  * table kept across steps with a skin, nor non-orthorhombic boxes.
  * -22, with a message naming the reason: a null handle, a GAMD_KIND_LJ handle, no accepted gamd_water_configure, a pending
@@ -969,13 +973,34 @@ int32_t gamd_water_minimize(gamd_handle* h, float* x_dev, const uint8_t* species
  *                the largest per-atom |F_c,i|.
  * Returns 0 / 1 / 2 / 3 as gamd_minimize_lbfgs, the largest wins.  -22, with a message naming the reason, before anything is
  * enqueued: what gamd_minimize_lbfgs refuses in the parameter block, and everything gamd_water_minimize refuses — a set M-site
- * (gamd_water_msite), particle-mesh Ewald on (gamd_water_pme) and the cell table on (gamd_water_cells) among them, which have
- * no minimiser here either — a frozen handle included.  -12 when an allocation fails.
+ * (gamd_water_msite), particle-mesh Ewald on (gamd_water_pme) and the cell table on (gamd_water_cells) among them while
+ * gamd_water_minimize_potential is off — a frozen handle included.  -12 when an allocation fails.
  * Device memory besides the water classical observer's work buffers: 24 (2 m + 5) + 12 B per atom, the ring sized for the
  * largest m a call has asked for (x, x_t, F, F_t, d and the ring in double, the fp32 force). */
 int32_t gamd_water_minimize_lbfgs(gamd_handle* h, float* x_dev, const uint8_t* species_dev, const float* box, float length_per_nm,
                                   double r_oh, double r_hh, float* f_dev, double* x64_dev, const gamd_lbfgs_params* params,
                                   double* rows_host, void* stream);
+
+/* The two water minimisers under the potential AS THE HANDLE IS CONFIGURED: an optional, sticky property of the handle, switched
+ * as the M-site, PME and the cell table are.  on = 0 (the default): gamd_water_minimize and gamd_water_minimize_lbfgs know the
+ * 3-site, plain-sum, all-pairs form alone, refuse the other forms with -22, launch what they launched before this switch
+ * existed and give the same bits.  on = 1: both minimise under whatever gamd_water_msite, gamd_water_pme (orders 4 and 6, every
+ * offered grid) and gamd_water_cells have set, in any combination, none of them included; with none set the results are the
+ * switch-off results bit for bit.  The contract of each entry keeps its shape: x whole molecules with the oxygen in [0, L), x64
+ * exactly rigid, nothing written for a failed box, the same states and rows, f bit for bit the fp32 rounding of
+ * gamd_water_eval's forces on x UNDER THE CONFIGURATION IN FORCE, and the tolerance bounds the rms over 3N components of the
+ * projected force in kJ/mol/nm — the projection of the force on the three real atoms, after M's force has been spread with the
+ * weights 1 - 2 w_h, w_h, w_h.  U in the rows is the configured potential's (U_recip by PME where PME is on).
+ * Launches per iteration / evaluation on the caller's stream: the pair pass 1 (the cell table: 6), the reciprocal part 3
+ * (PME: 10), with the M-site a site prepass on the double positions and the O-O pass on top (+ 2), the per-molecule pass and the
+ * update: 6 for the 3-site plain all-pairs form, 25 for M-site + PME + cells.  A box that has stopped is skipped by the
+ * minimisers' own kernels; the potential's reused kernels evaluate it again into work buffers nobody reads for it: its x64,
+ * state and row stay, and a box gets the bits it gets alone.
+ * Still not built: vector transport of the L-BFGS ring, a Wolfe line search, flexible water, minimising inside an enqueued run;
+ * the PME virial remains refused.
+ * -22, with a message naming the reason: a null handle, a GAMD_KIND_LJ handle, no accepted gamd_water_configure, a pending
+ * run, on not 0 or 1.  No device memory of its own. */
+int32_t gamd_water_minimize_potential(gamd_handle* h, int32_t on);
 
 /* Event-timed replay of one force evaluation: per-kernel milliseconds of the last gamd_profile call.
  * names: newline-separated kernel labels; ms: one float per label.  For bench.py's roofline block. */
